@@ -19,6 +19,12 @@ per-query recovery on the rank that holds those rows, and only there).
 Prints ONE JSON line on rank 0 (see the keys below); `roofline` is for the dominant kernel
 (`mips_filter16p_kernel`: MFMA-bound above ~312 queries per batch, HBM-bound below), `cpu_baseline` is the
 oracle-side faiss-CPU restatement timed on the host cores of this box (rank 0, N = 1 only).
+
+A plain run does what the headline needs and nothing else: build the store, W untimed + K timed steps, the line.
+`--full` adds everything else it measures or checks, after the timed steps: the float64 verification of a query
+sample and the integer twin (`verify`), the side workloads (`side`, N = 1 on the default workload) and the CPU
+baseline (`cpu_baseline`); `--no-verify` / `--no-side` / `--no-cpu-baseline` drop single parts of it.
+`--dump-outputs DIR` writes the last timed step's result to DIR (`scores.npy` float32, `ids.npy` float64, [nq, k]).
 """
 from __future__ import annotations
 
@@ -84,10 +90,16 @@ def parse_args() -> argparse.Namespace:
     p.add_argument("--node-devices", type=str, default=None,
                    help="--engine node: comma-separated device ordinals, one per shard (default 0 .. gpus-1); repeating a device (0,0) puts several "
                         "shards on one GPU with the exchange forced through pinned host memory - the N > 1 code path on a 1-GPU box")
+    p.add_argument("--full", action="store_true",
+                   help="after the timed steps, also run the verification (float64 brute force + integer twin), the side workloads and the CPU "
+                        "baseline; without it the run times the headline only")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="write the last timed step's result (scores.npy float32, ids.npy float64, [nq, k]; a fixed sample of the query rows "
+                        "above 64 MB, their indices in rows.npy) to DIR")
     p.add_argument("--no-cpu-baseline", action="store_true")
     p.add_argument("--no-verify", action="store_true")
     p.add_argument("--no-side", action="store_true",
-                   help="skip the side workloads (C2, nq = 256, clustered C3, the 1.25 M-row shard with the exchange) the default 1-GPU run appends as `side`")
+                   help="skip the side workloads (C2, nq = 256, clustered C3, the 1.25 M-row shard with the exchange) a --full 1-GPU run appends as `side`")
     p.add_argument("--verify-queries", type=int, default=64)
     p.add_argument("--cpu-seconds", type=float, default=15.0)
     p.add_argument("--init-timeout", type=float, default=300.0,
@@ -97,7 +109,10 @@ def parse_args() -> argparse.Namespace:
     pre, _ = p.parse_known_args()
     if pre.config == "c4":  # a preset = new defaults: explicit --rows / --nq ... still win
         p.set_defaults(rows=40_000_000, dim=1024, nq=512, k=200, dtype="bf16")
-    return p.parse_args()
+    args = p.parse_args()
+    if args.steps < 1 and not args.launch_check:
+        p.error("--steps must be at least 1")
+    return args
 
 
 def _free_rendezvous_port(socket) -> int:
@@ -662,7 +677,31 @@ def run_workload(rig: Rig, index, row_lo: int, *, rows: int, dim: int, nq: int, 
     return {"elapsed": elapsed, "filter_ns": state["ns"], "filter_launches": state["launches"], "recovery_passes": state["recovery_passes"],
             "recovery_ns": state["recovery_ns"], "verify": verify, "n_local": n_local, "steps": steps, "warmup": warmup,
             "rows": rows, "dim": dim, "nq": nq, "k": k, "dtype": dtype, "data": data, "multi": multi, "tile": tile, "exact": exact,
-            "per_rank": per_rank}
+            "per_rank": per_rank, "result": state["res"]}
+
+
+DUMP_LIMIT = 64 << 20  # bytes: what --dump-outputs may write in all
+
+
+def dump_outputs(dst, scores, ids) -> None:
+    """`--dump-outputs DIR`: the result a caller of the timed path receives, scores.npy (float32) and ids.npy (float64: exact for every
+    id below 2^53), [nq, k].  A result above DUMP_LIMIT is cut to a fixed, seeded sample of its query rows, whose indices go to rows.npy."""
+    import numpy as np
+
+    out = pathlib.Path(dst)
+    out.mkdir(parents=True, exist_ok=True)
+    s = scores.float().cpu().numpy()
+    i = ids.cpu().numpy().astype(np.float64)
+    nq, k = s.shape
+    if nq * k * 12 > DUMP_LIMIT - 4096:  # (4 KB: the three .npy headers)
+        keep = max(1, (DUMP_LIMIT - 4096) // (k * 12 + 8))
+        rows = np.sort(np.random.default_rng(0).choice(nq, size=keep, replace=False))
+        s, i = s[rows], i[rows]
+        np.save(out / "rows.npy", rows.astype(np.float64))
+    else:
+        (out / "rows.npy").unlink(missing_ok=True)
+    np.save(out / "scores.npy", np.ascontiguousarray(s, dtype=np.float32))
+    np.save(out / "ids.npy", np.ascontiguousarray(i, dtype=np.float64))
 
 
 def _m(v: int) -> str:
@@ -1137,9 +1176,11 @@ def run_node_engine(args) -> None:
     merge_ns = index.get_stat("last_merge_ns") * args.steps        # (HIP events of the last batch's merge / slowest copy: read once, after the
     copy_ns = index.get_stat("last_copy_ns_max") * args.steps      # timed region - reading them per batch would wait for every merge)
     index.set_param("profile", 0)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, *res)
     shard_rows = [max(0, min(n_total, (g + 1) * -(-n_total // G)) - g * -(-n_total // G)) for g in range(G)]
     verify = None
-    if not args.no_verify and args.verify_queries > 0:
+    if args.full and not args.no_verify and args.verify_queries > 0:
         fs, fi = res
         n_v = min(nq, args.verify_queries)
         sample = sorted(set(int(round(j * (nq - 1) / max(1, n_v - 1))) for j in range(n_v))) if n_v > 1 else [0]
@@ -1157,7 +1198,7 @@ def run_node_engine(args) -> None:
          "per_shard": [{"shard": g, "device": devices[g], "rows": shard_rows[g], "kernel_ms": shard_ns[g] * 1e-6 / args.steps} for g in range(G)],
          "merge_us": merge_ns * 1e-3 / args.steps, "copy_us_max": copy_ns * 1e-3 / args.steps, "peer_access": peer}
     cpu = None
-    if G == 1 and not args.no_cpu_baseline:
+    if args.full and G == 1 and not args.no_cpu_baseline:
         from oracle.cpu_baseline import time_cpu_baseline  # the reported CPU baseline, never the product path
 
         cpu = time_cpu_baseline(d, nq, k, n_total, target_seconds=args.cpu_seconds)
@@ -1205,11 +1246,13 @@ def main() -> None:
     index, row_lo, t_build = build_index(rig, rows=n_total, dim=d, dtype=args.dtype, data=args.data, tile=args.tile, growth=args.growth,
                                          params=args.param, exact=args.exact_f32)
     m = run_workload(rig, index, row_lo, rows=n_total, dim=d, nq=nq, k=k, dtype=args.dtype, data=args.data, multi=multi,
-                     steps=args.steps, warmup=args.warmup, verify_queries=0 if args.no_verify else args.verify_queries, tile=args.tile,
-                     exact=args.exact_f32)
+                     steps=args.steps, warmup=args.warmup, verify_queries=args.verify_queries if args.full and not args.no_verify else 0,
+                     tile=args.tile, exact=args.exact_f32)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, *m["result"])
     default_workload = (n_total, d, nq, k, args.dtype, args.data, args.tile, args.growth, tuple(args.param), args.exact_f32) == (10_000_000, 768, 1024, 100, "f16", "iid", 0, 0, (), False)
     side = None
-    if world == 1 and not args.force_collective and not args.no_side and default_workload:
+    if args.full and world == 1 and not args.force_collective and not args.no_side and default_workload:
         side = side_workloads(rig, args, index, row_lo)
     if m["verify"] is not None:  # (last use of the headline store: it is refilled with the integer twin)
         m["verify"]["ids_bit_exact_on_integer_twin"] = integer_twin_check(
@@ -1219,7 +1262,7 @@ def main() -> None:
     line = None
     if rank == 0:
         cpu = None
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             from oracle.cpu_baseline import time_cpu_baseline  # the reported CPU baseline, never the product path
 
             cpu = time_cpu_baseline(d, nq, k, n_total, target_seconds=args.cpu_seconds)

@@ -13,7 +13,7 @@ for rep in $(seq 1 $REPS); do
       set -- $arm; lib=$1; tile=$2; kf=${3:-0}
       if [ $lib = abl ]; then export VODHIP_LIB=$ABL; else unset VODHIP_LIB; fi
       set -- $(echo $cfg | cut -d" " -f2-)
-      res=$(timeout 600 python bench.py "$@" --tile $tile --param kflags=$kf --no-side --no-cpu-baseline --verify-queries 16 2>/dev/null | tail -1 | \
+      res=$(timeout 600 python bench.py --full "$@" --tile $tile --param kflags=$kf --no-side --no-cpu-baseline --verify-queries 16 2>/dev/null | tail -1 | \
             python -c "import sys,json; d=json.loads(sys.stdin.read()); v=d['verify']; r=d['roofline']; print(round(d['ms_per_step'],4), 'kernel_ms', round(r['kernel_ms_per_step'],4), 'mfma_frac', round(r['mfma_frac_of_2.5PF'],4), 'recall', v['recall_at_k'], 'diff', v['max_abs_score_diff'], 'twin', v['ids_bit_exact_on_integer_twin']['ids_bit_exact'])")
       echo "$name lib=$lib tile=$tile kflags=$kf rep$rep ms $res" | tee -a $OUT
     done

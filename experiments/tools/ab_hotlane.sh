@@ -2,7 +2,7 @@
 # same-box A/B: cooperative emptying of hot lanes in the filter kernel's cold path (libvodhip.so) vs the parent build (libvodhip_old.so)
 A=vod_amd/csrc/libvodhip_old.so; B=vod_amd/csrc/libvodhip.so
 out=gpurun_out/ab_hotlane.txt; mkdir -p gpurun_out; : > $out
-run() { lib=$1; shift; echo -n "$(basename $lib) $*: " >> $out; VODHIP_LIB=$PWD/$lib timeout 600 python3 bench.py --no-cpu-baseline --no-side "$@" 2>/dev/null | python3 -c "
+run() { lib=$1; shift; echo -n "$(basename $lib) $*: " >> $out; VODHIP_LIB=$PWD/$lib timeout 600 python3 bench.py --full --no-cpu-baseline --no-side "$@" 2>/dev/null | python3 -c "
 import sys,json
 for l in sys.stdin:
     if l.startswith('{'):

@@ -3,7 +3,7 @@
 set -u
 ROOTD=${GRAFT_REPO_ROOT:-$(pwd)}
 one() { name=$1; l=$2; shift 2
-  python3 $ROOTD/bench.py "$@" --no-side --no-cpu-baseline --verify-queries 8 --param lanes=$l 2>/dev/null | tail -1 | \
+  python3 $ROOTD/bench.py --full "$@" --no-side --no-cpu-baseline --verify-queries 8 --param lanes=$l 2>/dev/null | tail -1 | \
     python3 -c "import sys,json; d=json.loads(sys.stdin.read()); v=d.get('verify') or {}; print('$name', 'lanes', $l, 'ms', round(d['ms_per_step'],4), 'recall', v.get('recall_at_k'), (v.get('integer_twin') or {}).get('ids_bit_exact'))"
 }
 for rep in 1 2 3; do

@@ -14,7 +14,7 @@ print(sys.argv[1], sys.argv[2], "kernel_ms", round(d["roofline"]["kernel_ms_per_
 PY
 one() { # tag, name, bench args
   tag=$1; name=$2; shift 2
-  VODHIP_LIB=$ROOTD/experiments/_build/libvodhip_p8_$tag.so python3 $ROOTD/bench.py "$@" --tile 14 --no-side --no-cpu-baseline --verify-queries ${VQ:-0} 2>/dev/null | tail -1 | python3 /tmp/ab_p8_line.py $name $tag
+  VODHIP_LIB=$ROOTD/experiments/_build/libvodhip_p8_$tag.so python3 $ROOTD/bench.py --full "$@" --tile 14 --no-side --no-cpu-baseline --verify-queries ${VQ:-0} 2>/dev/null | tail -1 | python3 /tmp/ab_p8_line.py $name $tag
 }
 for rep in $(seq $R); do
   for t in $1; do one $t C3 --steps 12 --warmup 3; done

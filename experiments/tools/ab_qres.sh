@@ -9,7 +9,7 @@ run() { # name, bench args...
   name=$1; shift
   for r in $(seq $R); do
     for tile in 14 ${TILE:-17}; do
-      python3 $ROOTD/bench.py "$@" --tile $tile --no-side --no-cpu-baseline --verify-queries 16 2>/dev/null | tail -1 | \
+      python3 $ROOTD/bench.py --full "$@" --tile $tile --no-side --no-cpu-baseline --verify-queries 16 2>/dev/null | tail -1 | \
         python3 -c "import sys,json; d=json.loads(sys.stdin.read()); v=d['verify']; print('$name tile $tile ms', round(d['ms_per_step'],4), 'kernel_ms', round(d['roofline']['kernel_ms_per_step'],4), 'recall', v['recall_at_k'], 'twin', v['integer_twin']['ids_bit_exact'], v['integer_twin']['scores_bit_exact'])"
     done
   done

@@ -6,7 +6,7 @@ for rep in 1 2 3; do
   for w in "c3 --steps 20 --warmup 3" "shard --rows 1250000 --steps 100 --warmup 10" "c4nq512 --rows 10000000 --nq 512 --steps 30 --warmup 3"; do
     set -- $w; name=$1; shift
     for r in 1 0; do
-      python bench.py "$@" --param rendezvous=$r --no-cpu-baseline --no-side --verify-queries 16 2>/dev/null | tail -1 | python -c "
+      python bench.py --full "$@" --param rendezvous=$r --no-cpu-baseline --no-side --verify-queries 16 2>/dev/null | tail -1 | python -c "
 import sys,json; d=json.loads(sys.stdin.read()); print('$name rendezvous=$r rep=$rep', round(d['ms_per_step'],4), 'ms kernel', round(d['roofline']['kernel_ms_per_step'],4), 'recall', d['verify']['recall_at_k_vs_torch_fp32'])"
     done
   done

@@ -2,7 +2,7 @@
 # same-box A/B: the register-resident select kernel (libvodhip.so) against the round-2 one (libvodhip_old.so = the parent commit's build)
 A=vod_amd/csrc/libvodhip_old.so; B=vod_amd/csrc/libvodhip.so
 out=gpurun_out/ab_select.txt; mkdir -p gpurun_out; : > $out
-run() { lib=$1; shift; echo -n "$(basename $lib) $*: " >> $out; VODHIP_LIB=$PWD/$lib timeout 600 python3 bench.py --no-cpu-baseline --no-side "$@" 2>/dev/null | python3 -c "
+run() { lib=$1; shift; echo -n "$(basename $lib) $*: " >> $out; VODHIP_LIB=$PWD/$lib timeout 600 python3 bench.py --full --no-cpu-baseline --no-side "$@" 2>/dev/null | python3 -c "
 import sys,json
 for l in sys.stdin:
     if l.startswith('{'):

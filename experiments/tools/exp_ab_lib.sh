@@ -2,7 +2,7 @@
 # A/B of two builds of the library on one box: tools/exp_ab_lib.sh <libA.so> <libB.so> [bench args...]  (alternates A B A B)
 A=$1; B=$2; shift 2
 out=gpurun_out/exp_ab.txt; mkdir -p gpurun_out; : > $out
-run() { lib=$1; shift; echo "== $(basename $lib) $*" >> $out; VODHIP_LIB=$lib timeout 600 python3 bench.py --no-cpu-baseline "$@" 2>/dev/null | python3 -c "
+run() { lib=$1; shift; echo "== $(basename $lib) $*" >> $out; VODHIP_LIB=$lib timeout 600 python3 bench.py --full --no-cpu-baseline "$@" 2>/dev/null | python3 -c "
 import sys,json
 for l in sys.stdin:
     if l.startswith('{'):

@@ -7,7 +7,7 @@ if [ -n "$PARITY" ]; then
   sed -e "s/^TILES = \[1, 8, 9, 42, 46\]/TILES = [1, 8, 9, 10, 11, 42, 46]/" tests/test_mips_gpu.py > tests/test_mips_ring_tmp_gpu.py
   VODHIP_LIB=$EXP_LIB timeout 900 python -m pytest tests/test_mips_ring_tmp_gpu.py -x -q -m gpu -k "not full_size" 2>&1 | tail -5 >> $out; rm -f tests/test_mips_ring_tmp_gpu.py
 fi
-run() { echo "== $*" >> $out; lib=$PWD/vod_amd/csrc/libvodhip.so; case "$*" in *tile=1[0-2]*) lib=$EXP_LIB;; esac; VODHIP_LIB=$lib timeout 600 python3 bench.py --no-cpu-baseline "$@" 2>/dev/null | python3 -c "
+run() { echo "== $*" >> $out; lib=$PWD/vod_amd/csrc/libvodhip.so; case "$*" in *tile=1[0-2]*) lib=$EXP_LIB;; esac; VODHIP_LIB=$lib timeout 600 python3 bench.py --full --no-cpu-baseline "$@" 2>/dev/null | python3 -c "
 import sys,json
 for l in sys.stdin:
     if l.startswith('{'):

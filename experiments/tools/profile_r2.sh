@@ -18,7 +18,7 @@ cd /tmp && export TMPDIR=/tmp
 for w in $LIST; do
   a="${W[$w]}"
   extra="--no-cpu-baseline"; [ "$w" = "c3" ] && extra=""
-  timeout 900 python3 $ROOTD/bench.py $a $extra > $OUT/${w}_bench.json 2> $OUT/${w}_bench.err
+  timeout 900 python3 $ROOTD/bench.py --full $a $extra > $OUT/${w}_bench.json 2> $OUT/${w}_bench.err
   tail -1 $OUT/${w}_bench.json | cut -c1-400
   [ "$w" = "shardfc" ] && continue
   P="--steps 5 --warmup 2 --no-cpu-baseline --no-verify"

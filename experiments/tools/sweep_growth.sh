@@ -10,7 +10,7 @@ v = d.get("verify") or {}
 print(*sys.argv[1:], "kernel_ms", round(d["roofline"]["kernel_ms_per_step"], 4), "ms", round(d["ms_per_step"], 4), "launches", d["roofline"].get("launches_per_step"), "recall", v.get("recall_at_k"))
 PY
 one() { name=$1; g=$2; sd=$3; shift 3
-  python3 $ROOTD/bench.py "$@" --growth $g --param sample_div=$sd --no-side --no-cpu-baseline --verify-queries 8 2>/dev/null | tail -1 | python3 /tmp/sweep_line.py $name growth $g sample_div $sd
+  python3 $ROOTD/bench.py --full "$@" --growth $g --param sample_div=$sd --no-side --no-cpu-baseline --verify-queries 8 2>/dev/null | tail -1 | python3 /tmp/sweep_line.py $name growth $g sample_div $sd
 }
 for rep in 1 2; do
   for sd in $2; do for g in $1; do one C3 $g $sd --steps 12 --warmup 3; done; done

@@ -3,7 +3,7 @@
 set -u
 ROOTD=${GRAFT_REPO_ROOT:-$(pwd)}
 one() { name=$1; g=$2; sd=$3; shift 3
-  python3 $ROOTD/bench.py "$@" --growth $g --param sample_div=$sd --no-side --no-cpu-baseline --verify-queries 8 2>/dev/null | tail -1 | python3 /tmp/sweep_line.py $name growth $g sample_div $sd
+  python3 $ROOTD/bench.py --full "$@" --growth $g --param sample_div=$sd --no-side --no-cpu-baseline --verify-queries 8 2>/dev/null | tail -1 | python3 /tmp/sweep_line.py $name growth $g sample_div $sd
 }
 cat > /tmp/sweep_line.py <<'PY'
 import json, sys

@@ -209,3 +209,39 @@ def test_roofline_bound_follows_the_nameplate_peaks_and_the_traffic_key_carries_
     assert r["bound"] == "mfma" and r["peak"] == 2500.0 and abs(r["frac"] - r["mfma_frac_of_2.5PF"]) < 1e-12
     assert bench.traffic_key(10_000_000, 768, 1024, 1) == "10000000x768x1024@1"
     assert bench.traffic_key(10_000_000, 768, 1024, 1, "clustered", True) == "10000000x768x1024@1/clustered/exact"
+
+
+# ---- --full / --dump-outputs ------------------------------------------------------------------------------------------------
+
+def test_full_and_dump_outputs_are_options_and_steps_must_be_positive():
+    out = _bench("--help")
+    assert out.returncode == 0 and "--full" in out.stdout and "--dump-outputs" in out.stdout
+    out = _bench("--steps", "0")
+    assert out.returncode == 2 and "--steps must be at least 1" in out.stderr
+
+
+def test_dump_outputs_writes_the_result_as_float_arrays_and_samples_a_large_one(tmp_path):
+    import numpy as np
+    import torch
+
+    bench = _load_bench()
+    g = torch.Generator().manual_seed(5)
+    s = torch.sort(torch.randn((300, 7), generator=g), dim=1, descending=True).values
+    i = torch.randint(0, 2**40, (300, 7), generator=g, dtype=torch.int64)
+    bench.dump_outputs(tmp_path / "small", s, i)
+    got_s, got_i = np.load(tmp_path / "small" / "scores.npy"), np.load(tmp_path / "small" / "ids.npy")
+    assert got_s.dtype == np.float32 and got_i.dtype == np.float64 and got_s.shape == got_i.shape == (300, 7)
+    assert np.array_equal(got_s, s.numpy()) and np.array_equal(got_i.astype(np.int64), i.numpy())
+    assert not (tmp_path / "small" / "rows.npy").exists()
+    # above the limit: a fixed sample of the query rows, the same from run to run, every file within the limit together
+    bench.DUMP_LIMIT = 4096 + 100 * (7 * 12 + 8)
+    for name in ("big_a", "big_b"):
+        bench.dump_outputs(tmp_path / name, s, i)
+    rows = np.load(tmp_path / "big_a" / "rows.npy")
+    assert rows.dtype == np.float64 and len(rows) == 100 and np.all(np.diff(rows) > 0)
+    r = rows.astype(np.int64)
+    assert np.array_equal(np.load(tmp_path / "big_a" / "scores.npy"), s.numpy()[r])
+    assert np.array_equal(np.load(tmp_path / "big_a" / "ids.npy").astype(np.int64), i.numpy()[r])
+    for f in ("rows.npy", "scores.npy", "ids.npy"):
+        assert (tmp_path / "big_a" / f).read_bytes() == (tmp_path / "big_b" / f).read_bytes()
+    assert sum((tmp_path / "big_a" / f).stat().st_size for f in ("rows.npy", "scores.npy", "ids.npy")) <= bench.DUMP_LIMIT

@@ -24,8 +24,9 @@ def _strict_loads(txt):
 
 
 def _run(*extra):
+    """A `--full` run (verify, CPU baseline) of a small store."""
     env = dict(os.environ, MASTER_ADDR="127.0.0.1", MASTER_PORT="29533")
-    out = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--rows", "300000", "--nq", "1024", "--steps", "3", "--warmup", "1", *extra],
+    out = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--full", "--rows", "300000", "--nq", "1024", "--steps", "3", "--warmup", "1", *extra],
                          capture_output=True, text=True, timeout=900, env=env, cwd=str(ROOT))
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.strip()]
@@ -48,6 +49,43 @@ def test_multi_gpu_step_runs_with_one_rank():
     line = _run("--force-collective", "--no-cpu-baseline")
     assert "all-gather" in line["config"]["parallelism"]
     assert line["verify"]["recall_at_k"] == 1.0
+
+
+def test_plain_run_times_the_headline_only_and_dumps_its_result(tmp_path):
+    """Without `--full` the line carries the headline alone (no verify / side / CPU baseline), and `--dump-outputs` writes the last timed
+    step's result: the top-k of the synthetic store, checked here against a float64 product over the same generated rows and queries."""
+    import importlib.util
+
+    import numpy as np
+    import torch
+
+    n, d, nq, k = 300_000, 128, 64, 10
+    env = dict(os.environ, MASTER_ADDR="127.0.0.1", MASTER_PORT="29535")
+    out = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--rows", str(n), "--dim", str(d), "--nq", str(nq), "--k", str(k), "--steps", "4",
+                          "--warmup", "1", "--dump-outputs", str(tmp_path / "dump")], capture_output=True, text=True, timeout=600, env=env, cwd=str(ROOT))
+    assert out.returncode == 0, out.stderr[-2000:]
+    lines = [ln for ln in out.stdout.splitlines() if ln.strip()]
+    line = _strict_loads(lines[-1])
+    assert REQUIRED <= set(line) and line["steps"] == 4 and line["ms_per_step"] > 0 and line["value"] > 0
+    assert not {"verify", "side", "cpu_baseline", "side_file"} & set(line), set(line)
+    s = np.load(tmp_path / "dump" / "scores.npy")
+    i = np.load(tmp_path / "dump" / "ids.npy")
+    assert s.dtype == np.float32 and i.dtype == np.float64 and s.shape == i.shape == (nq, k)
+    assert not (tmp_path / "dump" / "rows.npy").exists()
+    assert np.all(np.diff(s, axis=1) <= 0) and np.all((i >= 0) & (i < n) & (i == np.round(i)))
+
+    spec = importlib.util.spec_from_file_location("bench_under_test", ROOT / "bench.py")
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    dev = torch.device("cuda", 0)
+    x = torch.cat([bench.make_rows(torch, dev, torch.float16, "iid", c, min(bench.GEN_CHUNK, n - c * bench.GEN_CHUNK), d, n)
+                   for c in range(-(-n // bench.GEN_CHUNK))]).double()
+    q = bench.make_queries(torch, dev, torch.float16, "iid", nq, d, n).double()
+    sc = q @ x.T
+    kth = torch.topk(sc, k, dim=1).values[:, -1].cpu().numpy()
+    at_ids = sc.gather(1, torch.from_numpy(i.astype(np.int64)).to(dev)).cpu().numpy()
+    assert np.abs(at_ids - s).max() < 1e-3           # every returned score is its row's score ...
+    assert np.all(s[:, -1] >= kth - 1e-3)            # ... and the rows are the top k
 
 
 def test_sharded_index_exchange_on_rccl_with_one_rank(tmp_path):
@@ -139,8 +177,9 @@ print(f"rank {{rank}} ok", flush=True)
 
 
 def _run_bench(*args, timeout=900):
+    """`bench.py --full <args>`: the record with `verify` (and, on the default workload, `side` and `cpu_baseline`)."""
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
-    out = subprocess.run([sys.executable, str(ROOT / "bench.py"), *args], capture_output=True, text=True, timeout=timeout, env=env, cwd=str(ROOT))
+    out = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--full", *args], capture_output=True, text=True, timeout=timeout, env=env, cwd=str(ROOT))
     assert out.returncode == 0, (out.stderr[-3000:], out.stdout[-1000:])
     lines = [ln for ln in out.stdout.splitlines() if ln.lstrip().startswith("{")]
     assert len(lines) == 1, out.stdout[-2000:]   # exactly ONE line of stdout parses as JSON ...

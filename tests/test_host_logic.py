@@ -633,13 +633,35 @@ def test_http_shell_routes_wire_format_and_errors(shell):
         stop()
 
 
+@pytest.fixture
+def short_tmp_path():
+    """A fresh directory whose socket paths fit `sun_path` (108 bytes): pytest's `tmp_path` can be longer than that under a deep
+    temporary root, and the library then refuses the path before it binds."""
+    import os
+    import pathlib
+    import shutil
+    import tempfile
+
+    base = tempfile.gettempdir()
+    if len(base) > 60 and os.access("/tmp", os.W_OK):
+        base = "/tmp"
+    d = tempfile.mkdtemp(prefix="vh", dir=base)
+    try:
+        yield pathlib.Path(d)
+    finally:
+        shutil.rmtree(d, ignore_errors=True)
+
+
 @pytest.mark.parametrize("shell", SHELLS)
-def test_http_shell_on_a_unix_domain_socket(tmp_path, shell):
+def test_http_shell_on_a_unix_domain_socket(short_tmp_path, shell):
     """the same routes on a Unix-domain socket (`--uds`); the client's searches go through it, `ping` keeps using TCP,
     a pickled client (DataLoader worker) re-opens its own connection, and the socket file is removed on shutdown."""
     import os
 
     from oracle.flat_ip import flat_ip_topk
+
+    tmp_path = short_tmp_path
+    assert len(str(tmp_path / "nobody-listens.sock")) < 108
 
     rng = np.random.default_rng(6)
     x = rng.integers(-4, 5, size=(200, 8)).astype(np.float32)

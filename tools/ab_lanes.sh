@@ -10,7 +10,7 @@ for rep in $(seq 1 $REPS); do
     set -- $cfg; name=$1; shift
     if [ -n "${ONLY:-}" ] && ! echo " $ONLY " | grep -q " $name "; then continue; fi
     for lanes in 1 2; do
-      res=$(timeout 600 python bench.py "$@" --no-side --no-cpu-baseline --verify-queries 16 --param lanes=$lanes 2>/dev/null | tail -1 | \
+      res=$(timeout 600 python bench.py --full "$@" --no-side --no-cpu-baseline --verify-queries 16 --param lanes=$lanes 2>/dev/null | tail -1 | \
             python -c "import sys,json; d=json.loads(sys.stdin.read()); v=d['verify']; print(round(d['ms_per_step'],4), 'kernel_ms', round(d['roofline']['kernel_ms_per_step'],4), 'recall', v['recall_at_k'], 'diff', v['max_abs_score_diff'], 'twin', v['integer_twin']['ids_bit_exact'])")
       echo "$name lanes=$lanes rep$rep ms $res" | tee -a $OUT
     done

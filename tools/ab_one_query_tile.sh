@@ -5,7 +5,7 @@ for rep in 1 2 3; do
     set -- $cfg; name=$1; shift
     for tile in 8 14; do
       for lanes in 1 2; do
-        res=$(timeout 600 python bench.py "$@" --tile $tile --param lanes=$lanes --no-side --no-cpu-baseline --verify-queries 16 2>/dev/null | tail -1 | python -c "import sys,json; d=json.loads(sys.stdin.read()); print(round(d['ms_per_step'],4), d['verify']['recall_at_k'])")
+        res=$(timeout 600 python bench.py --full "$@" --tile $tile --param lanes=$lanes --no-side --no-cpu-baseline --verify-queries 16 2>/dev/null | tail -1 | python -c "import sys,json; d=json.loads(sys.stdin.read()); print(round(d['ms_per_step'],4), d['verify']['recall_at_k'])")
         echo "$name tile=$tile lanes=$lanes rep$rep ms $res" | tee -a $OUT
       done
     done

@@ -13,7 +13,7 @@ case $P in
     python -c "import __graft_entry__ as g; g.build(); g.smoke()" > $OUT/smoke.log 2>&1
     timeout 1200 python -m pytest tests -x -q -m gpu > $OUT/pytest_gpu.log 2>&1; tail -3 $OUT/pytest_gpu.log ;;
   bench)
-    timeout 900 python bench.py > $OUT/bench_default.json 2> $OUT/bench_default.err; tail -c 1500 $OUT/bench_default.json ;;
+    timeout 900 python bench.py --full > $OUT/bench_default.json 2> $OUT/bench_default.err; tail -c 1500 $OUT/bench_default.json ;;
   serve)
     timeout 900 python -m pytest tests/test_server_gpu.py tests/test_fuzz_gpu.py tests/test_node_index_gpu.py -x -q -m gpu > $OUT/pytest_serve.log 2>&1; tail -5 $OUT/pytest_serve.log
     timeout 1500 python tools/bench_http_load.py --out $OUT/http_load_native.json > $OUT/http_load_native.log 2>&1; tail -25 $OUT/http_load_native.log | cut -c1-400 ;;
@@ -32,7 +32,7 @@ case $P in
         set -- $cfg; name=$1; shift
         for v in "ring" "twoslot --param ring_single_qtile=0"; do
           set -- $v; vn=$1; shift
-          ms=$(timeout 600 python bench.py $(echo $cfg | cut -d" " -f2-) --no-side --no-cpu-baseline --verify-queries 16 "$@" 2>/dev/null | tail -1 | python -c "import sys,json; d=json.loads(sys.stdin.read()); print(round(d['ms_per_step'],4), d['verify']['recall_at_k'], d['verify']['max_abs_score_diff'])")
+          ms=$(timeout 600 python bench.py --full $(echo $cfg | cut -d" " -f2-) --no-side --no-cpu-baseline --verify-queries 16 "$@" 2>/dev/null | tail -1 | python -c "import sys,json; d=json.loads(sys.stdin.read()); print(round(d['ms_per_step'],4), d['verify']['recall_at_k'], d['verify']['max_abs_score_diff'])")
           echo "$name $vn rep$rep $ms" | tee -a $OUT/ab_ring.txt
         done
       done

@@ -21,7 +21,7 @@ cd /tmp && export TMPDIR=/tmp
 for w in $LIST; do
   a="${W[$w]}"
   extra="--no-cpu-baseline --no-side"; [ "$w" = "c3" ] && extra=""   # c3 = the default command: headline + side workloads + CPU baseline
-  timeout 900 python3 $ROOTD/bench.py $a $extra > $OUT/${w}_bench.json 2> $OUT/${w}_bench.err
+  timeout 900 python3 $ROOTD/bench.py --full $a $extra > $OUT/${w}_bench.json 2> $OUT/${w}_bench.err
   tail -1 $OUT/${w}_bench.json | cut -c1-400
   P="--steps 5 --warmup 2 --no-cpu-baseline --no-verify --no-side"
   # one-query-tile workloads run on two lanes (two searches overlap on the device): the kernel trace of those is taken with ONE lane, so that

@@ -1,7 +1,7 @@
 #!/bin/bash
 # Bench lines only (no profiler), one line per workload: tools/quick_bench.sh [extra bench args applied to every workload]
 out=gpurun_out/quick_bench.txt; mkdir -p gpurun_out; : > $out
-run() { echo "== $*" >> $out; timeout 600 python3 bench.py --no-cpu-baseline "$@" 2>/dev/null | python3 -c "
+run() { echo "== $*" >> $out; timeout 600 python3 bench.py --full --no-cpu-baseline "$@" 2>/dev/null | python3 -c "
 import sys,json
 for l in sys.stdin:
     if l.startswith('{'):
