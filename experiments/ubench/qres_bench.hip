@@ -13,6 +13,11 @@
 
 #include "vodhip_internal.h"
 
+namespace vodhip {  // experiments/csrc/kernels_mips_qres.hip
+hipError_t launch_filter_qres(int store_dtype, const void* store, const void* q_pad, int64_t dim_pad, int64_t row_begin, int64_t row_end,
+                              int64_t nq, int64_t nq_pad, const SearchWorkspace& ws, hipStream_t stream);
+}
+
 #define CK(x)                                                                                  \
     do {                                                                                       \
         hipError_t e_ = (x);                                                                   \
@@ -81,7 +86,7 @@ int main(int argc, char** argv) {
     auto run = [&](int tile) {
         CK(hipMemsetAsync(ws.cnt, 0, nq_pad * vodhip::CNT_STRIDE * 4, s));
         if (tile == 17) CK(vodhip::launch_filter_qres(0, X, Q, dim, 0, rows, nq, nq_pad, ws, s));
-        else CK(vodhip::launch_filter_8phase(0, 14, X, Q, dim, 0, rows, nq, nq_pad, ws, s));
+        else CK(vodhip::launch_filter_8phase(0, 7, true, X, Q, dim, 0, rows, nq, nq_pad, ws, s));
     };
     double ms[2] = {0, 0};
     unsigned cnt_sum[2] = {0, 0};

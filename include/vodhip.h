@@ -159,7 +159,8 @@ int vodhip_index_set_query_labels(vodhip_index_t* index, const int32_t* q_labels
 int vodhip_index_set_param(vodhip_index_t* index, const char* key, int64_t value);
 /* Host-side planning only (no device and no HIP runtime call): the stage list a search of `nq` queries for the top `k` of
  * `ntotal` rows would run on a device with `n_cu` compute units (<= 0 = 256, the MI355X), with the given tunables (<= 0 =
- * library default; tile 0 = auto; recovery_pass 0 = the normal schedule).  An index reads its device's CU count once, at create.
+ * library default; tile 0 = auto, else a filter-kernel id that vodhip_index_set_param("tile") accepts in this build - any other
+ * id is refused; recovery_pass 0 = the normal schedule).  An index reads its device's CU count once, at create.
  * out: int64 [max_stages][6] = {kind (0 FILTER, 1 DENSE, 2 GMAX bootstrap), row_begin, row_end, sampled tiles, sample row
  * stride, sample groups}.  Returns the number of stages, or -1. */
 int vodhip_debug_schedule(int64_t ntotal, int k, int64_t nq, int64_t cand_cap, int64_t dense_rows, int64_t sample_div,

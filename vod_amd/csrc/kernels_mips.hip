@@ -1114,10 +1114,6 @@ hipError_t launch_search_prepare(const SearchWorkspace& ws, const void* q_src, i
     return hipGetLastError();
 }
 
-int filter_tile_rows(int tile) { return tile == 1 ? 128 : 256; }
-int filter_tile_cols(int tile) { return tile == 42 ? 64 : (tile == 46 || tile == 1) ? 128 : 256; }
-int filter_group_rows(int tile) { return filter_tile_is_persistent(tile) ? 32 : 16; }  // rows per GMAX group (tiles 10 / 11 bootstrap on tile 8's kernel)
-
 hipError_t allow_dynamic_lds(const void* kernel, int bytes) {
     static std::mutex mu;
     static std::map<std::pair<int, const void*>, int> granted;
@@ -1158,8 +1154,9 @@ hipError_t launch_generic(const FilterLaunch& L) {
     return hipGetLastError();
 }
 
-template <int DT, int BM, int BN, int WM, int WN, int NSTAGE>
+template <int DT, FilterKernel K, int BM, int BN, int WM, int WN, int NSTAGE>
 hipError_t launch_generic_mode(const FilterLaunch& L, int mode, bool subset) {
+    static_assert(geometry(K).rows == BM && geometry(K).cols == BN && !geometry(K).persistent, "the planner's geometry of this kernel");
     if (mode == MODE_GMAX) return launch_generic<DT, BM, BN, WM, WN, NSTAGE, MODE_GMAX, false>(L);
     if (mode == MODE_DENSE)
         return subset ? launch_generic<DT, BM, BN, WM, WN, NSTAGE, MODE_DENSE, true>(L)
@@ -1189,55 +1186,37 @@ hipError_t launch_persistent(const FilterLaunch& L) {
 
 template <int DT, bool STAGGER>
 hipError_t launch_persistent_mode(const FilterLaunch& L, int mode, bool subset) {
+    constexpr FilterGeometry G = geometry(STAGGER ? FilterKernel::Staggered : FilterKernel::Persistent);
+    static_assert(G.rows == 256 && G.cols == 256 && G.group_rows == 32 && G.persistent, "the planner's geometry of mips_filter16p_kernel");
+    if (mode == MODE_DENSE) return hipErrorInvalidValue;  // dense chunks run on mips_filter_kernel
     if (mode == MODE_GMAX) return launch_persistent<DT, MODE_GMAX, false, STAGGER>(L);
     return subset ? launch_persistent<DT, MODE_FILTER, true, STAGGER>(L) : launch_persistent<DT, MODE_FILTER, false, STAGGER>(L);
 }
 
 template <int DT>
-hipError_t launch_filter_dt(int tile, int mode, bool subset, const FilterLaunch& L) {
-    switch (tile) {
-        case 1: return launch_generic_mode<DT, 128, 128, 2, 2, 2>(L, mode, subset);   // 64 KB LDS, 2 workgroups / CU: short chunks, dense chunks
-        case 42: return launch_generic_mode<DT, 256, 64, 4, 1, 3>(L, mode, subset);   // nq <= 64 (HBM-bound): 256 rows x 64 queries, 4 waves, 3-slot ring (120 KB)
-        case 46: return launch_generic_mode<DT, 256, 128, 4, 2, 3>(L, mode, subset);  // 65..128 queries: 256 x 128, 8 waves, 3-slot ring (144 KB)
-        case 8: return launch_persistent_mode<DT, false>(L, mode, subset);             // persistent 256 x 256, both waves of a SIMD in lockstep
-        case 9: return launch_persistent_mode<DT, true>(L, mode, subset);              // persistent 256 x 256, waves 4..7 staggered by one k-step
+hipError_t launch_filter_dt(FilterKernel kernel, int mode, bool subset, const FilterLaunch& L) {
+    switch (kernel) {
+        case FilterKernel::Generic128: return launch_generic_mode<DT, FilterKernel::Generic128, 128, 128, 2, 2, 2>(L, mode, subset);
+        case FilterKernel::Generic256x64: return launch_generic_mode<DT, FilterKernel::Generic256x64, 256, 64, 4, 1, 3>(L, mode, subset);
+        case FilterKernel::Generic256x128: return launch_generic_mode<DT, FilterKernel::Generic256x128, 256, 128, 4, 2, 3>(L, mode, subset);
+        case FilterKernel::Persistent: return launch_persistent_mode<DT, false>(L, mode, subset);
+        case FilterKernel::Staggered: return launch_persistent_mode<DT, true>(L, mode, subset);
         default: return hipErrorInvalidValue;
     }
 }
 
 }  // namespace
 
-hipError_t launch_filter(int store_dtype, int tile, int mode, const void* store, const void* q_pad, int64_t dim_pad,
+hipError_t launch_filter(int store_dtype, FilterKernel kernel, int mode, const void* store, const void* q_pad, int64_t dim_pad,
                          int64_t row_begin, int64_t row_end, int64_t n_sample_tiles, int64_t nq, int64_t nq_pad,
-                         const SearchWorkspace& ws, hipStream_t stream) {
+                         const SearchWorkspace& ws, hipStream_t stream, FilterStageFn experiment) {
     if (mode != MODE_GMAX && row_end <= row_begin) return hipSuccess;
     if (mode == MODE_GMAX && n_sample_tiles <= 0) return hipSuccess;
-    const bool subset = ws.extra.row_label != nullptr;
-    if (filter_tile_is_persistent(tile) && mode == MODE_DENSE) tile = 1;  // nq_pad is a multiple of 256, which the 128-wide tile divides
-    if (tile == 14 && mode == MODE_FILTER)  // the 8-phase K loop (kernels_mips_8phase.hip): FILTER stages of batches with >= 2 query tiles
-        return launch_filter_8phase(store_dtype, 14, store, q_pad, dim_pad, row_begin, row_end, nq, nq_pad, ws, stream);
-    if (tile == 17 || tile == 18) {  // query tile resident in registers (experiment builds; shapes they do not take run the production 8-phase kernel)
-#ifdef VODHIP_EXPERIMENTS
-        if (tile == 17 && mode == MODE_FILTER && !subset && filter_qres_supports(dim_pad))
-            return launch_filter_qres(store_dtype, store, q_pad, dim_pad, row_begin, row_end, nq, nq_pad, ws, stream);
-        if (tile == 18 && mode == MODE_FILTER && !subset && filter_ksplit_supports(dim_pad))
-            return launch_filter_ksplit(store_dtype, store, q_pad, dim_pad, row_begin, row_end, nq, nq_pad, ws, stream);
-#endif
-        if (mode == MODE_FILTER) return launch_filter_8phase(store_dtype, 14, store, q_pad, dim_pad, row_begin, row_end, nq, nq_pad, ws, stream);
-        tile = 8;
-    }
-    if (tile >= 10 && tile <= 16) {  // 10 - 13: experiment FILTER kernels, `make ABLATION=1 EXPERIMENTS=1` builds only (vodhip_index_set_param refuses the ids otherwise)
-#ifdef VODHIP_EXPERIMENTS
-        if (mode == MODE_FILTER && (tile == 13 || tile >= 15))  // 8-phase K loop variants: B0 re-read in phase 4 (13), LDS-DMA lead 6 / 5 (15 / 16)
-            return launch_filter_8phase(store_dtype, tile, store, q_pad, dim_pad, row_begin, row_end, nq, nq_pad, ws, stream);
-        if (mode == MODE_FILTER && tile == 12)  // 384 x 256 workgroup tile
-            return launch_filter_wide(store_dtype, store, q_pad, dim_pad, row_begin, row_end, nq, nq_pad, ws, stream);
-        if (mode == MODE_FILTER)  // deep ring (10), with fragments read a k-step ahead (11)
-            return launch_filter_ring(store_dtype, tile == 11, store, q_pad, dim_pad, row_begin, row_end, nq, nq_pad, ws, stream);
-#endif
-        tile = 8;  // the bootstrap (group maxima of a row sample) and dense chunks run on the two-slot kernel's family
-    }
-    const int bm = filter_tile_rows(tile);
+    if (experiment && mode == MODE_FILTER) return experiment(store_dtype, store, q_pad, dim_pad, row_begin, row_end, nq, nq_pad, ws, stream);
+    if (kernel == FilterKernel::EightPhase)  // FILTER stages only
+        return mode == MODE_FILTER ? launch_filter_8phase(store_dtype, 7, true, store, q_pad, dim_pad, row_begin, row_end, nq, nq_pad, ws, stream)
+                                   : hipErrorInvalidValue;
+    const int bm = geometry(kernel).rows;
     int n_xtiles = mode == MODE_GMAX ? (int)n_sample_tiles : (int)((row_end - row_begin + bm - 1) / bm);
     if (mode == MODE_FILTER && ws.extra.perm_mod > 0) {
         // permuted stage order: whole 256-row positions (the partly filled super-tile may sit at any of them), rows masked at ntotal
@@ -1245,7 +1224,8 @@ hipError_t launch_filter(int store_dtype, int tile, int mode, const void* store,
         row_end = ws.extra.row_bound;
     }
     FilterLaunch L{store, q_pad, dim_pad, row_begin, row_end, nq, nq_pad, n_xtiles, &ws, stream};
-    return store_dtype == 0 ? launch_filter_dt<0>(tile, mode, subset, L) : launch_filter_dt<1>(tile, mode, subset, L);
+    const bool subset = ws.extra.row_label != nullptr;
+    return store_dtype == 0 ? launch_filter_dt<0>(kernel, mode, subset, L) : launch_filter_dt<1>(kernel, mode, subset, L);
 }
 
 template <int KPT>

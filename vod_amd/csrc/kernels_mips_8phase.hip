@@ -1,6 +1,6 @@
 // libvodhip -- the FILTER stage on the guide's "256^2 8-phase" K loop (round 5).  Tile 14 = the production kernel of batches with two or
-// more query tiles (C3: -2.4 %, C4 shard: -4.0 % against tile 8, profiles/r05_ab_8phase.txt); tile 13 = the guide's read schedule
-// (B0 fragments re-read in phase 4), experiment builds only.
+// more query tiles (C3: -2.4 %, C4 shard: -4.0 % against tile 8, profiles/r05_ab_8phase.txt); KEEPB0 = false is the guide's read
+// schedule (B0 fragments re-read in phase 4), experiment builds only.
 //
 // Same tile, wave layout (8 waves = 2 x 4 of 128 x 64), fragment maps (v_mfma_f32_16x16x32), epilogue, survivor lists and stage
 // order as the persistent kernel of kernels_mips.hip; the K loop is rebuilt after /opt/skills/guides/cdna_hip_programming.md
@@ -48,7 +48,7 @@ static_assert(P8_LDS <= 160 * 1024, "LDS budget");
 }  // namespace
 
 // KEEPB0 (tile 14): the B0 fragments stay in registers from phase qd 0 to qd 3 (16 more VGPRs, 4 fewer ds_read_b128 per K-tile)
-// LEAD = half-tiles the LDS-DMA stream runs ahead of the phase that issues it (7 = the guide's; 6 / 5: experiment builds, tiles 15 / 16)
+// LEAD = half-tiles the LDS-DMA stream runs ahead of the phase that issues it (7 = the guide's; 6 / 5: experiment builds)
 template <int DT, bool SUBSET, bool KEEPB0, int LEAD = 7>
 __global__ __launch_bounds__(512, 2) void mips_filter8ph_kernel(
     const uint16_t* __restrict__ X, const uint16_t* __restrict__ Q, int dim_pad, int row_begin, int row_end, int n_xtiles,
@@ -541,8 +541,8 @@ __global__ __launch_bounds__(512, 2) void mips_filter8ph_kernel(
     wl_flush();
 }
 
-template <int DT, bool KEEPB0, int LEAD = 7>
-static hipError_t launch_8phase_dt(const void* store, const void* q_pad, int64_t dim_pad, int64_t row_begin, int64_t row_end, int n_xtiles,
+template <bool KEEPB0, int LEAD = 7>
+static hipError_t launch_8phase(int store_dtype, const void* store, const void* q_pad, int64_t dim_pad, int64_t row_begin, int64_t row_end, int n_xtiles,
                                    int64_t nq, int64_t nq_pad, const SearchWorkspace& ws, hipStream_t stream) {
     const bool subset = ws.extra.row_label != nullptr;
     const int n_qtiles = (int)(nq_pad / 256);
@@ -559,29 +559,26 @@ static hipError_t launch_8phase_dt(const void* store, const void* q_pad, int64_t
                            ws.overflow, ws.extra);
         return hipGetLastError();
     };
-    if constexpr (LEAD != 7) return launch(mips_filter8ph_kernel<DT, false, KEEPB0, LEAD>);  // (experiment builds: no subset instantiation)
-    else return subset ? launch(mips_filter8ph_kernel<DT, true, KEEPB0>) : launch(mips_filter8ph_kernel<DT, false, KEEPB0>);
+    if constexpr (LEAD != 7)  // (experiment builds: no subset instantiation)
+        return store_dtype == 0 ? launch(mips_filter8ph_kernel<0, false, KEEPB0, LEAD>) : launch(mips_filter8ph_kernel<1, false, KEEPB0, LEAD>);
+    else if (subset) return store_dtype == 0 ? launch(mips_filter8ph_kernel<0, true, KEEPB0>) : launch(mips_filter8ph_kernel<1, true, KEEPB0>);
+    else return store_dtype == 0 ? launch(mips_filter8ph_kernel<0, false, KEEPB0>) : launch(mips_filter8ph_kernel<1, false, KEEPB0>);
 }
 
-hipError_t launch_filter_8phase(int store_dtype, int variant, const void* store, const void* q_pad, int64_t dim_pad, int64_t row_begin, int64_t row_end,
-                                int64_t nq, int64_t nq_pad, const SearchWorkspace& ws, hipStream_t stream) {
+hipError_t launch_filter_8phase(int store_dtype, int lead, bool keep_b0, const void* store, const void* q_pad, int64_t dim_pad, int64_t row_begin,
+                                int64_t row_end, int64_t nq, int64_t nq_pad, const SearchWorkspace& ws, hipStream_t stream) {
+    constexpr FilterGeometry G = geometry(FilterKernel::EightPhase);
+    static_assert(G.rows == 256 && G.cols == 256 && G.persistent, "the planner's geometry of mips_filter8ph_kernel");
     int n_xtiles = (int)((row_end - row_begin + 255) / 256);
     if (ws.extra.perm_mod > 0) row_end = ws.extra.row_bound;  // permuted stage order: whole positions, rows masked at ntotal
-    const bool keep_b0 = variant != 13;
 #ifdef VODHIP_EXPERIMENTS
-    if (variant == 15)
-        return store_dtype == 0 ? launch_8phase_dt<0, true, 6>(store, q_pad, dim_pad, row_begin, row_end, n_xtiles, nq, nq_pad, ws, stream)
-                                : launch_8phase_dt<1, true, 6>(store, q_pad, dim_pad, row_begin, row_end, n_xtiles, nq, nq_pad, ws, stream);
-    if (variant == 16)
-        return store_dtype == 0 ? launch_8phase_dt<0, true, 5>(store, q_pad, dim_pad, row_begin, row_end, n_xtiles, nq, nq_pad, ws, stream)
-                                : launch_8phase_dt<1, true, 5>(store, q_pad, dim_pad, row_begin, row_end, n_xtiles, nq, nq_pad, ws, stream);
-    if (!keep_b0)
-        return store_dtype == 0 ? launch_8phase_dt<0, false>(store, q_pad, dim_pad, row_begin, row_end, n_xtiles, nq, nq_pad, ws, stream)
-                                : launch_8phase_dt<1, false>(store, q_pad, dim_pad, row_begin, row_end, n_xtiles, nq, nq_pad, ws, stream);
+    if (lead == 6) return launch_8phase<true, 6>(store_dtype, store, q_pad, dim_pad, row_begin, row_end, n_xtiles, nq, nq_pad, ws, stream);
+    if (lead == 5) return launch_8phase<true, 5>(store_dtype, store, q_pad, dim_pad, row_begin, row_end, n_xtiles, nq, nq_pad, ws, stream);
+    if (!keep_b0) return launch_8phase<false>(store_dtype, store, q_pad, dim_pad, row_begin, row_end, n_xtiles, nq, nq_pad, ws, stream);
 #endif
+    (void)lead;
     (void)keep_b0;
-    return store_dtype == 0 ? launch_8phase_dt<0, true>(store, q_pad, dim_pad, row_begin, row_end, n_xtiles, nq, nq_pad, ws, stream)
-                            : launch_8phase_dt<1, true>(store, q_pad, dim_pad, row_begin, row_end, n_xtiles, nq, nq_pad, ws, stream);
+    return launch_8phase<true>(store_dtype, store, q_pad, dim_pad, row_begin, row_end, n_xtiles, nq, nq_pad, ws, stream);
 }
 
 }  // namespace vodhip

@@ -14,6 +14,7 @@
 #include <thread>
 #include <vector>
 
+#include "search_plan.h"
 #include "vodhip_internal.h"
 
 using namespace vodhip;
@@ -49,10 +50,6 @@ namespace {
         }                                                                                       \
     } while (0)
 
-inline int64_t round_up(int64_t v, int64_t m) { return (v + m - 1) / m * m; }
-
-constexpr int64_t ROW_ALIGN = 256;       // largest tile height; chunk boundaries and capacity padding
-constexpr int64_t MAX_NQ_PER_PASS = 2048;
 constexpr int64_t STAGE_BYTES = 64ll << 20;
 
 struct PendingSearch {
@@ -132,16 +129,9 @@ struct vodhip_index {
     int unfinished = 0;                     // searches popped by a vodhip_index_search_finish that is still waiting for their event
     int next_slot = 0;
     // tunables
-    int64_t cand_cap = 16384;
-    int64_t dense_rows = 2048;   // indexes up to this many rows are scored densely in one launch
-    int64_t growth_x100 = 0;     // FILTER stage = growth x the rows its threshold was calibrated on; 0 = auto (8; 3 for batches above 512 queries on stores of 4 M rows and more)
-    int64_t sample_div = 0;      // GMAX bootstrap scores ~ ntotal / sample_div sampled rows; 0 = auto (96; 192 where growth is 3)
+    PlanTunables tune;  // the planner's (n_cu: read once at create)
     int64_t force_safe = 0;
-    int64_t tile = 0;
     int64_t kflags = 0;
-    int64_t tile_order = 0;      // 0 = FILTER stages walk the store's super-tiles in a low-discrepancy order (default); 1 = in row order
-    int64_t small_chunk_tiles = 256;  // launches with fewer 256x256 tiles than this (less than one per CU) use the 128x128 kernel
-    int n_cu = 256;       // compute units of `device` (read once at create; the planner never touches the runtime)
     int64_t profile = 0;  // 1: bracket every filter launch with HIP events (bench / roofline accounting)
     // stats
     int64_t last_overflow = 0, last_chunks = 0, last_safe_reruns = 0, last_recovered_queries = 0;
@@ -199,161 +189,6 @@ int ensure_workspace(vodhip_index* ix, int lane, int64_t nq_pad, int64_t cap, in
     return 0;
 }
 
-// ---- stage schedule ------------------------------------------------------------------------------------------
-// A search is a list of stages, each one filter launch + one select launch:
-//   GMAX    threshold bootstrap.  S sampled rows (8-row groups spread evenly over the whole store) are scored and every
-//           lane writes the maximum of its group of 16 / 32 rows; the k-th largest group maximum is a lower bound of the
-//           k-th best score (k distinct rows reach it) however the rows are ordered.  Emits no candidates.
-//   FILTER  rows [b, e) filtered against the running threshold; survivors -> candidate lists -> running top-k.
-//           Stage i covers `growth` x the rows the threshold was calibrated on, so it emits ~ growth * k survivors per
-//           query for exchangeable row order, and never more than the GMAX bound allows (~ k * rows / S) for any order.
-//   DENSE   every score of <= cap rows becomes a candidate (indexes of a few thousand rows; the exhaustive fallback).
-enum : int { ST_FILTER = 0, ST_DENSE = 1, ST_GMAX = 2 };
-struct Stage {
-    int kind;
-    int64_t b, e;        // rows (FILTER / DENSE)
-    int64_t n_tiles;     // sampled tiles (GMAX)
-    int64_t rstride;     // store rows between consecutive sampled rows (GMAX)
-    int64_t n_groups;    // lane groups of the sample = candidate slots per query (GMAX)
-};
-
-void make_safe_schedule(int64_t n, int64_t cap, std::vector<Stage>& st) {
-    const int64_t step = std::max<int64_t>(ROW_ALIGN, cap / ROW_ALIGN * ROW_ALIGN);
-    for (int64_t b = 0; b < n; b += step) st.push_back({ST_DENSE, b, std::min(n, b + step), 0, 0, 0});
-}
-
-// dense head of <= cap rows, then FILTER stages that grow by 1 + cap / 4k (each emits ~ (growth - 1) k survivors per query for
-// exchangeable row order): the schedule for searches that cannot use the bootstrap (subset filters; k too large for cap)
-void make_geometric_schedule(int64_t n, int k, int64_t cap, std::vector<Stage>& st) {
-    int64_t b = std::min(n, std::max<int64_t>(ROW_ALIGN, std::min<int64_t>(cap, 2048) / ROW_ALIGN * ROW_ALIGN));
-    if (b < k && b < n) return make_safe_schedule(n, cap, st);
-    st.push_back({ST_DENSE, 0, b, 0, 0, 0});
-    const double growth = std::min(8.0, std::max(1.25, 1.0 + (double)cap / (4.0 * k)));
-    while (b < n) {
-        const int64_t e = std::min(n, round_up(std::max((int64_t)((double)b * growth), b + ROW_ALIGN), ROW_ALIGN));
-        st.push_back({ST_FILTER, b, e, 0, 0, 0});
-        b = e;
-    }
-}
-
-// The multiplier of the low-discrepancy stage order over T super-tiles: position p -> super-tile (p * P) mod T with P the largest
-// integer <= T / golden ratio that is coprime to T (a bijection of [0, T); consecutive positions land ~0.618 T apart, so any run of L
-// positions leaves gaps of O(T / L) - three-distance theorem).  <= 1: no permutation.
-int64_t tile_order_multiplier(int64_t T) {
-    if (T < 8) return 0;
-    // Candidates around T / golden ratio; among those coprime to T the one whose continued fraction P / T has the smallest largest
-    // partial quotient: a run of L consecutive multiples of P (mod T) then leaves gaps within a small factor of T / L at EVERY scale L
-    // (three-distance theorem; a candidate that merely is coprime can sit next to a fraction with a small denominator and leave gaps
-    // 12x the mean - seen at T = 99,684).
-    const int64_t P0 = (int64_t)((double)T * 0.6180339887498949);
-    int64_t best = 0, best_q = INT64_MAX;
-    for (int64_t d = 0; d <= 64; ++d) {
-        for (int sgn = 0; sgn < 2; ++sgn) {
-            const int64_t P = sgn ? P0 - d : P0 + d;
-            if (P <= 1 || P >= T || (d == 0 && sgn)) continue;
-            int64_t a = T, b = P, worst = 0;
-            bool first = true;
-            while (b) {  // Euclid: the partial quotients of T / P
-                const int64_t quo = a / b, rem = a % b;
-                if (!first) worst = std::max(worst, quo);  // (the first is floor(T / P) = 1 by construction)
-                first = false;
-                a = b;
-                b = rem;
-            }
-            if (a != 1) continue;  // not coprime
-            if (worst < best_q) {
-                best_q = worst;
-                best = P;
-            }
-        }
-    }
-    return best;
-}
-
-// `recovery` > 0: pass number after a candidate-list overflow - no bootstrap (the thresholds are seeded from the previous
-// result), 2^(recovery-1) equal FILTER stages, and the exhaustive schedule once a stage would be <= cap rows.
-void make_schedule(const vodhip_index* ix, int k, int gmax_tile, int64_t nq_pad, bool safe, int recovery, std::vector<Stage>& st) {
-    st.clear();
-    const int64_t n = ix->ntotal, cap = ix->cand_cap;
-    if (n <= 0) return;
-    int64_t dense_limit = std::max(ix->dense_rows, round_up(k, ROW_ALIGN));
-    dense_limit = std::min(dense_limit, cap / ROW_ALIGN * ROW_ALIGN);
-    if (safe || n <= dense_limit) return make_safe_schedule(n, cap, st);
-    if (recovery > 0) {
-        const int64_t n_st = 1ll << std::min(recovery - 1, 30);
-        const int64_t rows = round_up((n + n_st - 1) / n_st, ROW_ALIGN);
-        if (rows <= cap) return make_safe_schedule(n, cap, st);
-        for (int64_t b = 0; b < n; b += rows) st.push_back({ST_FILTER, b, std::min(n, b + rows), 0, 0, 0});
-        return;
-    }
-    const int64_t bm = filter_tile_rows(gmax_tile), rg = filter_group_rows(gmax_tile);
-    // 4k groups wanted, 2k needed: the k-th largest of G group maxima is exceeded by a fraction -ln(1 - k/G) / rg of the rows,
-    // ~1.15 k/S at G = 4k, 1.39 k/S at G = 2k (the stage-size bound below allows 1.6 k/S), and it blows up as G approaches k
-    int64_t kp = 64;
-    while (kp < k) kp <<= 1;
-    // one candidate slot per group, and the select kernel takes the group maxima in ONE round of its largest buffer
-    const int64_t g_max = std::min<int64_t>(cap, 8192 - kp);
-    const int64_t s_max = std::min(rg * g_max, n / 2) / bm * bm;
-    const int64_t s_need = round_up(std::max<int64_t>(2 * rg * (int64_t)k, 2048), bm);
-    if (s_max < s_need) {  // no usable bootstrap (few rows, or k too large for cap): all dense when that is a few launches
-        if (n <= 64 * cap) return make_safe_schedule(n, cap, st);
-        return make_geometric_schedule(n, k, cap, st);
-    }
-    const int64_t s_min = std::min(s_max, round_up(std::max<int64_t>(4 * rg * (int64_t)k, 2048), bm));
-    // Round 6: the survivor path of the FILTER epilogue is 7-10 % of a C3 batch (kernels_mips_8phase.hip), and a stage lets ~ growth * k
-    // rows per query pass: on a large store searched with a large batch, more and smaller stages behind a smaller bootstrap pay (10 M x
-    // 768, nq 1024: growth 3 + N / 192 = 6 launches against growth 8 + N / 96 = 4: -2.0 %, exact-f32 -2.1 %, clustered rows -1.9 %).  At
-    // 512 queries and fewer (half the survivors per corpus tile) and on small stores a stage's own cost - a select launch, a partial round
-    // of the persistent grid - weighs as much: measured +-0.4 % (5 M / 40 M x 1024 at nq 512, 10 M at nq 256, 1.25 M), the round-3 rule
-    // stays there (profiles/r06_ab_epilogue.txt).
-    const bool many_small_stages = n >= 4000000 && nq_pad > 512;
-    const int64_t sdiv = ix->sample_div > 0 ? ix->sample_div : (many_small_stages ? 192 : 96);
-    int64_t s = std::min(s_max, std::max(s_min, round_up(n / std::max<int64_t>(sdiv, 2), bm)));
-    int64_t round_rows = ROW_ALIGN;  // corpus rows ONE round of the persistent grid covers (one 256 x 256 tile per CU)
-    if (filter_tile_is_persistent(gmax_tile)) {
-        round_rows = std::max<int64_t>(1, std::max(1, ix->n_cu) / std::max<int64_t>(1, nq_pad / 256)) * bm;
-        // the persistent kernel runs one workgroup per CU: a bootstrap of r.x "rounds" of tiles costs as much as r+1 full ones.
-        // Whole rounds only: down when that keeps >= 4k groups (a cheaper bootstrap), up otherwise (a tighter bound for free)
-        const int64_t n_cu = std::max(1, ix->n_cu);
-        const int64_t per_round = std::max<int64_t>(1, n_cu / std::max<int64_t>(1, nq_pad / 256)) * bm;  // sampled rows per round
-        const int64_t down = s / per_round * per_round, up = round_up(s, per_round);
-        if (down >= s_min) s = down;
-        else if (up <= s_max) s = up;
-    }
-    // S sampled rows at stride (n-1)/(S-1): the last one is row (S-1)*rstride <= n-1, all distinct (S <= n/2)
-    st.push_back({ST_GMAX, 0, 0, s / bm, (n - 1) / (s - 1), s / rg});
-    // however the rows are ordered, rows [b, e) hold about k * (e - b) / S scores above the bootstrap bound (the sample is
-    // stratified over the whole store): a stage never covers more rows than the candidate lists can take with 60 % headroom
-    const int64_t rows_safe = std::max<int64_t>(ROW_ALIGN, (int64_t)((double)cap * (double)s / (1.6 * (double)k)) / ROW_ALIGN * ROW_ALIGN);
-    const size_t n_head = st.size();
-    auto plan = [&](double growth) {
-        st.resize(n_head);
-        int64_t b = 0, calibrated = s;
-        while (b < n) {
-            int64_t rows = std::min(rows_safe, round_up((int64_t)((double)calibrated * growth), ROW_ALIGN));
-            // stages held down by the capacity bound share what is left evenly (40 M x 1024 at growth 3: 3 x 10.06 M + a 0.38 M tail otherwise)
-            if (rows == rows_safe && n - b > rows) {
-                const int64_t m = (n - b + rows_safe - 1) / rows_safe;
-                rows = std::min(rows_safe, round_up((n - b + m - 1) / m, ROW_ALIGN));
-            }
-            // whole rounds of the persistent grid: a stage of r.x rounds costs r + 1 (its last round runs on a fraction of the CUs), so
-            // only the LAST stage of a search may end inside a round (round 4; the capacity bound rows_safe only ever rounds DOWN)
-            if (rows > round_rows) rows = rows / round_rows * round_rows;
-            int64_t e = std::min(n, b + rows);
-            if (n - e < rows / 4 && n - b <= rows_safe) e = n;  // no short tail stage
-            st.push_back({ST_FILTER, b, e, 0, 0, 0});
-            b = e;
-            calibrated = e;
-        }
-    };
-    plan(std::min(256.0, std::max(1.25, ix->growth_x100 > 0 ? ix->growth_x100 / 100.0 : (many_small_stages ? 3.0 : 8.0))));
-    // A store of ~10-20 sample sizes comes out as a short first stage followed by ONE stage with all the rest (the 1.25 M-row shard
-    // of the headline: 131 k + 1,119 k rows).  Three stages at growth 4 (65 k + 327 k + 858 k) measure 1.3 % faster there, six out of
-    // six interleaved runs (profiles/r03_ab_growth.txt); stores that already get three or more stages are unaffected (10 M rows: growth
-    // 4 is 0.5 % slower than 8, so the default stays).
-    if (ix->growth_x100 <= 0 && st.size() == n_head + 2 && (st[n_head + 1].e - st[n_head + 1].b) > 6 * (st[n_head].e - st[n_head].b)) plan(4.0);
-}
-
 // exact mode: the statistics of the error bound as the re-scoring launches take them (host copies: refresh_exact_stats)
 void exact_bound_args(const vodhip_index* ix, ExactArgs& xa) {
     xa.ord_n2 = ix->ord_n2;
@@ -386,77 +221,90 @@ int refresh_exact_stats(vodhip_index* ix, hipStream_t stream) {
     return 0;
 }
 
+// one stage's filter launch on a pass of nq queries, bracketed by profile events (bench / roofline accounting)
+int launch_stage(vodhip_index* ix, SearchWorkspace& W, const SearchPlan& plan, const Stage& sg, int64_t nq, int64_t nq_pad,
+                 FilterStageFn experiment, hipStream_t stream) {
+    hipEvent_t ev1 = nullptr;
+    if (ix->profile) {
+        while (ix->ev_pool.size() < ix->ev_used + 2) {
+            hipEvent_t ev;
+            HIP_OK(hipEventCreate(&ev));
+            ix->ev_pool.push_back(ev);
+        }
+        hipEvent_t ev0 = ix->ev_pool[ix->ev_used++];
+        ev1 = ix->ev_pool[ix->ev_used++];
+        HIP_OK(hipEventRecord(ev0, stream));
+    }
+    W.extra.sample_rstride = (int)sg.rstride;
+    W.extra.sample_offset = (int)sg.sample_offset;
+    W.extra.sample_groups = (int)sg.n_groups;
+    HIP_OK(launch_filter(ix->dtype, plan.kernel(sg, nq_pad), sg.kind, ix->data, W.q_pad, ix->dim_pad, sg.b, sg.e, sg.n_tiles, nq, nq_pad, W,
+                         stream, experiment));
+    if (ix->profile) HIP_OK(hipEventRecord(ev1, stream));
+    return 0;
+}
+
+// exact mode (a BAND pass): the re-scoring of stage `sg`'s candidates from the float32 plane into the caller's rows [row0, row0 + nq)
+ExactArgs exact_stage_args(const vodhip_index* ix, const PendingSearch& ps, const SearchWorkspace& ws, int64_t row0, const Stage& sg, bool first) {
+    ExactArgs xa;
+    xa.plane = ix->data32;
+    xa.stride = ix->dim_pad;
+    xa.dim = (int)ix->dim;
+    xa.dim_pad = (int)ix->dim_pad;
+    xa.q_src = (const char*)ps.queries + (size_t)row0 * ix->dim * elem_size(ps.q_dtype);
+    xa.q_dtype = ps.q_dtype;
+    xa.q_map = ws.extra.q_map;
+    xa.store_dtype = ix->dtype;
+    exact_bound_args(ix, xa);
+    xa.row_label = ws.extra.row_label;
+    xa.q_label = ws.extra.q_label;
+    xa.n_qlab = ws.extra.n_qlab;
+    xa.mode = EXACT_CAND | (first ? EXACT_FIRST : 0);
+    xa.cand = ws.cand;
+    xa.cnt = ws.cnt;
+    xa.cap = (int)ws.cap;
+    xa.dense_n = sg.kind == ST_DENSE ? (int)(sg.e - sg.b) : -1;
+    xa.thr_s = ws.thr_s;
+    xa.thr_key = ws.thr_key;
+    xa.kr = 2;
+    while (xa.kr < ps.k) xa.kr <<= 1;
+    xa.P = std::max(2 * xa.kr, 1024);
+    xa.k = ps.k;
+    xa.id_base = ps.id_base;
+    xa.out_scores = ps.out_scores + row0 * ps.k;
+    xa.out_ids = ps.out_ids + row0 * ps.k;
+    xa.flag_word = ws.overflow;
+    return xa;
+}
+
 int enqueue_search_impl(vodhip_index* ix, const PendingSearch& ps, bool safe, int recovery, hipStream_t stream) {
     SearchWorkspace& W = ix->ws_lane[ps.lane];  // this search's lane
     const int k = ps.k;
     int64_t kp = 64;
     while (kp < k) kp <<= 1;
-    const int64_t cap = ix->cand_cap;
+    const int64_t cap = ix->tune.cand_cap;
     if (cap / ROW_ALIGN * ROW_ALIGN < k) return fail("cand_cap=%lld is too small for k=%d", (long long)cap, k);
 
-    int tile = (int)ix->tile;
-    // auto: up to 128 queries the search is HBM-bound: 256 corpus rows x 64 / 128 queries per workgroup on a 3-slot LDS
-    // ring (few query bytes per corpus byte through the LDS-DMA path); above, the persistent 256x256 tile on
-    // v_mfma_f32_16x16x32 (8; variant 9 staggers the two waves of every SIMD by one k-step: measured equal or 1-2 % slower)
-    if (tile == 0) tile = ps.nq > 128 ? 8 : (ps.nq > 64 ? 46 : 42);
-    // ... and the FILTER stages of those batches run the 8-phase K loop (tile 14: C3 -2.4 %, C4 shard -4.0 %; with ONE query tile and the
-    // corpus stream on the `nt` policy C2 -3.5 %, nq 256 on 10 M rows -2.7 %: profiles/r05_ab_8phase.txt, r05_ab_one_query_tile.txt); its
-    // subset instantiation spilled through round 6a and is 4-5 % slower than tile 8 on filtered searches since it no longer does (2.5 M x
-    // 768, a quarter of the rows eligible: 3.95-3.99 vs 3.78-3.80 ms, experiments/tools/probe_subset_tile.py): they stay on tile 8, as does
-    // the bootstrap
-    const bool auto_8phase = ix->tile == 0 && ps.nq > 128 && !(ix->row_label && ps.q_label);
-    const bool persistent = filter_tile_is_persistent(tile);
-    const int64_t bn = filter_tile_cols(tile);
-
-    // The bootstrap of a SMALL store (C2, a 1.25 M-row shard) samples fewer 256-row tiles than the chip has CUs: on the persistent
-    // kernel ~40-200 workgroups would each run one whole 256 x 256 x dim tile (a ~25 us latency chain) while the other CUs idle.
-    // Those bootstraps run on the 128 x 128 kernel instead (4x the workgroups, a quarter of the chain each; 16-row groups).
-    std::vector<Stage> stages;
-    make_schedule(ix, k, tile, round_up(std::min(MAX_NQ_PER_PASS, ps.nq), bn), safe, recovery, stages);
-    ix->last_chunks = (int64_t)stages.size();
+    // the subset labels in force when THIS search was enqueued (a recovery pass may run after younger searches changed them)
+    const int* row_label = (ix->row_label && ps.q_label) ? ix->row_label : nullptr;
+    PlanTunables tune = ix->tune;
+    const FilterStageFn experiment = experiment_filter(tune);
+    const SearchPlan plan = plan_search(ix->ntotal, k, ps.nq, tune, row_label != nullptr, safe, recovery);
+    ix->last_chunks = (int64_t)plan.stages.size();
 
     const int q_es = elem_size(ps.q_dtype);
     if (ensure_workspace(ix, ps.lane, round_up(std::min(MAX_NQ_PER_PASS, ps.nq), 256), cap, kp)) return -1;
-    W.extra.flags = (int)ix->kflags << 8;  // timing knobs of diagnostic builds (ignored by production kernels)
-    // ONE q-tile: every corpus line is read by exactly one workgroup, once - fetch it with the `nt` policy so it does not
-    // push the query tile out of L2 (measured -2 % at nq = 256 on 10 M rows; +8 % with 4 q-tiles sharing the lines, so only here)
-    if (persistent && round_up(std::min(MAX_NQ_PER_PASS, ps.nq), bn) == 256) W.extra.flags |= FILTER_FLAG_CORPUS_NT;
-    // the subset labels in force when THIS search was enqueued (a recovery pass may run after younger searches changed them)
-    W.extra.row_label = (ix->row_label && ps.q_label) ? ix->row_label : nullptr;
+    W.extra.flags = ((int)ix->kflags << 8) | (plan.corpus_nt ? FILTER_FLAG_CORPUS_NT : 0);  // (the knobs: diagnostic builds only)
+    W.extra.row_label = row_label;
     W.extra.n_qlab = ps.n_qlab;
-    const bool track_ovf = ps.nq <= OVF_ROWS;  // per-query overflow flags of this search's slot
-    const bool subset = W.extra.row_label != nullptr;
-    if (subset && !safe && recovery == 0) {
-        // group maxima would include ineligible rows: a subset search runs the exhaustive-free geometric schedule instead
-        // (dense head of <= cap rows, then FILTER stages growing by `growth`)
-        stages.clear();
-        make_geometric_schedule(ix->ntotal, k, cap, stages);
-        ix->last_chunks = (int64_t)stages.size();
-    }
-    // The order in which the FILTER stages walk the store's 256-row super-tiles: a low-discrepancy permutation (position p ->
-    // super-tile p * P mod T, P ~ 0.618 T coprime to T), so that every stage - any run of consecutive positions - is spread evenly
-    // over the whole store.  The reference ingests documents in corpus order (build.py:65-73): with contiguous stages a topic that
-    // only the LAST stage contains meets a threshold calibrated without it, and all its tiles are scanned at the same moment
-    // (bench.py --data clustered: 1.22x the i.i.d. time, L2-miss traffic 1.9x).  Only when every stage after the bootstrap is a FILTER
-    // stage (they must tile the store together); results do not depend on the order.
-    W.extra.perm_mul = W.extra.perm_mod = 0;
+    W.extra.perm_mul = (int)plan.perm_mul;
+    W.extra.perm_mod = (int)plan.perm_mod;
     W.extra.row_bound = (int)ix->ntotal;
-    {
-        bool all_filter = !stages.empty();
-        for (const Stage& sg : stages) all_filter = all_filter && (sg.kind == ST_FILTER || sg.kind == ST_GMAX);
-        const int64_t T = (ix->ntotal + ROW_ALIGN - 1) / ROW_ALIGN;
-        if (all_filter && ix->tile_order == 0 && T >= 8 && !(tile >= 10 && tile <= 12)) {
-            const int64_t P = tile_order_multiplier(T);
-            if (P > 1) {
-                W.extra.perm_mul = (int)P;
-                W.extra.perm_mod = (int)T;
-            }
-        }
-    }
+    const bool track_ovf = ps.nq <= OVF_ROWS;  // per-query overflow flags of this search's slot
     const SearchWorkspace& ws = W;
     for (int64_t qb = 0; qb < ps.nq; qb += MAX_NQ_PER_PASS) {
         const int64_t nq = std::min(MAX_NQ_PER_PASS, ps.nq - qb);
-        const int64_t nq_pad = round_up(nq, bn);
+        const int64_t nq_pad = round_up(nq, plan.bn);
         // one launch: queries -> store dtype with zero padded rows / columns, running top-k and counters cleared,
         // thresholds -inf (or seeded from the previous result in a recovery pass), overflow word cleared at the first pass
         // with a query map (recovery of a few queries) workspace row r is row q_map[qb + r] of the caller's arrays
@@ -469,83 +317,23 @@ int enqueue_search_impl(vodhip_index* ix, const PendingSearch& ps, bool safe, in
                                      recovery > 0 ? ps.out_ids + row0 * k : nullptr, k, q_map, stream, margin));
         W.extra.q_label = ps.q_label ? ps.q_label + (size_t)row0 * ps.n_qlab : nullptr;
         W.extra.q_map = q_map;
-        for (size_t c = 0; c < stages.size(); ++c) {
-            const Stage& sg = stages[c];
-            // one filter launch, bracketed by profile events (bench / roofline accounting)
-            auto launch_one = [&](int tile_c, int64_t b, int64_t e) -> int {
-                hipEvent_t ev1 = nullptr;
-                if (ix->profile) {
-                    while (ix->ev_pool.size() < ix->ev_used + 2) {
-                        hipEvent_t ev;
-                        HIP_OK(hipEventCreate(&ev));
-                        ix->ev_pool.push_back(ev);
-                    }
-                    hipEvent_t ev0 = ix->ev_pool[ix->ev_used++];
-                    ev1 = ix->ev_pool[ix->ev_used++];
-                    HIP_OK(hipEventRecord(ev0, stream));
-                }
-                W.extra.sample_rstride = (int)sg.rstride;
-                // S sampled rows at offset + i * rstride, i < S: the (ntotal - 1) % rstride-ish rows the integer stride leaves out
-                // are split between the head and the tail of the store
-                W.extra.sample_offset = sg.kind == ST_GMAX ? (int)(((ix->ntotal - 1) - (sg.n_tiles * filter_tile_rows(tile_c) - 1) * sg.rstride) / 2) : 0;
-                W.extra.sample_groups = (int)sg.n_groups;
-                HIP_OK(launch_filter(ix->dtype, tile_c, sg.kind, ix->data, ws.q_pad, ix->dim_pad, b, e, sg.n_tiles, nq, nq_pad, ws, stream));
-                if (ix->profile) HIP_OK(hipEventRecord(ev1, stream));
-                return 0;
-            };
-            const bool last = c + 1 == stages.size();
-            int tile_c = (auto_8phase && sg.kind == ST_FILTER) ? 14 : tile;
-            if (persistent && ix->tile == 0 && sg.kind == ST_FILTER) {  // (nq_pad is a multiple of 256 there, which the 128-wide tile divides)
-                const int64_t q_tiles = nq_pad / 256;
-                const int64_t x_tiles = (sg.e - sg.b + 255) / 256;
-                // short FILTER stages do not fill the CUs with 256x256 tiles: those launches run on 128x128 tiles, 2 workgroups per CU
-                if (x_tiles * q_tiles < ix->small_chunk_tiles) {
-                    tile_c = 1;
-                }
+        for (size_t c = 0; c < plan.stages.size(); ++c) {
+            const Stage& sg = plan.stages[c];
+            if (launch_stage(ix, W, plan, sg, nq, nq_pad, experiment, stream)) return -1;
+            if (ps.band) {
+                HIP_OK(launch_exact_rescore(exact_stage_args(ix, ps, ws, row0, sg, c == 0), nq, stream));
+                continue;
             }
-            if (launch_one(tile_c, sg.b, sg.e)) return -1;
             int64_t dense_n = -1;
-            int flags = last ? 1 : 0;
+            int flags = c + 1 == plan.stages.size() ? 1 : 0;
             if (sg.kind == ST_DENSE) dense_n = sg.e - sg.b;
             if (sg.kind == ST_GMAX) {
                 dense_n = sg.n_groups;
                 flags |= 2;
             }
-            if (ps.band) {  // exact mode: the stage's candidates are re-scored from the float32 plane into the caller's rows
-                ExactArgs xa;
-                xa.plane = ix->data32;
-                xa.stride = ix->dim_pad;
-                xa.dim = (int)ix->dim;
-                xa.dim_pad = (int)ix->dim_pad;
-                xa.q_src = (const char*)ps.queries + (size_t)row0 * ix->dim * q_es;
-                xa.q_dtype = ps.q_dtype;
-                xa.q_map = q_map;
-                xa.store_dtype = ix->dtype;
-                exact_bound_args(ix, xa);
-                xa.row_label = W.extra.row_label;
-                xa.q_label = W.extra.q_label;
-                xa.n_qlab = W.extra.n_qlab;
-                xa.mode = EXACT_CAND | (c == 0 ? EXACT_FIRST : 0);
-                xa.cand = ws.cand;
-                xa.cnt = ws.cnt;
-                xa.cap = (int)ws.cap;
-                xa.dense_n = sg.kind == ST_DENSE ? (int)(sg.e - sg.b) : -1;
-                xa.thr_s = ws.thr_s;
-                xa.thr_key = ws.thr_key;
-                xa.kr = 2;
-                while (xa.kr < k) xa.kr <<= 1;
-                xa.P = std::max(2 * xa.kr, 1024);
-                xa.k = k;
-                xa.id_base = ps.id_base;
-                xa.out_scores = ps.out_scores + row0 * k;
-                xa.out_ids = ps.out_ids + row0 * k;
-                xa.flag_word = ws.overflow;
-                HIP_OK(launch_exact_rescore(xa, nq, stream));
-                continue;
-            }
             HIP_OK(launch_select(ws, nq, k, dense_n, flags, stream, ps.id_base, ps.out_scores + row0 * k, ps.out_ids + row0 * k, q_map));
         }
-        if (stages.empty())  // empty index: nothing was selected, the cleared top-k leaves as pads
+        if (plan.stages.empty())  // empty index: nothing was selected, the cleared top-k leaves as pads
             HIP_OK(launch_output(ws, nq, k, ps.id_base, ps.out_scores + qb * k, ps.out_ids + qb * k, stream));
     }
     if (ps.defer_flags) return 0;
@@ -570,7 +358,7 @@ int exact_kx(const vodhip_index* ix, int k, bool upper_limit = false) {
     // fp16 at dim 1024 / k 200 needs ~1.3 k, more than its 1.1 k + 16 starting point)
     const int64_t x100 = ix->exact_expand_x100 > 0 ? ix->exact_expand_x100 : ((ix->dtype == VODHIP_F16 && !upper_limit) ? 110 : 200);
     const int64_t kx = ((int64_t)k * x100 + 99) / 100 + 16;
-    const int64_t fits = std::max<int64_t>(k, ix->cand_cap / ROW_ALIGN * ROW_ALIGN);  // the scan needs cand_cap >= its list length
+    const int64_t fits = std::max<int64_t>(k, ix->tune.cand_cap / ROW_ALIGN * ROW_ALIGN);  // the scan needs cand_cap >= its list length
     return (int)std::min<int64_t>(std::min<int64_t>(VODHIP_MAX_K, fits), std::max<int64_t>(kx, k));
 }
 
@@ -657,8 +445,8 @@ int vodhip_index_create(int device, int64_t dim, int store_dtype, int64_t capaci
     ix->capacity_pad = round_up(capacity_rows, ROW_ALIGN) + 2 * ROW_ALIGN;  // the last tile (up to 384 rows from a 256-aligned start) never reads past the allocation
     ix->dtype = store_dtype;
     ix->exact = exact;
-    if (hipDeviceGetAttribute(&ix->n_cu, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess || ix->n_cu < 1) ix->n_cu = 256;
-    ix->ws_lane[0].n_cu = ix->ws_lane[1].n_cu = ix->n_cu;
+    if (hipDeviceGetAttribute(&ix->tune.n_cu, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess || ix->tune.n_cu < 1) ix->tune.n_cu = 256;
+    ix->ws_lane[0].n_cu = ix->ws_lane[1].n_cu = ix->tune.n_cu;
     const size_t bytes = (size_t)ix->capacity_pad * ix->dim_pad * 2;
     hipError_t e = hipMalloc((void**)&ix->data, bytes);
     if (e != hipSuccess) {
@@ -944,7 +732,7 @@ int vodhip_index_search_async(vodhip_index_t* ix, const void* queries, int q_dty
     if (nq < 0 || (nq > 0 && (!queries || !out_scores || !out_ids))) return fail("invalid query / output pointers");
     if (q_dtype < 0 || q_dtype > 2) return fail("invalid q_dtype %d", q_dtype);
     std::lock_guard<std::mutex> guard(ix->mu);
-    if (ix->cand_cap < ROW_ALIGN || ix->cand_cap < k) return fail("cand_cap too small");
+    if (ix->tune.cand_cap < ROW_ALIGN || ix->tune.cand_cap < k) return fail("cand_cap too small");
     if ((int)ix->inflight.size() + ix->unfinished >= MAX_IN_FLIGHT)
         return fail("%d searches are already in flight on this index: call vodhip_index_search_finish first", MAX_IN_FLIGHT);
     if (ix->exact && nq > OVF_ROWS) return fail("VODHIP_EXACT_F32: at most %lld queries per search", (long long)OVF_ROWS);
@@ -1157,26 +945,20 @@ int vodhip_index_search(vodhip_index_t* ix, const void* queries, int q_dtype, in
 
 int vodhip_debug_schedule(int64_t ntotal, int k, int64_t nq, int64_t cand_cap, int64_t dense_rows, int64_t sample_div,
                           int64_t growth_x100, int tile, int recovery_pass, int n_cu, int64_t* out, int max_stages) {
-    if (!out || max_stages < 1 || k < 1 || nq < 1 || ntotal < 0) return fail("invalid arguments");
-    vodhip_index tmp;  // host-side planning only: no device call uses it
-    tmp.ntotal = ntotal;
-    tmp.n_cu = n_cu > 0 ? n_cu : 256;
-    if (cand_cap > 0) tmp.cand_cap = cand_cap;
-    if (dense_rows > 0) tmp.dense_rows = round_up(dense_rows, ROW_ALIGN);
-    if (sample_div > 0) tmp.sample_div = sample_div;
-    tmp.growth_x100 = growth_x100;
-    if (tile == 0) tile = nq > 128 ? 8 : (nq > 64 ? 46 : 42);
-    std::vector<Stage> st;
-    make_schedule(&tmp, k, tile, round_up(std::min(MAX_NQ_PER_PASS, nq), filter_tile_cols(tile)), false, recovery_pass, st);
+    PlanTunables t;
+    if (cand_cap > 0) t.cand_cap = cand_cap;
+    if (dense_rows > 0) t.dense_rows = round_up(dense_rows, ROW_ALIGN);
+    if (sample_div > 0) t.sample_div = sample_div;
+    t.growth_x100 = growth_x100;
+    t.tile = tile;
+    if (n_cu > 0) t.n_cu = n_cu;
+    if (!out || max_stages < 1 || k < 1 || nq < 1 || ntotal < 0 || (tile != 0 && !find_kernel(tile) && !experiment_filter(t)))
+        return fail("invalid arguments");
+    const std::vector<Stage> st = plan_search(ntotal, k, nq, t, false, false, recovery_pass).stages;
     if ((int)st.size() > max_stages) return fail("%d stages do not fit max_stages=%d", (int)st.size(), max_stages);
     for (size_t i = 0; i < st.size(); ++i) {
-        int64_t* o = out + i * 6;
-        o[0] = st[i].kind;
-        o[1] = st[i].b;
-        o[2] = st[i].e;
-        o[3] = st[i].n_tiles;
-        o[4] = st[i].rstride;
-        o[5] = st[i].n_groups;
+        const int64_t row[6] = {st[i].kind, st[i].b, st[i].e, st[i].n_tiles, st[i].rstride, st[i].n_groups};
+        memcpy(out + i * 6, row, sizeof(row));
     }
     return (int)st.size();
 }
@@ -1192,21 +974,21 @@ int vodhip_index_set_param(vodhip_index_t* ix, const char* key, int64_t value) {
     if (!ix || !key) return fail("NULL argument");
     if (!strcmp(key, "cand_cap")) {
         if (value < ROW_ALIGN || value > (1 << 16)) return fail("cand_cap must be in [256, 65536]");
-        ix->cand_cap = value;
+        ix->tune.cand_cap = value;
     } else if (!strcmp(key, "dense_rows")) {
         if (value < ROW_ALIGN) return fail("dense_rows must be >= 256");
-        ix->dense_rows = round_up(value, ROW_ALIGN);
+        ix->tune.dense_rows = round_up(value, ROW_ALIGN);
     } else if (!strcmp(key, "growth")) {
-        ix->growth_x100 = value;  // growth factor * 100; 0 = derive from k
+        ix->tune.growth_x100 = value;  // growth factor * 100; 0 = derive from k
     } else if (!strcmp(key, "force_safe")) {
         ix->force_safe = value;
     } else if (!strcmp(key, "small_chunk_tiles")) {
-        ix->small_chunk_tiles = value;
+        ix->tune.small_chunk_tiles = value;
     } else if (!strcmp(key, "kflags")) {
         ix->kflags = value;
     } else if (!strcmp(key, "sample_div")) {
         if (value != 0 && value < 2) return fail("sample_div must be 0 (auto) or >= 2");
-        ix->sample_div = value;
+        ix->tune.sample_div = value;
     } else if (!strcmp(key, "profile")) {
         ix->profile = value;
     } else if (!strcmp(key, "ingest_threads")) {
@@ -1218,7 +1000,7 @@ int vodhip_index_set_param(vodhip_index_t* ix, const char* key, int64_t value) {
         ix->lanes = value;
     } else if (!strcmp(key, "tile_order")) {
         if (value != 0 && value != 1) return fail("tile_order must be 0 (low-discrepancy stage order) or 1 (row order)");
-        ix->tile_order = value;
+        ix->tune.tile_order = value;
     } else if (!strcmp(key, "exact_adapt")) {
         if (value < 0 || value > 1) return fail("exact_adapt must be 0 or 1");
         ix->exact_adapt = value;
@@ -1227,14 +1009,11 @@ int vodhip_index_set_param(vodhip_index_t* ix, const char* key, int64_t value) {
         if (value < 0 || value > 100000) return fail("exact_expand (x100) must be in [0, 100000]");
         ix->exact_expand_x100 = value;
     } else if (!strcmp(key, "tile")) {
-#ifdef VODHIP_EXPERIMENTS
-        const bool ring_ok = true;  // tiles 10 / 11 / 12: the FILTER kernels of experiment builds
-#else
-        const bool ring_ok = false;
-#endif
-        if (value != 0 && value != 1 && value != 8 && value != 9 && value != 14 && value != 42 && value != 46 && !(ring_ok && ((value >= 10 && value <= 13) || (value >= 15 && value <= 18))))
+        PlanTunables t;
+        t.tile = value;
+        if (value != 0 && !find_kernel(value) && !experiment_filter(t))
             return fail("tile must be 0 (auto) or a filter-kernel variant id: 1, 8, 9, 14, 42, 46 (DESIGN.md 4)");
-        ix->tile = value;
+        ix->tune.tile = value;
     } else {
         return fail("unknown parameter '%s'", key);
     }
@@ -1272,11 +1051,11 @@ int vodhip_index_get_stat(const vodhip_index_t* ix, const char* key, int64_t* ou
     else if (!strcmp(key, "last_exact_band_passes"))
         *out = ix->last_exact_band_passes;
     else if (!strcmp(key, "cand_cap"))
-        *out = ix->cand_cap;
+        *out = ix->tune.cand_cap;
     else if (!strcmp(key, "dense_rows"))
-        *out = ix->dense_rows;
+        *out = ix->tune.dense_rows;
     else if (!strcmp(key, "sample_div"))
-        *out = ix->sample_div;
+        *out = ix->tune.sample_div;
     else if (!strcmp(key, "dim_pad"))
         *out = ix->dim_pad;
     else if (!strcmp(key, "last_ingest_pinned_src"))

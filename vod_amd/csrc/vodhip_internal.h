@@ -3,6 +3,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "search_plan.h"
+
 // Diagnostic builds (`make ABLATION=1`): phase stamps of workgroup 0 of the collate-side kernels - shader-clock cycles
 // (s_memtime) and the constant 100 MHz counter (s_memrealtime) - read back with vodhip_debug_read_probe.  Nothing in production.
 #ifdef VODHIP_ABLATION
@@ -85,7 +87,7 @@ struct SearchWorkspace {
 };
 
 // ---- launchers (kernels_mips.hip) -------------------------------------------------------------
-// store_dtype: 0 = f16, 1 = bf16.  tile: filter-kernel variant (kernels_mips.hip: 1, 42, 46 generic; 8, 9 persistent).
+// store_dtype: 0 = f16, 1 = bf16.  kernel: the filter kernel (search_plan.h: the planner picks it per stage).
 // mode: 0 = FILTER (threshold survivors -> candidate lists), 1 = DENSE (every score of rows [row_begin, row_end) is a
 // candidate), 2 = GMAX (threshold bootstrap: group maxima of `n_sample_tiles` sampled tiles, see FilterExtra::sample_rstride).
 hipError_t launch_convert_rows(const void* src, int src_dtype, int64_t n_rows, int64_t dim, void* dst, int dst_dtype,
@@ -98,9 +100,6 @@ hipError_t launch_search_prepare(const SearchWorkspace& ws, const void* q_src, i
                                  int store_dtype, int64_t nq_pad, int64_t dim_pad, bool clear_overflow,
                                  const float* seed_scores, const int64_t* seed_ids, int k, const int* q_map, hipStream_t stream,
                                  const float* seed_margin = nullptr);
-hipError_t launch_filter(int store_dtype, int tile, int mode, const void* store, const void* q_pad, int64_t dim_pad,
-                         int64_t row_begin, int64_t row_end, int64_t n_sample_tiles, int64_t nq, int64_t nq_pad,
-                         const SearchWorkspace& ws, hipStream_t stream);
 // flags: 1 = final (sort; the top-k also leaves as float32 scores / int64 ids (+ id_base) in out_scores / out_ids [nq, k]),
 //        2 = threshold only (the candidates are GMAX group maxima: nothing enters the running top-k)
 //        q_map: result row r is written to row q_map[r] of out_scores / out_ids
@@ -110,29 +109,24 @@ hipError_t launch_output(const SearchWorkspace& ws, int64_t nq, int k, int64_t i
                          int64_t* out_ids, hipStream_t stream);
 hipError_t launch_merge_topk(const float* scores, const int64_t* ids, int64_t stride_s, int64_t stride_i, int n_shards,
                              int64_t nq, int k, int k_out, float* out_scores, int64_t* out_ids, hipStream_t stream);
-// the FILTER stage on the deeper LDS ring (kernels_mips_ring.hip; tiles 10 = plain, 11 = fragments read one k-step ahead)
-hipError_t launch_filter_ring(int store_dtype, bool pipe, const void* store, const void* q_pad, int64_t dim_pad, int64_t row_begin,
-                              int64_t row_end, int64_t nq, int64_t nq_pad, const SearchWorkspace& ws, hipStream_t stream);
-// the FILTER stage on the 384 x 256 workgroup tile (kernels_mips_wide.hip; tile 12)
-hipError_t launch_filter_wide(int store_dtype, const void* store, const void* q_pad, int64_t dim_pad, int64_t row_begin, int64_t row_end,
-                              int64_t nq, int64_t nq_pad, const SearchWorkspace& ws, hipStream_t stream);
 // hipFuncSetAttribute(MaxDynamicSharedMemorySize) once per (device, kernel): it is a driver call on the launch path
 hipError_t allow_dynamic_lds(const void* kernel, int bytes);
-// the FILTER stage on the guide's 8-phase K loop (experiments/csrc/kernels_mips_8phase.hip; tiles 13 / 14)
-hipError_t launch_filter_8phase(int store_dtype, int variant /* 14 = production; 13, 15, 16: experiment builds */, const void* store, const void* q_pad, int64_t dim_pad, int64_t row_begin, int64_t row_end,
-                                int64_t nq, int64_t nq_pad, const SearchWorkspace& ws, hipStream_t stream);
-// the FILTER stage with the query tile resident in registers (experiments/csrc/kernels_mips_qres.hip; tile 17; dim_pad 384 / 768 only)
-bool filter_qres_supports(int64_t dim_pad);
-hipError_t launch_filter_qres(int store_dtype, const void* store, const void* q_pad, int64_t dim_pad, int64_t row_begin, int64_t row_end,
-                              int64_t nq, int64_t nq_pad, const SearchWorkspace& ws, hipStream_t stream);
-// ... and with a K-split wave pair, two waves per SIMD (experiments/csrc/kernels_mips_ksplit.hip; tile 18; dim_pad 768 only)
-bool filter_ksplit_supports(int64_t dim_pad);
-hipError_t launch_filter_ksplit(int store_dtype, const void* store, const void* q_pad, int64_t dim_pad, int64_t row_begin, int64_t row_end,
-                                int64_t nq, int64_t nq_pad, const SearchWorkspace& ws, hipStream_t stream);
-inline bool filter_tile_is_persistent(int tile) { return tile >= 8 && tile <= 18; }  // one 256 x 256 workgroup per CU walking tiles
-int filter_tile_rows(int tile);  // BM of the tile config
-int filter_tile_cols(int tile);  // BN of the tile config
-int filter_group_rows(int tile); // rows per GMAX group (one lane's rows of one column block)
+// the FILTER stage on the guide's 8-phase K loop (kernels_mips_8phase.hip); lead / keep_b0 other than 7 / true: experiment builds only
+hipError_t launch_filter_8phase(int store_dtype, int lead, bool keep_b0, const void* store, const void* q_pad, int64_t dim_pad, int64_t row_begin,
+                                int64_t row_end, int64_t nq, int64_t nq_pad, const SearchWorkspace& ws, hipStream_t stream);
+// A FILTER stage on the kernel of an experiment id (experiment_filter).
+using FilterStageFn = hipError_t (*)(int store_dtype, const void* store, const void* q_pad, int64_t dim_pad, int64_t row_begin, int64_t row_end,
+                                     int64_t nq, int64_t nq_pad, const SearchWorkspace& ws, hipStream_t stream);
+// When t.tile is an experiment id: its FILTER kernel, and t becomes what the search plans with (the persistent kernel); else nullptr.
+#ifdef VODHIP_EXPERIMENTS
+FilterStageFn experiment_filter(PlanTunables& t);  // experiments/csrc/experiment_filter.hip
+#else
+inline FilterStageFn experiment_filter(PlanTunables&) { return nullptr; }
+#endif
+// experiment: the FILTER kernel of an experiment id (experiment_filter) that FILTER stages run instead of `kernel`, or nullptr
+hipError_t launch_filter(int store_dtype, FilterKernel kernel, int mode, const void* store, const void* q_pad, int64_t dim_pad,
+                         int64_t row_begin, int64_t row_end, int64_t n_sample_tiles, int64_t nq, int64_t nq_pad,
+                         const SearchWorkspace& ws, hipStream_t stream, FilterStageFn experiment = nullptr);
 
 // ---- launchers (kernels_exact.hip): the float32 plane of VODHIP_EXACT_F32 stores ----------------
 enum : int { EXACT_LIST = 0, EXACT_CAND = 1, EXACT_FIRST = 2 };
