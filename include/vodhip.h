@@ -145,14 +145,18 @@ int vodhip_index_set_query_labels(vodhip_index_t* index, const int32_t* q_labels
  *   every search on the caller's stream.  add / reset / set_row_labels refuse while searches are in flight),
  *   "exact_expand" (x100, VODHIP_EXACT_F32 stores: the scan lists k' = k * exact_expand / 100 + 16 rows per
  *   query; 0 = default: 110 for an fp16 store, 200 for bf16 as the upper limit, with k' following what the last searches of the same k
- *   needed ("exact_adapt" = 1, default; 0 = always the formula); speed only - results are exact for any value).
+ *   needed ("exact_adapt" = 1, default; 0 = always the formula); speed only - results are exact for any value),
+ *   "survivor_ring" (records per wave of the 8-phase filter kernel's survivor rings, in [0, 8192]; 0 = auto, sized by the planner for
+ *   the search's largest stage, at most 1024 (8 x CUs x 1024 x 132 B = 277 MB of workspace per lane on 256 CUs); the rings are skipped
+ *   when the device cannot hold them; a query block that does not fit takes the in-loop path; speed and workspace only - results are the same).
  * VODHIP_EXACT_F32 input range: finite float32 rows and queries of ANY magnitude whose squared norm is finite in float32 (|x| < 1.8e19)
  *   give the float32 brute-force result; values beyond the scan dtype's range (fp16: |v| > 65504) saturate in the scan copy only, and
  *   the up to 64 rows whose norm / rounding error exceeds the rest of the store's by 2x or more ("outliers") are scored exactly by
  *   every query instead of widening the error bound.  Rows with NaN / inf components never enter a result (NaN scores are dropped).
  * stats (of the search completed by the last vodhip_index_search_finish): "last_overflow" (a candidate list overflowed),
  *   "last_safe_reruns" (recovery passes run), "last_recovered_queries" (queries the first recovery pass re-searched),
- *   "last_chunks" (stages), "last_filter_launches", "last_filter_ns" (with "profile"), "last_recovery_launches",
+ *   "last_chunks" (stages), "last_survivor_ring" (records per wave of its survivor rings, 0 = none), "last_ring_fallbacks" (query blocks
+ *   with survivors that did not fit into those rings and took the in-loop path, first pass), "last_filter_launches", "last_filter_ns" (with "profile"), "last_recovery_launches",
  *   "last_recovery_ns" (the filter launches of the recovery passes, accounted separately); "exact" (1 for a VODHIP_EXACT_F32 store),
  *   "last_exact_kx" (k' of the last search), "last_exact_band_queries" (queries whose list did not prove complete and ran a band
  *   pass), "last_exact_band_passes". */

@@ -1097,6 +1097,7 @@ __global__ void mips_prepare_kernel(const void* __restrict__ q_src, int q_dtype,
         overflow[0] = 0u;
         overflow[1] = 0u;  // exact mode's "some list did not prove complete" word (kernels_exact.hip)
         overflow[2] = 0u;  // exact mode's "list entries within eps of the k-th exact score, maximum over the queries" word
+        overflow[3] = 0u;  // query blocks the 8-phase FILTER kernel could not defer to its survivor rings (kernels_mips_8phase.hip)
     }
 }
 

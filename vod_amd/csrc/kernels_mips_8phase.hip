@@ -37,12 +37,15 @@ constexpr int P8_OPERANDS = 8 * P8_HALF;   // 128 KB
 constexpr int P8_WL_CAP = 256;             // records per wave list
 constexpr int P8_WL_FLUSH = 176;
 #ifndef P8_TRANSPOSE_EMIT
-#define P8_TRANSPOSE_EMIT 1  // 0: the survivor path of rounds 1-6a (per-lane hit mask + select tree), kept for A/B builds
+#define P8_TRANSPOSE_EMIT 1  // 0: the survivor path of rounds 1-6a (per-lane hit mask + select tree, no ring), kept for A/B builds
 #endif
 #ifndef P8_TRANSPOSE_MAX_LANES
-#define P8_TRANSPOSE_MAX_LANES 2  // query blocks with at most this many lanes holding survivors take the transpose path
+#define P8_TRANSPOSE_MAX_LANES 2  // query blocks in the loop with at most this many lanes holding survivors take the transpose path
 #endif
 constexpr int P8_XPOSE = 8 * 2 * 32 * 4;   // survivor transpose: per wave 2 slots of a lane's 32 sums of one query (2 KB)
+constexpr int P8_DRAIN_RECORDS = 112;      // the ring's drain: records per LDS-DMA copy (14 KB + 448 B of metadata of a wave's 16 KB)
+constexpr int P8_SC1 = 16;                 // cache-policy immediate `sc1` (device scope): the load misses the CU's L1
+static_assert(P8_DRAIN_RECORDS % 8 == 0 && P8_DRAIN_RECORDS * 132 + 256 <= P8_OPERANDS / 8, "drain staging");
 constexpr int P8_LDS = P8_OPERANDS + 8 * P8_WL_CAP * 12 + P8_XPOSE;
 static_assert(P8_LDS <= 160 * 1024, "LDS budget");
 }  // namespace
@@ -53,7 +56,7 @@ template <int DT, bool SUBSET, bool KEEPB0, int LEAD = 7>
 __global__ __launch_bounds__(512, 2) void mips_filter8ph_kernel(
     const uint16_t* __restrict__ X, const uint16_t* __restrict__ Q, int dim_pad, int row_begin, int row_end, int n_xtiles,
     int n_qtiles, int nq, const float* __restrict__ thr_s, const key_t64* __restrict__ thr_key, key_t64* __restrict__ cand,
-    unsigned int* __restrict__ cnt, int cap, unsigned int* __restrict__ overflow, FilterExtra ex) {
+    unsigned int* __restrict__ cnt, int cap, unsigned int* __restrict__ overflow, FilterExtra ex, float* __restrict__ ring, int ring_cap) {
     constexpr int BM = 256, BN = 256, WN = 4, NWAVES = 8, TM = 128, TN = 64, MB = TM / 16, NB16 = TN / 16, ROW_BYTES = 128;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int bid = blockIdx.x;
@@ -204,6 +207,13 @@ __global__ __launch_bounds__(512, 2) void mips_filter8ph_kernel(
         wl_n = 0;
         wait_vmcnt<0>();  // the counted waits of the K loop must only ever see LDS-DMA pieces (loads and stores retire independently)
     };
+    // ---- per-wave survivor ring: the 32 sums of a (hit lane, query block) + one metadata word (corpus tile row | block << 6 | lane) per
+    // record, written during the K loop and turned into list entries after the last tile (the drain below).  ring_n: wave-uniform.
+    const size_t ring_wave = (size_t)bid * NWAVES + wave;
+    float* const ring_w = ring + ring_wave * ring_cap * 32;
+    unsigned* const ring_meta = (unsigned*)(ring + (size_t)gridDim.x * NWAVES * ring_cap * 32) + ring_wave * ring_cap;
+    int ring_n = 0;
+    int ring_fallbacks = 0;  // query blocks with survivors that took the in-loop path (wave-uniform; flag word [3] of `overflow`)
     auto wl_append = [&](bool p, key_t64 key, int q) {
         const unsigned long long bal = __ballot(p);
         if (bal == 0ull) return;
@@ -359,18 +369,36 @@ __global__ __launch_bounds__(512, 2) void mips_filter8ph_kernel(
 #endif
             const bool hit = m >= thr[j];  // false for NaN and for padded queries (thr = +inf)
 #if P8_TRANSPOSE_EMIT
-            // The survivor path (7-10 % of a C3 batch, profiles/r06_ab_epilogue.txt), two forms:
-            //  * TRANSPOSE: a lane that holds a survivor writes its 32 sums of this query to LDS (8 ds_write_b128) and lane t of a 32-lane half
-            //    reads sum t back: one compare, one key and one append per half handle all 32 in parallel, with row offsets that depend on the
-            //    lane number alone - no mask, no select, no per-survivor loop.  Two source lanes per pass; the source lane's threshold and
-            //    coordinates travel as scalars (v_readlane, s_ff1).  Cheapest when few lanes hold survivors (the late, large stages of a
-            //    search: one survivor in one lane is the common case) and when a lane holds several (rows sorted by topic: -4.7 %).
-            //  * MASK (rounds 1-6a): every lane compares its 32 sums into a hit mask and appends its own survivors, all lanes at once; the
-            //    score of a single survivor is the lane's maximum.  Cheapest when many lanes hold one survivor each (the early, small stages;
-            //    a 1.25 M-row shard is mostly those: all-transpose was +5.8 % there).
-            // Same records either way, in a different order (the select kernel's result does not depend on it).
+            // The survivor path, two forms (the same records either way, in a different order: the select kernel's result does not
+            // depend on it):
+            //  * RING (the common case): every hit lane stores its 32 sums (8 x 16 B) and one metadata word to the next free record of the
+            //    wave's ring - no compare, no key, no list, no branch per lane; the drain after the last tile does the rest, out of the
+            //    barrier-synchronous loop.  In the loop a query block that holds any survivor cost the tile ~1.2 us in its slowest wave
+            //    (the other seven wait at the next barrier), ~5 % of a C3 batch (profiles/r07_survivor_ring.txt).  The stores retire in
+            //    vmcnt like the LDS-DMA pieces: the counted waits stay safe (loads still retire in order among themselves).
+            //  * IN THE LOOP (a block that does not fit into the rest of the ring; the path of the previous rounds, unchanged):
+            //    - TRANSPOSE (<= P8_TRANSPOSE_MAX_LANES lanes hold survivors): a lane that holds a survivor writes its 32 sums of this query
+            //      to LDS (8 ds_write_b128) and lane t of a 32-lane half reads sum t back: one compare, one key and one append per half
+            //      handle all 32 in parallel, with row offsets that depend on the lane number alone.  Two source lanes per pass; the source
+            //      lane's threshold and coordinates travel as scalars (v_readlane, s_ff1).
+            //    - MASK (more lanes): every lane compares its 32 sums into a hit mask and appends its own survivors, all lanes at once; the
+            //      score of a single survivor is the lane's maximum; lanes with several go through the transpose.  Dense overflowing
+            //      blocks (large k, tiny rings) need it: transpose-only was +1.4 % at k 1000 on C3, +7.6 % with a 1-record ring on a shard.
             const unsigned long long hit_lanes = hl[j];
-            if (hit_lanes != 0ull) {
+            if (hit_lanes != 0ull && ring_n + __builtin_popcountll(hit_lanes) <= ring_cap) {
+                if (hit) {
+                    const int slot = ring_n + (int)__builtin_amdgcn_mbcnt_hi((unsigned)(hit_lanes >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)hit_lanes, 0u));
+                    f32x4* const rec = (f32x4*)(ring_w + (size_t)slot * 32);
+#pragma unroll
+                    for (int i = 0; i < MB; ++i) rec[i] = acc[i][j];
+                    int x0_o = x0, lane_o = lane;  // (opaque: see below)
+                    asm volatile("" : "+s"(x0_o));
+                    asm volatile("" : "+v"(lane_o));
+                    ring_meta[slot] = (unsigned)x0_o | (unsigned)(j << 6) | (unsigned)lane_o;  // (x0: a multiple of 256)
+                }
+                ring_n += __builtin_popcountll(hit_lanes);
+            } else if (hit_lanes != 0ull) {
+                ++ring_fallbacks;
                 // (opaque: or hipcc computes the lane-dependent offsets of all four query blocks once, outside the K loop, and holds them in
                 // vector registers the loop does not have - it spilled 18)
                 int x0_o = x0, row_end_o = row_end, lane_o = lane;
@@ -538,7 +566,57 @@ __global__ __launch_bounds__(512, 2) void mips_filter8ph_kernel(
         }
     }
     if (wm == 0 && !knob_no_stagger) __builtin_amdgcn_s_barrier();  // balances the stagger
+
+    // ---- the drain: the ring's records -> the wave's list, as the transpose path does it (lane t of half h takes sum t of record
+    // 2 p + h).  The operand buffers are idle now (every wave is past its last fragment read: the barrier above): the wave copies
+    // P8_DRAIN_RECORDS records at a time into its 16 KB of them with LDS-DMA (one round trip per copy, device-scope `sc1` loads that miss
+    // the CU's L1, whatever it holds of these lines) and reads them from there.
+#ifndef P8_ABL_NO_DRAIN  // (timing only: the records are dropped)
+    if (ring_n > 0) {
+        wait_vmcnt<0>();  // the records have landed
+        if (fq == 0) {
+#pragma unroll
+            for (int j = 0; j < NB16; ++j) xpose[j * 16 + fr] = thr[j];  // the thresholds by (block, query), for any lane to read
+        }
+        char* const stage_w = smem + wave * (P8_OPERANDS / NWAVES);
+        const float* const sums = (const float*)stage_w;
+        const unsigned* const meta = (const unsigned*)(stage_w + P8_DRAIN_RECORDS * 128);
+        const int half = lane >> 5, t = lane & 31;
+        for (int r0 = 0; r0 < ring_n; r0 += P8_DRAIN_RECORDS) {
+            // (sources clamped to the wave's last record: every address stays inside its ring)
+#pragma unroll
+            for (int i = 0; i < P8_DRAIN_RECORDS / 8; ++i) {  // 8 records of 128 B per instruction
+                const int r = min(r0 + i * 8 + (lane >> 3), ring_n - 1);
+                __builtin_amdgcn_global_load_lds((const VOD_AS1 void*)(ring_w + (size_t)r * 32 + (lane & 7) * 4),
+                                                 (VOD_AS3 void*)(stage_w + i * 1024), 16, 0, P8_SC1);
+            }
+#pragma unroll
+            for (int i = 0; i < (P8_DRAIN_RECORDS + 63) / 64; ++i) {
+                const int r = min(r0 + i * 64 + lane, ring_n - 1);
+                __builtin_amdgcn_global_load_lds((const VOD_AS1 void*)(ring_meta + r), (VOD_AS3 void*)(stage_w + P8_DRAIN_RECORDS * 128 + i * 256),
+                                                 4, 0, P8_SC1);
+            }
+            wait_vmcnt<0>();
+            const int nr = min(ring_n - r0, P8_DRAIN_RECORDS);
+            // two passes per step and one flush check: a pass appends <= 64 entries, so <= 128 before the step keeps the list in bounds
+            for (int r4 = 0; r4 < nr; r4 += 4) {
+                if (wl_n > P8_WL_CAP - 128) wl_flush();
+                const int r = r4 + half;
+#pragma unroll
+                for (int u = 0; u < 4; u += 2) {
+                    const float v = sums[(r + u) * 32 + t];  // (r + u < P8_DRAIN_RECORDS + 3: inside the wave's 16 KB; past nr read, not used)
+                    const unsigned m = meta[r + u];
+                    const int src = (int)(m & 63u), jb = (int)((m >> 6) & 3u), x0 = (int)(m & ~255u);
+                    const int q_src = q0 + wn * TN + jb * 16 + (src & 15);
+                    const int rw = x0 + wm * TM + 4 * (src >> 4) + (t >> 2) * 16 + (t & 3);
+                    wl_append(r + u < nr && v >= xpose[jb * 16 + (src & 15)] && rw < row_end, make_key(v, (unsigned)rw), q_src);
+                }
+            }
+        }
+    }
+#endif
     wl_flush();
+    if (ring_fallbacks > 0 && lane == 0) atomicAdd(overflow + 3, (unsigned)ring_fallbacks);
 }
 
 template <bool KEEPB0, int LEAD = 7>
@@ -552,11 +630,13 @@ static hipError_t launch_8phase(int store_dtype, const void* store, const void* 
     int grid = (n_cu / unit) * unit;
     if (grid < unit) grid = unit;
     if (grid > total) grid = total;
+    // the survivor rings: ws.ring_cap records per wave, fewer if the allocation is short of this grid's waves (none: in-loop path only)
+    const int ring_cap = ws.ring ? (int)std::min<int64_t>(ws.ring_cap, ws.ring_floats / ((int64_t)grid * 8 * 33)) : 0;
     auto launch = [&](auto kern) -> hipError_t {
         if (hipError_t e = allow_dynamic_lds((const void*)kern, P8_LDS); e != hipSuccess) return e;
         hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(512), P8_LDS, stream, (const uint16_t*)store, (const uint16_t*)q_pad, (int)dim_pad,
                            (int)row_begin, (int)row_end, n_xtiles, n_qtiles, (int)nq, ws.thr_s, ws.thr_key, ws.cand, ws.cnt, (int)ws.cap,
-                           ws.overflow, ws.extra);
+                           ws.overflow, ws.extra, ws.ring, ring_cap);
         return hipGetLastError();
     };
     if constexpr (LEAD != 7)  // (experiment builds: no subset instantiation)

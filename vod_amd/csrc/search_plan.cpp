@@ -162,7 +162,27 @@ SearchPlan plan_search(int64_t ntotal, int k, int64_t nq, const PlanTunables& t,
         // between the head and the tail of the store
         if (sg.kind == ST_GMAX) sg.sample_offset = ((ntotal - 1) - (sg.n_tiles * geometry(sg.kernel).rows - 1) * sg.rstride) / 2;
     }
+    // the survivor rings of the 8-phase kernel, sized for its largest stage: a FILTER stage against a threshold calibrated on C rows
+    // passes ~k * rows / C rows per query (the k-th best of C rows; 1.15-1.39 x that behind the bootstrap's group maxima); a
+    // recovery pass's thresholds come from a result over the whole store
+    double per_query = 0.0;
+    int64_t calibrated = ntotal;
+    for (const Stage& sg : st) {
+        if (sg.kind == ST_GMAX) calibrated = sg.n_tiles * geometry(sg.kernel).rows;
+        if (sg.kind == ST_FILTER && sg.kernel == FilterKernel::EightPhase)
+            per_query = std::max(per_query, 1.4 * k * (double)(sg.e - sg.b) / (double)std::max<int64_t>(1, calibrated));
+        if (sg.kind != ST_GMAX) calibrated = sg.e;
+    }
+    if (per_query > 0.0) p.ring = t.survivor_ring > 0 ? t.survivor_ring : survivor_ring_records(per_query, nq_pad, t.n_cu);
     return p;
+}
+
+int64_t survivor_ring_records(double per_query, int64_t nq_pad, int n_cu) {
+    const int64_t n_qt = std::max<int64_t>(1, nq_pad / 256);
+    const int64_t unit = 8 * n_qt;  // the 8-phase launcher's grid: whole multiples of 8 workgroups per query tile
+    const int64_t grid = std::max(unit, std::max(1, n_cu) / unit * unit);
+    const double per_wave = per_query * 64.0 / (double)(2 * grid / n_qt);
+    return std::min<int64_t>(MAX_AUTO_SURVIVOR_RING, round_up((int64_t)(2.0 * per_wave) + 64, 64));
 }
 
 // The multiplier of the low-discrepancy stage order over T super-tiles: position p -> super-tile (p * P) mod T with P the largest

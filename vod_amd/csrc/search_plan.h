@@ -12,6 +12,8 @@ inline int64_t round_up(int64_t v, int64_t m) { return (v + m - 1) / m * m; }
 
 constexpr int64_t ROW_ALIGN = 256;  // largest tile height; chunk boundaries and capacity padding
 constexpr int64_t MAX_NQ_PER_PASS = 2048;
+constexpr int64_t MAX_SURVIVOR_RING = 8192;       // records per wave a caller may force (vodhip_index_set_param "survivor_ring")
+constexpr int64_t MAX_AUTO_SURVIVOR_RING = 1024;  // ... and the planner's own sizes stop at: 8 x 256 waves x 1024 x 132 B = 277 MB per lane
 
 // The production filter kernels.  The values are the public "tile" ids (vodhip_index_set_param, bench.py --tile).
 enum class FilterKernel : int { Generic128 = 1, Generic256x64 = 42, Generic256x128 = 46, Persistent = 8, Staggered = 9, EightPhase = 14 };
@@ -65,6 +67,7 @@ struct PlanTunables {
     int64_t tile = 0;            // the requested kernel: 0 = auto (by nq), else a FilterKernel id (find_kernel)
     int64_t tile_order = 0;      // 0 = FILTER stages walk the store's super-tiles in a low-discrepancy order (default); 1 = in row order
     int64_t small_chunk_tiles = 256;  // launches with fewer 256x256 tiles than this (less than one per CU) use the 128x128 kernel
+    int64_t survivor_ring = 0;   // survivor records per wave of the 8-phase kernel's rings: 0 = auto (survivor_ring_records), n = n
     int n_cu = 256;              // compute units of the device
 };
 
@@ -75,6 +78,7 @@ struct SearchPlan {
     int64_t perm_mul = 0, perm_mod = 0;  // FilterExtra: the stage order (0: row order)
     int64_t small_tiles = 0;  // FILTER stages of fewer 256x256 tiles than this on a pass run on the 128x128 kernel (less than one per CU)
     std::vector<Stage> stages;
+    int64_t ring = 0;         // survivor records per wave of the 8-phase FILTER launches (0: no stage runs that kernel)
     FilterKernel kernel(const Stage& sg, int64_t nq_pad) const {  // the kernel of stage `sg` on a pass of nq_pad queries
         return sg.kind == ST_FILTER && (sg.e - sg.b + 255) / 256 * (nq_pad / 256) < small_tiles ? FilterKernel::Generic128 : sg.kernel;
     }
@@ -82,6 +86,12 @@ struct SearchPlan {
 
 // recovery > 0: pass number after a candidate-list overflow; safe: exhaustive DENSE stages only; subset: a subset filter is in force
 SearchPlan plan_search(int64_t ntotal, int k, int64_t nq, const PlanTunables& t, bool subset, bool safe, int recovery);
+
+// Survivor records per wave the rings of the 8-phase FILTER kernel (kernels_mips_8phase.hip) are sized for: `per_query` expected
+// survivors per query in a stage, shared by the waves of the persistent grid that see the query (two wave rows per workgroup of its
+// query tile), twice that plus one record per lane, in whole 64-record steps, at most MAX_AUTO_SURVIVOR_RING (large k, many query
+// tiles: the blocks that do not fit take the in-loop path).
+int64_t survivor_ring_records(double per_query, int64_t nq_pad, int n_cu);
 
 // The multiplier of the low-discrepancy stage order over T super-tiles (FilterExtra::perm_mul); <= 1: no permutation.
 int64_t tile_order_multiplier(int64_t T);

@@ -72,7 +72,7 @@ struct PendingSearch {
     int lane = 0;                  // which of the index's two workspaces / streams this search runs on (1 = the index's own stream)
 };
 
-constexpr int FLAG_WORDS = 4;     // flag words of a workspace / of a slot's host copy
+constexpr int FLAG_WORDS = 4;     // flag words of a workspace / of a slot's host copy ([3]: blocks that missed the survivor rings)
 constexpr int MAX_IN_FLIGHT = 4;  // searches that may be enqueued before the oldest is finished
 constexpr int64_t OVF_ROWS = 65536;  // per-query overflow flags are kept for batches up to this many queries
 
@@ -134,7 +134,7 @@ struct vodhip_index {
     int64_t kflags = 0;
     int64_t profile = 0;  // 1: bracket every filter launch with HIP events (bench / roofline accounting)
     // stats
-    int64_t last_overflow = 0, last_chunks = 0, last_safe_reruns = 0, last_recovered_queries = 0;
+    int64_t last_overflow = 0, last_chunks = 0, last_survivor_ring = 0, last_ring_fallbacks = 0, last_safe_reruns = 0, last_recovered_queries = 0;
     int64_t last_filter_launches = 0, last_filter_ns = 0;
     int64_t last_recovery_launches = 0, last_recovery_ns = 0;  // filter launches of the recovery passes (with "profile")
     std::vector<hipEvent_t> ev_pool;  // pairs (start, stop), reused across searches
@@ -158,6 +158,7 @@ int free_workspace(vodhip_index* ix, int lane) {
     (void)hipFree(w.thr_s);
     (void)hipFree(w.thr_key);
     (void)hipFree(w.overflow);
+    (void)hipFree(w.ring);
     const int n_cu = w.n_cu;
     w = SearchWorkspace();
     w.n_cu = n_cu;
@@ -186,6 +187,28 @@ int ensure_workspace(vodhip_index* ix, int lane, int64_t nq_pad, int64_t cap, in
     w.cap = cap;
     w.kp = kp;
     w.kp_cap = kp_cap;
+    return 0;
+}
+
+// the survivor rings of the 8-phase kernel for `records` per wave (SearchPlan::ring), on the largest grid its launcher makes: one workgroup
+// per CU, at least 8 per query tile (<= 64: MAX_NQ_PER_PASS / 256 query tiles).  The rings only buy speed: when the device cannot hold
+// them the search runs without (ring_cap 0: every block takes the in-loop path), it does not fail.
+int ensure_ring(vodhip_index* ix, int lane, int64_t records) {
+    SearchWorkspace& w = ix->ws_lane[lane];
+    const int64_t floats = (int64_t)std::max(w.n_cu, 64) * 8 * records * 33;
+    if (floats > w.ring_floats) {
+        (void)hipFree(w.ring);
+        w.ring = nullptr;
+        w.ring_floats = 0;
+        if (hipMalloc((void**)&w.ring, (size_t)floats * sizeof(float)) != hipSuccess) {
+            (void)hipGetLastError();  // (not sticky for the launches that follow)
+            w.ring = nullptr;
+            w.ring_cap = 0;
+            return 0;
+        }
+        w.ring_floats = floats;
+    }
+    w.ring_cap = records;
     return 0;
 }
 
@@ -291,9 +314,11 @@ int enqueue_search_impl(vodhip_index* ix, const PendingSearch& ps, bool safe, in
     const FilterStageFn experiment = experiment_filter(tune);
     const SearchPlan plan = plan_search(ix->ntotal, k, ps.nq, tune, row_label != nullptr, safe, recovery);
     ix->last_chunks = (int64_t)plan.stages.size();
+    ix->last_survivor_ring = plan.ring;
 
     const int q_es = elem_size(ps.q_dtype);
     if (ensure_workspace(ix, ps.lane, round_up(std::min(MAX_NQ_PER_PASS, ps.nq), 256), cap, kp)) return -1;
+    if (ensure_ring(ix, ps.lane, plan.ring)) return -1;
     W.extra.flags = ((int)ix->kflags << 8) | (plan.corpus_nt ? FILTER_FLAG_CORPUS_NT : 0);  // (the knobs: diagnostic builds only)
     W.extra.row_label = row_label;
     W.extra.n_qlab = ps.n_qlab;
@@ -337,7 +362,7 @@ int enqueue_search_impl(vodhip_index* ix, const PendingSearch& ps, bool safe, in
             HIP_OK(launch_output(ws, nq, k, ps.id_base, ps.out_scores + qb * k, ps.out_ids + qb * k, stream));
     }
     if (ps.defer_flags) return 0;
-    HIP_OK(hipMemcpyAsync(ix->overflow_host + FLAG_WORDS * ps.slot, ws.overflow, sizeof(unsigned int), hipMemcpyDeviceToHost, stream));
+    HIP_OK(hipMemcpyAsync(ix->overflow_host + FLAG_WORDS * ps.slot, ws.overflow, FLAG_WORDS * sizeof(unsigned int), hipMemcpyDeviceToHost, stream));
     HIP_OK(hipEventRecord(ix->done[ps.slot], stream));
     return 0;
 }
@@ -403,7 +428,7 @@ int enqueue_exact_list(vodhip_index* ix, const PendingSearch& ps, hipStream_t st
     xa.flag_word = ix->ws_lane[ps.lane].overflow + 1;
     xa.flag_q = ix->x_flag_q + (size_t)ps.slot * OVF_ROWS;
     HIP_OK(launch_exact_rescore(xa, ps.nq, stream));
-    HIP_OK(hipMemcpyAsync(ix->overflow_host + FLAG_WORDS * ps.slot, ix->ws_lane[ps.lane].overflow, 3 * sizeof(unsigned int), hipMemcpyDeviceToHost, stream));
+    HIP_OK(hipMemcpyAsync(ix->overflow_host + FLAG_WORDS * ps.slot, ix->ws_lane[ps.lane].overflow, FLAG_WORDS * sizeof(unsigned int), hipMemcpyDeviceToHost, stream));
     HIP_OK(hipEventRecord(ix->done[ps.slot], stream));
     return 0;
 }
@@ -867,6 +892,7 @@ int vodhip_index_search_finish(vodhip_index_t* ix, void* stream_) {
     ix->last_exact_band_queries = 0;
     ix->last_exact_band_passes = 0;
     ix->last_exact_need = ps.kx > 0 && ps.nq > 0 ? (int64_t)ix->overflow_host[FLAG_WORDS * ps.slot + 2] : 0;
+    ix->last_ring_fallbacks = ps.nq > 0 ? (int64_t)ix->overflow_host[FLAG_WORDS * ps.slot + 3] : 0;  // (before any recovery pass)
     if (ps.kx > 0 && ps.nq > 0 && ix->exact_adapt && ix->exact_expand_x100 == 0) {
         // The list length of the NEXT searches of this k: what this one needed (the list entries within eps of the k-th exact score,
         // maximum over the queries) + 1/16 + 8, rounded up to 8; it rises at once and falls by a quarter of the gap per search.  A list
@@ -998,6 +1024,9 @@ int vodhip_index_set_param(vodhip_index_t* ix, const char* key, int64_t value) {
         if (value < 0 || value > 2) return fail("lanes must be 0 (auto: 2 for batches of one query tile), 1 or 2");
         if (!ix->inflight.empty()) return fail("searches are in flight: finish them before changing the lanes");
         ix->lanes = value;
+    } else if (!strcmp(key, "survivor_ring")) {
+        if (value < 0 || value > MAX_SURVIVOR_RING) return fail("survivor_ring must be in [0, 8192] (0 = auto)");
+        ix->tune.survivor_ring = value;
     } else if (!strcmp(key, "tile_order")) {
         if (value != 0 && value != 1) return fail("tile_order must be 0 (low-discrepancy stage order) or 1 (row order)");
         ix->tune.tile_order = value;
@@ -1026,6 +1055,10 @@ int vodhip_index_get_stat(const vodhip_index_t* ix, const char* key, int64_t* ou
         *out = ix->last_overflow;
     else if (!strcmp(key, "last_chunks"))
         *out = ix->last_chunks;
+    else if (!strcmp(key, "last_survivor_ring"))
+        *out = ix->last_survivor_ring;
+    else if (!strcmp(key, "last_ring_fallbacks"))
+        *out = ix->last_ring_fallbacks;
     else if (!strcmp(key, "last_safe_reruns"))
         *out = ix->last_safe_reruns;
     else if (!strcmp(key, "last_recovered_queries"))
@@ -1056,6 +1089,8 @@ int vodhip_index_get_stat(const vodhip_index_t* ix, const char* key, int64_t* ou
         *out = ix->tune.dense_rows;
     else if (!strcmp(key, "sample_div"))
         *out = ix->tune.sample_div;
+    else if (!strcmp(key, "survivor_ring"))
+        *out = ix->tune.survivor_ring;
     else if (!strcmp(key, "dim_pad"))
         *out = ix->dim_pad;
     else if (!strcmp(key, "last_ingest_pinned_src"))

@@ -76,8 +76,13 @@ struct SearchWorkspace {
     unsigned int* cnt = nullptr;     // [nq_pad * CNT_STRIDE] candidates appended in the current stage (one counter per 128-B line)
     float* thr_s = nullptr;          // [nq_pad] score of the current k-th best (-inf until k hits exist)
     key_t64* thr_key = nullptr;      // [nq_pad] key of the current k-th best (0 until k hits exist)
-    unsigned int* overflow = nullptr;  // [4] flag words: [0] a candidate buffer overflowed; exact mode: [1] some list did not prove complete, [2] max needed list length
+    unsigned int* overflow = nullptr;  // [4] flag words: [0] a candidate buffer overflowed; exact mode: [1] some list did not prove complete, [2] max needed list length; [3] blocks that missed the 8-phase kernel's survivor rings
     unsigned int* ovf_q = nullptr;     // [nq] per query: its candidate list overflowed in some stage (set by the select kernel), or NULL
+    // the 8-phase FILTER kernel's per-wave survivor rings (kernels_mips_8phase.hip): [waves][ring_cap][32] sums, then [waves][ring_cap]
+    // metadata words, waves = 8 x the launch's grid; grow-only, `ring_floats` floats allocated
+    float* ring = nullptr;
+    int64_t ring_floats = 0;
+    int64_t ring_cap = 0;              // records per wave of the search being enqueued (SearchPlan::ring; 0: no ring)
     int n_cu = 256;                    // compute units of the device (read once at index create)
     int64_t nq_cap = 0;
     int64_t cap = 0;
