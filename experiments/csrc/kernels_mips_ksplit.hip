@@ -168,57 +168,12 @@ __global__ __launch_bounds__(512, 2) void mips_filter_ksplit_kernel(
         for (int j = 0; j < NB16; ++j) asm volatile("" : "+v"(fb[s][j]));
     ks_wait_vmcnt<0>();  // (also the prologue half-units: everything issued so far has landed)
 
-    // ---- per-wave survivor list of the second-half waves (as in the persistent kernels) --------------
-    key_t64* const wl_key = (key_t64*)(smem + LISTS) + pair * KS_WL_CAP;
-    int* const wl_q = (int*)(smem + LISTS + 4 * KS_WL_CAP * 8) + pair * KS_WL_CAP;
-    int wl_n = 0;  // wave-uniform
-    auto wl_flush = [&]() {
-        const int n = wl_n < KS_WL_CAP ? wl_n : KS_WL_CAP;
-        constexpr int PER_LANE = KS_WL_CAP / 64;
-        key_t64 fk[PER_LANE];
-        int fq_[PER_LANE];
-        bool ok[PER_LANE];
-        unsigned slot[PER_LANE];
-#pragma unroll
-        for (int u = 0; u < PER_LANE; ++u) {
-            const int e = lane + 64 * u;
-            ok[u] = e < n;
-            fk[u] = ok[u] ? wl_key[e] : 0ull;
-            fq_[u] = ok[u] ? wl_q[e] : 0;
-        }
-#pragma unroll
-        for (int u = 0; u < PER_LANE; ++u) ok[u] = ok[u] && fk[u] > thr_key[fq_[u]];
-#pragma unroll
-        for (int u = 0; u < PER_LANE; ++u) slot[u] = ok[u] ? atomicAdd(&cnt[(size_t)fq_[u] * CNT_STRIDE], 1u) : 0u;
-#pragma unroll
-        for (int u = 0; u < PER_LANE; ++u) {
-            if (ok[u]) {
-                if (slot[u] < (unsigned)cap)
-                    cand[(size_t)fq_[u] * cap + slot[u]] = fk[u];
-                else
-                    atomicOr(overflow, 1u);
-            }
-        }
-        wl_n = 0;
-        ks_wait_vmcnt<0>();  // the counted waits of the step loop must only ever see LDS-DMA pieces
-    };
-    auto wl_append = [&](bool p, key_t64 key, int q) {
-        const unsigned long long bal = __ballot(p);
-        if (bal == 0ull) return;
-        const int pos = wl_n + (int)__builtin_amdgcn_mbcnt_hi((unsigned)(bal >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)bal, 0u));
-        bool direct = false;
-        if (p) {
-            if (pos < KS_WL_CAP) {
-                wl_key[pos] = key;
-                wl_q[pos] = q;
-            } else {
-                emit_candidate<false>(key, q, thr_key, cand, cnt, cap, overflow, ex);
-                direct = true;
-            }
-        }
-        wl_n += __builtin_popcountll(bal);
-        if (__any(direct)) ks_wait_vmcnt<0>();
-    };
+    // ---- per-wave survivor list of the second-half waves (mips_common.h, as in the persistent kernels; one per pair).  After a flush
+    // or a direct emit: ks_wait_vmcnt<0>(), the counted waits of the step loop must only ever see LDS-DMA pieces
+    WaveSurvivorList<KS_WL_CAP, false> wl(smem + LISTS, 4, pair);
+    const SurvivorOut out{thr_key, cand, cnt, cap, overflow, ex};
+    auto wl_append = [&](bool p, key_t64 key, int q) { if (wl.append(p, key, q, out)) ks_wait_vmcnt<0>(); };
+    auto wl_flush = [&]() { wl.flush(out); ks_wait_vmcnt<0>(); };
 
     f32x4 acc[NB16];
     u32x4 fa[2][GS];  // the A fragments of the k-step group being multiplied and of the next one
@@ -279,7 +234,7 @@ __global__ __launch_bounds__(512, 2) void mips_filter_ksplit_kernel(
                 } while (__any(mask != 0u));
             }
         }
-        if (wl_n >= KS_WL_FLUSH) wl_flush();
+        if (wl.n >= KS_WL_FLUSH) wl_flush();
     };
 
     __builtin_amdgcn_s_barrier();  // every wave's pieces of the prologue half-units have landed

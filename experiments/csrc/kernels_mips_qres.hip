@@ -147,57 +147,12 @@ __global__ __launch_bounds__(256, 1) void mips_filter_qres_kernel(
             else asm volatile("" : "+v"(fb[s][j]));
         }
 
-    // ---- per-wave survivor list (as in the persistent kernels) -------------------------------------
-    key_t64* const wl_key = (key_t64*)(smem + QR_LISTS) + wave * QR_WL_CAP;
-    int* const wl_q = (int*)(smem + QR_LISTS + NWAVES * QR_WL_CAP * 8) + wave * QR_WL_CAP;
-    int wl_n = 0;  // wave-uniform
-    auto wl_flush = [&]() {
-        const int n = wl_n < QR_WL_CAP ? wl_n : QR_WL_CAP;
-        constexpr int PER_LANE = QR_WL_CAP / 64;
-        key_t64 fk[PER_LANE];
-        int fq_[PER_LANE];
-        bool ok[PER_LANE];
-        unsigned slot[PER_LANE];
-#pragma unroll
-        for (int u = 0; u < PER_LANE; ++u) {
-            const int e = lane + 64 * u;
-            ok[u] = e < n;
-            fk[u] = ok[u] ? wl_key[e] : 0ull;
-            fq_[u] = ok[u] ? wl_q[e] : 0;
-        }
-#pragma unroll
-        for (int u = 0; u < PER_LANE; ++u) ok[u] = ok[u] && fk[u] > thr_key[fq_[u]];
-#pragma unroll
-        for (int u = 0; u < PER_LANE; ++u) slot[u] = ok[u] ? atomicAdd(&cnt[(size_t)fq_[u] * CNT_STRIDE], 1u) : 0u;
-#pragma unroll
-        for (int u = 0; u < PER_LANE; ++u) {
-            if (ok[u]) {
-                if (slot[u] < (unsigned)cap)
-                    cand[(size_t)fq_[u] * cap + slot[u]] = fk[u];
-                else
-                    atomicOr(overflow, 1u);
-            }
-        }
-        wl_n = 0;
-        qr_wait_vmcnt<0>();  // the counted waits of the unit loop must only ever see LDS-DMA pieces
-    };
-    auto wl_append = [&](bool p, key_t64 key, int q) {
-        const unsigned long long bal = __ballot(p);
-        if (bal == 0ull) return;
-        const int pos = wl_n + (int)__builtin_amdgcn_mbcnt_hi((unsigned)(bal >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)bal, 0u));
-        bool direct = false;
-        if (p) {
-            if (pos < QR_WL_CAP) {
-                wl_key[pos] = key;
-                wl_q[pos] = q;
-            } else {
-                emit_candidate<false>(key, q, thr_key, cand, cnt, cap, overflow, ex);
-                direct = true;
-            }
-        }
-        wl_n += __builtin_popcountll(bal);
-        if (__any(direct)) qr_wait_vmcnt<0>();
-    };
+    // ---- per-wave survivor list (mips_common.h, as in the persistent kernels).  After a flush or a direct emit: qr_wait_vmcnt<0>(),
+    // the counted waits of the unit loop must only ever see LDS-DMA pieces
+    WaveSurvivorList<QR_WL_CAP, false> wl(smem + QR_LISTS, NWAVES, wave);
+    const SurvivorOut out{thr_key, cand, cnt, cap, overflow, ex};
+    auto wl_append = [&](bool p, key_t64 key, int q) { if (wl.append(p, key, q, out)) qr_wait_vmcnt<0>(); };
+    auto wl_flush = [&]() { wl.flush(out); qr_wait_vmcnt<0>(); };
 
     f32x4 acc[2][NB16];
     u32x4 fa[2][2][2];  // [buffer][k-step][row block]: the A fragments of the unit being multiplied and of the next one
@@ -245,7 +200,7 @@ __global__ __launch_bounds__(256, 1) void mips_filter_qres_kernel(
                 } while (__any(mask != 0u));
             }
         }
-        if (wl_n >= QR_WL_FLUSH) wl_flush();
+        if (wl.n >= QR_WL_FLUSH) wl_flush();
     };
 
     __builtin_amdgcn_s_barrier();  // every wave's pieces of the prologue units have landed

@@ -137,61 +137,13 @@ __global__ __launch_bounds__(512, 2) void mips_filter16r_kernel(
         q_slot = q_slot == 2 ? 0 : q_slot + 1;
     };
 
-    // ---- per-wave survivor list (see kernels_mips.hip) -------------------------------------------------
-    key_t64* const wl_key = (key_t64*)(smem + RING_LIST_BASE) + wave * RING_WL_CAP;
-    int* const wl_q = (int*)(smem + RING_LIST_BASE + NWAVES * RING_WL_CAP * 8) + wave * RING_WL_CAP;
-    int wl_n = 0;  // wave-uniform
-    auto wl_flush = [&]() {
-        const int n = wl_n < RING_WL_CAP ? wl_n : RING_WL_CAP;
-        constexpr int PER_LANE = (RING_WL_CAP + 63) / 64;
-        key_t64 fk[PER_LANE];
-        int fq_[PER_LANE];
-        bool ok[PER_LANE];
-        unsigned slot[PER_LANE];
-#pragma unroll
-        for (int u = 0; u < PER_LANE; ++u) {
-            const int e = lane + 64 * u;
-            ok[u] = e < n;
-            fk[u] = ok[u] ? wl_key[e] : 0ull;
-            fq_[u] = ok[u] ? wl_q[e] : 0;
-        }
-#pragma unroll
-        for (int u = 0; u < PER_LANE; ++u) {
-            ok[u] = ok[u] && fk[u] > thr_key[fq_[u]];
-            if constexpr (SUBSET) ok[u] = ok[u] && subset_allows(ex, fq_[u], (int)(0xFFFFFFFFu - (unsigned)fk[u]));
-        }
-#pragma unroll
-        for (int u = 0; u < PER_LANE; ++u) slot[u] = ok[u] ? atomicAdd(&cnt[(size_t)fq_[u] * CNT_STRIDE], 1u) : 0u;
-#pragma unroll
-        for (int u = 0; u < PER_LANE; ++u) {
-            if (ok[u]) {
-                if (slot[u] < (unsigned)cap)
-                    cand[(size_t)fq_[u] * cap + slot[u]] = fk[u];
-                else
-                    atomicOr(overflow, 1u);
-            }
-        }
-        // a wait the compiler's waitcnt pass can SEE (the builtin, not inline asm): otherwise it carries the returning atomics
-        // of this cold path to the head of the tile loop as possibly pending and drains the whole LDS-DMA ring there with a
-        // vmcnt(0) of its own, once per tile
-        __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0)
-        wl_n = 0;
-    };
-    auto wl_append = [&](bool p, key_t64 key, int q) {
-        const unsigned long long bal = __ballot(p);
-        if (bal == 0ull) return;
-        const int pos = wl_n + (int)__builtin_amdgcn_mbcnt_hi((unsigned)(bal >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)bal, 0u));
-        if (p) {
-            if (pos < RING_WL_CAP) {
-                wl_key[pos] = key;
-                wl_q[pos] = q;
-            } else {
-                emit_candidate<SUBSET>(key, q, thr_key, cand, cnt, cap, overflow, ex);
-            }
-        }
-        if (wl_n + __builtin_popcountll(bal) > RING_WL_CAP) __builtin_amdgcn_s_waitcnt(0x0F70);  // (see wl_flush)
-        wl_n += __builtin_popcountll(bal);
-    };
+    // ---- per-wave survivor list (mips_common.h).  After a flush or a direct emit: vmcnt(0) as a wait the compiler's waitcnt pass
+    // can SEE (the builtin 0x0F70, not inline asm): otherwise it carries the returning atomics of this cold path to the head of the
+    // tile loop as possibly pending and drains the whole LDS-DMA ring there with a vmcnt(0) of its own, once per tile
+    WaveSurvivorList<RING_WL_CAP, SUBSET> wl(smem + RING_LIST_BASE, NWAVES, wave);
+    const SurvivorOut out{thr_key, cand, cnt, cap, overflow, ex};
+    auto wl_append = [&](bool p, key_t64 key, int q) { if (wl.append(p, key, q, out)) __builtin_amdgcn_s_waitcnt(0x0F70); };
+    auto wl_flush = [&]() { wl.flush(out); __builtin_amdgcn_s_waitcnt(0x0F70); };
 
     struct Frags {
         u32x4 b[NB16], a[MB];
@@ -246,33 +198,13 @@ __global__ __launch_bounds__(512, 2) void mips_filter16r_kernel(
                     const int b = p ? __builtin_ctz(mask) : 0;
                     mask &= mask - 1u;
                     float sc = m;
-                    if (multi) {
-                        // register select by the bits of b (inline asm: as C++ selects LLVM turns the tree into an indexed
-                        // load from a SCRATCH copy of the accumulator, stored after every MFMA of the hot loop)
-                        const unsigned long long s0 = __ballot(b & 1), s1 = __ballot(b & 2), s2 = __ballot(b & 4),
-                                                 s3 = __ballot(b & 8), s4 = __ballot(b & 16);
-                        auto sel = [](float lo, float hi, unsigned long long sm) {
-                            float r;
-                            asm("v_cndmask_b32_e64 %0, %1, %2, %3" : "=v"(r) : "v"(lo), "v"(hi), "s"(sm));
-                            return r;
-                        };
-                        float t16[16], t8[8], t4[4], t2[2];
-#pragma unroll
-                        for (int u = 0; u < 16; ++u) t16[u] = sel(val(2 * u), val(2 * u + 1), s0);
-#pragma unroll
-                        for (int u = 0; u < 8; ++u) t8[u] = sel(t16[2 * u], t16[2 * u + 1], s1);
-#pragma unroll
-                        for (int u = 0; u < 4; ++u) t4[u] = sel(t8[2 * u], t8[2 * u + 1], s2);
-#pragma unroll
-                        for (int u = 0; u < 2; ++u) t2[u] = sel(t4[2 * u], t4[2 * u + 1], s3);
-                        sc = sel(t2[0], t2[1], s4);
-                    }
+                    if (multi) sc = select_by_bits<MB * 4>(val, b);  // (inline asm: see there)
                     const int rw = x0_o + wm * TM + 4 * fq + (b >> 2) * 16 + (b & 3);
                     wl_append(p && rw < row_end_o, make_key(sc, (unsigned)rw), q_o);
                 } while (__any(mask != 0u));
             }
         }
-        if (wl_n >= RING_WL_FLUSH) wl_flush();
+        if (wl.n >= RING_WL_FLUSH) wl_flush();
     };
 
     // ---- the k-step stream ------------------------------------------------------------------------------

@@ -377,7 +377,7 @@ def test_persistent_kernel_odd_qtile_counts(nq, tile):
         _assert_exact(ix, q, x, 10)
 
 
-@pytest.mark.parametrize("tile", [0, 1, 8, 9, 42, 46])
+@pytest.mark.parametrize("tile", [0, 1, 8, 9, 14, 42, 46])
 def test_subset_filtered_search(tile):
     """per-row labels + per-query allowed labels; exact top-k over the eligible rows only."""
     from oracle.flat_ip import topk_desc_tiebreak

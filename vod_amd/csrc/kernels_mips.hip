@@ -269,10 +269,8 @@ void mips_filter_kernel(
 // next slice (interval = M R M R for waves 4..7, R M R M for waves 0..3), and their tile epilogue moves into the next
 // tile's first interval, beside the partner's MFMAs.  Results are bit-identical (same products, same summation order).
 //
-// Survivors go to a per-wave list in LDS (positions from a ballot prefix: no atomic, no workgroup barrier) that the wave
-// itself flushes to the global candidate lists (exact-key test, subset test, one global atomic per record; all records of a
-// flush share the two memory round trips) when it holds WSTG_FLUSH records and at kernel end; a record that does not fit
-// is emitted directly.
+// Survivors go to a per-wave list in LDS (WaveSurvivorList, mips_common.h) that the wave flushes when it holds WSTG_FLUSH
+// records and at kernel end.
 constexpr int WSTG_CAP = 256;    // records per wave list (8 lists x 3 KB next to the two 64 KB operand slots)
 constexpr int WSTG_FLUSH = 176;  // flush when at least this many are pending (checked once per tile)
 constexpr int WSTG_BYTES = 8 * WSTG_CAP * 12;
@@ -384,60 +382,9 @@ __global__ __launch_bounds__(512, 2) void mips_filter16p_kernel(
 
     stage_part(0, 0, 0, 1);
 
-    // ---- per-wave survivor list ------------------------------------------------------------------
-    key_t64* const wl_key = (key_t64*)(smem + NSTAGE * STAGE_BYTES) + wave * WSTG_CAP;
-    int* const wl_q = (int*)(smem + NSTAGE * STAGE_BYTES + NWAVES * WSTG_CAP * 8) + wave * WSTG_CAP;
-    int wl_n = 0;  // wave-uniform
-    // A flush costs the wave (and, at the next barrier, its workgroup) two dependent global round trips - the exact-key
-    // test against thr_key, then the returning atomic that reserves the slot - whatever the number of records, so all
-    // (up to 4 per lane) go through each phase together and the list is sized to make flushes rare.
-    auto wl_flush = [&]() {
-        const int n = wl_n < WSTG_CAP ? wl_n : WSTG_CAP;
-        constexpr int PER_LANE = WSTG_CAP / 64;
-        key_t64 fk[PER_LANE];
-        int fq_[PER_LANE];
-        bool ok[PER_LANE];
-        unsigned slot[PER_LANE];
-#pragma unroll
-        for (int u = 0; u < PER_LANE; ++u) {
-            const int e = lane + 64 * u;
-            ok[u] = e < n;
-            fk[u] = ok[u] ? wl_key[e] : 0ull;
-            fq_[u] = ok[u] ? wl_q[e] : 0;
-        }
-#pragma unroll
-        for (int u = 0; u < PER_LANE; ++u) {
-            ok[u] = ok[u] && fk[u] > thr_key[fq_[u]];
-            if constexpr (SUBSET) ok[u] = ok[u] && subset_allows(ex, fq_[u], (int)(0xFFFFFFFFu - (unsigned)fk[u]));
-        }
-#pragma unroll
-        for (int u = 0; u < PER_LANE; ++u) slot[u] = ok[u] ? atomicAdd(&cnt[(size_t)fq_[u] * CNT_STRIDE], 1u) : 0u;
-#pragma unroll
-        for (int u = 0; u < PER_LANE; ++u) {
-            if (ok[u]) {
-                if (slot[u] < (unsigned)cap)
-                    cand[(size_t)fq_[u] * cap + slot[u]] = fk[u];
-                else
-                    atomicOr(overflow, 1u);
-            }
-        }
-        wl_n = 0;
-    };
-    // every lane with `p` appends (key, q): list position = wl_n + rank of the lane among the appending lanes
-    auto wl_append = [&](bool p, key_t64 key, int q) {
-        const unsigned long long bal = __ballot(p);
-        if (bal == 0ull) return;
-        const int pos = wl_n + (int)__builtin_amdgcn_mbcnt_hi((unsigned)(bal >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)bal, 0u));
-        if (p) {
-            if (pos < WSTG_CAP) {
-                wl_key[pos] = key;
-                wl_q[pos] = q;
-            } else {
-                emit_candidate<SUBSET>(key, q, thr_key, cand, cnt, cap, overflow, ex);
-            }
-        }
-        wl_n += __builtin_popcountll(bal);
-    };
+    // ---- per-wave survivor list (no wait after a flush or a direct emit: every slice starts with vmcnt(0)) -------------------------
+    WaveSurvivorList<WSTG_CAP, SUBSET> wl(smem + NSTAGE * STAGE_BYTES, NWAVES, wave);
+    const SurvivorOut out{thr_key, cand, cnt, cap, overflow, ex};
 
     struct Frags {
         u32x4 b[NB16], a[MB];
@@ -501,36 +448,15 @@ __global__ __launch_bounds__(512, 2) void mips_filter16p_kernel(
                         const int b = p ? __builtin_ctz(mask) : 0;
                         mask &= mask - 1u;
                         float sc = m;
-                        if (multi) {
-                            // register select by the bits of b: 16 + 8 + 4 + 2 + 1 v_cndmask.  Inline asm on purpose: written
-                            // as C++ selects LLVM rewrites the tree into an indexed load from a SCRATCH copy of the whole
-                            // accumulator, stored after every MFMA of the hot loop
-                            const unsigned long long s0 = __ballot(b & 1), s1 = __ballot(b & 2), s2 = __ballot(b & 4),
-                                                     s3 = __ballot(b & 8), s4 = __ballot(b & 16);
-                            auto sel = [](float lo, float hi, unsigned long long sm) {
-                                float r;
-                                asm("v_cndmask_b32_e64 %0, %1, %2, %3" : "=v"(r) : "v"(lo), "v"(hi), "s"(sm));
-                                return r;
-                            };
-                            float t16[16], t8[8], t4[4], t2[2];
-#pragma unroll
-                            for (int u = 0; u < 16; ++u) t16[u] = sel(val(2 * u), val(2 * u + 1), s0);
-#pragma unroll
-                            for (int u = 0; u < 8; ++u) t8[u] = sel(t16[2 * u], t16[2 * u + 1], s1);
-#pragma unroll
-                            for (int u = 0; u < 4; ++u) t4[u] = sel(t8[2 * u], t8[2 * u + 1], s2);
-#pragma unroll
-                            for (int u = 0; u < 2; ++u) t2[u] = sel(t4[2 * u], t4[2 * u + 1], s3);
-                            sc = sel(t2[0], t2[1], s4);
-                        }
+                        if (multi) sc = select_by_bits<MB * 4>(val, b);
                         const int rw = x0_o + wm * TM + 4 * fq + (b >> 2) * 16 + (b & 3);
-                        wl_append(p && rw < row_end_o, make_key(sc, (unsigned)rw), q);
+                        wl.append(p && rw < row_end_o, make_key(sc, (unsigned)rw), q, out);
                     } while (__any(mask != 0u));
                 }
             }
         }
         if constexpr (MODE == MODE_FILTER) {
-            if (wl_n >= WSTG_FLUSH) wl_flush();
+            if (wl.n >= WSTG_FLUSH) wl.flush(out);
         }
     };
 
@@ -651,7 +577,7 @@ __global__ __launch_bounds__(512, 2) void mips_filter16p_kernel(
             }
         }
     }
-    if constexpr (MODE == MODE_FILTER) wl_flush();
+    if constexpr (MODE == MODE_FILTER) wl.flush(out);
 }
 
 // ------------------------------------------------------------------------------------------------

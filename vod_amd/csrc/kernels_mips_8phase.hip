@@ -36,12 +36,7 @@ constexpr int P8_HALF = 128 * 128;         // one half-tile: 128 rows x 128 B
 constexpr int P8_OPERANDS = 8 * P8_HALF;   // 128 KB
 constexpr int P8_WL_CAP = 256;             // records per wave list
 constexpr int P8_WL_FLUSH = 176;
-#ifndef P8_TRANSPOSE_EMIT
-#define P8_TRANSPOSE_EMIT 1  // 0: the survivor path of rounds 1-6a (per-lane hit mask + select tree, no ring), kept for A/B builds
-#endif
-#ifndef P8_TRANSPOSE_MAX_LANES
-#define P8_TRANSPOSE_MAX_LANES 2  // query blocks in the loop with at most this many lanes holding survivors take the transpose path
-#endif
+constexpr int P8_TRANSPOSE_MAX_LANES = 2;  // query blocks in the loop with at most this many lanes holding survivors take the transpose path
 constexpr int P8_XPOSE = 8 * 2 * 32 * 4;   // survivor transpose: per wave 2 slots of a lane's 32 sums of one query (2 KB)
 constexpr int P8_DRAIN_RECORDS = 112;      // the ring's drain: records per LDS-DMA copy (14 KB + 448 B of metadata of a wave's 16 KB)
 constexpr int P8_SC1 = 16;                 // cache-policy immediate `sc1` (device scope): the load misses the CU's L1
@@ -169,44 +164,13 @@ __global__ __launch_bounds__(512, 2) void mips_filter8ph_kernel(
     for (int j = 0; j < NB16; ++j) asm volatile("" : "+v"(thr[j]));
     wait_vmcnt<0>();
 
-    // ---- per-wave survivor list (as in the persistent kernel) -------------------------------------
-    key_t64* const wl_key = (key_t64*)(smem + P8_OPERANDS) + wave * P8_WL_CAP;
-    int* const wl_q = (int*)(smem + P8_OPERANDS + NWAVES * P8_WL_CAP * 8) + wave * P8_WL_CAP;
-    int wl_n = 0;  // wave-uniform
-    [[maybe_unused]] float* const xpose = (float*)(smem + P8_OPERANDS + NWAVES * P8_WL_CAP * 12) + wave * 64;
-    auto wl_flush = [&]() {
-        const int n = wl_n < P8_WL_CAP ? wl_n : P8_WL_CAP;
-        constexpr int PER_LANE = P8_WL_CAP / 64;
-        key_t64 fk[PER_LANE];
-        int fq_[PER_LANE];
-        bool ok[PER_LANE];
-        unsigned slot[PER_LANE];
-#pragma unroll
-        for (int u = 0; u < PER_LANE; ++u) {
-            const int e = lane + 64 * u;
-            ok[u] = e < n;
-            fk[u] = ok[u] ? wl_key[e] : 0ull;
-            fq_[u] = ok[u] ? wl_q[e] : 0;
-        }
-#pragma unroll
-        for (int u = 0; u < PER_LANE; ++u) {
-            ok[u] = ok[u] && fk[u] > thr_key[fq_[u]];
-            if constexpr (SUBSET) ok[u] = ok[u] && subset_allows(ex, fq_[u], (int)(0xFFFFFFFFu - (unsigned)fk[u]));
-        }
-#pragma unroll
-        for (int u = 0; u < PER_LANE; ++u) slot[u] = ok[u] ? atomicAdd(&cnt[(size_t)fq_[u] * CNT_STRIDE], 1u) : 0u;
-#pragma unroll
-        for (int u = 0; u < PER_LANE; ++u) {
-            if (ok[u]) {
-                if (slot[u] < (unsigned)cap)
-                    cand[(size_t)fq_[u] * cap + slot[u]] = fk[u];
-                else
-                    atomicOr(overflow, 1u);
-            }
-        }
-        wl_n = 0;
-        wait_vmcnt<0>();  // the counted waits of the K loop must only ever see LDS-DMA pieces (loads and stores retire independently)
-    };
+    // ---- per-wave survivor list (mips_common.h, as in the persistent kernel of kernels_mips.hip).  After a flush or a direct emit:
+    // wait_vmcnt<0>(), the counted waits of the K loop must only ever see LDS-DMA pieces (loads and stores retire independently).
+    WaveSurvivorList<P8_WL_CAP, SUBSET> wl(smem + P8_OPERANDS, NWAVES, wave);
+    const SurvivorOut out{thr_key, cand, cnt, cap, overflow, ex};
+    auto wl_append = [&](bool p, key_t64 key, int q) { if (wl.append(p, key, q, out)) wait_vmcnt<0>(); };
+    auto wl_flush = [&]() { wl.flush(out); wait_vmcnt<0>(); };
+    float* const xpose = (float*)(smem + P8_OPERANDS + NWAVES * P8_WL_CAP * 12) + wave * 64;
     // ---- per-wave survivor ring: the 32 sums of a (hit lane, query block) + one metadata word (corpus tile row | block << 6 | lane) per
     // record, written during the K loop and turned into list entries after the last tile (the drain below).  ring_n: wave-uniform.
     const size_t ring_wave = (size_t)bid * NWAVES + wave;
@@ -214,23 +178,6 @@ __global__ __launch_bounds__(512, 2) void mips_filter8ph_kernel(
     unsigned* const ring_meta = (unsigned*)(ring + (size_t)gridDim.x * NWAVES * ring_cap * 32) + ring_wave * ring_cap;
     int ring_n = 0;
     int ring_fallbacks = 0;  // query blocks with survivors that took the in-loop path (wave-uniform; flag word [3] of `overflow`)
-    auto wl_append = [&](bool p, key_t64 key, int q) {
-        const unsigned long long bal = __ballot(p);
-        if (bal == 0ull) return;
-        const int pos = wl_n + (int)__builtin_amdgcn_mbcnt_hi((unsigned)(bal >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)bal, 0u));
-        bool direct = false;
-        if (p) {
-            if (pos < P8_WL_CAP) {
-                wl_key[pos] = key;
-                wl_q[pos] = q;
-            } else {
-                emit_candidate<SUBSET>(key, q, thr_key, cand, cnt, cap, overflow, ex);
-                direct = true;
-            }
-        }
-        wl_n += __builtin_popcountll(bal);
-        if (__any(direct)) wait_vmcnt<0>();
-    };
 
     f32x4 acc[MB][NB16];
     u32x4 fa[4], fb[2], fa1[4], fb1[2];  // the quadrant's fragments: k-step 0 (fa, fb) and k-step 1 (fa1, fb1)
@@ -350,25 +297,19 @@ __global__ __launch_bounds__(512, 2) void mips_filter8ph_kernel(
         (void)x0;
         return;
 #else
-#if P8_TRANSPOSE_EMIT
         // ... and the four tests: most tiles of a search's late stages hold no survivor for any of the wave's 64 queries - one branch, not four
         unsigned long long hl[NB16];
 #pragma unroll
         for (int j = 0; j < NB16; ++j) hl[j] = __ballot(mj[j] >= thr[j]);  // (false for NaN and for padded queries: thr = +inf)
         if ((hl[0] | hl[1] | hl[2] | hl[3]) == 0ull) {
-            if (wl_n >= P8_WL_FLUSH) wl_flush();
+            if (wl.n >= P8_WL_FLUSH) wl_flush();
             return;
         }
         static_assert(NB16 == 4, "the early-out above");
-#endif
 #pragma unroll
         for (int j = 0; j < NB16; ++j) {
             const float m = mj[j];
-#if !P8_TRANSPOSE_EMIT
-            const int q = q0 + wn * TN + j * 16 + fr;
-#endif
             const bool hit = m >= thr[j];  // false for NaN and for padded queries (thr = +inf)
-#if P8_TRANSPOSE_EMIT
             // The survivor path, two forms (the same records either way, in a different order: the select kernel's result does not
             // depend on it):
             //  * RING (the common case): every hit lane stores its 32 sums (8 x 16 B) and one metadata word to the next free record of the
@@ -417,6 +358,7 @@ __global__ __launch_bounds__(512, 2) void mips_filter8ph_kernel(
 #pragma unroll
                             for (int i = 0; i < MB; ++i) *(f32x4*)(dst + 4 * i) = acc[i][j];
                         }
+                        wave_lds_exchange();
                         const int l0 = __builtin_ctzll(rest);
                         rest &= rest - 1ull;
                         const bool two = rest != 0ull;
@@ -424,13 +366,14 @@ __global__ __launch_bounds__(512, 2) void mips_filter8ph_kernel(
                         rest &= rest - 1ull;  // (0 stays 0)
                         const float t0 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, thr[j]), l0));
                         const float t1 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, thr[j]), l1));
-                        const float sc = xpose[lane_o];  // (LDS operations of one wave execute in order: the stores above have landed)
+                        const float sc = xpose[lane_o];
                         const int src = half ? l1 : l0;
                         const float thr_src = half ? t1 : t0;
                         const int q_src = q0 + wn * TN + j * 16 + (src & 15);
                         const int rw = x0_o + wm * TM + 4 * (src >> 4) + (t >> 2) * 16 + (t & 3);
                         wl_append((half == 0 || two) && sc >= thr_src && rw < row_end_o, make_key(sc, (unsigned)rw), q_src);
                         done += 2;
+                        wave_lds_exchange();  // (this pass's loads before the next pass's stores)
                     } while (rest != 0ull);
                 };
                 if (__builtin_popcountll(hit_lanes) <= P8_TRANSPOSE_MAX_LANES) {
@@ -453,48 +396,7 @@ __global__ __launch_bounds__(512, 2) void mips_filter8ph_kernel(
                 }
             }
         }
-#else
-            if (__any(hit)) {
-                int x0_o = x0, row_end_o = row_end;
-                asm volatile("" : "+s"(x0_o), "+s"(row_end_o));
-                auto val = [&](int v) { return acc[v >> 2][j][v & 3]; };
-                unsigned mask = 0;
-                if (hit) {
-#pragma unroll
-                    for (int v = 0; v < MB * 4; ++v) mask |= (val(v) >= thr[j]) ? (1u << v) : 0u;
-                }
-                const bool multi = __any((mask & (mask - 1u)) != 0u);
-                do {
-                    const bool p = mask != 0u;
-                    const int b = p ? __builtin_ctz(mask) : 0;
-                    mask &= mask - 1u;
-                    float sc = m;
-                    if (multi) {
-                        const unsigned long long s0 = __ballot(b & 1), s1 = __ballot(b & 2), s2 = __ballot(b & 4), s3 = __ballot(b & 8),
-                                                 s4 = __ballot(b & 16);
-                        auto sel = [](float lo, float hi, unsigned long long sm) {
-                            float r;
-                            asm("v_cndmask_b32_e64 %0, %1, %2, %3" : "=v"(r) : "v"(lo), "v"(hi), "s"(sm));
-                            return r;
-                        };
-                        float t16[16], t8[8], t4[4], t2[2];
-#pragma unroll
-                        for (int u = 0; u < 16; ++u) t16[u] = sel(val(2 * u), val(2 * u + 1), s0);
-#pragma unroll
-                        for (int u = 0; u < 8; ++u) t8[u] = sel(t16[2 * u], t16[2 * u + 1], s1);
-#pragma unroll
-                        for (int u = 0; u < 4; ++u) t4[u] = sel(t8[2 * u], t8[2 * u + 1], s2);
-#pragma unroll
-                        for (int u = 0; u < 2; ++u) t2[u] = sel(t4[2 * u], t4[2 * u + 1], s3);
-                        sc = sel(t2[0], t2[1], s4);
-                    }
-                    const int rw = x0_o + wm * TM + 4 * fq + (b >> 2) * 16 + (b & 3);
-                    wl_append(p && rw < row_end_o, make_key(sc, (unsigned)rw), q);
-                } while (__any(mask != 0u));
-            }
-        }
-#endif
-        if (wl_n >= P8_WL_FLUSH) wl_flush();
+        if (wl.n >= P8_WL_FLUSH) wl_flush();
 #endif  // P8_ABL_NO_EMIT
 #endif  // P8_ABL_NO_EPILOGUE
     };
@@ -578,6 +480,7 @@ __global__ __launch_bounds__(512, 2) void mips_filter8ph_kernel(
 #pragma unroll
             for (int j = 0; j < NB16; ++j) xpose[j * 16 + fr] = thr[j];  // the thresholds by (block, query), for any lane to read
         }
+        wave_lds_exchange();
         char* const stage_w = smem + wave * (P8_OPERANDS / NWAVES);
         const float* const sums = (const float*)stage_w;
         const unsigned* const meta = (const unsigned*)(stage_w + P8_DRAIN_RECORDS * 128);
@@ -600,7 +503,7 @@ __global__ __launch_bounds__(512, 2) void mips_filter8ph_kernel(
             const int nr = min(ring_n - r0, P8_DRAIN_RECORDS);
             // two passes per step and one flush check: a pass appends <= 64 entries, so <= 128 before the step keeps the list in bounds
             for (int r4 = 0; r4 < nr; r4 += 4) {
-                if (wl_n > P8_WL_CAP - 128) wl_flush();
+                if (wl.n > P8_WL_CAP - 128) wl_flush();
                 const int r = r4 + half;
 #pragma unroll
                 for (int u = 0; u < 4; u += 2) {

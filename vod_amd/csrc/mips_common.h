@@ -1,5 +1,5 @@
 // Device helpers shared by the MIPS kernels (kernels_mips.hip): result-key packing, LDS-DMA, counted waits,
-// MFMA wrappers, the subset predicate and the direct (global-atomic) survivor append.
+// MFMA wrappers, the subset predicate, the per-wave survivor list and the direct (global-atomic) survivor append.
 #pragma once
 #include "vodhip_internal.h"
 
@@ -132,20 +132,131 @@ __device__ __forceinline__ bool subset_allows(const FilterExtra& ex, int q, int 
     return ok || !any;
 }
 
+// Where a FILTER launch's survivors go: the global candidate lists and what admits a key to them
+struct SurvivorOut {
+    const key_t64* thr_key;
+    key_t64* cand;
+    unsigned int* cnt;
+    int cap;
+    unsigned int* overflow;
+    const FilterExtra& ex;
+};
+
 // one survivor -> the query's global candidate list (exact-key test against the running k-th best, subset test)
 template <bool SUBSET>
-__device__ __forceinline__ void emit_candidate(key_t64 key, int q, const key_t64* __restrict__ thr_key,
-                                               key_t64* __restrict__ cand, unsigned int* __restrict__ cnt, int cap,
-                                               unsigned int* __restrict__ overflow, const FilterExtra& ex) {
-    bool ok = key > thr_key[q];
-    if constexpr (SUBSET) ok = ok && subset_allows(ex, q, (int)(0xFFFFFFFFu - (unsigned)key));
+__device__ __forceinline__ void emit_candidate(key_t64 key, int q, const SurvivorOut& out) {
+    bool ok = key > out.thr_key[q];
+    if constexpr (SUBSET) ok = ok && subset_allows(out.ex, q, (int)(0xFFFFFFFFu - (unsigned)key));
     if (ok) {
-        const unsigned slot = atomicAdd(&cnt[(size_t)q * CNT_STRIDE], 1u);
-        if (slot < (unsigned)cap)
-            cand[(size_t)q * cap + slot] = key;
+        const unsigned slot = atomicAdd(&out.cnt[(size_t)q * CNT_STRIDE], 1u);
+        if (slot < (unsigned)out.cap)
+            out.cand[(size_t)q * out.cap + slot] = key;
         else
-            atomicOr(overflow, 1u);
+            atomicOr(out.overflow, 1u);
     }
+}
+
+// The per-wave survivor list of the persistent FILTER kernels: CAP (key, query) records of one wave in LDS.  The workgroup's lists
+// are one LDS area: `n_lists` key arrays (8 B per record), then as many query arrays (4 B per record).  A flush costs the wave two
+// dependent global round trips (the exact-key test against thr_key, then the returning atomic that reserves the slot) whatever the
+// number of records, so all (up to CAP / 64 per lane) go through each phase together and the lists are sized to make flushes rare.
+// Neither flush() nor a direct emit by append() waits for its global operations: which wait follows is the kernel's choice.
+template <int CAP, bool SUBSET>
+struct WaveSurvivorList {
+    key_t64* const key;
+    int* const q;
+    const int lane = (int)threadIdx.x & 63;
+    int n = 0;  // wave-uniform
+
+    __device__ WaveSurvivorList(char* area, int n_lists, int list)
+        : key((key_t64*)area + list * CAP), q((int*)(area + n_lists * CAP * 8) + list * CAP) {}
+
+    // every lane with `p` appends (k, qq): list position = n + rank of the lane among the appending lanes.  A lane whose position is
+    // past the end emits its record directly; returns whether any lane did.
+    __device__ bool append(bool p, key_t64 k, int qq, const SurvivorOut& out) {
+        const unsigned long long bal = __ballot(p);
+        if (bal == 0ull) return false;
+        const int pos = n + (int)__builtin_amdgcn_mbcnt_hi((unsigned)(bal >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)bal, 0u));
+        bool direct = false;
+        if (p) {
+            if (pos < CAP) {
+                key[pos] = k;
+                q[pos] = qq;
+            } else {
+                emit_candidate<SUBSET>(k, qq, out);
+                direct = true;
+            }
+        }
+        n += __builtin_popcountll(bal);
+        return __any(direct);
+    }
+
+    __device__ void flush(const SurvivorOut& out) {
+        const int m = n < CAP ? n : CAP;
+        constexpr int PER_LANE = (CAP + 63) / 64;
+        key_t64 fk[PER_LANE];
+        int fq[PER_LANE];
+        bool ok[PER_LANE];
+        unsigned slot[PER_LANE];
+#pragma unroll
+        for (int u = 0; u < PER_LANE; ++u) {
+            const int e = lane + 64 * u;
+            ok[u] = e < m;
+            fk[u] = ok[u] ? key[e] : 0ull;
+            fq[u] = ok[u] ? q[e] : 0;
+        }
+#pragma unroll
+        for (int u = 0; u < PER_LANE; ++u) {
+            ok[u] = ok[u] && fk[u] > out.thr_key[fq[u]];
+            if constexpr (SUBSET) ok[u] = ok[u] && subset_allows(out.ex, fq[u], (int)(0xFFFFFFFFu - (unsigned)fk[u]));
+        }
+#pragma unroll
+        for (int u = 0; u < PER_LANE; ++u) slot[u] = ok[u] ? atomicAdd(&out.cnt[(size_t)fq[u] * CNT_STRIDE], 1u) : 0u;
+#pragma unroll
+        for (int u = 0; u < PER_LANE; ++u) {
+            if (ok[u]) {
+                if (slot[u] < (unsigned)out.cap)
+                    out.cand[(size_t)fq[u] * out.cap + slot[u]] = fk[u];
+                else
+                    atomicOr(out.overflow, 1u);
+            }
+        }
+        n = 0;
+    }
+};
+
+// Register select of value b (0 .. N-1, N = 32 or 24) of the lane's `val(0 .. N-1)` by the ballots of the bits of b: a tree of
+// v_cndmask, 16 + 8 + 4 + 2 + 1 for 32 values, 12 + 6 + 3 + 1 + 1 for 24.  Inline asm on purpose: written as C++ selects LLVM rewrites
+// the tree into an indexed load from a SCRATCH copy of the whole accumulator, stored after every MFMA of the hot loop.
+template <int N, typename ValFn>
+__device__ __forceinline__ float select_by_bits(ValFn val, int b) {
+    static_assert(N == 32 || N == 24, "the select tree");
+    const unsigned long long s0 = __ballot(b & 1), s1 = __ballot(b & 2), s2 = __ballot(b & 4), s3 = __ballot(b & 8), s4 = __ballot(b & 16);
+    auto sel = [](float lo, float hi, unsigned long long sm) {
+        float r;
+        asm("v_cndmask_b32_e64 %0, %1, %2, %3" : "=v"(r) : "v"(lo), "v"(hi), "s"(sm));
+        return r;
+    };
+    float t1[N / 2], t2[N / 4], t3[N / 8];
+#pragma unroll
+    for (int u = 0; u < N / 2; ++u) t1[u] = sel(val(2 * u), val(2 * u + 1), s0);
+#pragma unroll
+    for (int u = 0; u < N / 4; ++u) t2[u] = sel(t1[2 * u], t1[2 * u + 1], s1);
+#pragma unroll
+    for (int u = 0; u < N / 8; ++u) t3[u] = sel(t2[2 * u], t2[2 * u + 1], s2);
+    if constexpr (N == 24) {
+        return sel(sel(t3[0], t3[1], s3), t3[2], s4);  // b < 16: bit 3 picks t3[0] / t3[1]; b >= 16: t3[2]
+    } else {
+        return sel(sel(t3[0], t3[1], s3), sel(t3[2], t3[3], s3), s4);
+    }
+}
+
+// Order a cross-lane exchange through LDS inside one wave: this lane's LDS stores before, another lane's loads of them after.  (The
+// wave's LDS operations execute in order; this keeps the compiler from moving or merging the accesses across the exchange.)
+__device__ __forceinline__ void wave_lds_exchange() {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
 // Append the survivors among NV scores of ONE query held by this lane: count first, reserve the slots with ONE
