@@ -310,6 +310,42 @@ int vodhip_retrieval_backward(const void* q, const void* s, int enc_dtype, int s
                               float* dq, float* ds, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * H5m retrieval metrics of the monitor that follows the loss: every (metric, topk) of one update in two launches.
+ * Replaces: RetrievalMonitor.update (src/vod_models/monitoring/monitor.py:83-105) with prepare_for_metric_computation /
+ *           _mask_rank_inputs (src/vod_models/monitoring/functional.py:15-25,164-178), the nine _compute_* functions
+ *           (functional.py:41-161) and MeanAggregator.update (src/vod_models/monitoring/aggregator.py:43-50).
+ * scores float32 [B, width] and relevances int64 [B, width] are DEVICE pointers, width <= 4096.  `specs` is a HOST array of
+ * n_specs <= VODHIP_MAX_METRIC_SPECS pairs (metric, topk); topk = 0 means no cut.  Per row: n_positives = count(relevance > 0)
+ * BEFORE masking; a NaN or +inf score becomes -inf with relevance 0; -inf is padding, ranked last and not masked; the row is
+ * ranked by score descending, ties to the smaller column (-0.0 ranks as +0.0; the reference's argsort is unstable), cut at topk.
+ *   MRR / HITRATE (0 or 1) / PRECISION (over the FINITE scores of the cut; 0/0 = NaN) / RECALL (over n_positives; 0/0 = NaN)
+ *   NDCG: graded relevances / log2(rank + 1), the ideal order taken over the CUT list; 0 where the ideal DCG is 0
+ *   KLDIV: log-softmax over the graded relevances of the cut's positives against log-softmax over its finite scores, summed
+ *          where both are finite; NaN without a positive in the cut
+ *   MIN / MAX over the finite scores of the cut (+inf / -inf without one)
+ *   ENTROPY: -(exp(score) * log_softmax(score)) summed over the finite entries - exp of the SCORE, as the reference has it
+ * values (DEVICE float32 [n_specs][B], may be NULL) receives the per-row values.  state (DEVICE float64 [n_specs][2], may be
+ * NULL) is updated in place: state[m][0] += sum, state[m][1] += count of the non-NaN row values of spec m, reduced in a fixed
+ * order (bit-reproducible).  With values == NULL the row values are kept in `workspace` (DEVICE, >= n_specs * B * 4 bytes).
+ * Invalid arguments return a negative status before anything is launched.
+ * ------------------------------------------------------------------------------------------- */
+#define VODHIP_METRIC_MRR 0
+#define VODHIP_METRIC_HITRATE 1
+#define VODHIP_METRIC_PRECISION 2
+#define VODHIP_METRIC_RECALL 3
+#define VODHIP_METRIC_NDCG 4
+#define VODHIP_METRIC_KLDIV 5
+#define VODHIP_METRIC_MIN 6
+#define VODHIP_METRIC_MAX 7
+#define VODHIP_METRIC_ENTROPY 8
+#define VODHIP_MAX_METRIC_SPECS 32
+int vodhip_retrieval_metrics(const float* scores, const int64_t* relevances, int64_t B, int width,
+                             const int32_t* specs /* HOST [n_specs][2]: metric, topk (0 = none) */, int n_specs,
+                             float* values /* DEVICE [n_specs][B], may be NULL */,
+                             double* state /* DEVICE [n_specs][2], += ; may be NULL */,
+                             void* workspace, int64_t workspace_bytes, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * H7  labeled priority sampling of the merged candidates (the collate stage right after the merge).
  * Replaces: _labeled_priority_sampling_2d_ / _labeled_priority_sampling_1d_ / _priority_sampling_1d
  *           (src/vod_dataloaders/core/sample.py:160-219,245-352) and the numba log-softmax helpers

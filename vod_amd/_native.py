@@ -90,6 +90,7 @@ SIGNATURES: dict[str, tuple] = {
         _i32, [_vp, _vp, _i32, _i32, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _i32, _c.c_float, _c.c_float, _c.c_float,
                _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp],
     ),
+    "vodhip_retrieval_metrics": (_i32, [_vp, _vp, _i64, _i32, _vp, _i32, _vp, _vp, _vp, _i64, _vp]),
     "vodhip_priority_sample": (
         _i32, [_vp, _vp, _vp, _i64, _i32, _i32, _i32, _c.c_float, _i32, _i32, _vp, _vp, _vp, _vp, _vp],
     ),

@@ -1239,6 +1239,32 @@ int vodhip_retrieval_backward(const void* q, const void* s, int enc_dtype, int s
     return 0;
 }
 
+int vodhip_retrieval_metrics(const float* scores, const int64_t* relevances, int64_t B, int width, const int32_t* specs, int n_specs,
+                             float* values, double* state, void* workspace, int64_t workspace_bytes, void* stream) {
+    if (B <= 0 || width <= 0) return fail("invalid sizes B=%lld width=%d", (long long)B, width);
+    if (width > 4096) return fail("width=%d exceeds 4096 candidates per row", width);
+    if (n_specs < 1 || n_specs > VODHIP_MAX_METRIC_SPECS) return fail("n_specs=%d is outside 1..%d", n_specs, VODHIP_MAX_METRIC_SPECS);
+    if (!scores || !relevances || !specs) return fail("NULL argument");
+    if (!values && !state) return fail("values and state are both NULL: nothing to compute");
+    MetricSpecs ms{};
+    ms.n = n_specs;
+    for (int i = 0; i < n_specs; ++i) {
+        const int metric = specs[2 * i], topk = specs[2 * i + 1];
+        if (metric < VODHIP_METRIC_MRR || metric > VODHIP_METRIC_ENTROPY) return fail("spec %d: unknown metric id %d", i, metric);
+        if (topk < 0) return fail("spec %d: topk=%d is negative (0 = no cut)", i, topk);
+        ms.metric[i] = metric;
+        ms.topk[i] = topk;
+    }
+    if (!values) {  // the per-row values live in the caller's workspace
+        const int64_t need = (int64_t)n_specs * B * (int64_t)sizeof(float);
+        if (!workspace || workspace_bytes < need)
+            return fail("workspace_bytes=%lld < %lld (n_specs * B floats, needed when values is NULL)", (long long)workspace_bytes, (long long)need);
+        values = (float*)workspace;
+    }
+    HIP_OK(launch_retrieval_metrics(scores, relevances, B, width, ms, values, state, (hipStream_t)stream));
+    return 0;
+}
+
 int vodhip_priority_sample(const float* scores, const uint8_t* labels, const float* noise, int64_t nq, int width,
                            int k_positive, int k_total, float temperature, int max_support_size, int normalized,
                            int64_t* out_samples, float* out_log_weights, uint8_t* out_labels, float* out_lse,

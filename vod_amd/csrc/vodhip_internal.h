@@ -266,4 +266,15 @@ hipError_t launch_gather_by_id(const int64_t* queries, int64_t n_queries, const 
                                int n_values, const float* const* values, const float* fill, float* const* outs,
                                hipStream_t stream);
 
+// ---- launchers (kernels_metrics.hip) ----------------------------------------------------------
+// the (metric, topk) list of one monitor update, passed to the kernel by value
+struct MetricSpecs {
+    int n;
+    int metric[32];  // VODHIP_METRIC_*
+    int topk[32];    // 0 = no cut
+};
+// per-row values -> values [specs.n][B] (required); state [specs.n][2] += (sum, count of the non-NaN values) when not NULL
+hipError_t launch_retrieval_metrics(const float* scores, const int64_t* relevances, int64_t B, int width, const MetricSpecs& specs,
+                                    float* values, double* state, hipStream_t stream);
+
 }  // namespace vodhip

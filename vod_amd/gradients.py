@@ -175,13 +175,17 @@ class GraphedRetrievalStep:
     of `batch` - write the step's inputs into them (`load(...)` copies, or produce them there), `replay()`, then read `output.loss`,
     `output.retriever_scores`, `output.diagnostics` and the gradients `dq` / `ds` (to continue into the encoders:
     `torch.autograd.backward([q_enc, s_enc], [step.dq, step.ds])`).  Shapes, dtypes and the set of optional fields are fixed at capture.
+    With `monitor=` (a `vod_amd.monitoring.RetrievalMonitor`) every replay also updates the monitor from the step's relevances and
+    `retriever_scores`: two more kernels in the same graph, no host work; read it with `monitor.get()` / `compute()` as usual.
     """
 
     def __init__(self, gradients: RetrievalGradients, *, batch_size: int, n_sections: int, hidden: int, sections_3d: bool = False,
-                 dtype: torch.dtype = torch.float32, device: torch.device | int = 0, sparse: bool = True, dense: bool = True):
+                 dtype: torch.dtype = torch.float32, device: torch.device | int = 0, sparse: bool = True, dense: bool = True,
+                 monitor: typ.Any = None):
         dev = torch.device("cuda", device) if isinstance(device, int) else torch.device(device)
         B, D, H = int(batch_size), int(n_sections), int(hidden)
         self.gradients = gradients
+        self.monitor = monitor  # a vod_amd.monitoring.RetrievalMonitor: its update is captured behind the loss and replayed with it
         self.query_encoding = torch.zeros((B, H), dtype=dtype, device=dev, requires_grad=True)
         self.section_encoding = torch.zeros(((B, D, H) if sections_3d else (D, H)), dtype=dtype, device=dev, requires_grad=True)
         self.batch = {"section__score": torch.zeros((B, D), device=dev), "section__relevance": torch.zeros((B, D), dtype=torch.int64, device=dev),
@@ -190,6 +194,11 @@ class GraphedRetrievalStep:
         self.batch["section__relevance"][:, 0] = 1  # a well-formed batch for the warm-up steps
         self.query_encoding.grad = torch.zeros_like(self.query_encoding)
         self.section_encoding.grad = torch.zeros_like(self.section_encoding)
+        # the warm-up steps run the monitor's update for real (its buffers must exist before the capture): its state is put back after them
+        kept = None
+        if monitor is not None:
+            monitor.to(dev)
+            kept = monitor.state.clone()
         # warm-up on a side stream (allocator pools, one-time driver calls such as the LDS attribute), then the capture
         side = torch.cuda.Stream(device=dev)
         side.wait_stream(torch.cuda.current_stream(dev))
@@ -197,6 +206,8 @@ class GraphedRetrievalStep:
             for _ in range(3):
                 self._step()
         torch.cuda.current_stream(dev).wait_stream(side)
+        if monitor is not None:
+            monitor.state.copy_(kept)
         torch.cuda.synchronize(dev)
         self.graph = torch.cuda.CUDAGraph()
         with torch.cuda.graph(self.graph):
@@ -207,6 +218,8 @@ class GraphedRetrievalStep:
         self.section_encoding.grad.zero_()
         out = self.gradients(batch=self.batch, query_encoding=self.query_encoding, section_encoding=self.section_encoding)
         out.loss.backward()
+        if self.monitor is not None:
+            self.monitor.update(self.batch, out)
         return out
 
     @property
