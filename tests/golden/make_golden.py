@@ -494,6 +494,75 @@ def gen_gradients_aux() -> None:
         5, 12, 32, False, 0.2, True, 36)
 
 
+def gen_gradients_edges() -> None:
+    """Row-kernel edges of RetrievalGradients, each in 2-D and 3-D, without and with all three auxiliary terms:
+    `padrow` (row 2 fully padded), `onelive` (row 2 keeps one live column, its positive), `tie` (row 2 has exactly two positives with
+    identical encodings and identical section__score: the self-supervision arg-max ties and takes the first) and `d1` (D = 1)."""
+    import torch
+
+    grad = M["gradients"]
+    RealmBatch = M["batch"].RealmBatch
+    aux_cfg = {"guidance": "sparse", "guidance_weight": 0.3, "self_supervision_weight": 0.4, "score_decay": 0.02}
+
+    def run(case, three_d, cfg, seed):
+        nq, nd, h = (5, 1, 32) if case == "d1" else (5, 12, 32)
+        fn = grad.RetrievalGradients(**cfg)
+        g = torch.Generator().manual_seed(seed)
+        q = 0.3 * torch.randn(nq, h, generator=g, dtype=torch.float32)
+        s = torch.randn(*((nq, nd, h) if three_d else (nd, h)), generator=g, dtype=torch.float32)
+        score = torch.randn(nq, nd, generator=g)
+        pad = torch.rand(nq, nd, generator=g) < 0.2
+        pad[:, 0] = False
+        rel = (torch.rand(nq, nd, generator=g) < 0.25).long()
+        rel[:, 0] = 1
+        if case == "padrow":
+            pad[2, :] = True
+        elif case == "onelive":
+            pad[2, 1:] = True
+        elif case == "tie":
+            pad[2, :] = False
+            rel[2, :] = 0
+            rel[2, 3] = rel[2, 7] = 1
+            score[2, 7] = score[2, 3]
+            if three_d:
+                s[2, 7] = s[2, 3]
+            else:
+                s[7] = s[3]
+        score = score.masked_fill(pad, -float("inf"))
+        q.requires_grad_(True)
+        s.requires_grad_(True)
+        sparse = (-2.0 + torch.randn(nq, nd, generator=g)).masked_fill(torch.rand(nq, nd, generator=g) < 0.2, float("nan"))
+        dense = torch.randn(nq, nd, generator=g).masked_fill(torch.rand(nq, nd, generator=g) < 0.2, float("nan"))
+        dummy = torch.zeros(1, dtype=torch.long)
+        batch = RealmBatch(
+            query__input_ids=dummy, query__attention_mask=dummy, query__id="", query__subset_ids=[], query__section_ids=[],
+            section__input_ids=dummy, section__attention_mask=dummy, section__id="",
+            section__relevance=rel, section__idx=torch.zeros(nq, nd, dtype=torch.long), section__score=score,
+            section__sparse=sparse, section__dense=dense, section__log_weight=torch.zeros(nq, nd),
+            section__lse_pos=torch.zeros(nq), section__lse_neg=torch.zeros(nq),
+        )
+        out = fn(batch=batch, query_encoding=q, section_encoding=s)
+        dq, ds = torch.autograd.grad(out.loss, [q, s])
+        if case == "tie":  # the fixture is only worth its name if the reference's own scores tie bit for bit
+            assert out.retriever_scores[2, 3] == out.retriever_scores[2, 7]
+        diag = {k: v.detach().numpy() for k, v in out.diagnostics.items()}
+        _save(
+            f"retrieval_edge_{case}_{'3d' if three_d else '2d'}_{'aux' if cfg else 'plain'}",
+            {"case": case, "three_d": three_d, "seed": seed, "config": cfg, "diagnostic_keys": list(out.diagnostics)},
+            q=q.detach().numpy(), s=s.detach().numpy(), score=score.numpy(), relevance=rel.numpy(),
+            sparse=sparse.numpy(), dense=dense.numpy(),
+            loss=out.loss.detach().numpy(), retriever_scores=out.retriever_scores.detach().numpy(),
+            dq=dq.numpy(), ds=ds.numpy(), **{f"diag_{k}": v for k, v in diag.items()},
+        )
+
+    seed = 60
+    for case in ("padrow", "onelive", "tie", "d1"):
+        for three_d in (False, True):
+            for cfg in ({}, aux_cfg):
+                seed += 1
+                run(case, three_d, cfg, seed)
+
+
 def gen_metrics() -> None:
     """`metrics_recall_ndcg`: the reference's retrieval metrics on seeded [B, N] scores / graded relevances with NaN, +inf and
     -inf scores, rows without positives and a row whose positives are all masked; topk in {None, 1, 5, 10}."""
@@ -554,6 +623,11 @@ if __name__ == "__main__":
         gen_metrics()
         (HERE / "manifest.json").write_text(json.dumps(manifest, indent=1, sort_keys=True))
         raise SystemExit(0)
+    if sys.argv[1:] == ["gradients_edges"]:
+        manifest.update(json.loads((HERE / "manifest.json").read_text()))
+        gen_gradients_edges()
+        (HERE / "manifest.json").write_text(json.dumps(manifest, indent=1, sort_keys=True))
+        raise SystemExit(0)
     if sys.argv[1:] == ["merge_corners"]:
         manifest.update(json.loads((HERE / "manifest.json").read_text()))
         gen_merge_corners()
@@ -568,6 +642,7 @@ if __name__ == "__main__":
     gen_search_plumbing()
     gen_gradients()
     gen_gradients_aux()
+    gen_gradients_edges()
     gen_metrics()
     gen_flat_ip()
     (HERE / "manifest.json").write_text(json.dumps(manifest, indent=1, sort_keys=True))

@@ -183,6 +183,64 @@ def test_auxiliary_losses_match_reference(name):
         np.testing.assert_allclose(out[key], g[f"diag_{key}"], **tol)
 
 
+EDGE_NAMES = [f"retrieval_edge_{case}_{dim}_{aux}" for case in ("padrow", "onelive", "tie", "d1") for dim in ("2d", "3d")
+              for aux in ("plain", "aux")]
+_GRAD_TOL = dict(rtol=1e-5, atol=1e-6)  # the float64 tests' own, above: the float32 mode must be at least as close
+
+
+def _check_retrieval_fixture(name, dtype):
+    g = _load(name)
+    params = MANIFEST[name]["params"]
+    out = ograd.retrieval_gradients(g["q"], g["s"], g["score"], g["relevance"], g["sparse"], g["dense"], dtype=dtype,
+                                    **params.get("config", {}))
+    for key in ("loss", "retriever_scores", "dq", "ds"):
+        assert np.asarray(out[key]).dtype == dtype, key
+    np.testing.assert_allclose(out["loss"], g["loss"], **_GRAD_TOL)
+    np.testing.assert_allclose(out["retriever_scores"], g["retriever_scores"], rtol=1e-5, atol=1e-5)
+    np.testing.assert_allclose(out["dq"], g["dq"], **_GRAD_TOL)
+    np.testing.assert_allclose(out["ds"], g["ds"], **_GRAD_TOL)
+    if "diagnostic_keys" in params:
+        for key in params["diagnostic_keys"]:
+            np.testing.assert_allclose(out[key], g[f"diag_{key}"], **_GRAD_TOL)
+    else:
+        for key in ("kl_score", "kl_sparse", "kl_dense"):
+            np.testing.assert_allclose(out[key], g[key], **_GRAD_TOL)
+    return g, out
+
+
+@pytest.mark.parametrize("name", ["retrieval_grad_2d", "retrieval_grad_3d", "retrieval_grad_nopos", "retrieval_grad_padded",
+                                  "retrieval_grad_inbatch"] + AUX_NAMES)
+def test_float32_oracle_matches_reference(name):
+    """`dtype=np.float32`: the same formulae in float32 NumPy reproduce the reference's float32 torch run as closely as float64 does."""
+    _check_retrieval_fixture(name, np.float32)
+
+
+@pytest.mark.parametrize("dtype", [np.float64, np.float32])
+@pytest.mark.parametrize("name", EDGE_NAMES)
+def test_row_edge_fixtures_match_reference(name, dtype):
+    """A fully padded row, a row with one live column, exactly tied positives and D = 1, each 2-D and 3-D, plain and with the three
+    auxiliary terms (reference-generated): the oracle in both dtypes, loss / scores / gradients / every diagnostic; no NaN anywhere."""
+    g, out = _check_retrieval_fixture(name, dtype)
+    case = MANIFEST[name]["params"]["case"]
+    pad = np.isneginf(g["score"])
+    assert np.isfinite(g["loss"]) and np.isfinite(g["dq"]).all() and np.isfinite(g["ds"]).all()
+    if case == "padrow":
+        assert pad[2].all() and not pad[[0, 1, 3, 4]].all(axis=1).any()
+        assert not g["dq"][2].any()  # the fully padded row sends no gradient
+    elif case == "onelive":
+        assert (~pad[2]).sum() == 1
+    elif case == "tie":
+        pos = np.flatnonzero(g["relevance"][2] > 0)
+        assert pos.tolist() == [3, 7] and g["retriever_scores"][2, 3] == g["retriever_scores"][2, 7]
+        assert out["retriever_scores"][2, 3] == out["retriever_scores"][2, 7]
+        if MANIFEST[name]["params"]["config"]:
+            # the arg-max takes the FIRST tied index: d_scores of the pair differ by the one-hot, weight / rows apart
+            gap = out["d_scores"][2, 7] - out["d_scores"][2, 3]
+            np.testing.assert_allclose(gap, 0.4 / 5, rtol=1e-5)
+    else:
+        assert g["score"].shape[1] == 1
+
+
 @pytest.mark.parametrize("name", ["flat_ip_exact_small", "flat_ip_exact_768"])
 def test_flat_ip_fixture_selfconsistent(name):
     """Build-owned fixture (faiss parity unpinned): blocked fp64 top-k == full-matrix lexsort, ties -> smaller id."""

@@ -419,7 +419,8 @@ __global__ __launch_bounds__(256) void small_gemm_kernel(const void* __restrict_
                                                          const float* __restrict__ alpha_ptr, int k_per_split,
                                                          int64_t c_split_stride) {
     // K tile 64.  Staging moves 4 consecutive elements of the unit-stride dimension per load (a 16-byte load for f32, 8 bytes for
-    // f16 / bf16) where the tile is interior and the row pitch keeps them aligned; the scalar loop handles edges and odd pitches.
+    // f16 / bf16) where the tile is interior and the base address and the row pitch keep them aligned; the scalar loop handles edges,
+    // odd pitches and misaligned bases.
     constexpr int TMN = 64, KT = 64;
     __shared__ float As[TMN][KT + 1];
     __shared__ float Bs[KT][TMN + 1];
@@ -440,7 +441,10 @@ __global__ __launch_bounds__(256) void small_gemm_kernel(const void* __restrict_
     // element (r, c) of a [R][Ccols] tile whose unit-stride dimension is `c`: src[(r0 + r) * pitch + c0 + c]
     auto stage_vec = [&](auto dt_tag, const void* src, int64_t pitch, int r0, int c0, int R_lim, int C_lim, auto store) {
         constexpr int DT = decltype(dt_tag)::value;
-        const bool vec_ok = (pitch % 4 == 0) && (c0 % 4 == 0) && r0 + TMN <= R_lim && c0 + KT <= C_lim && TMN == KT;
+        // (the base pointer too: a contiguous view that starts mid-storage has an aligned pitch and a misaligned first element)
+        constexpr uintptr_t VEC_BYTES = DT == 2 ? 16 : 8;
+        const bool vec_ok = (pitch % 4 == 0) && (c0 % 4 == 0) && ((uintptr_t)src % VEC_BYTES == 0) && r0 + TMN <= R_lim &&
+                            c0 + KT <= C_lim && TMN == KT;
         if (vec_ok) {
             for (int e = tid; e < TMN * (KT / 4); e += 256) {
                 const int r = e / (KT / 4), c = (e % (KT / 4)) * 4;

@@ -171,7 +171,9 @@ class GraphedRetrievalStep:
     Eager, a step of `RetrievalGradients` costs ~170-190 us of host time (two ctypes calls, four small allocations and ~80 us of torch
     autograd machinery around a custom Function) for ~90 us of kernels; a replay of the captured step is launch-free on the host:
     81 us (3-D, 64 x 32 x 768) / 118 us (in-batch, 64 x 2048 x 768) wall including the device synchronisation (tools/probe_h5_graph.py),
-    bit-identical to the eager step.  The captured step owns static buffers: `query_encoding`, `section_encoding`, the `section__*` fields
+    bit-identical to an eager step that accumulates into zeroed `.grad` buffers, as the captured one does (0 + (-0.0) = +0.0: where a
+    16-bit gradient underflows to -0.0, an eager backward into an empty `.grad` keeps the sign and the captured step returns +0.0).
+    The captured step owns static buffers: `query_encoding`, `section_encoding`, the `section__*` fields
     of `batch` - write the step's inputs into them (`load(...)` copies, or produce them there), `replay()`, then read `output.loss`,
     `output.retriever_scores`, `output.diagnostics` and the gradients `dq` / `ds` (to continue into the encoders:
     `torch.autograd.backward([q_enc, s_enc], [step.dq, step.ds])`).  Shapes, dtypes and the set of optional fields are fixed at capture.
