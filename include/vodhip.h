@@ -310,6 +310,46 @@ int vodhip_retrieval_backward(const void* q, const void* s, int enc_dtype, int s
                               float* dq, float* ds, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * H5l marginal likelihood of a retrieval-augmented LM: fused token log-probs, marginal loss and every gradient.
+ * Replaces: MarginalLikelihoodGradients.__call__ (src/vod_models/vod_gradients/marginal_likelihood.py:12-48) with
+ *           _compute_lm_logprobs (:51-66: shift, masked_fill, log_softmax over V, gather, masked_fill, masked mean over L),
+ *           _compute_retriever_scores (src/vod_models/vod_gradients/retrieval.py:186-203) and the autograd backward of those.
+ * Three calls on one stream, split so that a caller can reuse the token log-probs; all pointers DEVICE, nothing synchronises.
+ * lm_logits [N = B*D, L, V] contiguous, of `logits_dtype` (F32 | F16 | BF16), L >= 2, V and N*L below 2^31; input_ids int64 [N, L];
+ * attention_mask [N, L] with elements of `mask_elem_bytes` (1 | 2 | 4 | 8) bytes, live when any bit is set.
+ * Position t < L-1 of sequence n is LIVE when attention_mask[n, t+1] is; its target is input_ids[n, t+1].
+ *   vodhip_lm_token_logprob_forward: tok_logp float32 [N, L-1] = logits[n,t,target] - logsumexp_v logits[n,t,:]; tok_lse float32
+ *     [N, L-1, 2] = (row maximum, log sum exp(x - maximum)), kept for the backward.  Live rows are read once, 16 bytes per lane
+ *     when V * element size is a multiple of 16 and the base is 16-byte aligned; masked positions write zeros, and neither
+ *     their logits nor their ids are looked at.
+ *   vodhip_marginal_forward: q [B,H], s [D,H] | [B,D,H] of `enc_dtype`, score float32 [B,D] (-inf = padded section).
+ *     n = live positions of (b,d); lp_xz = sum of the live tok_logp / n; r = masked scores -> retriever_scores float32 [B,D];
+ *     a = log_softmax_d(r) + lp_xz; loss float32 [1] = -mean_b logsumexp_d a; d_scores float32 [B,D] = dLoss/dr;
+ *     coef float32 [B,D] = -exp(a - logsumexp_d a) / (B n).  workspace: workspace_floats >= B floats; with >= B + 4*B*D
+ *     (2-D sections, H >= 512) the in-batch contraction is split over K into four slabs.  D <= 8192, and H + 3*D + 4 floats must fit 160 KiB.
+ *     dq / ds follow from d_scores with vodhip_retrieval_backward.
+ *   vodhip_lm_token_logprob_backward: d_logits [N, L, V] of `logits_dtype` = *grad_out * coef[n] * (1[v = target] - softmax_v)
+ *     at live positions, exactly 0 at masked positions and at t = L-1: one read and one write of the tensor.
+ * NaN rules (the reference raises an index error instead, which would need a host synchronisation): a LIVE target outside
+ * [0, V-2] (the reference gathers from log_softmax(...)[..., :-1]) gives tok_logp = NaN, hence a NaN loss, with finite
+ * retriever_scores; ids are compared before they index.  n = 0 gives NaN (0 / 0); a row whose sections are all padded gives
+ * NaN.  -inf logits are legal, at the target too (that section then carries zero posterior; every gradient stays finite).
+ * No atomics: two runs are bitwise equal.
+ * ------------------------------------------------------------------------------------------- */
+int vodhip_lm_token_logprob_forward(const void* lm_logits, int logits_dtype, int64_t N, int64_t L, int64_t V,
+                                    const int64_t* input_ids, const void* attention_mask, int mask_elem_bytes,
+                                    float* tok_logp, float* tok_lse, void* stream);
+int vodhip_marginal_forward(const void* q, const void* s, int enc_dtype, int sections_3d,
+                            int64_t B, int64_t D, int64_t H, const float* score, const float* tok_logp,
+                            const void* attention_mask, int mask_elem_bytes, int64_t L,
+                            float* retriever_scores, float* d_scores, float* coef, float* loss,
+                            float* workspace /* DEVICE scratch */, int64_t workspace_floats, void* stream);
+int vodhip_lm_token_logprob_backward(const void* lm_logits, int logits_dtype, int64_t N, int64_t L, int64_t V,
+                                     const int64_t* input_ids, const void* attention_mask, int mask_elem_bytes,
+                                     const float* tok_lse, const float* coef, const float* grad_out,
+                                     void* d_logits, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * H5m retrieval metrics of the monitor that follows the loss: every (metric, topk) of one update in two launches.
  * Replaces: RetrievalMonitor.update (src/vod_models/monitoring/monitor.py:83-105) with prepare_for_metric_computation /
  *           _mask_rank_inputs (src/vod_models/monitoring/functional.py:15-25,164-178), the nine _compute_* functions

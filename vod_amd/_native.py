@@ -101,6 +101,12 @@ SIGNATURES: dict[str, tuple] = {
     "vodhip_collate": (_i32, [_vp, _vp]),
     "vodhip_flatten_inbatch": (_i32, [_vp, _i64, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "vodhip_retrieval_backward": (_i32, [_vp, _vp, _i32, _i32, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp]),
+    # H5l marginal likelihood (kernels_marginal.hip)
+    "vodhip_lm_token_logprob_forward": (_i32, [_vp, _i32, _i64, _i64, _i64, _vp, _vp, _i32, _vp, _vp, _vp]),
+    "vodhip_marginal_forward": (
+        _i32, [_vp, _vp, _i32, _i32, _i64, _i64, _i64, _vp, _vp, _vp, _i32, _i64, _vp, _vp, _vp, _vp, _vp, _i64, _vp],
+    ),
+    "vodhip_lm_token_logprob_backward": (_i32, [_vp, _i32, _i64, _i64, _i64, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp]),
     "vodhip_gather_by_id": (_i32, [_vp, _i64, _vp, _i64, _i32, _i32, _vp, _vp, _vp, _vp]),
     "vodhip_b64url_encode": (_i64, [_vp, _i64, _vp, _i64, _vp]),
     "vodhip_b64url_decode": (_i64, [_vp, _i64, _vp]),

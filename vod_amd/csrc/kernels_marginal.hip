@@ -1,0 +1,450 @@
+// Marginal-likelihood objective of a retrieval-augmented LM (REALM), forward and backward, on gfx950.
+//
+// Replaces the reference's src/vod_models/vod_gradients/marginal_likelihood.py:
+//   MarginalLikelihoodGradients.__call__ :12-48, _compute_lm_logprobs :51-66 (shift, masked_fill, log_softmax over V, gather,
+//   masked_fill, masked mean over L) and the autograd backward of those.
+//
+// lm_logits is [B, D, L, V] (~1 GB in bf16 at 8 x 8 x 256 x 32128): the stage is a memory-bound stream, unlike the launch-bound
+// retrieval loss next door.  Three kernels touch it as little as the arithmetic allows:
+//   lm_token_forward_kernel   one workgroup per (b, d, t < L-1): live rows are read ONCE (online max / sum-exp), masked rows not at all;
+//                             leaves the token log-prob and the row's (max, log sum-exp) = 3 floats per token
+//   marginal_row_kernel       one workgroup per query row b: masked mean over L, the retriever scores, the marginal, dLoss/dScores
+//                             and coef[b,d] = dLoss/d(sum of the live token log-probs of (b,d))
+//   lm_token_backward_kernel  one workgroup per (b, d, t): one read and one write of the tensor, softmax recomputed from the saved
+//                             (max, log sum-exp) - no max / sum pass
+// No atomics (bitwise reproducible), no device allocation, no host synchronisation: one dependent chain on the caller's stream.
+#include "vodhip_internal.h"
+#include "row_reduce.h"
+
+#include <algorithm>
+
+namespace vodhip {
+
+constexpr int ML_THREADS = 256;
+// rows of at most this many 16-byte vectors (8 KiB) go to a one-wave workgroup: a 256-thread group would idle 3 of its 4 waves and
+// pay two barriers for the cross-wave reduction
+constexpr int ML_WAVE_ROW_VECS = 512;
+
+__device__ __forceinline__ bool mask_live(const void* mask, int64_t i, int eb) {
+    switch (eb) {
+        case 1: return ((const uint8_t*)mask)[i] != 0;
+        case 2: return ((const uint16_t*)mask)[i] != 0;
+        case 4: return ((const uint32_t*)mask)[i] != 0;
+        default: return ((const uint64_t*)mask)[i] != 0;
+    }
+}
+
+template <int DT>
+constexpr int elems_per_vec() { return DT == 2 ? 4 : 8; }
+
+// 16 bytes of logits -> 4 (f32) or 8 (f16 / bf16) floats
+template <int DT>
+__device__ __forceinline__ void unpack16(const uint4& raw, float* v) {
+    const unsigned w[4] = {raw.x, raw.y, raw.z, raw.w};
+    if constexpr (DT == 2) {
+#pragma unroll
+        for (int u = 0; u < 4; ++u) v[u] = __builtin_bit_cast(float, w[u]);
+    } else {
+#pragma unroll
+        for (int u = 0; u < 8; ++u) {
+            const uint16_t h = (uint16_t)(w[u >> 1] >> (16 * (u & 1)));
+            if constexpr (DT == 0) v[u] = (float)__builtin_bit_cast(_Float16, h);
+            else v[u] = __builtin_bit_cast(float, (unsigned)h << 16);
+        }
+    }
+}
+
+template <int DT>
+__device__ __forceinline__ uint16_t to_bits16(float v) {
+    if constexpr (DT == 0) return __builtin_bit_cast(uint16_t, (_Float16)v);
+    else return __builtin_bit_cast(uint16_t, (__bf16)v);  // round to nearest even
+}
+
+template <int DT>
+__device__ __forceinline__ uint4 pack16(const float* v) {
+    unsigned w[4];
+    if constexpr (DT == 2) {
+#pragma unroll
+        for (int u = 0; u < 4; ++u) w[u] = __builtin_bit_cast(unsigned, v[u]);
+    } else {
+#pragma unroll
+        for (int u = 0; u < 4; ++u) w[u] = (unsigned)to_bits16<DT>(v[2 * u]) | ((unsigned)to_bits16<DT>(v[2 * u + 1]) << 16);
+    }
+    return make_uint4(w[0], w[1], w[2], w[3]);
+}
+
+template <int DT>
+__device__ __forceinline__ void st_enc(void* p, int64_t i, float v) {
+    if constexpr (DT == 2) ((float*)p)[i] = v;
+    else if constexpr (DT == 0) ((_Float16*)p)[i] = (_Float16)v;
+    else ((__bf16*)p)[i] = (__bf16)v;
+}
+
+// running (max, sum of exp(x - max)) of one lane, fed N values at a time: one rescale per group instead of one per value
+template <int N>
+__device__ __forceinline__ void online_absorb(float& m, float& s, const float* v) {
+    float vm = v[0];
+#pragma unroll
+    for (int u = 1; u < N; ++u) vm = fmaxf(vm, v[u]);
+    if (vm > m) {
+        s *= __expf(m - vm);  // m = -inf: s is 0 and stays 0
+        m = vm;
+    }
+    if (m > -__builtin_inff()) {  // a maximum that is still -inf: every value so far is -inf and adds nothing (-inf - -inf = NaN)
+#pragma unroll
+        for (int u = 0; u < N; ++u) s += __expf(v[u] - m);
+    }
+}
+
+__device__ __forceinline__ void online_merge(float& m, float& s, float m2, float s2) {
+    const float mn = fmaxf(m, m2);
+    const float sh = mn > -__builtin_inff() ? mn : 0.f;
+    s = s * expf(m - sh) + s2 * expf(m2 - sh);
+    m = mn;
+}
+
+// ------------------------------------------------------------------------------------------------
+// 1. token forward.  blockIdx.x = bd * (L-1) + t.  tok_logp[pos] = logits[bd,t,ids[bd,t+1]] - logsumexp_v logits[bd,t,:]
+//    tok_lse[pos] = (row max, log sum exp(x - max)): kept apart so that the backward's exp((x - max) - log sum) is as exact at
+//    |logits| ~ 1e4 as at 1 (max + log sum in one float carries half an ulp of 1e4 = 5e-4 into every probability).
+//    Masked positions write zeros and never touch the row.  A live target outside [0, V-2] gives NaN (it is never an index).
+// ------------------------------------------------------------------------------------------------
+template <int DT, int T>
+__global__ __launch_bounds__(T) void lm_token_forward_kernel(const void* __restrict__ logits, int64_t L, int64_t V,
+                                                             const int64_t* __restrict__ ids, const void* __restrict__ mask,
+                                                             int mask_eb, int vec, float* __restrict__ tok_logp,
+                                                             float* __restrict__ tok_lse) {
+    constexpr int EPV = elems_per_vec<DT>();
+    const int64_t pos = blockIdx.x;
+    const int64_t bd = pos / (L - 1), t = pos - bd * (L - 1);
+    const int64_t nxt = bd * L + t + 1;
+    const int tid = threadIdx.x;
+    if (!mask_live(mask, nxt, mask_eb)) {
+        if (tid == 0) {
+            tok_logp[pos] = 0.f;
+            tok_lse[2 * pos] = 0.f;
+            tok_lse[2 * pos + 1] = 0.f;
+        }
+        return;
+    }
+    const int64_t base = (bd * L + t) * V;  // in elements
+    float m = -__builtin_inff(), s = 0.f;
+    if (vec) {
+        const uint4* __restrict__ r4 = (const uint4*)((const char*)logits + base * (DT == 2 ? 4 : 2));
+        const int nvec = (int)(V / EPV);
+        int i = tid;
+        for (; i + 3 * T < nvec; i += 4 * T) {  // four loads in flight per lane
+            const uint4 a = r4[i], b = r4[i + T], c = r4[i + 2 * T], d = r4[i + 3 * T];
+            float v[EPV];
+            unpack16<DT>(a, v);
+            online_absorb<EPV>(m, s, v);
+            unpack16<DT>(b, v);
+            online_absorb<EPV>(m, s, v);
+            unpack16<DT>(c, v);
+            online_absorb<EPV>(m, s, v);
+            unpack16<DT>(d, v);
+            online_absorb<EPV>(m, s, v);
+        }
+        for (; i < nvec; i += T) {
+            float v[EPV];
+            unpack16<DT>(r4[i], v);
+            online_absorb<EPV>(m, s, v);
+        }
+    } else {
+        for (int64_t e = tid; e < V; e += T) {
+            const float x = ld_enc<DT>(logits, base + e);
+            online_absorb<1>(m, s, &x);
+        }
+    }
+    // lanes -> wave (butterfly: every lane ends with the same pair), waves -> workgroup through LDS in wave order
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const float m2 = __shfl_xor(m, o), s2 = __shfl_xor(s, o);
+        online_merge(m, s, m2, s2);
+    }
+    if constexpr (T > 64) {
+        __shared__ float red_m[T / 64], red_s[T / 64];
+        if ((tid & 63) == 0) {
+            red_m[tid >> 6] = m;
+            red_s[tid >> 6] = s;
+        }
+        __syncthreads();
+        if (tid == 0) {
+            m = red_m[0], s = red_s[0];
+#pragma unroll
+            for (int w = 1; w < T / 64; ++w) online_merge(m, s, red_m[w], red_s[w]);
+        }
+    }
+    if (tid == 0) {
+        const float lg = logf(s);
+        const int64_t tgt = ids[nxt];
+        const bool ok = tgt >= 0 && tgt < V - 1;  // the reference gathers from log_softmax(...)[..., :-1]
+        tok_logp[pos] = ok ? (ld_enc<DT>(logits, base + tgt) - m) - lg : __builtin_nanf("");
+        tok_lse[2 * pos] = m;
+        tok_lse[2 * pos + 1] = lg;
+    }
+}
+
+// ------------------------------------------------------------------------------------------------
+// 3. logits backward.  blockIdx.x = bd * L + t.  d_logits[bd,t,v] = go * coef[bd] * (1[v == tgt] - exp((x_v - max) - log sum)) at
+//    live positions, 0 at masked positions and at t = L-1.
+// ------------------------------------------------------------------------------------------------
+template <int DT, int T>
+__global__ __launch_bounds__(T) void lm_token_backward_kernel(const void* __restrict__ logits, int64_t L, int64_t V,
+                                                              const int64_t* __restrict__ ids, const void* __restrict__ mask,
+                                                              int mask_eb, int vec, const float* __restrict__ tok_lse,
+                                                              const float* __restrict__ coef, const float* __restrict__ grad_out,
+                                                              void* __restrict__ d_logits) {
+    constexpr int EPV = elems_per_vec<DT>();
+    constexpr int ES = DT == 2 ? 4 : 2;
+    const int64_t pos = blockIdx.x;
+    const int64_t bd = pos / L, t = pos - bd * L;
+    const int tid = threadIdx.x;
+    const int64_t base = pos * V;
+    const bool live = t < L - 1 && mask_live(mask, pos + 1, mask_eb);
+    if (!live) {
+        if (vec) {
+            uint4* __restrict__ o4 = (uint4*)((char*)d_logits + base * ES);
+            const int nvec = (int)(V / EPV);
+            const uint4 z = make_uint4(0u, 0u, 0u, 0u);
+            for (int i = tid; i < nvec; i += T) o4[i] = z;
+        } else {
+            for (int64_t e = tid; e < V; e += T) st_enc<DT>(d_logits, base + e, 0.f);
+        }
+        return;
+    }
+    const int64_t tgt64 = ids[pos + 1];
+    const int tgt = (tgt64 >= 0 && tgt64 < V - 1) ? (int)tgt64 : -1;  // an invalid live target: coef is NaN already, nothing to mark
+    const int64_t sp = bd * (L - 1) + t;
+    const float m = tok_lse[2 * sp], lg = tok_lse[2 * sp + 1];
+    const float c = grad_out[0] * coef[bd];
+    if (vec) {
+        const uint4* __restrict__ r4 = (const uint4*)((const char*)logits + base * ES);
+        uint4* __restrict__ o4 = (uint4*)((char*)d_logits + base * ES);
+        const int nvec = (int)(V / EPV);
+        auto one = [&](const uint4& raw, int i) {
+            float v[EPV];
+            unpack16<DT>(raw, v);
+#pragma unroll
+            for (int u = 0; u < EPV; ++u) v[u] = c * ((i * EPV + u == tgt ? 1.f : 0.f) - __expf((v[u] - m) - lg));
+            o4[i] = pack16<DT>(v);
+        };
+        int i = tid;
+        for (; i + 3 * T < nvec; i += 4 * T) {
+            const uint4 a = r4[i], b = r4[i + T], cc = r4[i + 2 * T], d = r4[i + 3 * T];
+            one(a, i);
+            one(b, i + T);
+            one(cc, i + 2 * T);
+            one(d, i + 3 * T);
+        }
+        for (; i < nvec; i += T) one(r4[i], i);
+    } else {
+        for (int64_t e = tid; e < V; e += T) {
+            const float x = ld_enc<DT>(logits, base + e);
+            st_enc<DT>(d_logits, base + e, c * ((e == tgt ? 1.f : 0.f) - __expf((x - m) - lg)));
+        }
+    }
+}
+
+// ------------------------------------------------------------------------------------------------
+// 2. row kernel.  One 256-thread workgroup per query row b:
+//      lp_xz[d] = sum_{live t} tok_logp[b,d,t] / n[d]           (n = 0: NaN, the reference's 0 / 0)
+//      r[d]     = <q[b], s[(b,)d]>, -inf where section__score is -inf        -> retriever_scores
+//      lp_r = log_softmax_d r ; a = lp_r + lp_xz ; lp_x = logsumexp_d a      -> row partial
+//      post = exp(a - lp_x), p = exp(lp_r) ; d_scores = (p - post) / B (0 at padded sections) ; coef = -post / (B n)
+// ------------------------------------------------------------------------------------------------
+template <int DT, bool S3D, bool PRE>
+__global__ __launch_bounds__(ML_THREADS) void marginal_row_kernel(
+    const void* __restrict__ q, const void* __restrict__ s, int D, int H, const float* __restrict__ score,
+    const float* __restrict__ tok_logp, const void* __restrict__ mask, int mask_eb, int64_t L,
+    // no `restrict` on the two score outputs: with one slab the contraction was written INTO retriever_scores (read to LDS first)
+    float* retriever_scores, float* d_scores, float* __restrict__ coef, float* __restrict__ row_lpx, float inv_B,
+    const float* pre_slabs, int n_slabs, int64_t slab_stride) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    float* qrow = (float*)smem;  // [H]
+    float* S = qrow + H;         // [D] scores -> a = lp_r + lp_xz
+    float* X = S + D;            // [D] lp_xz
+    float* Nn = X + D;           // [D] live tokens
+    float* red = Nn + D;         // [4]
+    const int64_t b = blockIdx.x;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const float ninf = -__builtin_inff();
+
+    if constexpr (PRE) {
+        // the contraction was done by small_gemm_kernel (MFMA) in `n_slabs` split-K slabs: summed here in slab order
+        for (int d = tid; d < D; d += ML_THREADS) {
+            float acc = pre_slabs[b * D + d];
+            for (int z = 1; z < n_slabs; ++z) acc += pre_slabs[(int64_t)z * slab_stride + b * D + d];
+            S[d] = acc;
+        }
+    } else {
+        for (int h = tid; h < H; h += ML_THREADS) qrow[h] = ld_enc<DT>(q, b * H + h);
+        __syncthreads();
+        // one wavefront per section, lanes split the hidden dimension (coalesced reads of s)
+        const int64_t s_base = S3D ? b * (int64_t)D * H : 0;
+        for (int d = wave; d < D; d += ML_THREADS / 64) {
+            const int64_t off = s_base + (int64_t)d * H;
+            float acc = 0.f;
+            for (int h = lane; h < H; h += 64) acc = fmaf(qrow[h], ld_enc<DT>(s, off + h), acc);
+            acc = wave_sum(acc);
+            if (lane == 0) S[d] = acc;
+        }
+    }
+    // masked mean of the token log-probs: one wavefront per section, lanes split L, fixed order
+    for (int d = wave; d < D; d += ML_THREADS / 64) {
+        const int64_t bd = b * D + d;
+        float acc = 0.f, cnt = 0.f;
+        for (int64_t t = lane; t < L - 1; t += 64) {
+            if (mask_live(mask, bd * L + t + 1, mask_eb)) {
+                acc += tok_logp[bd * (L - 1) + t];
+                cnt += 1.f;
+            }
+        }
+        acc = wave_sum(acc);
+        cnt = wave_sum(cnt);
+        if (lane == 0) {
+            X[d] = acc / cnt;
+            Nn[d] = cnt;
+        }
+    }
+    __syncthreads();
+
+    const float* score_row = score + b * D;
+    float mx = ninf;
+    for (int d = tid; d < D; d += ML_THREADS) {
+        const float sc = score_row[d];
+        const bool pad = __builtin_isinf(sc) && sc < 0;
+        const float v = pad ? ninf : S[d];
+        S[d] = v;
+        retriever_scores[b * D + d] = v;
+        mx = fmaxf(mx, v);
+    }
+    mx = block_max(mx, red);
+    float se = 0.f;
+    for (int d = tid; d < D; d += ML_THREADS) se += expf(S[d] - mx);  // an all-padded row: NaN, exactly as torch
+    se = block_sum(se, red);
+    const float lse = logf(se);
+    float amax = ninf;
+    for (int d = tid; d < D; d += ML_THREADS) {
+        const float lp_r = S[d] - mx - lse;
+        d_scores[b * D + d] = lp_r;  // parked until the posterior is known
+        const float a = lp_r + X[d];
+        S[d] = a;
+        amax = fmaxf(amax, a);  // (skips NaN: the sum below does not)
+    }
+    amax = block_max(amax, red);
+    const float ash = amax > ninf ? amax : 0.f;  // every a = -inf: lp_x = -inf like torch.logsumexp, not NaN
+    float ae = 0.f;
+    for (int d = tid; d < D; d += ML_THREADS) ae += expf(S[d] - ash);
+    ae = block_sum(ae, red);
+    const float lp_x = ash + logf(ae);
+    for (int d = tid; d < D; d += ML_THREADS) {
+        const float sc = score_row[d];
+        const bool pad = __builtin_isinf(sc) && sc < 0;
+        const float post = expf(S[d] - lp_x);
+        const float p = expf(d_scores[b * D + d]);
+        d_scores[b * D + d] = pad ? 0.f : (p - post) * inv_B;
+        coef[b * D + d] = -post * inv_B / Nn[d];
+    }
+    if (tid == 0) row_lpx[b] = lp_x;
+}
+
+__global__ __launch_bounds__(ML_THREADS) void marginal_finalize_kernel(const float* __restrict__ row_lpx, int B,
+                                                                       float* __restrict__ loss) {
+    __shared__ float red[4];
+    float acc = 0.f;
+    for (int b = threadIdx.x; b < B; b += ML_THREADS) acc += row_lpx[b];
+    acc = block_sum(acc, red);
+    if (threadIdx.x == 0) loss[0] = -acc / (float)B;
+}
+
+// 16-byte accesses need every row base on a 16-byte boundary: the tensor's and a row's pitch
+static bool rows_aligned(const void* p, int64_t V, int dtype) {
+    const int64_t es = dtype == 2 ? 4 : 2;
+    return ((uintptr_t)p % 16 == 0) && (V * es % 16 == 0);
+}
+
+hipError_t launch_lm_token_forward(const void* logits, int dtype, int64_t N, int64_t L, int64_t V, const int64_t* ids,
+                                   const void* mask, int mask_eb, float* tok_logp, float* tok_lse, hipStream_t stream) {
+    const int vec = rows_aligned(logits, V, dtype) ? 1 : 0;
+    const int64_t row_vecs = (V * (dtype == 2 ? 4 : 2) + 15) / 16;
+    const dim3 grid((unsigned)(N * (L - 1)));
+#define VOD_TF(DT, T)                                                                                                    \
+    if (dtype == DT && (row_vecs <= ML_WAVE_ROW_VECS) == (T == 64)) {                                                    \
+        hipLaunchKernelGGL((lm_token_forward_kernel<DT, T>), grid, dim3(T), 0, stream, logits, L, V, ids, mask, mask_eb, \
+                           vec, tok_logp, tok_lse);                                                                      \
+        return hipGetLastError();                                                                                        \
+    }
+    VOD_TF(0, 64) VOD_TF(0, ML_THREADS) VOD_TF(1, 64) VOD_TF(1, ML_THREADS) VOD_TF(2, 64) VOD_TF(2, ML_THREADS)
+#undef VOD_TF
+    return hipErrorInvalidValue;
+}
+
+hipError_t launch_lm_token_backward(const void* logits, int dtype, int64_t N, int64_t L, int64_t V, const int64_t* ids,
+                                    const void* mask, int mask_eb, const float* tok_lse, const float* coef, const float* grad_out,
+                                    void* d_logits, hipStream_t stream) {
+    const int vec = (rows_aligned(logits, V, dtype) && rows_aligned(d_logits, V, dtype)) ? 1 : 0;
+    const int64_t row_vecs = (V * (dtype == 2 ? 4 : 2) + 15) / 16;
+    const dim3 grid((unsigned)(N * L));
+#define VOD_TB(DT, T)                                                                                                     \
+    if (dtype == DT && (row_vecs <= ML_WAVE_ROW_VECS) == (T == 64)) {                                                     \
+        hipLaunchKernelGGL((lm_token_backward_kernel<DT, T>), grid, dim3(T), 0, stream, logits, L, V, ids, mask, mask_eb, \
+                           vec, tok_lse, coef, grad_out, d_logits);                                                       \
+        return hipGetLastError();                                                                                         \
+    }
+    VOD_TB(0, 64) VOD_TB(0, ML_THREADS) VOD_TB(1, 64) VOD_TB(1, ML_THREADS) VOD_TB(2, 64) VOD_TB(2, ML_THREADS)
+#undef VOD_TB
+    return hipErrorInvalidValue;
+}
+
+hipError_t launch_marginal_forward(const void* q, const void* s, int enc_dtype, int sections_3d, int64_t B, int64_t D, int64_t H,
+                                   const float* score, const float* tok_logp, const void* mask, int mask_eb, int64_t L,
+                                   float* retriever_scores, float* d_scores, float* coef, float* loss, float* workspace,
+                                   int64_t workspace_floats, hipStream_t stream) {
+    const size_t lds = (size_t)(H + 3 * D + 4) * sizeof(float);
+    if (lds > 160 * 1024) return hipErrorInvalidValue;
+    const float inv_B = 1.f / (float)B;
+    float* row_lpx = workspace;  // [B]
+    hipError_t e;
+    if (!sections_3d) {
+        // einsum("bh,dh->bd") on the MFMA GEMM of the retrieval loss; K split into 4 slabs behind the row words when the workspace
+        // has room (launch_retrieval_forward explains the split), else one slab: retriever_scores itself
+        int n_splits = 1;
+        float* slabs = retriever_scores;
+        if (H >= 512 && workspace_floats >= B + 4 * B * D) {
+            n_splits = 4;
+            slabs = workspace + B;
+        }
+        e = launch_small_gemm(enc_dtype, enc_dtype, q, H, 1, s, 1, H, slabs, D, (int)B, (int)D, (int)H, nullptr, stream, n_splits, B * D);
+        if (e != hipSuccess) return e;
+#define VOD_MRP(DT)                                                                                                          \
+    if (enc_dtype == DT) {                                                                                                   \
+        auto kern = marginal_row_kernel<DT, false, true>;                                                                    \
+        e = allow_dynamic_lds((const void*)kern, 160 * 1024);                                                                \
+        if (e != hipSuccess) return e;                                                                                       \
+        hipLaunchKernelGGL(kern, dim3((unsigned)B), dim3(ML_THREADS), lds, stream, q, s, (int)D, (int)H, score, tok_logp,    \
+                           mask, mask_eb, L, retriever_scores, d_scores, coef, row_lpx, inv_B, (const float*)slabs, n_splits, \
+                           B * D);                                                                                           \
+    }
+        VOD_MRP(0) VOD_MRP(1) VOD_MRP(2)
+#undef VOD_MRP
+    } else {
+#define VOD_MR(DT)                                                                                                        \
+    if (enc_dtype == DT) {                                                                                                \
+        auto kern = marginal_row_kernel<DT, true, false>;                                                                 \
+        e = allow_dynamic_lds((const void*)kern, 160 * 1024);                                                             \
+        if (e != hipSuccess) return e;                                                                                    \
+        hipLaunchKernelGGL(kern, dim3((unsigned)B), dim3(ML_THREADS), lds, stream, q, s, (int)D, (int)H, score, tok_logp, \
+                           mask, mask_eb, L, retriever_scores, d_scores, coef, row_lpx, inv_B, (const float*)nullptr, 0,  \
+                           (int64_t)0);                                                                                   \
+    }
+        VOD_MR(0) VOD_MR(1) VOD_MR(2)
+#undef VOD_MR
+    }
+    e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(marginal_finalize_kernel, dim3(1), dim3(ML_THREADS), 0, stream, row_lpx, (int)B, loss);
+    return hipGetLastError();
+}
+
+}  // namespace vodhip

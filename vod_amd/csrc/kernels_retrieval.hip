@@ -11,6 +11,7 @@
 // 1/n_rows.  Sizes here are tiny (B=64 rows x D<=2048 sections x H<=1024): the stage is launch-latency
 // bound, so the design goal is "2 launches instead of ~15", not MFMA utilisation.
 #include "vodhip_internal.h"
+#include "row_reduce.h"
 
 #include <algorithm>
 
@@ -19,45 +20,6 @@ namespace vodhip {
 constexpr int RT_THREADS = 256;
 constexpr int WS_STRIDE = 8;       // floats of workspace per row: loss, has_pos, kl_score, kl_sparse, kl_dense
 constexpr int WS_STRIDE_AUX = 16;  // ... + huber sum, huber count, cross entropy, row counted, score^2 sum, finite count
-
-template <int DT>
-__device__ __forceinline__ float ld_enc(const void* p, int64_t i) {
-    if constexpr (DT == 2) {
-        return ((const float*)p)[i];
-    } else if constexpr (DT == 0) {
-        return (float)((const _Float16*)p)[i];
-    } else {
-        return (float)((const __bf16*)p)[i];
-    }
-}
-
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
-__device__ __forceinline__ float wave_max(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o));
-    return v;
-}
-// block-wide reductions through a 4-float LDS scratch (256 threads = 4 waves)
-__device__ __forceinline__ float block_sum(float v, float* red) {
-    v = wave_sum(v);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return red[0] + red[1] + red[2] + red[3];
-}
-__device__ __forceinline__ float block_max(float v, float* red) {
-    v = wave_max(v);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
-}
-
-__device__ __forceinline__ bool finite_f(float v) { return !(__builtin_isinf(v) || v != v); }
 
 // KL(q || p) over entries finite in both; p_lp is already the renormalised model log-prob (LDS).
 __device__ float row_kld(const float* __restrict__ ref_row, const float* p_lp, int D, float* red) {
@@ -517,9 +479,9 @@ __global__ void reduce_slabs_kernel(const float* __restrict__ slabs, int n_slabs
     out[i] = acc;
 }
 
-static hipError_t launch_small_gemm(int dta, int dtb, const void* A, int64_t sa_m, int64_t sa_k, const void* B, int64_t sb_k,
-                                    int64_t sb_n, float* C, int64_t ldc, int M, int N, int K, const float* alpha,
-                                    hipStream_t stream, int n_splits = 1, int64_t c_split_stride = 0) {
+hipError_t launch_small_gemm(int dta, int dtb, const void* A, int64_t sa_m, int64_t sa_k, const void* B, int64_t sb_k,
+                             int64_t sb_n, float* C, int64_t ldc, int M, int N, int K, const float* alpha,
+                             hipStream_t stream, int n_splits, int64_t c_split_stride) {
     const int k_per_split = ((K + n_splits - 1) / n_splits + 63) / 64 * 64;
     const dim3 grid((unsigned)((N + 63) / 64), (unsigned)((M + 63) / 64), (unsigned)n_splits);
 #define VOD_SG(X, Y)                                                                                              \

@@ -1239,6 +1239,56 @@ int vodhip_retrieval_backward(const void* q, const void* s, int enc_dtype, int s
     return 0;
 }
 
+static int marginal_mask_ok(int mask_elem_bytes) {
+    return mask_elem_bytes == 1 || mask_elem_bytes == 2 || mask_elem_bytes == 4 || mask_elem_bytes == 8;
+}
+
+int vodhip_lm_token_logprob_forward(const void* lm_logits, int logits_dtype, int64_t N, int64_t L, int64_t V,
+                                    const int64_t* input_ids, const void* attention_mask, int mask_elem_bytes, float* tok_logp,
+                                    float* tok_lse, void* stream) {
+    if (!lm_logits || !input_ids || !attention_mask || !tok_logp || !tok_lse) return fail("NULL argument");
+    if (N <= 0 || V <= 0) return fail("invalid sizes");
+    if (L < 2) return fail("L=%lld: the shifted sequence needs L >= 2", (long long)L);
+    if (V > 0x7fffffffLL || N * L > 0x7fffffffLL) return fail("V or N * L exceeds 2^31 - 1");
+    if (logits_dtype < 0 || logits_dtype > 2) return fail("invalid logits_dtype");
+    if (!marginal_mask_ok(mask_elem_bytes)) return fail("mask_elem_bytes must be 1, 2, 4 or 8");
+    HIP_OK(launch_lm_token_forward(lm_logits, logits_dtype, N, L, V, input_ids, attention_mask, mask_elem_bytes, tok_logp, tok_lse,
+                                   (hipStream_t)stream));
+    return 0;
+}
+
+int vodhip_marginal_forward(const void* q, const void* s, int enc_dtype, int sections_3d, int64_t B, int64_t D, int64_t H,
+                            const float* score, const float* tok_logp, const void* attention_mask, int mask_elem_bytes, int64_t L,
+                            float* retriever_scores, float* d_scores, float* coef, float* loss, float* workspace,
+                            int64_t workspace_floats, void* stream) {
+    if (!q || !s || !score || !tok_logp || !attention_mask || !retriever_scores || !d_scores || !coef || !loss || !workspace)
+        return fail("NULL argument");
+    if (B <= 0 || D <= 0 || H <= 0) return fail("invalid sizes");
+    if (L < 2) return fail("L=%lld: the shifted sequence needs L >= 2", (long long)L);
+    if (D > 8192) return fail("D=%lld exceeds 8192 sections per row", (long long)D);
+    if ((H + 3 * D + 4) * 4 > 160 * 1024) return fail("H + 3 * D = %lld floats exceed the 160 KiB of LDS", (long long)(H + 3 * D));
+    if (enc_dtype < 0 || enc_dtype > 2) return fail("invalid enc_dtype");
+    if (!marginal_mask_ok(mask_elem_bytes)) return fail("mask_elem_bytes must be 1, 2, 4 or 8");
+    if (workspace_floats < B) return fail("workspace_floats=%lld < B", (long long)workspace_floats);
+    HIP_OK(launch_marginal_forward(q, s, enc_dtype, sections_3d, B, D, H, score, tok_logp, attention_mask, mask_elem_bytes, L,
+                                   retriever_scores, d_scores, coef, loss, workspace, workspace_floats, (hipStream_t)stream));
+    return 0;
+}
+
+int vodhip_lm_token_logprob_backward(const void* lm_logits, int logits_dtype, int64_t N, int64_t L, int64_t V,
+                                     const int64_t* input_ids, const void* attention_mask, int mask_elem_bytes,
+                                     const float* tok_lse, const float* coef, const float* grad_out, void* d_logits, void* stream) {
+    if (!lm_logits || !input_ids || !attention_mask || !tok_lse || !coef || !grad_out || !d_logits) return fail("NULL argument");
+    if (N <= 0 || V <= 0) return fail("invalid sizes");
+    if (L < 2) return fail("L=%lld: the shifted sequence needs L >= 2", (long long)L);
+    if (V > 0x7fffffffLL || N * L > 0x7fffffffLL) return fail("V or N * L exceeds 2^31 - 1");
+    if (logits_dtype < 0 || logits_dtype > 2) return fail("invalid logits_dtype");
+    if (!marginal_mask_ok(mask_elem_bytes)) return fail("mask_elem_bytes must be 1, 2, 4 or 8");
+    HIP_OK(launch_lm_token_backward(lm_logits, logits_dtype, N, L, V, input_ids, attention_mask, mask_elem_bytes, tok_lse, coef,
+                                    grad_out, d_logits, (hipStream_t)stream));
+    return 0;
+}
+
 int vodhip_retrieval_metrics(const float* scores, const int64_t* relevances, int64_t B, int width, const int32_t* specs, int n_specs,
                              float* values, double* state, void* workspace, int64_t workspace_bytes, void* stream) {
     if (B <= 0 || width <= 0) return fail("invalid sizes B=%lld width=%d", (long long)B, width);

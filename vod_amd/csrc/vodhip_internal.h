@@ -224,6 +224,24 @@ hipError_t launch_retrieval_forward(const void* q, const void* s, int enc_dtype,
 hipError_t launch_retrieval_backward(const void* q, const void* s, int enc_dtype, int sections_3d, int64_t B, int64_t D,
                                      int64_t H, const float* d_scores, const float* grad_out, float* dq, float* ds,
                                      hipStream_t stream);
+// C[M,N] (f32) = *alpha (device scalar, or NULL = 1) * A[M,K] * B[K,N] on the exact-f32 MFMA; element strides; dtype pairs (dta, dtb):
+// (0,0) (1,1) (2,2) (2,0) (2,1).  n_splits > 1: K split over blockIdx.z, split z writes the slab C + z * c_split_stride (the consumer
+// sums the slabs in order).
+hipError_t launch_small_gemm(int dta, int dtb, const void* A, int64_t sa_m, int64_t sa_k, const void* B, int64_t sb_k,
+                             int64_t sb_n, float* C, int64_t ldc, int M, int N, int K, const float* alpha,
+                             hipStream_t stream, int n_splits = 1, int64_t c_split_stride = 0);
+
+// ---- launchers (kernels_marginal.hip) ---------------------------------------------------------
+// mask_eb: bytes per attention-mask element (1 | 2 | 4 | 8; an element is live when any of its bits is set)
+hipError_t launch_lm_token_forward(const void* logits, int dtype, int64_t N, int64_t L, int64_t V, const int64_t* ids,
+                                   const void* mask, int mask_eb, float* tok_logp, float* tok_lse, hipStream_t stream);
+hipError_t launch_lm_token_backward(const void* logits, int dtype, int64_t N, int64_t L, int64_t V, const int64_t* ids,
+                                    const void* mask, int mask_eb, const float* tok_lse, const float* coef, const float* grad_out,
+                                    void* d_logits, hipStream_t stream);
+hipError_t launch_marginal_forward(const void* q, const void* s, int enc_dtype, int sections_3d, int64_t B, int64_t D, int64_t H,
+                                   const float* score, const float* tok_logp, const void* mask, int mask_eb, int64_t L,
+                                   float* retriever_scores, float* d_scores, float* coef, float* loss, float* workspace,
+                                   int64_t workspace_floats, hipStream_t stream);
 
 // ---- launchers (kernels_sample.hip) -----------------------------------------------------------
 hipError_t launch_priority_sample(const float* scores, const uint8_t* labels, const float* noise, int64_t nq, int width,

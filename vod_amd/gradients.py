@@ -1,4 +1,5 @@
-"""In-batch retrieval scoring + loss on the GPU (host wrapper over `vodhip_retrieval_forward/backward`).
+"""In-batch retrieval scoring + loss, and the marginal likelihood through the reader LM, on the GPU (host wrappers over
+`vodhip_retrieval_forward/backward` and `vodhip_lm_token_logprob_forward/backward` + `vodhip_marginal_forward`).
 
 Mirror of `RetrievalGradients` (/root/reference/src/vod_models/vod_gradients/retrieval.py:14-92): same
 constructor, same keyword-only call `(batch, query_encoding, section_encoding)`, same outputs (`loss`,
@@ -163,6 +164,124 @@ class RetrievalGradients:
         if get("section__dense") is not None:
             diagnostics["kl_dense"] = kl[2]
         return RealmOutput(loss=loss, retriever_scores=scores, diagnostics=diagnostics)
+
+
+class _MarginalLikelihood(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, q, s, score, lm_logits, input_ids, attention_mask):  # noqa: ANN001
+        lib = _native.load_library()
+        if not q.is_cuda:
+            raise _native.NativeLibraryError("MarginalLikelihoodGradients needs device tensors (there is no CPU path)")
+        for name, x in (("section_encoding", s), ("section__score", score), ("lm_logits", lm_logits), ("lm__input_ids", input_ids),
+                        ("lm__attention_mask", attention_mask)):
+            if x.device != q.device:  # the kernels get raw pointers: a host or other-device tensor must never reach them
+                raise _native.NativeLibraryError(f"`{name}` is on {x.device}, `query_encoding` on {q.device}: all tensors must share one GPU")
+        if lm_logits.dim() != 4:
+            raise ValueError(f"`lm_logits` must be [B, D, L, V], got {tuple(lm_logits.shape)}")
+        enc = q.dtype if q.dtype in _ENC else torch.float32
+        ldt = lm_logits.dtype if lm_logits.dtype in _ENC else torch.float32
+        qc, sc, lg = _as(q, enc), _as(s, enc), _as(lm_logits, ldt)
+        if sc.dim() not in (2, 3):
+            raise ValueError(f"Invalid dimension for `section_encoding`: {tuple(sc.shape)}")
+        three_d = sc.dim() == 3
+        B, H = qc.shape
+        D = sc.shape[1] if three_d else sc.shape[0]
+        _, _, L, V = lg.shape
+        if L < 2:
+            raise ValueError(f"`lm_logits` has L={L} positions: the shifted sequence needs L >= 2")
+        if lg.shape[:2] != (B, D) or input_ids.shape != (B, D, L) or attention_mask.shape != (B, D, L):
+            raise ValueError(f"lm_logits must be [{B}, {D}, L, V], lm__input_ids / lm__attention_mask [{B}, {D}, {L}]")
+        score_c, ids = _as(score, torch.float32), _as(input_ids, torch.int64)
+        if score_c.shape != (B, D):
+            raise ValueError(f"section__score must be [{B}, {D}]")
+        # the kernels test a mask element for any set bit: bool and integer masks are read as they are
+        mask = attention_mask if not (attention_mask.is_floating_point() or attention_mask.is_complex()) else attention_mask != 0
+        mask = mask.contiguous()
+        mask_eb = mask.element_size()
+        dev = q.device
+        stream = _native.current_stream_ptr(dev)
+        N = B * D
+        # per-token words: log-prob | (row max, log sum-exp); per-pair words: retriever scores | dLoss/dScores | coef
+        tok = torch.empty((3, N, L - 1), dtype=torch.float32, device=dev)
+        pairs = torch.empty((3, B, D), dtype=torch.float32, device=dev)
+        loss = torch.empty((1,), dtype=torch.float32, device=dev)
+        n_work = B + (4 * B * D if (not three_d and H >= 512) else 0)
+        work = torch.empty((n_work,), dtype=torch.float32, device=dev)
+        p_tok, p_pairs = tok.data_ptr(), pairs.data_ptr()
+        with _on_device(dev):
+            _native.check(
+                lib.vodhip_lm_token_logprob_forward(
+                    lg.data_ptr(), _native.torch_dtype_code(ldt), N, L, V, ids.data_ptr(), mask.data_ptr(), mask_eb,
+                    p_tok, p_tok + 4 * N * (L - 1), stream,
+                )
+            )
+            _native.check(
+                lib.vodhip_marginal_forward(
+                    qc.data_ptr(), sc.data_ptr(), _native.torch_dtype_code(enc), int(three_d), B, D, H, score_c.data_ptr(),
+                    p_tok, mask.data_ptr(), mask_eb, L, p_pairs, p_pairs + 4 * N, p_pairs + 8 * N, loss.data_ptr(),
+                    work.data_ptr(), n_work, stream,
+                )
+            )
+        scores, d_scores, coef = pairs[0], pairs[1], pairs[2]
+        tok_lse = tok[1:].view(N, L - 1, 2)  # (row max, log sum-exp) per token, the block behind tok_logp
+        ctx.save_for_backward(qc, sc, lg, ids, mask, tok_lse, coef, d_scores)
+        ctx.meta = (enc, ldt, three_d, B, D, H, L, V, q.dtype, s.dtype, lm_logits.dtype, mask_eb)
+        ctx.mark_non_differentiable(scores)
+        return loss[0], scores
+
+    @staticmethod
+    def backward(ctx, g_loss, _g_scores):  # noqa: ANN001
+        lib = _native.load_library()
+        qc, sc, lg, ids, mask, tok_lse, coef, d_scores = ctx.saved_tensors
+        enc, ldt, three_d, B, D, H, L, V, q_dt, s_dt, lg_dt, mask_eb = ctx.meta
+        dev = qc.device
+        stream = _native.current_stream_ptr(dev)
+        go = g_loss if (g_loss.dtype is torch.float32 and g_loss.is_contiguous()) else g_loss.float().contiguous()
+        need_q, need_s, need_lg = ctx.needs_input_grad[0], ctx.needs_input_grad[1], ctx.needs_input_grad[3]
+        dq = ds = d_lg = None
+        with _on_device(dev):
+            if need_q or need_s:
+                dq = torch.empty((B, H), dtype=torch.float32, device=dev)
+                ds = torch.empty(sc.shape, dtype=torch.float32, device=dev)
+                _native.check(
+                    lib.vodhip_retrieval_backward(
+                        qc.data_ptr(), sc.data_ptr(), _native.torch_dtype_code(enc), int(three_d), B, D, H,
+                        d_scores.data_ptr(), go.data_ptr(), dq.data_ptr(), ds.data_ptr(), stream,
+                    )
+                )
+                dq = dq if q_dt is torch.float32 else dq.to(q_dt)
+                ds = ds if s_dt is torch.float32 else ds.to(s_dt)
+            if need_lg:
+                d_lg = torch.empty_like(lg)  # the one logits-sized tensor of the step
+                _native.check(
+                    lib.vodhip_lm_token_logprob_backward(
+                        lg.data_ptr(), _native.torch_dtype_code(ldt), B * D, L, V, ids.data_ptr(), mask.data_ptr(), mask_eb,
+                        tok_lse.data_ptr(), coef.data_ptr(), go.data_ptr(), d_lg.data_ptr(), stream,
+                    )
+                )
+                d_lg = d_lg if lg_dt is ldt else d_lg.to(lg_dt)
+        return dq, ds, None, d_lg, None, None
+
+
+class MarginalLikelihoodGradients:
+    """Marginal likelihood of a retrieval-augmented LM (REALM) with the in-batch approximation, fused on the GPU.
+
+    Mirror of the reference's `MarginalLikelihoodGradients` (src/vod_models/vod_gradients/marginal_likelihood.py:9-66): the same
+    keyword-only call `(batch, query_encoding, section_encoding, lm_logits)`, reading `section__score`, `lm__input_ids` and
+    `lm__attention_mask` from `batch`, the same outputs (`loss`, `retriever_scores`).  `lm_logits [B, D, L, V]` is read once forward
+    (masked positions not at all) and read once / written once backward; between the two the step keeps three floats per token.
+    `loss.backward()` fills the gradients of the two encodings and of `lm_logits`, each in its own dtype.  Where the reference
+    raises on a target id outside [0, V-2] (a host synchronisation), a live one makes the loss NaN and a masked one is ignored.
+    """
+
+    def __call__(self, *, batch: typ.Any, query_encoding: torch.Tensor, section_encoding: torch.Tensor,
+                 lm_logits: torch.Tensor) -> RealmOutput:
+        get = (lambda k: batch.get(k)) if isinstance(batch, dict) else (lambda k: getattr(batch, k, None))
+        score, ids, mask = get("section__score"), get("lm__input_ids"), get("lm__attention_mask")
+        if score is None or ids is None or mask is None or lm_logits is None:
+            raise ValueError("MarginalLikelihoodGradients needs section__score, lm__input_ids, lm__attention_mask and lm_logits")
+        loss, scores = _MarginalLikelihood.apply(query_encoding, section_encoding, score, lm_logits, ids, mask)
+        return RealmOutput(loss=loss, retriever_scores=scores)
 
 
 class GraphedRetrievalStep:
