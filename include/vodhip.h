@@ -350,6 +350,61 @@ int vodhip_lm_token_logprob_backward(const void* lm_logits, int logits_dtype, in
                                      void* d_logits, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * H5p sequence pooling of the encoder's last hidden state: aggregate, activation, norm and scale, fused, with backward.
+ * Replaces: VodPooler.forward, MeanAgg, ClsAgg (src/vod_models/vod_encoder/modeling.py:76-89,164-174) and their autograd backward.
+ * All pointers DEVICE, every call runs on `stream`, nothing synchronises, no atomics: two runs are bitwise equal.
+ * hidden [N, L, H] contiguous of `hidden_dtype` (F32 | F16 | BF16); attention_mask [N, L] with elements of `mask_elem_bytes`
+ * (1 | 2 | 4 | 8) bytes, live when any bit is set; N*L below 2^31, L >= 1, 1 <= H <= 2^30.  All arithmetic is float32.
+ *   cnt[n] = live elements of mask row n; c = exp(0.5 * *log_scaler) (a float32 DEVICE word); eps = 1e-12.
+ *   aggregate a float32 [N, H]:
+ *     VODHIP_POOL_AGG_MEAN, VODHIP_POOL_MASK_REFERENCE: a = (sum over ALL L positions of hidden[n,l,:]) / cnt[n], the reference's
+ *       arithmetic (padded positions are summed);  VODHIP_POOL_MASK_MASKED: a = (sum over the live positions) / cnt[n], padded token
+ *       rows are not read.  cnt = 0 gives a = 0 in both.
+ *     VODHIP_POOL_AGG_CLS: a = hidden[n,0,:]; the mask is ignored.
+ *   finish on z (= a, or a projection of it, [N, P]): t = act(z) with VODHIP_POOL_ACT_* (gelu in its exact erf form);
+ *     u = t (NORM_NONE) | t / max(|t|_2, eps) (NORM_L2) | t / max(|t|_1, eps) (NORM_L1); y = c u.
+ *   vodhip_pool_forward: always writes a; with finish != 0 also y [N, H] of `y_dtype` (y may be NULL otherwise).  Token rows are
+ *     read once, 16 bytes per lane when H * element size is a multiple of 16 and the base is 16-byte aligned.  L is cut into chunks
+ *     of `l_chunk` tokens (0 = automatic, a function of (N, L, H) alone); with one chunk per row the call is ONE launch, with more
+ *     the chunks leave float32 partial sums in `workspace` (vodhip_pool_workspace_floats(N, L, H, l_chunk) floats; 0 for one chunk,
+ *     and CLS never needs any) and a second launch sums them in chunk order and runs the same finish routine: the same bits.
+ *   vodhip_pool_backward: with finish != 0, g = dL/dy [N, H] of `g_dtype`, da is recomputed from the saved a:
+ *       du = c g; l2, |t| > eps: dt = (du - u (u.du)) / |t|_2; l1, |t|_1 > eps: dt = (du - sign(t) (u.du)) / |t|_1; below eps:
+ *       dt = du / eps; da = dt act'(a);  gy float32 [N] = sum_h g y (dL/dlog_scaler = 0.5 * sum_n gy[n]).
+ *     with finish == 0, g IS da (gy is not written and may be NULL).
+ *     d_hidden [N, L, H] of `hidden_dtype`, written exactly once: da[n] / cnt[n] at every position (MEAN, REFERENCE) or at the live
+ *     ones (MEAN, MASKED), da[n] at l = 0 (CLS), exactly 0 elsewhere.  A MEAN row with cnt = 0 gets zeros (the reference: NaN).
+ *   vodhip_pool_finish_forward / _backward: the finish alone on z [N, P] of `z_dtype`, behind a projection; dz of `dz_dtype`.
+ * ------------------------------------------------------------------------------------------- */
+#define VODHIP_POOL_AGG_MEAN 0
+#define VODHIP_POOL_AGG_CLS 1
+#define VODHIP_POOL_MASK_REFERENCE 0
+#define VODHIP_POOL_MASK_MASKED 1
+#define VODHIP_POOL_ACT_NONE 0
+#define VODHIP_POOL_ACT_RELU 1
+#define VODHIP_POOL_ACT_TANH 2
+#define VODHIP_POOL_ACT_SIGMOID 3
+#define VODHIP_POOL_ACT_GELU 4
+#define VODHIP_POOL_NORM_NONE 0
+#define VODHIP_POOL_NORM_L2 1
+#define VODHIP_POOL_NORM_L1 2
+int64_t vodhip_pool_workspace_floats(int64_t N, int64_t L, int64_t H, int64_t l_chunk); /* < 0: invalid sizes */
+int vodhip_pool_forward(const void* hidden, int hidden_dtype, int64_t N, int64_t L, int64_t H,
+                        const void* attention_mask, int mask_elem_bytes, int agg, int mask_mode,
+                        int finish, int act, int norm, const float* log_scaler, int64_t l_chunk,
+                        float* a, void* y, int y_dtype,
+                        float* workspace /* DEVICE scratch */, int64_t workspace_floats, void* stream);
+int vodhip_pool_backward(const void* g, int g_dtype, const float* a, int64_t N, int64_t L, int64_t H,
+                         const void* attention_mask, int mask_elem_bytes, int agg, int mask_mode,
+                         int finish, int act, int norm, const float* log_scaler, int64_t l_chunk,
+                         void* d_hidden, int hidden_dtype, float* gy, void* stream);
+int vodhip_pool_finish_forward(const void* z, int z_dtype, int64_t N, int64_t P, int act, int norm,
+                               const float* log_scaler, void* y, int y_dtype, void* stream);
+int vodhip_pool_finish_backward(const void* z, int z_dtype, const void* g, int g_dtype, int64_t N, int64_t P,
+                                int act, int norm, const float* log_scaler,
+                                void* dz, int dz_dtype, float* gy, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * H5m retrieval metrics of the monitor that follows the loss: every (metric, topk) of one update in two launches.
  * Replaces: RetrievalMonitor.update (src/vod_models/monitoring/monitor.py:83-105) with prepare_for_metric_computation /
  *           _mask_rank_inputs (src/vod_models/monitoring/functional.py:15-25,164-178), the nine _compute_* functions

@@ -107,6 +107,16 @@ SIGNATURES: dict[str, tuple] = {
         _i32, [_vp, _vp, _i32, _i32, _i64, _i64, _i64, _vp, _vp, _vp, _i32, _i64, _vp, _vp, _vp, _vp, _vp, _i64, _vp],
     ),
     "vodhip_lm_token_logprob_backward": (_i32, [_vp, _i32, _i64, _i64, _i64, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp]),
+    # H5p sequence pooling (kernels_pool.hip)
+    "vodhip_pool_workspace_floats": (_i64, [_i64, _i64, _i64, _i64]),
+    "vodhip_pool_forward": (
+        _i32, [_vp, _i32, _i64, _i64, _i64, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _i64, _vp, _vp, _i32, _vp, _i64, _vp],
+    ),
+    "vodhip_pool_backward": (
+        _i32, [_vp, _i32, _vp, _i64, _i64, _i64, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _i64, _vp, _i32, _vp, _vp],
+    ),
+    "vodhip_pool_finish_forward": (_i32, [_vp, _i32, _i64, _i64, _i32, _i32, _vp, _vp, _i32, _vp]),
+    "vodhip_pool_finish_backward": (_i32, [_vp, _i32, _vp, _i32, _i64, _i64, _i32, _i32, _vp, _vp, _i32, _vp, _vp]),
     "vodhip_gather_by_id": (_i32, [_vp, _i64, _vp, _i64, _i32, _i32, _vp, _vp, _vp, _vp]),
     "vodhip_b64url_encode": (_i64, [_vp, _i64, _vp, _i64, _vp]),
     "vodhip_b64url_decode": (_i64, [_vp, _i64, _vp]),

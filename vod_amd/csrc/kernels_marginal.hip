@@ -25,61 +25,6 @@ constexpr int ML_THREADS = 256;
 // pay two barriers for the cross-wave reduction
 constexpr int ML_WAVE_ROW_VECS = 512;
 
-__device__ __forceinline__ bool mask_live(const void* mask, int64_t i, int eb) {
-    switch (eb) {
-        case 1: return ((const uint8_t*)mask)[i] != 0;
-        case 2: return ((const uint16_t*)mask)[i] != 0;
-        case 4: return ((const uint32_t*)mask)[i] != 0;
-        default: return ((const uint64_t*)mask)[i] != 0;
-    }
-}
-
-template <int DT>
-constexpr int elems_per_vec() { return DT == 2 ? 4 : 8; }
-
-// 16 bytes of logits -> 4 (f32) or 8 (f16 / bf16) floats
-template <int DT>
-__device__ __forceinline__ void unpack16(const uint4& raw, float* v) {
-    const unsigned w[4] = {raw.x, raw.y, raw.z, raw.w};
-    if constexpr (DT == 2) {
-#pragma unroll
-        for (int u = 0; u < 4; ++u) v[u] = __builtin_bit_cast(float, w[u]);
-    } else {
-#pragma unroll
-        for (int u = 0; u < 8; ++u) {
-            const uint16_t h = (uint16_t)(w[u >> 1] >> (16 * (u & 1)));
-            if constexpr (DT == 0) v[u] = (float)__builtin_bit_cast(_Float16, h);
-            else v[u] = __builtin_bit_cast(float, (unsigned)h << 16);
-        }
-    }
-}
-
-template <int DT>
-__device__ __forceinline__ uint16_t to_bits16(float v) {
-    if constexpr (DT == 0) return __builtin_bit_cast(uint16_t, (_Float16)v);
-    else return __builtin_bit_cast(uint16_t, (__bf16)v);  // round to nearest even
-}
-
-template <int DT>
-__device__ __forceinline__ uint4 pack16(const float* v) {
-    unsigned w[4];
-    if constexpr (DT == 2) {
-#pragma unroll
-        for (int u = 0; u < 4; ++u) w[u] = __builtin_bit_cast(unsigned, v[u]);
-    } else {
-#pragma unroll
-        for (int u = 0; u < 4; ++u) w[u] = (unsigned)to_bits16<DT>(v[2 * u]) | ((unsigned)to_bits16<DT>(v[2 * u + 1]) << 16);
-    }
-    return make_uint4(w[0], w[1], w[2], w[3]);
-}
-
-template <int DT>
-__device__ __forceinline__ void st_enc(void* p, int64_t i, float v) {
-    if constexpr (DT == 2) ((float*)p)[i] = v;
-    else if constexpr (DT == 0) ((_Float16*)p)[i] = (_Float16)v;
-    else ((__bf16*)p)[i] = (__bf16)v;
-}
-
 // running (max, sum of exp(x - max)) of one lane, fed N values at a time: one rescale per group instead of one per value
 template <int N>
 __device__ __forceinline__ void online_absorb(float& m, float& s, const float* v) {

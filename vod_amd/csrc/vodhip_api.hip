@@ -1289,6 +1289,82 @@ int vodhip_lm_token_logprob_backward(const void* lm_logits, int logits_dtype, in
     return 0;
 }
 
+static const char* pool_codes_error(int agg, int mask_mode, int act, int norm) {
+    if (agg != VODHIP_POOL_AGG_MEAN && agg != VODHIP_POOL_AGG_CLS) return "unknown aggregator code (0 = mean, 1 = cls)";
+    if (mask_mode != VODHIP_POOL_MASK_REFERENCE && mask_mode != VODHIP_POOL_MASK_MASKED) return "unknown mask_mode (0 = reference, 1 = masked)";
+    if (act < VODHIP_POOL_ACT_NONE || act > VODHIP_POOL_ACT_GELU) return "unknown activation code (0 none, 1 relu, 2 tanh, 3 sigmoid, 4 gelu)";
+    if (norm < VODHIP_POOL_NORM_NONE || norm > VODHIP_POOL_NORM_L1) return "unknown norm code (0 none, 1 l2, 2 l1)";
+    return nullptr;
+}
+static const char* pool_sizes_error(int64_t N, int64_t L, int64_t H, int64_t l_chunk) {
+    if (N <= 0 || L <= 0 || H <= 0 || l_chunk < 0) return "invalid sizes";
+    if (H > (1LL << 30)) return "H exceeds 2^30";
+    if (L > 0x7fffffffLL || N > 0x7fffffffLL / L) return "N * L exceeds 2^31 - 1";
+    return nullptr;
+}
+static bool pool_dtype_ok(int dt) { return dt >= 0 && dt <= 2; }
+
+int64_t vodhip_pool_workspace_floats(int64_t N, int64_t L, int64_t H, int64_t l_chunk) {
+    if (const char* m = pool_sizes_error(N, L, H, l_chunk)) return fail("%s", m);
+    const PoolPlan plan = pool_plan(N, L, H, l_chunk);
+    return plan.n_chunks == 1 ? 0 : N * plan.n_chunks * H;
+}
+
+int vodhip_pool_forward(const void* hidden, int hidden_dtype, int64_t N, int64_t L, int64_t H, const void* attention_mask,
+                        int mask_elem_bytes, int agg, int mask_mode, int finish, int act, int norm, const float* log_scaler,
+                        int64_t l_chunk, float* a, void* y, int y_dtype, float* workspace, int64_t workspace_floats, void* stream) {
+    if (!hidden || !attention_mask || !a || (finish && (!y || !log_scaler))) return fail("NULL argument");
+    if (const char* m = pool_sizes_error(N, L, H, l_chunk)) return fail("%s", m);
+    if (!pool_dtype_ok(hidden_dtype)) return fail("invalid hidden_dtype");
+    if (finish && !pool_dtype_ok(y_dtype)) return fail("invalid y_dtype");
+    if (!marginal_mask_ok(mask_elem_bytes)) return fail("mask_elem_bytes must be 1, 2, 4 or 8");
+    if (const char* m = pool_codes_error(agg, mask_mode, act, norm)) return fail("%s", m);
+    const PoolPlan plan = pool_plan(N, L, H, l_chunk);
+    if (agg == VODHIP_POOL_AGG_MEAN && plan.n_chunks > 1) {
+        const int64_t need = N * plan.n_chunks * H;
+        if (!workspace || workspace_floats < need)
+            return fail("workspace_floats=%lld < %lld (N * %lld chunks * H)", (long long)workspace_floats, (long long)need,
+                        (long long)plan.n_chunks);
+    }
+    HIP_OK(launch_pool_forward(hidden, hidden_dtype, N, L, H, attention_mask, mask_elem_bytes, agg, mask_mode, finish ? 1 : 0, act, norm,
+                               log_scaler, l_chunk, a, y, y_dtype, workspace, (hipStream_t)stream));
+    return 0;
+}
+
+int vodhip_pool_backward(const void* g, int g_dtype, const float* a, int64_t N, int64_t L, int64_t H, const void* attention_mask,
+                         int mask_elem_bytes, int agg, int mask_mode, int finish, int act, int norm, const float* log_scaler,
+                         int64_t l_chunk, void* d_hidden, int hidden_dtype, float* gy, void* stream) {
+    if (!g || !attention_mask || !d_hidden || (finish && (!a || !log_scaler || !gy))) return fail("NULL argument");
+    if (const char* m = pool_sizes_error(N, L, H, l_chunk)) return fail("%s", m);
+    if (!pool_dtype_ok(hidden_dtype)) return fail("invalid hidden_dtype");
+    if (!pool_dtype_ok(g_dtype)) return fail("invalid g_dtype");
+    if (!marginal_mask_ok(mask_elem_bytes)) return fail("mask_elem_bytes must be 1, 2, 4 or 8");
+    if (const char* m = pool_codes_error(agg, mask_mode, act, norm)) return fail("%s", m);
+    HIP_OK(launch_pool_backward(g, g_dtype, a, N, L, H, attention_mask, mask_elem_bytes, agg, mask_mode, finish ? 1 : 0, act, norm,
+                                log_scaler, l_chunk, d_hidden, hidden_dtype, gy, (hipStream_t)stream));
+    return 0;
+}
+
+int vodhip_pool_finish_forward(const void* z, int z_dtype, int64_t N, int64_t P, int act, int norm, const float* log_scaler, void* y,
+                               int y_dtype, void* stream) {
+    if (!z || !log_scaler || !y) return fail("NULL argument");
+    if (N <= 0 || P <= 0 || N > 0x7fffffffLL || P > (1LL << 30)) return fail("invalid sizes");
+    if (!pool_dtype_ok(z_dtype) || !pool_dtype_ok(y_dtype)) return fail("invalid z_dtype or y_dtype");
+    if (const char* m = pool_codes_error(VODHIP_POOL_AGG_MEAN, VODHIP_POOL_MASK_REFERENCE, act, norm)) return fail("%s", m);
+    HIP_OK(launch_pool_finish_forward(z, z_dtype, N, P, act, norm, log_scaler, y, y_dtype, (hipStream_t)stream));
+    return 0;
+}
+
+int vodhip_pool_finish_backward(const void* z, int z_dtype, const void* g, int g_dtype, int64_t N, int64_t P, int act, int norm,
+                                const float* log_scaler, void* dz, int dz_dtype, float* gy, void* stream) {
+    if (!z || !g || !log_scaler || !dz || !gy) return fail("NULL argument");
+    if (N <= 0 || P <= 0 || N > 0x7fffffffLL || P > (1LL << 30)) return fail("invalid sizes");
+    if (!pool_dtype_ok(z_dtype) || !pool_dtype_ok(g_dtype) || !pool_dtype_ok(dz_dtype)) return fail("invalid z_dtype, g_dtype or dz_dtype");
+    if (const char* m = pool_codes_error(VODHIP_POOL_AGG_MEAN, VODHIP_POOL_MASK_REFERENCE, act, norm)) return fail("%s", m);
+    HIP_OK(launch_pool_finish_backward(z, z_dtype, g, g_dtype, N, P, act, norm, log_scaler, dz, dz_dtype, gy, (hipStream_t)stream));
+    return 0;
+}
+
 int vodhip_retrieval_metrics(const float* scores, const int64_t* relevances, int64_t B, int width, const int32_t* specs, int n_specs,
                              float* values, double* state, void* workspace, int64_t workspace_bytes, void* stream) {
     if (B <= 0 || width <= 0) return fail("invalid sizes B=%lld width=%d", (long long)B, width);

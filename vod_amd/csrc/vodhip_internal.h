@@ -231,6 +231,23 @@ hipError_t launch_small_gemm(int dta, int dtb, const void* A, int64_t sa_m, int6
                              int64_t sb_n, float* C, int64_t ldc, int M, int N, int K, const float* alpha,
                              hipStream_t stream, int n_splits = 1, int64_t c_split_stride = 0);
 
+// ---- launchers (kernels_pool.hip) -------------------------------------------------------------
+struct PoolPlan {
+    int64_t l_chunk;   // tokens per workgroup
+    int64_t n_chunks;  // workgroups per row; 1 = the single-launch path, no workspace
+};
+PoolPlan pool_plan(int64_t N, int64_t L, int64_t H, int64_t l_chunk);  // l_chunk = 0: automatic, from (N, L, H) alone
+hipError_t launch_pool_forward(const void* hidden, int dtype, int64_t N, int64_t L, int64_t H, const void* mask, int mask_eb, int agg,
+                               int masked, int finish, int act, int norm, const float* log_scaler, int64_t l_chunk, float* a, void* y,
+                               int y_dtype, float* workspace, hipStream_t stream);
+hipError_t launch_pool_backward(const void* g, int g_dtype, const float* a, int64_t N, int64_t L, int64_t H, const void* mask,
+                                int mask_eb, int agg, int masked, int finish, int act, int norm, const float* log_scaler,
+                                int64_t l_chunk, void* d_hidden, int dtype, float* gy, hipStream_t stream);
+hipError_t launch_pool_finish_forward(const void* z, int z_dtype, int64_t N, int64_t P, int act, int norm, const float* log_scaler,
+                                      void* y, int y_dtype, hipStream_t stream);
+hipError_t launch_pool_finish_backward(const void* z, int z_dtype, const void* g, int g_dtype, int64_t N, int64_t P, int act, int norm,
+                                       const float* log_scaler, void* dz, int dz_dtype, float* gy, hipStream_t stream);
+
 // ---- launchers (kernels_marginal.hip) ---------------------------------------------------------
 // mask_eb: bytes per attention-mask element (1 | 2 | 4 | 8; an element is live when any of its bits is set)
 hipError_t launch_lm_token_forward(const void* logits, int dtype, int64_t N, int64_t L, int64_t V, const int64_t* ids,
