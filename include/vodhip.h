@@ -350,6 +350,49 @@ int vodhip_lm_token_logprob_backward(const void* lm_logits, int logits_dtype, in
                                      void* d_logits, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * H5v the Renyi VOD objective over priority-sampled sections (Lievin et al., arXiv 2210.06345): the row stage between
+ * vodhip_lm_token_logprob_forward and the two backward calls of H5 / H5l.
+ * Replaces: nothing that runs - VodGradients is `raise NotImplementedError` in the reference (src/vod_models/vod_gradients/vod.py:14-26).
+ * The quantity is the self-normalised importance-sampling estimate of the Renyi bound, differentiated as written with respect to
+ * the model, the sampler held constant.  All pointers DEVICE, one stream, nothing synchronises.
+ *   q [B,H], s [D,H] | [B,D,H] of `enc_dtype`; score, log_weight float32 [B,D] (section__score, -inf = padded section;
+ *   section__log_weight, -inf = not sampled); log_proposal float32 [B,D] = the log proposal up to a per-row constant, or NULL:
+ *   c = temperature * score.  tok_logp float32 [B*D, L-1] and attention_mask [B*D, L] as in H5l.
+ *   A section is PADDED when score is -inf, and LIVE when it is not padded and neither log_weight nor c is -inf.  log_weight and
+ *   c of a padded section are not looked at (c is not even formed: 0 * -inf).  Per query row, over its live set:
+ *     r    = <q, s>                               -> retriever_scores float32 [B,D], -inf at padded sections (finite elsewhere,
+ *                                                    live or not)
+ *     n    = live positions of (b,d) ; l = sum of the live tok_logp / n (VODHIP_VOD_TOKEN_MEAN) | the sum (VODHIP_VOD_TOKEN_SUM)
+ *     ls   = log_weight - logsumexp log_weight ; g = r - c ; lZ = logsumexp (ls + g) ; lw = l + g - lZ ; eps = 1 - alpha
+ *     Lhat = sum exp(ls) lw                                                       (eps == 0: the ELBO)
+ *          = m + log1p( sum exp(ls) expm1(eps (lw - m)) ) / eps                    (otherwise; continuous in float32 as alpha -> 1)
+ *            for any shift m, max lw for one; the kernel takes m = logsumexp(ls + eps lw) / eps, the plain form of the same bound,
+ *            so that the sum is ~ 0 and log1p does not magnify its rounding when the best section carries little weight
+ *     omega = softmax (ls + eps lw) ; pi = softmax (ls + g)
+ *   loss float32 [1] = -mean_b Lhat ; d_scores float32 [B,D] = -(omega - pi) / B ; coef float32 [B,D] = -omega / (B n) (MEAN) |
+ *   -omega / B (SUM); both exactly 0 at every section that is not live, whose tokens and ids take no part.
+ *   diag float32 [3] = mean_b of (Lhat at alpha = 0, Lhat at alpha = 1, 1 / sum omega^2): the importance-weighted bound, the ELBO
+ *   and the effective sample size, from the same launch.  dq / ds follow from d_scores with vodhip_retrieval_backward, d_logits
+ *   from coef with vodhip_lm_token_logprob_backward.
+ * alpha (in [0, 1]), temperature (finite) and token_reduction are passed by value; eps is formed in double.
+ * workspace: workspace_floats >= 4*B floats (the four row words); with >= 4*B + 4*B*D (2-D sections, H >= 512) the in-batch
+ * contraction is split over K into four slabs.  D <= 8192, and H + 4*D + 4 floats must fit 160 KiB; what does not is refused.
+ * NaN rules: a row without a live section gives a NaN loss (its gradients are 0).  NaN is not -inf: a NaN in log_weight or c of a
+ * live section, n = 0 on a live section (both reductions) and, through tok_logp, a live target outside [0, V-2] of a live section
+ * go through the formulas as written: the loss, the diagnostics and d_scores / coef of every live section of that row are NaN.  -inf logits at a target are legal: with eps > 0 that section gets omega = 0 and every gradient stays finite.
+ * No atomics: two runs are bitwise equal.
+ * ------------------------------------------------------------------------------------------- */
+#define VODHIP_VOD_TOKEN_MEAN 0
+#define VODHIP_VOD_TOKEN_SUM 1
+int vodhip_vod_forward(const void* q, const void* s, int enc_dtype, int sections_3d,
+                       int64_t B, int64_t D, int64_t H,
+                       const float* score, const float* log_weight, const float* log_proposal /* may be NULL */,
+                       const float* tok_logp, const void* attention_mask, int mask_elem_bytes, int64_t L,
+                       double alpha, double temperature, int token_reduction,
+                       float* retriever_scores, float* d_scores, float* coef, float* loss, float* diag,
+                       float* workspace /* DEVICE scratch */, int64_t workspace_floats, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * H5p sequence pooling of the encoder's last hidden state: aggregate, activation, norm and scale, fused, with backward.
  * Replaces: VodPooler.forward, MeanAgg, ClsAgg (src/vod_models/vod_encoder/modeling.py:76-89,164-174) and their autograd backward.
  * All pointers DEVICE, every call runs on `stream`, nothing synchronises, no atomics: two runs are bitwise equal.

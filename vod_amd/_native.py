@@ -107,6 +107,11 @@ SIGNATURES: dict[str, tuple] = {
         _i32, [_vp, _vp, _i32, _i32, _i64, _i64, _i64, _vp, _vp, _vp, _i32, _i64, _vp, _vp, _vp, _vp, _vp, _i64, _vp],
     ),
     "vodhip_lm_token_logprob_backward": (_i32, [_vp, _i32, _i64, _i64, _i64, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp]),
+    # H5v Renyi VOD objective (kernels_marginal.hip): the row stage between the token forward and the two backward calls
+    "vodhip_vod_forward": (
+        _i32, [_vp, _vp, _i32, _i32, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _i32, _i64, _c.c_double, _c.c_double, _i32,
+               _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp],
+    ),
     # H5p sequence pooling (kernels_pool.hip)
     "vodhip_pool_workspace_floats": (_i64, [_i64, _i64, _i64, _i64]),
     "vodhip_pool_forward": (

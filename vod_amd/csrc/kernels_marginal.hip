@@ -303,6 +303,225 @@ __global__ __launch_bounds__(ML_THREADS) void marginal_finalize_kernel(const flo
     if (threadIdx.x == 0) loss[0] = -acc / (float)B;
 }
 
+// ------------------------------------------------------------------------------------------------
+// The two stages that open vod_row_kernel, as functions: the contraction and the masked token reduction of marginal_row_kernel
+// (which keeps its own inline copy: its code object stays the one its measurements were taken on); 256 threads, LDS rows of D floats.
+// ------------------------------------------------------------------------------------------------
+// S[d] = <q[b], s[(b,)d]>.  Ends without a barrier.
+template <int DT, bool S3D, bool PRE>
+__device__ __forceinline__ void row_scores(const void* __restrict__ q, const void* __restrict__ s, int64_t b, int D, int H, float* qrow,
+                                           float* S, const float* pre_slabs, int n_slabs, int64_t slab_stride) {
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    if constexpr (PRE) {
+        // the contraction was done by small_gemm_kernel (MFMA) in `n_slabs` split-K slabs: summed here in slab order
+        for (int d = tid; d < D; d += ML_THREADS) {
+            float acc = pre_slabs[b * D + d];
+            for (int z = 1; z < n_slabs; ++z) acc += pre_slabs[(int64_t)z * slab_stride + b * D + d];
+            S[d] = acc;
+        }
+    } else {
+        for (int h = tid; h < H; h += ML_THREADS) qrow[h] = ld_enc<DT>(q, b * H + h);
+        __syncthreads();
+        // one wavefront per section, lanes split the hidden dimension (coalesced reads of s)
+        const int64_t s_base = S3D ? b * (int64_t)D * H : 0;
+        for (int d = wave; d < D; d += ML_THREADS / 64) {
+            const int64_t off = s_base + (int64_t)d * H;
+            float acc = 0.f;
+            for (int h = lane; h < H; h += 64) acc = fmaf(qrow[h], ld_enc<DT>(s, off + h), acc);
+            acc = wave_sum(acc);
+            if (lane == 0) S[d] = acc;
+        }
+    }
+}
+
+// Nn[d] = live tokens of (b, d); X[d] = the sum of their log-probs, over Nn[d] when `mean` (0 / 0 = NaN), else NaN when there is none.
+// One wavefront per section, lanes split L, fixed order.  Ends without a barrier.
+__device__ __forceinline__ void row_token_reduce(const float* __restrict__ tok_logp, const void* __restrict__ mask, int mask_eb,
+                                                 int64_t L, int64_t b, int D, float* X, float* Nn, bool mean) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    for (int d = wave; d < D; d += ML_THREADS / 64) {
+        const int64_t bd = b * D + d;
+        float acc = 0.f, cnt = 0.f;
+        for (int64_t t = lane; t < L - 1; t += 64) {
+            if (mask_live(mask, bd * L + t + 1, mask_eb)) {
+                acc += tok_logp[bd * (L - 1) + t];
+                cnt += 1.f;
+            }
+        }
+        acc = wave_sum(acc);
+        cnt = wave_sum(cnt);
+        if (lane == 0) {
+            X[d] = mean ? acc / cnt : (cnt > 0.f ? acc : __builtin_nanf(""));
+            Nn[d] = cnt;
+        }
+    }
+}
+
+// ------------------------------------------------------------------------------------------------
+// 4. VOD row kernel: the Renyi bound over the priority-sampled sections of one query row (include/vodhip.h H5v has the formulas).
+//    One 256-thread workgroup per row, the same opening as marginal_row_kernel.  A section is live when it is not padded and
+//    neither its log-weight nor its log-proposal c is -inf; LS[d] = -inf marks every other section, which no sum visits.
+//      LS: log_weight -> ls = log_weight - logsumexp   S: r -> g = r - c -> log pi = ls + g - lZ   X: l -> lw = l + g - lZ
+//    A NaN log-weight or proposal of a live section needs no test: it reaches every sum of the row, the four row words and the
+//    gradients of every live section of the row (fmaxf skips it, the sums do not).
+//    `eps == 0` (alpha = 1) is the same for every lane: the ELBO, and omega = exp(ls) without the product 0 * lw (lw may be -inf).
+//    row_words [4, B]: Lhat, Lhat at alpha = 0, Lhat at alpha = 1, 1 / sum omega^2.
+// ------------------------------------------------------------------------------------------------
+template <int DT, bool S3D, bool PRE>
+__global__ __launch_bounds__(ML_THREADS) void vod_row_kernel(
+    const void* __restrict__ q, const void* __restrict__ s, int D, int H, const float* __restrict__ score,
+    const float* __restrict__ log_weight, const float* __restrict__ log_proposal, const float* __restrict__ tok_logp,
+    const void* __restrict__ mask, int mask_eb, int64_t L, float eps, float temperature, int tok_mean,
+    // no `restrict` on retriever_scores: with one slab the contraction was written INTO it (read to LDS first)
+    float* retriever_scores, float* __restrict__ d_scores, float* __restrict__ coef, float* __restrict__ row_words, int B,
+    float inv_B, const float* pre_slabs, int n_slabs, int64_t slab_stride) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    float* qrow = (float*)smem;  // [H]
+    float* S = qrow + H;         // [D]
+    float* X = S + D;            // [D]
+    float* Nn = X + D;           // [D] live tokens
+    float* LS = Nn + D;          // [D]
+    float* red = LS + D;         // [4]
+    const int64_t b = blockIdx.x;
+    const int tid = threadIdx.x;
+    const float ninf = -__builtin_inff(), qnan = __builtin_nanf("");
+
+    row_scores<DT, S3D, PRE>(q, s, b, D, H, qrow, S, pre_slabs, n_slabs, slab_stride);
+    row_token_reduce(tok_logp, mask, mask_eb, L, b, D, X, Nn, tok_mean != 0);
+    __syncthreads();
+
+    const float* score_row = score + b * D;
+    const float* logw_row = log_weight + b * D;
+    float n_live = 0.f, mx = ninf;
+    for (int d = tid; d < D; d += ML_THREADS) {
+        const float sc = score_row[d];
+        const bool pad = __builtin_isinf(sc) && sc < 0;
+        const float r = pad ? ninf : S[d];
+        retriever_scores[b * D + d] = r;
+        // the three words are loaded side by side (one memory latency, not two); a padded section's log-weight and proposal are then
+        // dropped unseen (temperature 0 would make 0 * -inf of its score).  The product is rounded on its own: r - c is the same
+        // bits whether c was passed or formed here
+        const float lw_in = logw_row[d];
+        const float c = log_proposal ? log_proposal[b * D + d] : __fmul_rn(temperature, sc);
+        float lw = ninf, g = 0.f;
+        if (!pad) {
+            lw = c == ninf ? ninf : lw_in;
+            g = r - c;
+        }
+        const bool live = !(lw == ninf);
+        LS[d] = lw;
+        S[d] = live ? g : 0.f;
+        if (live) n_live += 1.f;
+        mx = fmaxf(mx, lw);
+    }
+    n_live = block_sum(n_live, red);
+    if (n_live == 0.f) {  // (the same for every thread) no live section: a NaN row without gradients
+        for (int d = tid; d < D; d += ML_THREADS) d_scores[b * D + d] = coef[b * D + d] = 0.f;
+        if (tid < 4) row_words[(int64_t)tid * B + b] = qnan;
+        return;
+    }
+    mx = block_max(mx, red);
+    float se = 0.f;
+    for (int d = tid; d < D; d += ML_THREADS)
+        if (!(LS[d] == ninf)) se += expf(LS[d] - mx);
+    se = block_sum(se, red);
+    const float lse_w = mx + logf(se);
+    float amax = ninf;
+    for (int d = tid; d < D; d += ML_THREADS) {
+        if (LS[d] == ninf) continue;
+        const float ls = LS[d] - lse_w;
+        LS[d] = ls;
+        amax = fmaxf(amax, ls + S[d]);
+    }
+    amax = block_max(amax, red);
+    float ae = 0.f;
+    for (int d = tid; d < D; d += ML_THREADS)
+        if (!(LS[d] == ninf)) ae += expf(LS[d] + S[d] - amax);
+    ae = block_sum(ae, red);
+    const float lZ = amax + logf(ae);
+    // u = ls + eps lw (the logits of omega) and u1 = ls + lw, with their maxima
+    float umax = ninf, u1max = ninf;
+    for (int d = tid; d < D; d += ML_THREADS) {
+        if (LS[d] == ninf) continue;
+        const float g = S[d];
+        const float lw = X[d] + g - lZ;
+        X[d] = lw;
+        S[d] = LS[d] + g - lZ;
+        umax = fmaxf(umax, eps > 0.f ? fmaf(eps, lw, LS[d]) : LS[d]);  // (fmaxf skips NaN: the sums below do not)
+        u1max = fmaxf(u1max, LS[d] + lw);
+    }
+    umax = block_max(umax, red);
+    u1max = block_max(u1max, red);
+    float t1 = 0.f, t2 = 0.f, t_iw = 0.f, s_elbo = 0.f;
+    for (int d = tid; d < D; d += ML_THREADS) {
+        if (LS[d] == ninf) continue;
+        const float lw = X[d];
+        const float e = expf((eps > 0.f ? fmaf(eps, lw, LS[d]) : LS[d]) - umax);
+        t1 += e;
+        t2 = fmaf(e, e, t2);
+        t_iw += expf(LS[d] + lw - u1max);
+        s_elbo = fmaf(expf(LS[d]), lw, s_elbo);
+    }
+    t1 = block_sum(t1, red);
+    t2 = block_sum(t2, red);
+    t_iw = block_sum(t_iw, red);
+    s_elbo = block_sum(s_elbo, red);
+    // Lhat = m + log1p(sum exp(ls) expm1(eps (lw - m))) / eps holds for EVERY shift m.  With m = max lw the sum can sit next to -1
+    // (little weight on the best section) and log1p multiplies its rounding error by 1 / (1 + sum); with m = the plain
+    // log-sum-exp value of the bound - exact to an ulp of u over eps - the sum is ~ 0 and what is left is the correction that the
+    // plain form loses as eps -> 0.  exp(ls) expm1(x) is formed as exp(ls + x) - exp(ls) where |x| >= 1: no cancellation there, and
+    // no overflow of exp(x) alone.
+    const float l_iw = u1max + logf(t_iw);
+    float l_hat = s_elbo;
+    if (eps > 0.f) {
+        const float m = (umax + logf(t1)) / eps;
+        float s_eps = 0.f;
+        for (int d = tid; d < D; d += ML_THREADS) {
+            if (LS[d] == ninf) continue;
+            const float x = eps * (X[d] - m);
+            s_eps += fabsf(x) < 1.f ? expf(LS[d]) * expm1f(x) : expf(LS[d] + x) - expf(LS[d]);
+        }
+        s_eps = block_sum(s_eps, red);
+        l_hat = m + log1pf(s_eps) / eps;
+    }
+    for (int d = tid; d < D; d += ML_THREADS) {
+        float ds = 0.f, cf = 0.f;
+        if (!(LS[d] == ninf)) {
+            const float omega = expf((eps > 0.f ? fmaf(eps, X[d], LS[d]) : LS[d]) - umax) / t1;
+            ds = -(omega - expf(S[d])) * inv_B;
+            cf = -omega * inv_B;
+            if (tok_mean) cf /= Nn[d];
+        }
+        d_scores[b * D + d] = ds;
+        coef[b * D + d] = cf;
+    }
+    if (tid == 0) {
+        row_words[b] = l_hat;
+        row_words[(int64_t)B + b] = l_iw;
+        row_words[2 * (int64_t)B + b] = s_elbo;
+        row_words[3 * (int64_t)B + b] = t1 * t1 / t2;
+    }
+}
+
+// loss = -mean Lhat ; diag = means of the other three row words
+__global__ __launch_bounds__(ML_THREADS) void vod_finalize_kernel(const float* __restrict__ row_words, int B, float* __restrict__ loss,
+                                                                  float* __restrict__ diag) {
+    __shared__ float red[4];
+    float part[4] = {0.f, 0.f, 0.f, 0.f};  // the four loads of a thread go out together
+    for (int b = threadIdx.x; b < B; b += ML_THREADS) {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) part[k] += row_words[(int64_t)k * B + b];
+    }
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const float acc = block_sum(part[k], red);
+        if (threadIdx.x == 0) {
+            if (k == 0) loss[0] = -acc / (float)B;
+            else diag[k - 1] = acc / (float)B;
+        }
+    }
+}
+
 // 16-byte accesses need every row base on a 16-byte boundary: the tensor's and a row's pitch
 static bool rows_aligned(const void* p, int64_t V, int dtype) {
     const int64_t es = dtype == 2 ? 4 : 2;
@@ -389,6 +608,46 @@ hipError_t launch_marginal_forward(const void* q, const void* s, int enc_dtype, 
     e = hipGetLastError();
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(marginal_finalize_kernel, dim3(1), dim3(ML_THREADS), 0, stream, row_lpx, (int)B, loss);
+    return hipGetLastError();
+}
+
+hipError_t launch_vod_forward(const void* q, const void* s, int enc_dtype, int sections_3d, int64_t B, int64_t D, int64_t H,
+                              const float* score, const float* log_weight, const float* log_proposal, const float* tok_logp,
+                              const void* mask, int mask_eb, int64_t L, float eps, float temperature, int tok_mean,
+                              float* retriever_scores, float* d_scores, float* coef, float* loss, float* diag, float* workspace,
+                              int64_t workspace_floats, hipStream_t stream) {
+    const size_t lds = (size_t)(H + 4 * D + 4) * sizeof(float);
+    if (lds > 160 * 1024) return hipErrorInvalidValue;
+    const float inv_B = 1.f / (float)B;
+    float* row_words = workspace;  // [4, B]
+    hipError_t e;
+    // the contraction of 2-D sections as in launch_marginal_forward: four split-K slabs behind the row words, or retriever_scores
+    int n_splits = 1;
+    float* slabs = retriever_scores;
+    if (!sections_3d) {
+        if (H >= 512 && workspace_floats >= 4 * B + 4 * B * D) {
+            n_splits = 4;
+            slabs = workspace + 4 * B;
+        }
+        e = launch_small_gemm(enc_dtype, enc_dtype, q, H, 1, s, 1, H, slabs, D, (int)B, (int)D, (int)H, nullptr, stream, n_splits, B * D);
+        if (e != hipSuccess) return e;
+    }
+#define VOD_VR(DT, S3D, PRE)                                                                                               \
+    if (enc_dtype == DT && (sections_3d != 0) == S3D) {                                                                    \
+        auto kern = vod_row_kernel<DT, S3D, PRE>;                                                                          \
+        e = allow_dynamic_lds((const void*)kern, 160 * 1024);                                                              \
+        if (e != hipSuccess) return e;                                                                                     \
+        hipLaunchKernelGGL(kern, dim3((unsigned)B), dim3(ML_THREADS), lds, stream, q, s, (int)D, (int)H, score, log_weight, \
+                           log_proposal, tok_logp, mask, mask_eb, L, eps, temperature, tok_mean, retriever_scores, d_scores, \
+                           coef, row_words, (int)B, inv_B, (const float*)(PRE ? slabs : nullptr), PRE ? n_splits : 0,      \
+                           PRE ? B * D : (int64_t)0);                                                                      \
+    }
+    VOD_VR(0, true, false) VOD_VR(1, true, false) VOD_VR(2, true, false)
+    VOD_VR(0, false, true) VOD_VR(1, false, true) VOD_VR(2, false, true)
+#undef VOD_VR
+    e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(vod_finalize_kernel, dim3(1), dim3(ML_THREADS), 0, stream, row_words, (int)B, loss, diag);
     return hipGetLastError();
 }
 

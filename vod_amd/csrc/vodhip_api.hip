@@ -4,6 +4,7 @@
 #include "../../include/vodhip.h"
 
 #include <algorithm>
+#include <cmath>
 #include <cstdarg>
 #include <cstdio>
 #include <cstdint>
@@ -1272,6 +1273,33 @@ int vodhip_marginal_forward(const void* q, const void* s, int enc_dtype, int sec
     if (workspace_floats < B) return fail("workspace_floats=%lld < B", (long long)workspace_floats);
     HIP_OK(launch_marginal_forward(q, s, enc_dtype, sections_3d, B, D, H, score, tok_logp, attention_mask, mask_elem_bytes, L,
                                    retriever_scores, d_scores, coef, loss, workspace, workspace_floats, (hipStream_t)stream));
+    return 0;
+}
+
+int vodhip_vod_forward(const void* q, const void* s, int enc_dtype, int sections_3d, int64_t B, int64_t D, int64_t H,
+                       const float* score, const float* log_weight, const float* log_proposal, const float* tok_logp,
+                       const void* attention_mask, int mask_elem_bytes, int64_t L, double alpha, double temperature,
+                       int token_reduction, float* retriever_scores, float* d_scores, float* coef, float* loss, float* diag,
+                       float* workspace, int64_t workspace_floats, void* stream) {
+    if (!q || !s || !score || !log_weight || !tok_logp || !attention_mask || !retriever_scores || !d_scores || !coef || !loss ||
+        !diag || !workspace)
+        return fail("NULL argument");
+    if (B <= 0 || D <= 0 || H <= 0) return fail("invalid sizes");
+    if (L < 2) return fail("L=%lld: the shifted sequence needs L >= 2", (long long)L);
+    if (D > 8192) return fail("D=%lld exceeds 8192 sections per row", (long long)D);
+    if ((H + 4 * D + 4) * 4 > 160 * 1024) return fail("H + 4 * D = %lld floats exceed the 160 KiB of LDS", (long long)(H + 4 * D));
+    if (B > 0x7fffffffLL / 4) return fail("B exceeds 2^29");
+    if (enc_dtype < 0 || enc_dtype > 2) return fail("invalid enc_dtype");
+    if (!marginal_mask_ok(mask_elem_bytes)) return fail("mask_elem_bytes must be 1, 2, 4 or 8");
+    if (!(alpha >= 0.0 && alpha <= 1.0)) return fail("alpha=%g is outside [0, 1]", alpha);
+    if (!std::isfinite(temperature)) return fail("temperature=%g is not finite", temperature);
+    if (token_reduction != VODHIP_VOD_TOKEN_MEAN && token_reduction != VODHIP_VOD_TOKEN_SUM)
+        return fail("unknown token_reduction (0 = mean, 1 = sum)");
+    if (workspace_floats < 4 * B) return fail("workspace_floats=%lld < 4 * B", (long long)workspace_floats);
+    HIP_OK(launch_vod_forward(q, s, enc_dtype, sections_3d, B, D, H, score, log_weight, log_proposal, tok_logp, attention_mask,
+                              mask_elem_bytes, L, (float)(1.0 - alpha), (float)temperature,
+                              token_reduction == VODHIP_VOD_TOKEN_MEAN ? 1 : 0, retriever_scores, d_scores, coef, loss, diag,
+                              workspace, workspace_floats, (hipStream_t)stream));
     return 0;
 }
 

@@ -259,6 +259,12 @@ hipError_t launch_marginal_forward(const void* q, const void* s, int enc_dtype, 
                                    const float* score, const float* tok_logp, const void* mask, int mask_eb, int64_t L,
                                    float* retriever_scores, float* d_scores, float* coef, float* loss, float* workspace,
                                    int64_t workspace_floats, hipStream_t stream);
+// eps = 1 - alpha; log_proposal may be NULL (temperature * score); tok_mean: 1 = mean over the live tokens, 0 = their sum
+hipError_t launch_vod_forward(const void* q, const void* s, int enc_dtype, int sections_3d, int64_t B, int64_t D, int64_t H,
+                              const float* score, const float* log_weight, const float* log_proposal, const float* tok_logp,
+                              const void* mask, int mask_eb, int64_t L, float eps, float temperature, int tok_mean,
+                              float* retriever_scores, float* d_scores, float* coef, float* loss, float* diag, float* workspace,
+                              int64_t workspace_floats, hipStream_t stream);
 
 // ---- launchers (kernels_sample.hip) -----------------------------------------------------------
 hipError_t launch_priority_sample(const float* scores, const uint8_t* labels, const float* noise, int64_t nq, int width,

@@ -1,5 +1,6 @@
-"""In-batch retrieval scoring + loss, and the marginal likelihood through the reader LM, on the GPU (host wrappers over
-`vodhip_retrieval_forward/backward` and `vodhip_lm_token_logprob_forward/backward` + `vodhip_marginal_forward`).
+"""In-batch retrieval scoring + loss, and the marginal likelihood and the Renyi VOD objective through the reader LM, on the GPU (host
+wrappers over `vodhip_retrieval_forward/backward` and `vodhip_lm_token_logprob_forward/backward` + `vodhip_marginal_forward` /
+`vodhip_vod_forward`).
 
 Mirror of `RetrievalGradients` (/root/reference/src/vod_models/vod_gradients/retrieval.py:14-92): same
 constructor, same keyword-only call `(batch, query_encoding, section_encoding)`, same outputs (`loss`,
@@ -13,6 +14,7 @@ row kernel: values in `diagnostics`, gradients folded into the same dLoss/dScore
 from __future__ import annotations
 
 import dataclasses
+import math
 import typing as typ
 
 import torch
@@ -166,37 +168,85 @@ class RetrievalGradients:
         return RealmOutput(loss=loss, retriever_scores=scores, diagnostics=diagnostics)
 
 
+def _lm_step_inputs(who, q, s, lm_logits, input_ids, attention_mask, pair_words):  # noqa: ANN001
+    """What the objectives through the reader LM share: every tensor on `q`'s GPU, shapes checked, in the layout the kernels read.
+
+    `pair_words` is a list of `(name, tensor | None)` that must be float32 `[B, D]` words of the batch (`section__score`, ...).
+    """
+    if not q.is_cuda:
+        raise _native.NativeLibraryError(f"{who} needs device tensors (there is no CPU path)")
+    for name, x in (("section_encoding", s), *pair_words, ("lm_logits", lm_logits), ("lm__input_ids", input_ids),
+                    ("lm__attention_mask", attention_mask)):
+        if x is not None and x.device != q.device:  # the kernels get raw pointers: a host or other-device tensor must never reach them
+            raise _native.NativeLibraryError(f"`{name}` is on {x.device}, `query_encoding` on {q.device}: all tensors must share one GPU")
+    if lm_logits.dim() != 4:
+        raise ValueError(f"`lm_logits` must be [B, D, L, V], got {tuple(lm_logits.shape)}")
+    enc = q.dtype if q.dtype in _ENC else torch.float32
+    ldt = lm_logits.dtype if lm_logits.dtype in _ENC else torch.float32
+    qc, sc, lg = _as(q, enc), _as(s, enc), _as(lm_logits, ldt)
+    if sc.dim() not in (2, 3):
+        raise ValueError(f"Invalid dimension for `section_encoding`: {tuple(sc.shape)}")
+    three_d = sc.dim() == 3
+    B, H = qc.shape
+    D = sc.shape[1] if three_d else sc.shape[0]
+    _, _, L, V = lg.shape
+    if L < 2:
+        raise ValueError(f"`lm_logits` has L={L} positions: the shifted sequence needs L >= 2")
+    if lg.shape[:2] != (B, D) or input_ids.shape != (B, D, L) or attention_mask.shape != (B, D, L):
+        raise ValueError(f"lm_logits must be [{B}, {D}, L, V], lm__input_ids / lm__attention_mask [{B}, {D}, {L}]")
+    words = []
+    for name, x in pair_words:
+        xc = None if x is None else _as(x, torch.float32)
+        if xc is not None and xc.shape != (B, D):
+            raise ValueError(f"{name} must be [{B}, {D}]")
+        words.append(xc)
+    ids = _as(input_ids, torch.int64)
+    # the kernels test a mask element for any set bit: bool and integer masks are read as they are
+    mask = attention_mask if not (attention_mask.is_floating_point() or attention_mask.is_complex()) else attention_mask != 0
+    mask = mask.contiguous()
+    return enc, ldt, qc, sc, lg, three_d, (B, D, H, L, V), words, ids, mask
+
+
+def _lm_step_backward(ctx, g_loss, logits_arg):  # noqa: ANN001
+    """`(dq, ds, d_logits)` from the forward's `d_scores` and `coef`; `lm_logits` was argument `logits_arg` of the forward."""
+    lib = _native.load_library()
+    qc, sc, lg, ids, mask, tok_lse, coef, d_scores = ctx.saved_tensors
+    enc, ldt, three_d, B, D, H, L, V, q_dt, s_dt, lg_dt, mask_eb = ctx.meta
+    dev = qc.device
+    stream = _native.current_stream_ptr(dev)
+    go = g_loss if (g_loss.dtype is torch.float32 and g_loss.is_contiguous()) else g_loss.float().contiguous()
+    need_q, need_s, need_lg = ctx.needs_input_grad[0], ctx.needs_input_grad[1], ctx.needs_input_grad[logits_arg]
+    dq = ds = d_lg = None
+    with _on_device(dev):
+        if need_q or need_s:
+            dq = torch.empty((B, H), dtype=torch.float32, device=dev)
+            ds = torch.empty(sc.shape, dtype=torch.float32, device=dev)
+            _native.check(
+                lib.vodhip_retrieval_backward(
+                    qc.data_ptr(), sc.data_ptr(), _native.torch_dtype_code(enc), int(three_d), B, D, H,
+                    d_scores.data_ptr(), go.data_ptr(), dq.data_ptr(), ds.data_ptr(), stream,
+                )
+            )
+            dq = dq if q_dt is torch.float32 else dq.to(q_dt)
+            ds = ds if s_dt is torch.float32 else ds.to(s_dt)
+        if need_lg:
+            d_lg = torch.empty_like(lg)  # the one logits-sized tensor of the step
+            _native.check(
+                lib.vodhip_lm_token_logprob_backward(
+                    lg.data_ptr(), _native.torch_dtype_code(ldt), B * D, L, V, ids.data_ptr(), mask.data_ptr(), mask_eb,
+                    tok_lse.data_ptr(), coef.data_ptr(), go.data_ptr(), d_lg.data_ptr(), stream,
+                )
+            )
+            d_lg = d_lg if lg_dt is ldt else d_lg.to(lg_dt)
+    return dq, ds, d_lg
+
+
 class _MarginalLikelihood(torch.autograd.Function):
     @staticmethod
     def forward(ctx, q, s, score, lm_logits, input_ids, attention_mask):  # noqa: ANN001
         lib = _native.load_library()
-        if not q.is_cuda:
-            raise _native.NativeLibraryError("MarginalLikelihoodGradients needs device tensors (there is no CPU path)")
-        for name, x in (("section_encoding", s), ("section__score", score), ("lm_logits", lm_logits), ("lm__input_ids", input_ids),
-                        ("lm__attention_mask", attention_mask)):
-            if x.device != q.device:  # the kernels get raw pointers: a host or other-device tensor must never reach them
-                raise _native.NativeLibraryError(f"`{name}` is on {x.device}, `query_encoding` on {q.device}: all tensors must share one GPU")
-        if lm_logits.dim() != 4:
-            raise ValueError(f"`lm_logits` must be [B, D, L, V], got {tuple(lm_logits.shape)}")
-        enc = q.dtype if q.dtype in _ENC else torch.float32
-        ldt = lm_logits.dtype if lm_logits.dtype in _ENC else torch.float32
-        qc, sc, lg = _as(q, enc), _as(s, enc), _as(lm_logits, ldt)
-        if sc.dim() not in (2, 3):
-            raise ValueError(f"Invalid dimension for `section_encoding`: {tuple(sc.shape)}")
-        three_d = sc.dim() == 3
-        B, H = qc.shape
-        D = sc.shape[1] if three_d else sc.shape[0]
-        _, _, L, V = lg.shape
-        if L < 2:
-            raise ValueError(f"`lm_logits` has L={L} positions: the shifted sequence needs L >= 2")
-        if lg.shape[:2] != (B, D) or input_ids.shape != (B, D, L) or attention_mask.shape != (B, D, L):
-            raise ValueError(f"lm_logits must be [{B}, {D}, L, V], lm__input_ids / lm__attention_mask [{B}, {D}, {L}]")
-        score_c, ids = _as(score, torch.float32), _as(input_ids, torch.int64)
-        if score_c.shape != (B, D):
-            raise ValueError(f"section__score must be [{B}, {D}]")
-        # the kernels test a mask element for any set bit: bool and integer masks are read as they are
-        mask = attention_mask if not (attention_mask.is_floating_point() or attention_mask.is_complex()) else attention_mask != 0
-        mask = mask.contiguous()
+        enc, ldt, qc, sc, lg, three_d, (B, D, H, L, V), (score_c,), ids, mask = _lm_step_inputs(
+            "MarginalLikelihoodGradients", q, s, lm_logits, input_ids, attention_mask, [("section__score", score)])
         mask_eb = mask.element_size()
         dev = q.device
         stream = _native.current_stream_ptr(dev)
@@ -231,35 +281,7 @@ class _MarginalLikelihood(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g_loss, _g_scores):  # noqa: ANN001
-        lib = _native.load_library()
-        qc, sc, lg, ids, mask, tok_lse, coef, d_scores = ctx.saved_tensors
-        enc, ldt, three_d, B, D, H, L, V, q_dt, s_dt, lg_dt, mask_eb = ctx.meta
-        dev = qc.device
-        stream = _native.current_stream_ptr(dev)
-        go = g_loss if (g_loss.dtype is torch.float32 and g_loss.is_contiguous()) else g_loss.float().contiguous()
-        need_q, need_s, need_lg = ctx.needs_input_grad[0], ctx.needs_input_grad[1], ctx.needs_input_grad[3]
-        dq = ds = d_lg = None
-        with _on_device(dev):
-            if need_q or need_s:
-                dq = torch.empty((B, H), dtype=torch.float32, device=dev)
-                ds = torch.empty(sc.shape, dtype=torch.float32, device=dev)
-                _native.check(
-                    lib.vodhip_retrieval_backward(
-                        qc.data_ptr(), sc.data_ptr(), _native.torch_dtype_code(enc), int(three_d), B, D, H,
-                        d_scores.data_ptr(), go.data_ptr(), dq.data_ptr(), ds.data_ptr(), stream,
-                    )
-                )
-                dq = dq if q_dt is torch.float32 else dq.to(q_dt)
-                ds = ds if s_dt is torch.float32 else ds.to(s_dt)
-            if need_lg:
-                d_lg = torch.empty_like(lg)  # the one logits-sized tensor of the step
-                _native.check(
-                    lib.vodhip_lm_token_logprob_backward(
-                        lg.data_ptr(), _native.torch_dtype_code(ldt), B * D, L, V, ids.data_ptr(), mask.data_ptr(), mask_eb,
-                        tok_lse.data_ptr(), coef.data_ptr(), go.data_ptr(), d_lg.data_ptr(), stream,
-                    )
-                )
-                d_lg = d_lg if lg_dt is ldt else d_lg.to(lg_dt)
+        dq, ds, d_lg = _lm_step_backward(ctx, g_loss, 3)
         return dq, ds, None, d_lg, None, None
 
 
@@ -282,6 +304,96 @@ class MarginalLikelihoodGradients:
             raise ValueError("MarginalLikelihoodGradients needs section__score, lm__input_ids, lm__attention_mask and lm_logits")
         loss, scores = _MarginalLikelihood.apply(query_encoding, section_encoding, score, lm_logits, ids, mask)
         return RealmOutput(loss=loss, retriever_scores=scores)
+
+
+class _Vod(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, q, s, score, log_weight, log_proposal, lm_logits, input_ids, attention_mask, cfg):  # noqa: ANN001
+        lib = _native.load_library()
+        alpha, temperature, reduction = cfg
+        enc, ldt, qc, sc, lg, three_d, (B, D, H, L, V), (score_c, logw_c, logc_c), ids, mask = _lm_step_inputs(
+            "VodGradients", q, s, lm_logits, input_ids, attention_mask,
+            [("section__score", score), ("section__log_weight", log_weight), ("section__log_proposal", log_proposal)])
+        mask_eb = mask.element_size()
+        dev = q.device
+        stream = _native.current_stream_ptr(dev)
+        N = B * D
+        # per-token words: log-prob | (row max, log sum-exp); per-pair words: retriever scores | dLoss/dScores | coef; loss [1] | diag [3]
+        tok = torch.empty((3, N, L - 1), dtype=torch.float32, device=dev)
+        pairs = torch.empty((3, B, D), dtype=torch.float32, device=dev)
+        small = torch.empty((4,), dtype=torch.float32, device=dev)
+        n_work = 4 * B + (4 * B * D if (not three_d and H >= 512) else 0)
+        work = torch.empty((n_work,), dtype=torch.float32, device=dev)
+        p_tok, p_pairs, p_small = tok.data_ptr(), pairs.data_ptr(), small.data_ptr()
+        with _on_device(dev):
+            _native.check(
+                lib.vodhip_lm_token_logprob_forward(
+                    lg.data_ptr(), _native.torch_dtype_code(ldt), N, L, V, ids.data_ptr(), mask.data_ptr(), mask_eb,
+                    p_tok, p_tok + 4 * N * (L - 1), stream,
+                )
+            )
+            _native.check(
+                lib.vodhip_vod_forward(
+                    qc.data_ptr(), sc.data_ptr(), _native.torch_dtype_code(enc), int(three_d), B, D, H, score_c.data_ptr(),
+                    logw_c.data_ptr(), None if logc_c is None else logc_c.data_ptr(), p_tok, mask.data_ptr(), mask_eb, L,
+                    alpha, temperature, reduction, p_pairs, p_pairs + 4 * N, p_pairs + 8 * N, p_small, p_small + 4,
+                    work.data_ptr(), n_work, stream,
+                )
+            )
+        scores, d_scores, coef = pairs[0], pairs[1], pairs[2]
+        tok_lse = tok[1:].view(N, L - 1, 2)
+        ctx.save_for_backward(qc, sc, lg, ids, mask, tok_lse, coef, d_scores)
+        ctx.meta = (enc, ldt, three_d, B, D, H, L, V, q.dtype, s.dtype, lm_logits.dtype, mask_eb)
+        diag = small[1:]
+        ctx.mark_non_differentiable(scores, diag)
+        return small[0], scores, diag
+
+    @staticmethod
+    def backward(ctx, g_loss, _g_scores, _g_diag):  # noqa: ANN001
+        dq, ds, d_lg = _lm_step_backward(ctx, g_loss, 5)
+        return dq, ds, None, None, None, d_lg, None, None, None
+
+
+class VodGradients:
+    """The Renyi VOD objective (Lievin et al., arXiv 2210.06345) over the priority-sampled sections of a batch, fused on the GPU.
+
+    The reference's `VodGradients` (src/vod_models/vod_gradients/vod.py:14-26) raises `NotImplementedError`; this is the objective
+    its collate was built for: the self-normalised importance-sampling estimate of the Renyi bound of order `alpha`, differentiated
+    with respect to the model with the sampler held constant (include/vodhip.h H5v has the formulas).  `alpha = 0` is the
+    importance-weighted bound, `alpha = 1` the ELBO; `alpha` is a plain attribute, so a schedule may set it between steps.
+    The keyword-only call `(batch, query_encoding, section_encoding, lm_logits)` reads `section__score`, `section__log_weight`
+    (what `vodhip_priority_sample` / the collate emit), `lm__input_ids`, `lm__attention_mask` and, when present,
+    `section__log_proposal`: the sampler's log proposal up to a per-row constant.  Without it the proposal is taken to be
+    `softmax(temperature * section__score)`, which is exact for a single-softmax sampler only.
+    `token_reduction` is "mean" (the convention of the reference's `_compute_lm_logprobs`) or "sum" (the paper's log p(x | z)).
+    Returns `loss`, `retriever_scores` and the detached diagnostics `iw_bound`, `elbo` and `ess` of the same launch.
+    """
+
+    def __init__(self, alpha: float = 0.0, temperature: float = 1.0, token_reduction: str = "mean"):
+        if token_reduction not in ("mean", "sum"):
+            raise ValueError(f"token_reduction must be 'mean' or 'sum', got {token_reduction!r}")
+        self.alpha = alpha
+        self.temperature = temperature
+        self.token_reduction = token_reduction
+
+    def __call__(self, *, batch: typ.Any, query_encoding: torch.Tensor, section_encoding: torch.Tensor,
+                 lm_logits: torch.Tensor) -> RealmOutput:
+        get = (lambda k: batch.get(k)) if isinstance(batch, dict) else (lambda k: getattr(batch, k, None))
+        alpha, temperature = float(self.alpha), float(self.temperature)
+        if not 0.0 <= alpha <= 1.0:  # (false for NaN)
+            raise ValueError(f"alpha must be in [0, 1], got {self.alpha!r}")
+        if not math.isfinite(temperature):
+            raise ValueError(f"temperature must be finite, got {self.temperature!r}")
+        score, ids, mask = get("section__score"), get("lm__input_ids"), get("lm__attention_mask")
+        if score is None or ids is None or mask is None or lm_logits is None:
+            raise ValueError("VodGradients needs section__score, lm__input_ids, lm__attention_mask and lm_logits")
+        log_weight = get("section__log_weight")
+        if log_weight is None:
+            raise ValueError("VodGradients needs section__log_weight, the importance weights of the sampled sections "
+                             "(`collate_on_device(...).to_dict('section__')` carries them)")
+        loss, scores, diag = _Vod.apply(query_encoding, section_encoding, score, log_weight, get("section__log_proposal"), lm_logits,
+                                        ids, mask, (alpha, temperature, 0 if self.token_reduction == "mean" else 1))
+        return RealmOutput(loss=loss, retriever_scores=scores, diagnostics={"iw_bound": diag[0], "elbo": diag[1], "ess": diag[2]})
 
 
 class GraphedRetrievalStep:
