@@ -484,7 +484,8 @@ int vodhip_retrieval_metrics(const float* scores, const int64_t* relevances, int
                              void* workspace, int64_t workspace_bytes, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
- * H7  labeled priority sampling of the merged candidates (the collate stage right after the merge).
+ * H7  labeled priority sampling of the merged candidates (the collate stage right after the merge).  The *_proposal entry points
+ *     below also emit the sampler's proposal (log_p per sample, the log-mass of each stratum, the joint weights): see there.
  * Replaces: _labeled_priority_sampling_2d_ / _labeled_priority_sampling_1d_ / _priority_sampling_1d
  *           (src/vod_dataloaders/core/sample.py:160-219,245-352) and the numba log-softmax helpers
  *           (src/vod_dataloaders/core/numpy_ops.py:162-216).
@@ -506,6 +507,23 @@ int vodhip_priority_sample(const float* scores, const uint8_t* labels, const flo
                            int64_t* out_samples, float* out_log_weights, uint8_t* out_labels, float* out_lse,
                            void* stream);
 
+/* The same sampling, also emitting the sampler's PROPOSAL: what an importance-weighted objective over the samples (H5v,
+ * vodhip_vod_forward) needs besides the per-stratum weights.
+ * Replaces: nothing the reference returns - it forms these quantities and discards them (src/vod_dataloaders/core/sample.py:180-184,
+ *           281-306): `log_norm_const` is taken AFTER log_softmax_1d_, so lse_pos / lse_neg above are ~0 and the share of each stratum
+ *           in the row's mass is lost.
+ * Per row, with a_i = t_inv * score_i (NaN -> -inf; after the support truncation) and a stratum S = the positives or the negatives:
+ *   out_log_mass [nq, 2]            log_mass_S = logsumexp_{i in S} a_i (-inf for an empty or an all -inf stratum)
+ *   out_log_proposal [nq, k_total]  log_p_j = a_j - log_mass_S(j): the float32 value the weight formula reads; -inf pad
+ *   out_joint_log_weights [nq, k_total]  out_log_weights_j + log_mass_S(j) - logaddexp(log_mass_pos, log_mass_neg): the weights of
+ *                                   ONE softmax over the whole row; -inf pad, -inf for a member of a stratum without mass.
+ *                                   Needs bit 0 of `normalized` (an error before launch otherwise).
+ * Each of the three may be NULL; with all three NULL the call writes the bits vodhip_priority_sample writes.  DEVICE pointers. */
+int vodhip_priority_sample_proposal(const float* scores, const uint8_t* labels, const float* noise, int64_t nq, int width,
+                                    int k_positive, int k_total, float temperature, int max_support_size, int normalized,
+                                    int64_t* out_samples, float* out_log_weights, uint8_t* out_labels, float* out_lse,
+                                    float* out_log_proposal, float* out_log_mass, float* out_joint_log_weights, void* stream);
+
 /* The same sampling fed straight from vodhip_merge_hybrid's full-stride outputs, with the gathers and the rank diagnostic of
  * sample_search_results (src/vod_dataloaders/core/sample.py:22-84) as an epilogue: the collate's merge -> sample chain stays on
  * the device (reference flow src/vod_dataloaders/realm_collate.py:110-122).
@@ -524,6 +542,17 @@ int vodhip_priority_sample_merged(const int64_t* ids, const float* scores, const
                                   int64_t* out_samples, int64_t* out_ids, float* out_scores, float* out_log_weights,
                                   uint8_t* out_labels, float* const* out_raw, float* out_lse, float* out_max_sampling_id,
                                   void* stream);
+
+/* vodhip_priority_sample_merged + the three proposal outputs of vodhip_priority_sample_proposal (same shapes, each may be NULL).
+ * Replaces: see vodhip_priority_sample_proposal (src/vod_dataloaders/core/sample.py:180-184, 281-306). */
+int vodhip_priority_sample_merged_proposal(const int64_t* ids, const float* scores, const int64_t* labels, int n_raw,
+                                           const float* const* raw, const float* noise, int64_t noise_stride, int64_t nq, int stride,
+                                           int width, const int32_t* merge_width, const int32_t* merge_row_cursor, int k_lookup,
+                                           int n_engines, const int* engine_k, int k_positive, int k_total, float temperature,
+                                           int max_support_size, int normalized, int64_t* out_samples, int64_t* out_ids,
+                                           float* out_scores, float* out_log_weights, uint8_t* out_labels, float* const* out_raw,
+                                           float* out_lse, float* out_max_sampling_id, float* out_log_proposal, float* out_log_mass,
+                                           float* out_joint_log_weights, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Gather by id: flattening of the sampled sections of a batch into ONE in-batch section set.
@@ -598,6 +627,25 @@ typedef struct vodhip_collate_args {
     int32_t* flat_n_unique;                           /* [1] or NULL */
 } vodhip_collate_args_t;
 int vodhip_collate(const vodhip_collate_args_t* args, void* stream);
+
+/* vodhip_collate + the sampler's proposal (vodhip_priority_sample_proposal has the definitions): merge -> sample -> (flatten) then
+ * feeds the VOD objective with no host work.  Two exact ways to feed it: "stratum" = out_log_weights as section__log_weight and
+ * out_log_proposal as section__log_proposal; "joint" = out_joint_log_weights as section__log_weight and no proposal (the objective's
+ * temperature must then be the sampler's).
+ * Replaces: what the reference discards in src/vod_dataloaders/core/sample.py:180-184, 281-306.
+ * `base` is the argument block of vodhip_collate, unchanged, at offset 0.  Every new pointer is a DEVICE pointer and may be NULL;
+ * with all of them NULL the call is vodhip_collate(&args->base, stream).  The flattened arrays fill with -inf (not NaN) where a
+ * row did not sample the id; each needs its [nq, k_total] source output and base.in_batch_negatives.  Same stream, same launches. */
+typedef struct vodhip_collate_proposal_args {
+    vodhip_collate_args_t base;
+    float* out_log_proposal;                          /* [nq, k_total] */
+    float* out_log_mass_pos;                          /* [nq] (with out_log_mass_neg, or both NULL) */
+    float* out_log_mass_neg;                          /* [nq] */
+    float* out_joint_log_weights;                     /* [nq, k_total] */
+    float* flat_log_proposal;                         /* [nq, U] */
+    float* flat_joint_log_weights;                    /* [nq, U] */
+} vodhip_collate_proposal_args_t;
+int vodhip_collate_proposal(const vodhip_collate_proposal_args_t* args, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Wire codec helper (HOST memory, no device work): urlsafe base64 of `head || data` and back.

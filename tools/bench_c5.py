@@ -1,6 +1,8 @@
 #!/usr/bin/env python3
 """Config 5 latency (hybrid merge + sampling + in-batch retrieval loss): B=64 queries, K=128 per engine x 3 engines,
-32 sampled sections, H=768.  Prints microseconds per call (median over repeats, device-tensor APIs, inputs resident)."""
+32 sampled sections, H=768.  Prints microseconds per call (median over repeats, device-tensor APIs, inputs resident).
+`--collate-only` stops before the loss; `--proposal` also times the same chain through `vodhip_collate_proposal` with every output on
+(`proposal_*` entries, measured like their `device_*` counterparts: profiles/collate_proposal.json)."""
 import json
 import statistics
 import sys
@@ -63,21 +65,28 @@ out["device_chain_with_device_noise_us"] = timeit(lambda: collate_on_device(l_id
                                                                             temperature=1.0, max_support_size=100, in_batch_negatives=True))
 
 
-def chain_events(n=200):
+def chain_events(n=200, **kw):
     """Device time of the chained launches (HIP events on the stream; excludes the host's launch cost)."""
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     for _ in range(10):
-        collate_on_device(l_idx, l_lbl, engines, wts, noise_full, total=NS, max_pos_sections=8, temperature=1.0, max_support_size=100, in_batch_negatives=True)
+        collate_on_device(l_idx, l_lbl, engines, wts, noise_full, total=NS, max_pos_sections=8, temperature=1.0, max_support_size=100, in_batch_negatives=True, **kw)
     torch.cuda.synchronize()
     e0.record()
     for _ in range(n):
-        collate_on_device(l_idx, l_lbl, engines, wts, noise_full, total=NS, max_pos_sections=8, temperature=1.0, max_support_size=100, in_batch_negatives=True)
+        collate_on_device(l_idx, l_lbl, engines, wts, noise_full, total=NS, max_pos_sections=8, temperature=1.0, max_support_size=100, in_batch_negatives=True, **kw)
     e1.record()
     torch.cuda.synchronize()
     return e0.elapsed_time(e1) * 1e3 / n
 
 
 out["device_chain_back_to_back_us"] = chain_events()
+if "--proposal" in sys.argv:  # the same chain with log_proposal / log_mass / joint_log_weights (and their flattened arrays) on
+    out["proposal_merge_sample_us"] = timeit(lambda: collate_on_device(l_idx, l_lbl, engines, wts, noise_full, total=NS, max_pos_sections=8,
+                                                                       temperature=1.0, max_support_size=100, proposal=True))
+    out["proposal_merge_sample_flatten_us"] = timeit(lambda: collate_on_device(l_idx, l_lbl, engines, wts, noise_full, total=NS, max_pos_sections=8,
+                                                                               temperature=1.0, max_support_size=100, in_batch_negatives=True,
+                                                                               proposal=True))
+    out["proposal_chain_back_to_back_us"] = chain_events(proposal=True)
 if "--collate-only" in sys.argv:
     print(json.dumps(out))
     raise SystemExit(0)

@@ -98,7 +98,15 @@ SIGNATURES: dict[str, tuple] = {
         _i32, [_vp, _vp, _vp, _i32, _vp, _vp, _i64, _i64, _i32, _i32, _vp, _vp, _i32, _i32, _vp, _i32, _i32, _c.c_float, _i32, _i32,
                _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     ),
+    "vodhip_priority_sample_proposal": (
+        _i32, [_vp, _vp, _vp, _i64, _i32, _i32, _i32, _c.c_float, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+    ),
+    "vodhip_priority_sample_merged_proposal": (
+        _i32, [_vp, _vp, _vp, _i32, _vp, _vp, _i64, _i64, _i32, _i32, _vp, _vp, _i32, _i32, _vp, _i32, _i32, _c.c_float, _i32, _i32,
+               _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+    ),
     "vodhip_collate": (_i32, [_vp, _vp]),
+    "vodhip_collate_proposal": (_i32, [_vp, _vp]),
     "vodhip_flatten_inbatch": (_i32, [_vp, _i64, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "vodhip_retrieval_backward": (_i32, [_vp, _vp, _i32, _i32, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp]),
     # H5l marginal likelihood (kernels_marginal.hip)
@@ -172,6 +180,16 @@ class CollateArgs(ctypes.Structure):
         ("out_raw", _vp * MAX_ENGINES), ("out_lse_pos", _vp), ("out_lse_neg", _vp), ("out_max_sampling_id", _vp),
         ("flat_ids", _vp), ("flat_scores", _vp), ("flat_log_weights", _vp), ("flat_labels", _vp), ("flat_raw", _vp * MAX_ENGINES),
         ("flat_n_unique", _vp),
+    ]
+
+
+class CollateProposalArgs(ctypes.Structure):
+    """`vodhip_collate_proposal_args_t` (include/vodhip.h): the unchanged `vodhip_collate_args_t` first, then the proposal outputs."""
+
+    _fields_ = [
+        ("base", CollateArgs),
+        ("out_log_proposal", _vp), ("out_log_mass_pos", _vp), ("out_log_mass_neg", _vp), ("out_joint_log_weights", _vp),
+        ("flat_log_proposal", _vp), ("flat_joint_log_weights", _vp),
     ]
 
 

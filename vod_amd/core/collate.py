@@ -15,6 +15,11 @@ three kernel launches on the caller's stream with NO host synchronisation in bet
 
 The NumPy drop-in functions (`vod_amd.core.{merge,sample,in_batch_negatives}`) run the same kernels and cut / copy on the
 host; this module is for callers that keep the batch on the device (e.g. a trainer that feeds `RetrievalGradients`).
+
+With `proposal=True` the same launches also emit the sampler's proposal (`vodhip_*_proposal`, include/vodhip.h H7): `log_proposal`
+(the stratum-normalised log-probability of every sample), `log_mass` (the log-sum-exp of each stratum before its softmax) and
+`joint_log_weights` (the weights of one softmax over the whole row).  `to_dict(..., weights="stratum" | "joint")` lays them out for
+`VodGradients`; both are exact, and the flattened arrays fill with -inf, so no host work sits between the collate and the objective.
 """
 from __future__ import annotations
 
@@ -42,9 +47,24 @@ class DeviceSampledSections:
     raw_scores: dict[str, torch.Tensor]
     local_ids: torch.Tensor | None = None   # int64 [B, n] column of the merged row each sample was taken from (-1 = pad)
     n_unique: torch.Tensor | None = None    # int32 [1] distinct ids of the batch (flattened only)
+    # the sampler's proposal (`proposal=True`): same shape as scores (-inf pad / -inf where a row did not sample the id); [B, 2]
+    log_proposal: torch.Tensor | None = None
+    log_mass: torch.Tensor | None = None
+    joint_log_weights: torch.Tensor | None = None
 
-    def to_dict(self, prefix: str = "", relevances: torch.Tensor | None = None) -> dict[str, torch.Tensor]:
-        """The `section__*` fields of `_samples_to_dict` (realm_collate.py:247-278), as device tensors."""
+    def to_dict(self, prefix: str = "", relevances: torch.Tensor | None = None, weights: str | None = None) -> dict[str, torch.Tensor]:
+        """The `section__*` fields of `_samples_to_dict` (realm_collate.py:247-278), as device tensors.
+
+        `weights` chooses how `VodGradients` is fed (None: the reference's keys, nothing else).  Both modes are exact:
+        "stratum" keeps `log_weight` (self-normalised per stratum) and adds `log_proposal`: the proposal is the sampler as built, the
+        mixture with equal mass on each non-empty stratum, whose log density up to a row constant is `log_proposal`;
+        "joint" puts `joint_log_weights` under `log_weight` and adds no proposal: the proposal is one softmax over the whole row, so
+        the objective's default `temperature * score` is exact - its temperature must be the sampler's.
+        Both add `log_mass_pos` / `log_mass_neg` and need an object built with `proposal=True`."""
+        if weights not in (None, "stratum", "joint"):
+            raise ValueError(f"weights must be None, 'stratum' or 'joint', got {weights!r}")
+        if weights is not None and (self.log_proposal is None or self.log_mass is None or self.joint_log_weights is None):
+            raise ValueError(f"weights={weights!r} needs the sampler's proposal: build the sections with proposal=True")
         out = {
             f"{prefix}idx": self.indices,
             f"{prefix}score": self.scores,
@@ -56,10 +76,16 @@ class DeviceSampledSections:
         }
         if relevances is not None:
             out[f"{prefix}relevance"] = relevances
+        if weights is not None:
+            if weights == "stratum":
+                out[f"{prefix}log_proposal"] = self.log_proposal
+            else:
+                out[f"{prefix}log_weight"] = self.joint_log_weights
+            out[f"{prefix}log_mass_pos"], out[f"{prefix}log_mass_neg"] = self.log_mass[:, 0], self.log_mass[:, 1]
         return out
 
 
-_WORKSPACES: dict[tuple, tuple[torch.Tensor, torch.Tensor]] = {}  # (device, stream, nq, stride, engines) -> merged-row buffers
+_WORKSPACES: dict[tuple, tuple[torch.Tensor, torch.Tensor]] = {}  # (device, stream, nq, stride, engines, proposal) -> merged-row buffers
 
 
 def _ptr_array(tensors: list[torch.Tensor]):
@@ -76,8 +102,10 @@ def sample_merged_on_device(
     max_support_size: int | None = None,
     width: int | None = None,
     support: str = "reference",
+    proposal: bool = False,
 ) -> DeviceSampledSections:
     """`sample_search_results` (sample.py:22-84) on the merge's device outputs: ONE launch, no host sync.
+    `proposal`: the same launch also fills `log_proposal`, `log_mass` and `joint_log_weights` (`vodhip_priority_sample_merged_proposal`).
 
     `noise`: float32 Exp(1) draws, one row per query, at least as wide as the merged rows (the reference draws
     `np.random.exponential(size=scores.shape)` on the host, sample.py:398; a device pipeline draws
@@ -109,27 +137,34 @@ def sample_merged_on_device(
     out_lab = torch.empty((nq, total), dtype=torch.uint8, device=dev)
     out_raw = [f32(nq, total) for _ in names]
     eng_k = (ctypes.c_int * 4)(*(merged.engine_k + [0] * (4 - len(merged.engine_k))))
+    args = [
+        merged.indices.data_ptr(), merged.scores.data_ptr(), labels.data_ptr(), len(names), _ptr_array(raws),
+        nz.data_ptr(), int(nz.stride(0)), nq, stride,
+        -1 if width is None else int(width), None if merged.stage_max is None else merged.stage_max.data_ptr(),
+        None if merged.row_cursor is None else merged.row_cursor.data_ptr(), merged.k_lookup, len(merged.engine_k), eng_k,
+        k_pos, total, float(temperature), max_support, 1 | support_flag(support),
+        samples.data_ptr(), out_ids.data_ptr(), out_scores.data_ptr(), out_logw.data_ptr(), out_lab.data_ptr(),
+        _ptr_array(out_raw), lse.data_ptr(), max_id.data_ptr(),
+    ]
+    log_p = log_mass = joint = None
+    if proposal:
+        log_p, log_mass, joint = f32(nq, total), f32(nq, 2), f32(nq, total)
+        args += [log_p.data_ptr(), log_mass.data_ptr(), joint.data_ptr()]
+    call = lib.vodhip_priority_sample_merged_proposal if proposal else lib.vodhip_priority_sample_merged
     with torch.cuda.device(dev):
-        _native.check(
-            lib.vodhip_priority_sample_merged(
-                merged.indices.data_ptr(), merged.scores.data_ptr(), labels.data_ptr(), len(names), _ptr_array(raws),
-                nz.data_ptr(), int(nz.stride(0)), nq, stride,
-                -1 if width is None else int(width), None if merged.stage_max is None else merged.stage_max.data_ptr(),
-                None if merged.row_cursor is None else merged.row_cursor.data_ptr(), merged.k_lookup, len(merged.engine_k), eng_k,
-                k_pos, total, float(temperature), max_support, 1 | support_flag(support),
-                samples.data_ptr(), out_ids.data_ptr(), out_scores.data_ptr(), out_logw.data_ptr(), out_lab.data_ptr(),
-                _ptr_array(out_raw), lse.data_ptr(), max_id.data_ptr(), _native.current_stream_ptr(dev),
-            )
-        )
+        _native.check(call(*args, _native.current_stream_ptr(dev)))
     return DeviceSampledSections(
         indices=out_ids, scores=out_scores, labels=out_lab.view(torch.bool), log_weights=out_logw, lse_pos=lse[:, 0], lse_neg=lse[:, 1],
         max_sampling_id=max_id, raw_scores=dict(zip(names, out_raw)), local_ids=samples,
+        log_proposal=log_p, log_mass=log_mass, joint_log_weights=joint,
     )
 
 
-def flatten_on_device(samples: DeviceSampledSections) -> DeviceSampledSections:
+def flatten_on_device(samples: DeviceSampledSections, proposal: bool = False) -> DeviceSampledSections:
     """`flatten_samples(samples, padding=True)` (in_batch_negatives.py:10-52) in ONE launch, no host sync: the batch's sorted
-    distinct ids padded to B * n entries with the reference's constant 1, every value array gathered onto that list."""
+    distinct ids padded to B * n entries with the reference's constant 1, every value array gathered onto that list.
+    `proposal`: `log_proposal` and `joint_log_weights` travel as two more value arrays of the same launch and fill with -inf (not
+    NaN) where a row did not sample the id; `log_mass` is per row and passes through."""
     lib = _native.load_library()
     ids = samples.indices.contiguous()
     dev = ids.device
@@ -139,8 +174,15 @@ def flatten_on_device(samples: DeviceSampledSections) -> DeviceSampledSections:
     f32 = lambda t: t if (t.dtype == torch.float32 and t.is_contiguous()) else t.float().contiguous()  # noqa: E731
     values = [f32(samples.scores), f32(samples.log_weights), *[f32(v) for v in samples.raw_scores.values()]]
     fills = [float("nan")] * len(values)
+    if proposal:
+        if samples.log_proposal is None or samples.log_mass is None or samples.joint_log_weights is None:
+            raise ValueError("proposal=True needs sections sampled with proposal=True")
+        names += ["__log_proposal__", "__joint_log_weights__"]
+        values += [f32(samples.log_proposal), f32(samples.joint_log_weights)]
+        fills += [float("-inf")] * 2
     if len(values) > 8:
-        raise ValueError("at most 6 raw score arrays can be flattened in one launch")
+        raise ValueError(f"{len(values)} value arrays: one launch flattens at most 8 (scores, log-weights, raw scores"
+                         + (", the 2 proposal arrays)" if proposal else ")"))
     lab = samples.labels
     lab = lab.view(torch.uint8) if lab.dtype == torch.bool else (lab > 0).view(torch.uint8)  # bool labels are gathered as they lie
     lab = lab if lab.is_contiguous() else lab.contiguous()
@@ -159,6 +201,8 @@ def flatten_on_device(samples: DeviceSampledSections) -> DeviceSampledSections:
         indices=unique, scores=got["scores"], labels=out_lab.view(torch.bool), log_weights=got["log_weights"], lse_pos=samples.lse_pos,
         lse_neg=samples.lse_neg, max_sampling_id=samples.max_sampling_id, raw_scores={k: got[k] for k in samples.raw_scores},
         local_ids=None, n_unique=n_unique,
+        log_proposal=got.get("__log_proposal__"), log_mass=samples.log_mass if proposal else None,
+        joint_log_weights=got.get("__joint_log_weights__"),
     )
 
 
@@ -176,9 +220,11 @@ def collate_on_device(
     in_batch_negatives: bool = False,
     generator: torch.Generator | None = None,
     support: str = "reference",
+    proposal: bool = False,
 ) -> DeviceSampledSections:
     """merge -> sample -> (flatten) without leaving the GPU: ONE call into libvodhip (`vodhip_collate`) that enqueues the 2 (3)
-    launches back to back on the current stream, zero host syncs.
+    launches back to back on the current stream, zero host syncs.  `proposal`: the same launches also emit the sampler's proposal
+    (`vodhip_collate_proposal`); `.to_dict("section__", weights="stratum" | "joint")` then feeds `VodGradients` exactly.
 
     lookup_idx int64 [B, k_lookup] and lookup_lbl int64 [B, k_lookup] (the lookup engine's hits and labels; its scores are
     discarded, search.py:92); engines[name] = (ids int64 [B, k], scores float32 [B, k]); weights[name]; `noise` float32
@@ -191,8 +237,8 @@ def collate_on_device(
         if noise is None:
             noise = torch.empty((merged.indices.shape[0], merged.stride), dtype=torch.float32, device=merged.indices.device).exponential_(generator=generator)
         out = sample_merged_on_device(merged, noise, total=total, max_pos_sections=max_pos_sections, temperature=temperature,
-                                      max_support_size=max_support_size, support=support)
-        return flatten_on_device(out) if in_batch_negatives else out
+                                      max_support_size=max_support_size, support=support, proposal=proposal)
+        return flatten_on_device(out, proposal=proposal) if in_batch_negatives else out
     lib = _native.load_library()
     dev = lookup_idx.device
     if dev.type != "cuda":
@@ -227,22 +273,26 @@ def collate_on_device(
     # The merged rows never leave this function: they live in a workspace that is reused by the next call on the same stream
     # (stream order keeps the reuse safe; a different stream gets its own)
     stream = _native.current_stream_ptr(dev)
-    ws_key = (dev.index, stream, nq, stride, n_e)
+    ws_key = (dev.index, stream, nq, stride, n_e, bool(proposal))
     ws = _WORKSPACES.get(ws_key)
     if ws is None:
-        if len(_WORKSPACES) >= 8:
-            _WORKSPACES.pop(next(iter(_WORKSPACES)))
-        ws = _WORKSPACES[ws_key] = (
+        ws = (
             torch.empty((2, nq, stride), dtype=torch.int64, device=dev),            # merged ids | labels
             torch.empty((1 + n_e, nq, stride), dtype=torch.float32, device=dev),    # merged scores | raw scores per engine
         )
+        if not torch.cuda.is_current_stream_capturing():  # a captured call's workspace belongs to its graph's pool: never cached
+            if len(_WORKSPACES) >= 8:
+                _WORKSPACES.pop(next(iter(_WORKSPACES)))
+            _WORKSPACES[ws_key] = ws
     m_i64, m_f32 = ws
     s_i64 = torch.empty((2, nq, total), dtype=torch.int64, device=dev)            # sampled columns | ids
-    s_f32 = torch.empty((2 + n_e, nq, total), dtype=torch.float32, device=dev)    # sampled scores | log-weights | raw scores
-    s_row = torch.empty((3, nq), dtype=torch.float32, device=dev)                 # lse_pos | lse_neg | max_sampling_id
+    n_p = 2 if proposal else 0
+    s_f32 = torch.empty((2 + n_e + n_p, nq, total), dtype=torch.float32, device=dev)  # sampled scores | log-weights | raw scores | log_p | joint
+    s_row = torch.empty((3 + n_p, nq), dtype=torch.float32, device=dev)               # lse_pos | lse_neg | max_sampling_id | log_mass_pos | neg
     s_lab = torch.empty((nq, total), dtype=torch.uint8, device=dev)
     cursors = torch.empty((nq * _native.MAX_ENGINES + 1,), dtype=torch.int32, device=dev)  # per-row cursors | n_unique
-    a = _native.CollateArgs()
+    ext = _native.CollateProposalArgs() if proposal else None
+    a = ext.base if proposal else _native.CollateArgs()
     a.lookup_idx, a.lookup_lbl = lookup_idx.data_ptr(), (None if lookup_lbl is None else lookup_lbl.data_ptr())
     a.k_lookup, a.n_engines, a.nq = kl, n_e, nq
     a.noise, a.noise_stride = noise.data_ptr(), noise.stride(0)
@@ -259,8 +309,11 @@ def collate_on_device(
         a.engine_idx[e], a.engine_scr[e], a.engine_k[e], a.engine_weight[e] = e_idx[e].data_ptr(), e_scr[e].data_ptr(), ks[e], float(weights[names[e]])
         a.merged_raw[e] = p_mf + (1 + e) * nq * stride * 4
         a.out_raw[e] = p_sf + (2 + e) * U * 4
+    if proposal:
+        ext.out_log_proposal, ext.out_joint_log_weights = p_sf + (2 + n_e) * U * 4, p_sf + (3 + n_e) * U * 4
+        ext.out_log_mass_pos, ext.out_log_mass_neg = p_row + nq * 12, p_row + nq * 16
     if flat:
-        f_f32 = torch.empty((2 + n_e, nq, U), dtype=torch.float32, device=dev)
+        f_f32 = torch.empty((2 + n_e + n_p, nq, U), dtype=torch.float32, device=dev)
         f_lab = torch.empty((nq, U), dtype=torch.uint8, device=dev)
         f_ids = torch.empty((U,), dtype=torch.int64, device=dev)
         p_ff = f_f32.data_ptr()
@@ -268,21 +321,27 @@ def collate_on_device(
         a.flat_n_unique = cursors.data_ptr() + nq * _native.MAX_ENGINES * 4
         for e in range(n_e):
             a.flat_raw[e] = p_ff + (2 + e) * nq * U * 4
+        if proposal:
+            ext.flat_log_proposal, ext.flat_joint_log_weights = p_ff + (2 + n_e) * nq * U * 4, p_ff + (3 + n_e) * nq * U * 4
+    call, ref = (lib.vodhip_collate_proposal, ctypes.byref(ext)) if proposal else (lib.vodhip_collate, ctypes.byref(a))
     if torch.cuda.current_device() != dev.index:
         with torch.cuda.device(dev):
-            _native.check(lib.vodhip_collate(ctypes.byref(a), stream))
+            _native.check(call(ref, stream))
     else:
-        _native.check(lib.vodhip_collate(ctypes.byref(a), stream))
-    lse_pos, lse_neg, max_id = s_row.unbind(0)
+        _native.check(call(ref, stream))
+    lse_pos, lse_neg, max_id = s_row[:3].unbind(0)
+    log_mass = s_row[3:].t() if proposal else None  # [nq, 2]: positives | negatives
     if flat:
         fv = f_f32.unbind(0)
         return DeviceSampledSections(
             indices=f_ids, scores=fv[0], labels=f_lab.view(torch.bool), log_weights=fv[1], lse_pos=lse_pos, lse_neg=lse_neg, max_sampling_id=max_id,
-            raw_scores=dict(zip(names, fv[2:])), local_ids=None, n_unique=cursors[-1:],
+            raw_scores=dict(zip(names, fv[2:2 + n_e])), local_ids=None, n_unique=cursors[-1:],
+            log_proposal=fv[2 + n_e] if proposal else None, log_mass=log_mass, joint_log_weights=fv[3 + n_e] if proposal else None,
         )
     local, ids = s_i64.unbind(0)
     sv = s_f32.unbind(0)
     return DeviceSampledSections(
         indices=ids, scores=sv[0], labels=s_lab.view(torch.bool), log_weights=sv[1], lse_pos=lse_pos, lse_neg=lse_neg, max_sampling_id=max_id,
-        raw_scores=dict(zip(names, sv[2:])), local_ids=local,
+        raw_scores=dict(zip(names, sv[2:2 + n_e])), local_ids=local,
+        log_proposal=sv[2 + n_e] if proposal else None, log_mass=log_mass, joint_log_weights=sv[3 + n_e] if proposal else None,
     )

@@ -47,14 +47,17 @@ def gather_by_id_tensors(queries: torch.Tensor, keys: torch.Tensor, values: list
     return outs
 
 
-def flatten_samples(samples: PrioritySampledSections, padding: bool = True, device: int = 0) -> PrioritySampledSections:
-    """Merge all sections (positive and negative) as a flat batch (in_batch_negatives.py:10-52)."""
+def flatten_samples(samples: PrioritySampledSections, padding: bool = True, device: int = 0, proposal: bool = False) -> PrioritySampledSections:
+    """Merge all sections (positive and negative) as a flat batch (in_batch_negatives.py:10-52).
+    `proposal`: `log_proposal` and `joint_log_weights` are flattened too, with -inf where a row did not sample the id."""
     if samples.batch.labels is None:
         raise ValueError("The `search_results` must have labels.")
+    if proposal and (samples.log_proposal is None or samples.log_mass is None or samples.joint_log_weights is None):
+        raise ValueError("proposal=True needs sections sampled with proposal=True")
     dev = torch.device("cuda", device)
-    if (0 < samples.batch.indices.size <= 8192 and len(samples.raw_scores) <= 5 and samples.batch.indices.ndim == 2
+    if (0 < samples.batch.indices.size <= 8192 and len(samples.raw_scores) <= (3 if proposal else 5) and samples.batch.indices.ndim == 2
             and samples.batch.indices.shape[1] <= 1024):
-        return _flatten_one_launch(samples, padding, dev)
+        return _flatten_one_launch(samples, padding, dev, proposal)
     indices = torch.from_numpy(np.ascontiguousarray(samples.batch.indices)).to(dev)
     unique = torch.unique(indices)  # sorted, like np.unique
     if padding:
@@ -63,6 +66,10 @@ def flatten_samples(samples: PrioritySampledSections, padding: bool = True, devi
     names = ["scores", "labels", "log_weights", *samples.raw_scores]
     arrays = [samples.batch.scores, samples.batch.labels, samples.log_weights, *samples.raw_scores.values()]
     fills = [float("nan"), 0.0, float("nan")] + [float("nan")] * len(samples.raw_scores)
+    if proposal:
+        names += ["__log_proposal__", "__joint_log_weights__"]
+        arrays += [samples.log_proposal, samples.joint_log_weights]
+        fills += [float("-inf")] * 2
     values = [torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).to(dev) for a in arrays]
     outs: dict[str, torch.Tensor] = {}
     for lo in range(0, len(values), 8):  # the kernel takes 8 value arrays per launch
@@ -81,10 +88,13 @@ def flatten_samples(samples: PrioritySampledSections, padding: bool = True, devi
         log_weights=host["log_weights"].astype(np.asarray(samples.log_weights).dtype, copy=False),
         lse_pos=samples.lse_pos,
         lse_neg=samples.lse_neg,
+        log_proposal=host.get("__log_proposal__"),
+        log_mass=samples.log_mass if proposal else None,
+        joint_log_weights=host.get("__joint_log_weights__"),
     )
 
 
-def _flatten_one_launch(samples: PrioritySampledSections, padding: bool, dev: torch.device) -> PrioritySampledSections:
+def _flatten_one_launch(samples: PrioritySampledSections, padding: bool, dev: torch.device, proposal: bool = False) -> PrioritySampledSections:
     """The whole flattening (distinct ids + padding + every gather) in one launch of `vodhip_flatten_inbatch`."""
     from vod_amd.core.collate import DeviceSampledSections, flatten_on_device
 
@@ -96,7 +106,9 @@ def _flatten_one_launch(samples: PrioritySampledSections, padding: bool, dev: to
         indices=up(samples.batch.indices, np.int64), scores=up(samples.batch.scores, np.float32), labels=up(samples.batch.labels != 0, np.bool_),
         log_weights=up(samples.log_weights, np.float32), lse_pos=zero, lse_neg=zero, max_sampling_id=zero,
         raw_scores={**{k: up(v, np.float32) for k, v in samples.raw_scores.items()}, "__label_values__": up(samples.batch.labels, np.float32)},
-    ))
+        log_proposal=up(samples.log_proposal, np.float32) if proposal else None, log_mass=zero if proposal else None,
+        joint_log_weights=up(samples.joint_log_weights, np.float32) if proposal else None,
+    ), proposal=proposal)
     n = None if padding else int(flat.n_unique.item())
     host = lambda t: t[..., :n].cpu().numpy()  # noqa: E731
     label_values = np.nan_to_num(host(flat.raw_scores.pop("__label_values__")), nan=0.0)
@@ -112,4 +124,7 @@ def _flatten_one_launch(samples: PrioritySampledSections, padding: bool, dev: to
         log_weights=host(flat.log_weights).astype(np.asarray(samples.log_weights).dtype, copy=False),
         lse_pos=samples.lse_pos,
         lse_neg=samples.lse_neg,
+        log_proposal=host(flat.log_proposal) if proposal else None,
+        log_mass=samples.log_mass if proposal else None,
+        joint_log_weights=host(flat.joint_log_weights) if proposal else None,
     )

@@ -33,6 +33,10 @@ class PrioritySampledSections:
     lse_pos: np.ndarray
     lse_neg: np.ndarray
     raw_scores: dict[str, np.ndarray]
+    # the sampler's proposal (`proposal=True`; vod_amd.core.collate has the definitions): [B, n] / [B, 2] / [B, n]
+    log_proposal: np.ndarray | None = None
+    log_mass: np.ndarray | None = None
+    joint_log_weights: np.ndarray | None = None
 
 
 def labeled_priority_sampling_tensors(
@@ -87,8 +91,10 @@ def sample_search_results(
     max_support_size: None | int = None,
     device: int = 0,
     support: str = "reference",
+    proposal: bool = False,
 ) -> PrioritySampledSections:
-    """Sample positive and negative sections with per-label priority sampling (sample.py:22-84)."""
+    """Sample positive and negative sections with per-label priority sampling (sample.py:22-84).
+    `proposal`: the same launch also returns `log_proposal`, `log_mass` and `joint_log_weights`."""
     from vod_amd.core.collate import sample_merged_on_device
     from vod_amd.core.merge import MergedOnDevice
 
@@ -110,7 +116,7 @@ def sample_search_results(
         raw={k: up(np.asarray(v, dtype=np.float32)) for k, v in raw_scores.items()}, stage_max=None, k_lookup=width, engine_k=[],
     )
     out = sample_merged_on_device(merged, up(noise), total=total, max_pos_sections=max_pos_sections, temperature=temperature,
-                                  max_support_size=max_support_size, width=width, support=support)
+                                  max_support_size=max_support_size, width=width, support=support, proposal=proposal)
     host = lambda t: t.cpu().numpy()  # noqa: E731
     return PrioritySampledSections(
         batch=vt.RetrievalBatch(indices=host(out.indices).astype(search_results.indices.dtype, copy=False), scores=host(out.scores),
@@ -120,6 +126,9 @@ def sample_search_results(
         lse_neg=host(out.lse_neg),
         log_weights=host(out.log_weights),
         raw_scores={k: host(v).astype(np.asarray(raw_scores[k]).dtype, copy=False) for k, v in out.raw_scores.items()},
+        log_proposal=host(out.log_proposal) if proposal else None,
+        log_mass=host(out.log_mass) if proposal else None,
+        joint_log_weights=host(out.joint_log_weights) if proposal else None,
     )
 
 

@@ -62,8 +62,8 @@ __device__ __forceinline__ unsigned ord32(float v, unsigned nan_image) {
 }
 
 // In-place log-softmax over `n` LDS floats (numpy_ops.py:198-204 semantics: NaN -> -inf, max falls back to 0 when it is -inf).
-// All threads call it.
-__device__ __forceinline__ void sm_log_softmax(float* x, int n, float* red) {
+// All threads call it.  Returns the log-sum-exp of the input (max + log of the shifted sum: -inf when every entry is -inf or n == 0).
+__device__ __forceinline__ float sm_log_softmax(float* x, int n, float* red) {
     const int tid = threadIdx.x;
     float mx = -__builtin_inff();
     for (int i = tid; i < n; i += SM_THREADS) {
@@ -84,6 +84,7 @@ __device__ __forceinline__ void sm_log_softmax(float* x, int n, float* red) {
     const float lse = logf(se);
     for (int i = tid; i < n; i += SM_THREADS) x[i] = x[i] - lse;
     __syncthreads();
+    return mx + lse;
 }
 
 // Descending sort of the first `m` packed keys of `keys` (LDS; the entries [m, P) are zeroed here: they sort last).  Classes of
@@ -144,8 +145,18 @@ struct SampleArgs {
     const float* raw[4];
     float* out_raw[4];
     float* out_max_sampling_id;
+    // the sampler's proposal (each may be NULL): what the VOD objective needs besides the per-stratum weights.  a_i = t_inv * score_i
+    // (NaN -> -inf) after the support truncation; log_mass of a class = logsumexp of its a_i (the quantity `out_lse` loses by
+    // being taken after the log-softmax, sample.py:180-184)
+    float* out_log_proposal;     // [nq, k_total] the log_p the weight formula reads (a_j - log_mass of j's class), -inf pad
+    float* out_log_mass;         // log_mass of class c of row r at out_log_mass[r * lse_row_stride + c * mass_cls_stride]
+    int64_t mass_cls_stride;
+    float* out_joint_logw;       // [nq, k_total] out_logw + log_mass(class) - logaddexp(log_mass_pos, log_mass_neg), -inf pad
 };
 
+// PROPOSAL = false is the kernel without the three proposal outputs, instruction for instruction: the entry points that do not ask for
+// them launch that instantiation (same code, same LDS footprint as before the outputs existed).
+template <bool PROPOSAL>
 __global__ __launch_bounds__(SM_THREADS) void priority_sample_kernel(SampleArgs a) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int k_total_in = a.k_total;
@@ -157,6 +168,8 @@ __global__ __launch_bounds__(SM_THREADS) void priority_sample_kernel(SampleArgs 
     int* order = sel_all + k_total_in;             // [P_cap] the columns of the positives, then of the negatives, ascending
     float* red = (float*)(order + a.P_cap);        // [4]
     int* red_i = (int*)(red + 4);                  // [16]
+    float* mass_s = (float*)(red_i + 16);          // PROPOSAL only: [2] log_mass of the positives, of the negatives
+    float* wall = mass_s + 2;                      // PROPOSAL only: [k_total] final log-weight of every selected slot (read by the joint weights)
 
     const int64_t row = blockIdx.x;
     const int tid = threadIdx.x;
@@ -200,6 +213,8 @@ __global__ __launch_bounds__(SM_THREADS) void priority_sample_kernel(SampleArgs 
     int64_t* out_samples = a.out_samples;
     float* out_logw = a.out_logw;
     uint8_t* out_labels = a.out_labels;
+    float* out_logp = PROPOSAL ? a.out_log_proposal : nullptr;
+    const bool want_joint = PROPOSAL && a.out_joint_logw != nullptr;
 
     SM_PROBE(1);
     // ---- class sizes, finite-negative count (sample.py:259-264) and an ORDER-PRESERVING compaction of the two classes:
@@ -260,7 +275,9 @@ __global__ __launch_bounds__(SM_THREADS) void priority_sample_kernel(SampleArgs 
                 float mxv = sm_wave_max(x);
                 if (__builtin_isinf(mxv) && mxv < 0) mxv = 0.f;
                 const float v = x - mxv;
-                const float lpv = v - logf(sm_wave_sum(has ? expf(v) : 0.f));
+                const float lsum = logf(sm_wave_sum(has ? expf(v) : 0.f));
+                const float lpv = v - lsum;
+                if (PROPOSAL && tid == 0) mass_s[cls] = mxv + lsum;  // read behind the barrier that ends the class
                 const float log_norm = logf(sm_wave_sum(has ? expf(lpv) : 0.f));
                 if (tid == 0) a.out_lse[row * a.lse_row_stride + cls * a.lse_cls_stride] = log_norm;
                 const float key = temperature > 0.f ? lpv - logf(has ? nz[col] : 1.f) : lpv;
@@ -297,6 +314,8 @@ __global__ __launch_bounds__(SM_THREADS) void priority_sample_kernel(SampleArgs 
                     out_logw[row * k_total_in + out_cursor + tid] = w;
                     out_labels[row * k_total_in + out_cursor + tid] = want_pos ? 1 : 0;
                     sel_all[out_cursor + tid] = s_col;
+                    if (out_logp) out_logp[row * k_total_in + out_cursor + tid] = s_lp;
+                    if (want_joint) wall[out_cursor + tid] = w;
                 }
             }
             out_cursor += n_sel;
@@ -322,7 +341,8 @@ __global__ __launch_bounds__(SM_THREADS) void priority_sample_kernel(SampleArgs 
             __syncthreads();
         }
         SM_PROBE(3 + cls * 5);
-        sm_log_softmax(lp, m, red);
+        const float log_mass = sm_log_softmax(lp, m, red);
+        if (PROPOSAL && tid == 0) mass_s[cls] = log_mass;
         SM_PROBE(4 + cls * 5);
         // normalising constant log(sum(exp(log_p)))  (:183)
         float se = 0.f;
@@ -354,14 +374,16 @@ __global__ __launch_bounds__(SM_THREADS) void priority_sample_kernel(SampleArgs 
             if (log_tau > -__builtin_inff()) w = log_pi - log1pf(-expf(-expf(log_pi - log_tau)));  // :209-213
             isel[j] = col_of[slot];
             wsel[j] = w;
+            if (out_logp) out_logp[row * k_total_in + out_cursor + j] = log_pi;
         }
         __syncthreads();
-        if (a.normalized && n_sel > 0) sm_log_softmax(wsel, n_sel, red);
+        if (a.normalized && n_sel > 0) (void)sm_log_softmax(wsel, n_sel, red);
         for (int j = tid; j < n_sel; j += SM_THREADS) {
             out_samples[row * k_total_in + out_cursor + j] = isel[j];
             out_logw[row * k_total_in + out_cursor + j] = wsel[j];
             out_labels[row * k_total_in + out_cursor + j] = want_pos ? 1 : 0;
             sel_all[out_cursor + j] = isel[j];
+            if (want_joint) wall[out_cursor + j] = wsel[j];
         }
         out_cursor += n_sel;
         if (want_pos) n_pos_selected = n_sel;
@@ -373,6 +395,21 @@ __global__ __launch_bounds__(SM_THREADS) void priority_sample_kernel(SampleArgs 
         out_logw[row * k_total_in + j] = -__builtin_inff();
         out_labels[row * k_total_in + j] = 0;
         sel_all[j] = -1;
+        if (out_logp) out_logp[row * k_total_in + j] = -__builtin_inff();
+        if (want_joint) a.out_joint_logw[row * k_total_in + j] = -__builtin_inff();
+    }
+    // ---- the proposal's masses and the joint weights: one softmax over the row = the per-stratum weights re-scaled by each
+    //      stratum's share of the row's mass.  mass_s / wall were published by the barrier that ended the last class ----
+    if (PROPOSAL && a.out_log_mass && tid < 2) a.out_log_mass[row * a.lse_row_stride + tid * a.mass_cls_stride] = mass_s[tid];
+    if (want_joint) {
+        const float mp = mass_s[0], mn = mass_s[1];
+        const float hi = fmaxf(mp, mn), lo = fminf(mp, mn);
+        const float tot = hi > -__builtin_inff() ? hi + log1pf(expf(lo - hi)) : -__builtin_inff();  // logaddexp
+        for (int j = tid; j < out_cursor; j += SM_THREADS) {
+            const float mc = j < n_pos_selected ? mp : mn;
+            // a member of a stratum without mass has probability 0 under the row's softmax (its per-stratum weight is NaN)
+            a.out_joint_logw[row * k_total_in + j] = mc > -__builtin_inff() ? wall[j] + (mc - tot) : -__builtin_inff();
+        }
     }
     if (!a.ids) return;
     __syncthreads();
@@ -407,19 +444,23 @@ static hipError_t launch_sample_args(SampleArgs& a, int64_t nq, int max_width, h
     int P = 256;
     while (P < max_width) P <<= 1;
     a.P_cap = P;
-    const size_t lds = (size_t)P * 8 + (size_t)P * 4 + (size_t)a.k_total * 12 + (size_t)P * 4 + 16 + 64 + 16;
+    const bool proposal = a.out_log_proposal || a.out_log_mass || a.out_joint_logw;
+    // (+ mass_s [2] and wall [k_total] behind red_i when the proposal is asked for)
+    const size_t lds = (size_t)P * 8 + (size_t)P * 4 + (size_t)a.k_total * 12 + (size_t)P * 4 + 16 + 64 + 16 + (proposal ? 8 + (size_t)a.k_total * 4 : 0);
+    const void* fn = proposal ? (const void*)priority_sample_kernel<true> : (const void*)priority_sample_kernel<false>;
     if (lds > 64 * 1024) {
-        hipError_t e = allow_dynamic_lds((const void*)priority_sample_kernel, (int)lds);
+        hipError_t e = allow_dynamic_lds(fn, (int)lds);
         if (e != hipSuccess) return e;
     }
-    hipLaunchKernelGGL(priority_sample_kernel, dim3((unsigned)nq), dim3(SM_THREADS), lds, stream, a);
+    if (proposal) hipLaunchKernelGGL(priority_sample_kernel<true>, dim3((unsigned)nq), dim3(SM_THREADS), lds, stream, a);
+    else hipLaunchKernelGGL(priority_sample_kernel<false>, dim3((unsigned)nq), dim3(SM_THREADS), lds, stream, a);
     return hipGetLastError();
 }
 
 hipError_t launch_priority_sample(const float* scores, const uint8_t* labels, const float* noise, int64_t nq, int width,
                                   int k_positive, int k_total, float temperature, int max_support_size, int normalized,
                                   int64_t* out_samples, float* out_log_weights, uint8_t* out_labels, float* out_lse,
-                                  hipStream_t stream) {
+                                  float* out_log_proposal, float* out_log_mass, float* out_joint_logw, hipStream_t stream) {
     SampleArgs a{};
     a.scores = scores;
     a.labels = labels;
@@ -438,6 +479,10 @@ hipError_t launch_priority_sample(const float* scores, const uint8_t* labels, co
     a.out_lse = out_lse;
     a.lse_row_stride = 2;
     a.lse_cls_stride = 1;
+    a.out_log_proposal = out_log_proposal;
+    a.out_log_mass = out_log_mass;
+    a.mass_cls_stride = 1;
+    a.out_joint_logw = out_joint_logw;
     return launch_sample_args(a, nq, width, stream);
 }
 
@@ -477,6 +522,10 @@ hipError_t launch_priority_sample_merged(const SampleMergedArgs& m, hipStream_t 
         a.out_raw[e] = m.out_raw[e];
     }
     a.out_max_sampling_id = m.out_max_sampling_id;
+    a.out_log_proposal = m.out_log_proposal;
+    a.out_log_mass = m.out_log_mass;
+    a.mass_cls_stride = m.mass_cls_stride;
+    a.out_joint_logw = m.out_joint_logw;
     return launch_sample_args(a, m.nq, m.width >= 0 ? m.width : (int)m.stride, stream);
 }
 

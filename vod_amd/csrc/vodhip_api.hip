@@ -1419,27 +1419,48 @@ int vodhip_retrieval_metrics(const float* scores, const int64_t* relevances, int
     return 0;
 }
 
+static int priority_sample_impl(const float* scores, const uint8_t* labels, const float* noise, int64_t nq, int width,
+                                int k_positive, int k_total, float temperature, int max_support_size, int normalized,
+                                int64_t* out_samples, float* out_log_weights, uint8_t* out_labels, float* out_lse,
+                                float* out_log_proposal, float* out_log_mass, float* out_joint_log_weights, void* stream) {
+    if (nq < 0 || width < 0 || k_total < 1 || k_positive < 0) return fail("invalid sizes");
+    if (width > 4096) return fail("width=%d exceeds 4096 candidates per row", width);
+    if (k_total > 4096) return fail("k_total=%d exceeds 4096", k_total);
+    if (out_joint_log_weights && !(normalized & 1)) return fail("out_joint_log_weights needs the `normalized` bit: the joint weights re-scale the self-normalised ones");
+    if (nq == 0) return 0;
+    if (!scores || !labels || !noise || !out_samples || !out_log_weights || !out_labels || !out_lse) return fail("NULL argument");
+    HIP_OK(launch_priority_sample(scores, labels, noise, nq, width, k_positive, k_total, temperature, max_support_size,
+                                  normalized, out_samples, out_log_weights, out_labels, out_lse, out_log_proposal, out_log_mass,
+                                  out_joint_log_weights, (hipStream_t)stream));
+    return 0;
+}
+
 int vodhip_priority_sample(const float* scores, const uint8_t* labels, const float* noise, int64_t nq, int width,
                            int k_positive, int k_total, float temperature, int max_support_size, int normalized,
                            int64_t* out_samples, float* out_log_weights, uint8_t* out_labels, float* out_lse,
                            void* stream) {
-    if (nq < 0 || width < 0 || k_total < 1 || k_positive < 0) return fail("invalid sizes");
-    if (width > 4096) return fail("width=%d exceeds 4096 candidates per row", width);
-    if (k_total > 4096) return fail("k_total=%d exceeds 4096", k_total);
-    if (nq == 0) return 0;
-    if (!scores || !labels || !noise || !out_samples || !out_log_weights || !out_labels || !out_lse) return fail("NULL argument");
-    HIP_OK(launch_priority_sample(scores, labels, noise, nq, width, k_positive, k_total, temperature, max_support_size,
-                                  normalized, out_samples, out_log_weights, out_labels, out_lse, (hipStream_t)stream));
-    return 0;
+    return priority_sample_impl(scores, labels, noise, nq, width, k_positive, k_total, temperature, max_support_size, normalized,
+                                out_samples, out_log_weights, out_labels, out_lse, nullptr, nullptr, nullptr, stream);
 }
 
-int vodhip_priority_sample_merged(const int64_t* ids, const float* scores, const int64_t* labels, int n_raw, const float* const* raw,
-                                  const float* noise, int64_t noise_stride, int64_t nq, int stride, int width,
-                                  const int32_t* merge_width, const int32_t* merge_row_cursor, int k_lookup, int n_engines,
-                                  const int* engine_k, int k_positive,
-                                  int k_total, float temperature, int max_support_size, int normalized, int64_t* out_samples,
-                                  int64_t* out_ids, float* out_scores, float* out_log_weights, uint8_t* out_labels,
-                                  float* const* out_raw, float* out_lse, float* out_max_sampling_id, void* stream) {
+int vodhip_priority_sample_proposal(const float* scores, const uint8_t* labels, const float* noise, int64_t nq, int width,
+                                    int k_positive, int k_total, float temperature, int max_support_size, int normalized,
+                                    int64_t* out_samples, float* out_log_weights, uint8_t* out_labels, float* out_lse,
+                                    float* out_log_proposal, float* out_log_mass, float* out_joint_log_weights, void* stream) {
+    return priority_sample_impl(scores, labels, noise, nq, width, k_positive, k_total, temperature, max_support_size, normalized,
+                                out_samples, out_log_weights, out_labels, out_lse, out_log_proposal, out_log_mass,
+                                out_joint_log_weights, stream);
+}
+
+static int priority_sample_merged_impl(const int64_t* ids, const float* scores, const int64_t* labels, int n_raw, const float* const* raw,
+                                       const float* noise, int64_t noise_stride, int64_t nq, int stride, int width,
+                                       const int32_t* merge_width, const int32_t* merge_row_cursor, int k_lookup, int n_engines,
+                                       const int* engine_k, int k_positive,
+                                       int k_total, float temperature, int max_support_size, int normalized, int64_t* out_samples,
+                                       int64_t* out_ids, float* out_scores, float* out_log_weights, uint8_t* out_labels,
+                                       float* const* out_raw, float* out_lse, float* out_max_sampling_id, float* out_log_proposal,
+                                       float* out_log_mass, float* out_joint_log_weights, void* stream) {
+    if (out_joint_log_weights && !(normalized & 1)) return fail("out_joint_log_weights needs the `normalized` bit: the joint weights re-scale the self-normalised ones");
     if (nq < 0 || stride < 0 || k_total < 1 || k_positive < 0) return fail("invalid sizes");
     if (stride > 4096 || width > stride) return fail("stride=%d / width=%d: at most 4096 candidates per row, width <= stride", stride, width);
     if (k_total > 4096) return fail("k_total=%d exceeds 4096", k_total);
@@ -1493,8 +1514,40 @@ int vodhip_priority_sample_merged(const int64_t* ids, const float* scores, const
     m.lse_row_stride = 2;
     m.lse_cls_stride = 1;
     m.out_max_sampling_id = out_max_sampling_id;
+    m.out_log_proposal = out_log_proposal;
+    m.out_log_mass = out_log_mass;
+    m.mass_cls_stride = 1;
+    m.out_joint_logw = out_joint_log_weights;
     HIP_OK(launch_priority_sample_merged(m, (hipStream_t)stream));
     return 0;
+}
+
+int vodhip_priority_sample_merged(const int64_t* ids, const float* scores, const int64_t* labels, int n_raw, const float* const* raw,
+                                  const float* noise, int64_t noise_stride, int64_t nq, int stride, int width,
+                                  const int32_t* merge_width, const int32_t* merge_row_cursor, int k_lookup, int n_engines,
+                                  const int* engine_k, int k_positive,
+                                  int k_total, float temperature, int max_support_size, int normalized, int64_t* out_samples,
+                                  int64_t* out_ids, float* out_scores, float* out_log_weights, uint8_t* out_labels,
+                                  float* const* out_raw, float* out_lse, float* out_max_sampling_id, void* stream) {
+    return priority_sample_merged_impl(ids, scores, labels, n_raw, raw, noise, noise_stride, nq, stride, width, merge_width,
+                                       merge_row_cursor, k_lookup, n_engines, engine_k, k_positive, k_total, temperature,
+                                       max_support_size, normalized, out_samples, out_ids, out_scores, out_log_weights, out_labels,
+                                       out_raw, out_lse, out_max_sampling_id, nullptr, nullptr, nullptr, stream);
+}
+
+int vodhip_priority_sample_merged_proposal(const int64_t* ids, const float* scores, const int64_t* labels, int n_raw,
+                                           const float* const* raw, const float* noise, int64_t noise_stride, int64_t nq, int stride,
+                                           int width, const int32_t* merge_width, const int32_t* merge_row_cursor, int k_lookup,
+                                           int n_engines, const int* engine_k, int k_positive, int k_total, float temperature,
+                                           int max_support_size, int normalized, int64_t* out_samples, int64_t* out_ids,
+                                           float* out_scores, float* out_log_weights, uint8_t* out_labels, float* const* out_raw,
+                                           float* out_lse, float* out_max_sampling_id, float* out_log_proposal, float* out_log_mass,
+                                           float* out_joint_log_weights, void* stream) {
+    return priority_sample_merged_impl(ids, scores, labels, n_raw, raw, noise, noise_stride, nq, stride, width, merge_width,
+                                       merge_row_cursor, k_lookup, n_engines, engine_k, k_positive, k_total, temperature,
+                                       max_support_size, normalized, out_samples, out_ids, out_scores, out_log_weights, out_labels,
+                                       out_raw, out_lse, out_max_sampling_id, out_log_proposal, out_log_mass, out_joint_log_weights,
+                                       stream);
 }
 
 int vodhip_flatten_inbatch(const int64_t* ids, int64_t n_rows, int n_keys, int n_values, const float* const* values, const float* fill,
@@ -1513,8 +1566,18 @@ int vodhip_flatten_inbatch(const int64_t* ids, int64_t n_rows, int n_keys, int n
     return 0;
 }
 
-int vodhip_collate(const vodhip_collate_args_t* c, void* stream_) {
+// `p`: the proposal outputs of vodhip_collate_proposal (NULL: plain vodhip_collate)
+static int collate_impl(const vodhip_collate_args_t* c, const vodhip_collate_proposal_args_t* p, void* stream_) {
     if (!c) return fail("args is NULL");
+    float* const out_logp = p ? p->out_log_proposal : nullptr;
+    float* const out_joint = p ? p->out_joint_log_weights : nullptr;
+    float* const flat_logp = p ? p->flat_log_proposal : nullptr;
+    float* const flat_joint = p ? p->flat_joint_log_weights : nullptr;
+    if (p) {
+        if ((p->out_log_mass_pos == nullptr) != (p->out_log_mass_neg == nullptr)) return fail("out_log_mass_pos and out_log_mass_neg go together");
+        if ((flat_logp && !out_logp) || (flat_joint && !out_joint)) return fail("a flattened proposal output needs its [nq, k_total] source output");
+        if ((flat_logp || flat_joint) && !c->in_batch_negatives) return fail("flattened proposal outputs need in_batch_negatives");
+    }
     hipStream_t stream = (hipStream_t)stream_;
     if (c->n_engines < 1 || c->n_engines > VODHIP_MAX_ENGINES) return fail("n_engines=%d out of range [1, %d]", c->n_engines, VODHIP_MAX_ENGINES);
     if (c->k_lookup < 0 || c->nq < 0 || c->k_total < 1 || c->k_positive < 0) return fail("invalid sizes");
@@ -1584,6 +1647,12 @@ int vodhip_collate(const vodhip_collate_args_t* c, void* stream_) {
     m.lse_row_stride = 1;
     m.lse_cls_stride = c->out_lse_neg - c->out_lse_pos;
     m.out_max_sampling_id = c->out_max_sampling_id;
+    if (p) {
+        m.out_log_proposal = out_logp;
+        m.out_log_mass = p->out_log_mass_pos;  // two [nq] arrays, addressed like lse_pos / lse_neg
+        m.mass_cls_stride = p->out_log_mass_pos ? p->out_log_mass_neg - p->out_log_mass_pos : 0;
+        m.out_joint_logw = out_joint;  // (the collate always samples with the `normalized` bit)
+    }
     HIP_OK(launch_priority_sample_merged(m, stream));
     if (!c->in_batch_negatives) return 0;
     if (c->nq * (int64_t)c->k_total > 8192) return fail("%lld ids in the batch: the one-launch flattening holds at most 8192", (long long)(c->nq * c->k_total));
@@ -1599,9 +1668,20 @@ int vodhip_collate(const vodhip_collate_args_t* c, void* stream_) {
         if (!c->flat_raw[e]) return fail("engine %d: NULL flattened raw-score output", e);
         values[nv] = c->out_raw[e], outs[nv] = c->flat_raw[e], fill[nv++] = __builtin_nanf("");
     }
+    // the proposal arrays fill with -inf: "this row did not sample the id" is weight 0 for the objective, not NaN
+    if (nv + (flat_logp != nullptr) + (flat_joint != nullptr) > 8) return fail("%d value arrays to flatten: the one-launch flattening carries at most 8", nv + (flat_logp != nullptr) + (flat_joint != nullptr));
+    if (flat_logp) values[nv] = out_logp, outs[nv] = flat_logp, fill[nv++] = -__builtin_inff();
+    if (flat_joint) values[nv] = out_joint, outs[nv] = flat_joint, fill[nv++] = -__builtin_inff();
     HIP_OK(launch_flatten_inbatch(c->out_ids, c->nq, c->k_total, nv, values, fill, outs, c->out_labels, c->flat_labels, c->flat_ids,
                                   c->flat_n_unique, stream));
     return 0;
+}
+
+int vodhip_collate(const vodhip_collate_args_t* args, void* stream) { return collate_impl(args, nullptr, stream); }
+
+int vodhip_collate_proposal(const vodhip_collate_proposal_args_t* args, void* stream) {
+    if (!args) return fail("args is NULL");
+    return collate_impl(&args->base, args, stream);
 }
 
 int vodhip_gather_by_id(const int64_t* queries, int64_t n_queries, const int64_t* keys, int64_t n_rows, int n_keys,

@@ -270,7 +270,7 @@ hipError_t launch_vod_forward(const void* q, const void* s, int enc_dtype, int s
 hipError_t launch_priority_sample(const float* scores, const uint8_t* labels, const float* noise, int64_t nq, int width,
                                   int k_positive, int k_total, float temperature, int max_support_size, int normalized,
                                   int64_t* out_samples, float* out_log_weights, uint8_t* out_labels, float* out_lse,
-                                  hipStream_t stream);
+                                  float* out_log_proposal, float* out_log_mass, float* out_joint_logw, hipStream_t stream);
 
 // sampling straight from the merge's full-stride outputs + the gather epilogue (device-resident collate)
 struct SampleMergedArgs {
@@ -297,6 +297,12 @@ struct SampleMergedArgs {
     float* out_lse;          // lse of class c of row r at out_lse[r * lse_row_stride + c * lse_cls_stride]
     int64_t lse_row_stride, lse_cls_stride;
     float* out_max_sampling_id;
+    // the sampler's proposal, each NULL or: log_p of the samples [nq, k_total]; log_mass of class c of row r at
+    // out_log_mass[r * lse_row_stride + c * mass_cls_stride]; joint log-weights [nq, k_total] (needs bit 0 of `normalized`)
+    float* out_log_proposal;
+    float* out_log_mass;
+    int64_t mass_cls_stride;
+    float* out_joint_logw;
 };
 hipError_t launch_priority_sample_merged(const SampleMergedArgs& m, hipStream_t stream);
 hipError_t launch_flatten_inbatch(const int64_t* ids, int64_t n_rows, int n_keys, int n_values, const float* const* values,
