@@ -34,7 +34,9 @@ enum { VODHIP_F16 = 0, VODHIP_BF16 = 1, VODHIP_F32 = 2 };
 /* OR-ed into the store dtype at create: the store ALSO keeps the float32 rows and every search returns what a float32 brute force
  * over the unrounded rows and queries returns (H2 below) - the reference's own arithmetic: faiss IndexFlat holds float32
  * (`index.add(vectors.astype(float32))`, src/vod_search/faiss_search/build.py:65-73; float32 queries, faiss_search/server.py:71,81).
- * Costs 4 more bytes per element of HBM and ~1-3 % of search time. */
+ * Costs 4 more bytes per element of HBM and ~1-3 % of search time.  Such a store takes dim <= 16384 (the float32 query sits in LDS
+ * during re-scoring: 64 KB at the limit); vodhip_index_create refuses a wider one ("VODHIP_EXACT_F32 stores take dim <= 16384").
+ * A plain store has no width limit of its own (tested up to dim 16384). */
 #define VODHIP_EXACT_F32 0x100
 /* where a caller buffer lives */
 enum { VODHIP_HOST = 0, VODHIP_DEVICE = 1 };
