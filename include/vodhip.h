@@ -116,6 +116,34 @@ int vodhip_index_search_async(vodhip_index_t* index, const void* queries, int q_
                               int64_t id_base, float* out_scores, int64_t* out_ids, void* stream);
 int vodhip_index_search_finish(vodhip_index_t* index, void* stream);
 
+/* H2i  scores of LISTED rows, and the top-k over a list: the dense counterpart of `ids` in the reference's SearchClient.search.
+ * Replaces: nothing the reference's dense engine does - its faiss client drops `ids` (src/vod_search/faiss_search/client.py:70); its
+ *           Elasticsearch client honours it with a `terms` filter on the section id, so that only listed sections can be hits, and
+ *           returns labels = scores > -inf (src/vod_search/es_search/client.py:145,177-183).  The gold-section lookup of the hybrid
+ *           search (src/vod_dataloaders/core/search.py:42-50) is such a request.  (faiss calls the primitive compute_distance_subset.)
+ * `ids_dev` is a DEVICE int64 [nq, m] array of section ids; queries as in H2 (rounded to the store dtype, saturating; VODHIP_EXACT_F32
+ * stores score the unrounded query against the float32 rows - the SAME BITS vodhip_index_search returns for that pair).  A slot is
+ * ABSENT, and scores -inf, when it is empty (id < 0), out of range (id - id_base outside [0, ntotal): rows past ntotal are never read)
+ * or ineligible: `q_labels_dev` (DEVICE int32 [nq, n_per_query], NULL = unrestricted) lists the subset labels a query allows, with the
+ * rule of vodhip_index_set_query_labels (-1 = empty slot, all -1 = unrestricted).  The labels are an ARGUMENT here, not index state.
+ * Every (query, row) pair is summed in one fixed order: its bits do not depend on the slot, on m, on nq or on the launch.  A NaN score
+ * is written as computed.
+ *   vodhip_index_score_ids   the aligned form: out_scores DEVICE float32 [nq, m], slot for slot; any m >= 1.
+ *   vodhip_index_search_ids  the k best DISTINCT listed rows by (score desc, id asc) - a listed id counts once, NaN and -inf never
+ *                            enter - as out_scores / out_ids DEVICE [nq, k], pads (-inf, -1); 1 <= k <= VODHIP_MAX_K,
+ *                            m <= VODHIP_MAX_LISTED (the aligned scores live in a hipMallocAsync temporary on `stream`).
+ * The calls only enqueue work: the outputs are complete on `stream`; nothing synchronises with the host and there is no finish -
+ * nothing here can overflow.  They use neither the index's search workspace nor its query labels: a call may run on any stream while
+ * searches of the same index are in flight, and from several threads; it must not overlap add / reset / set_row_labels (the rule of
+ * a search).  m < 1, m above the limit of the top-k form, k out of range, or labels without row labels return < 0. */
+#define VODHIP_MAX_LISTED 8192
+int vodhip_index_score_ids(vodhip_index_t* index, const void* queries, int q_dtype, int64_t nq, const int64_t* ids_dev, int64_t m,
+                           int64_t id_base, const int32_t* q_labels_dev /* NULL = unrestricted */, int n_per_query,
+                           float* out_scores, void* stream);
+int vodhip_index_search_ids(vodhip_index_t* index, const void* queries, int q_dtype, int64_t nq, const int64_t* ids_dev, int64_t m,
+                            int k, int64_t id_base, const int32_t* q_labels_dev, int n_per_query, float* out_scores,
+                            int64_t* out_ids, void* stream);
+
 /* Optional subset filter.  The reference's SearchClient.search carries `subset_ids`; its Elasticsearch and
  * Qdrant engines restrict hits to sections whose subset id is listed (src/vod_search/es_search/client.py:185-191,
  * qdrant_search/client.py:124-136) while its faiss client ignores it (faiss_search/client.py:67-72).  Here every stored
@@ -244,6 +272,18 @@ int vodhip_node_index_search(vodhip_node_index_t* index, const void* queries, in
 int vodhip_node_index_search_async(vodhip_node_index_t* index, const void* queries, int q_dtype, int64_t nq, int k, int location,
                                    float* out_scores, int64_t* out_ids, void* stream);
 int vodhip_node_index_search_finish(vodhip_node_index_t* index);
+/* H2i behind the one handle: queries, `ids` ([nq, m], GLOBAL row ids) and `q_labels` (may be NULL) are host buffers (location =
+ * VODHIP_HOST) or live on devices[0]; so do the outputs.  The batch is replicated to every shard, every shard scores the whole list
+ * into an aligned buffer of its own (rows of other shards are out of its range: -inf), the buffers meet on devices[0] and are combined
+ * BY OWNERSHIP (owner = id / R; no comparison of values: a NaN survives), then ONE select runs for the top-k form: results equal one
+ * index holding all the rows, bit for bit.  These calls synchronise with the host (the batch travels through host memory: listed
+ * requests are small); DEVICE outputs are complete on `stream` on return, HOST outputs in place.  Serialised with the other calls on the
+ * handle (its mutex); like a search, a call must not overlap add / reset / set_row_labels. */
+int vodhip_node_index_score_ids(vodhip_node_index_t* index, const void* queries, int q_dtype, int64_t nq, const int64_t* ids, int64_t m,
+                                const int32_t* q_labels, int n_per_query, int location, float* out_scores, void* stream);
+int vodhip_node_index_search_ids(vodhip_node_index_t* index, const void* queries, int q_dtype, int64_t nq, const int64_t* ids, int64_t m,
+                                 int k, const int32_t* q_labels, int n_per_query, int location, float* out_scores, int64_t* out_ids,
+                                 void* stream);
 /* With param "profile" = 1 (also set on every shard: their filter launches are bracketed, read per shard through vodhip_index_get_stat on
  * the handle vodhip_node_index_shard returns): "last_merge_ns" = the merge launch on devices[0], from the moment every shard's list had
  * arrived; "last_copy_ns_max" = the slowest shard's copy of its list towards devices[0] (peer copy over xGMI, or the down-leg to pinned

@@ -17,6 +17,7 @@ F16, BF16, F32 = 0, 1, 2
 EXACT_F32 = 0x100  # VODHIP_EXACT_F32: OR-ed into the store dtype at create
 HOST, DEVICE = 0, 1
 MAX_K = 2048
+MAX_LISTED = 8192  # VODHIP_MAX_LISTED: slots per query of the top-k form of `score_ids`
 MAX_ENGINES = 4
 
 
@@ -54,6 +55,8 @@ SIGNATURES: dict[str, tuple] = {
     "vodhip_index_search": (_i32, [_vp, _vp, _i32, _i64, _i32, _i64, _vp, _vp, _vp]),
     "vodhip_index_search_async": (_i32, [_vp, _vp, _i32, _i64, _i32, _i64, _vp, _vp, _vp]),
     "vodhip_index_search_finish": (_i32, [_vp, _vp]),
+    "vodhip_index_score_ids": (_i32, [_vp, _vp, _i32, _i64, _vp, _i64, _i64, _vp, _i32, _vp, _vp]),
+    "vodhip_index_search_ids": (_i32, [_vp, _vp, _i32, _i64, _vp, _i64, _i32, _i64, _vp, _i32, _vp, _vp, _vp]),
     "vodhip_index_set_row_labels": (_i32, [_vp, _vp, _i64, _i32, _vp]),
     "vodhip_index_set_query_labels": (_i32, [_vp, _vp, _i32]),
     "vodhip_index_set_param": (_i32, [_vp, _c.c_char_p, _i64]),
@@ -76,6 +79,8 @@ SIGNATURES: dict[str, tuple] = {
     "vodhip_node_index_search": (_i32, [_vp, _vp, _i32, _i64, _i32, _i32, _vp, _vp, _vp]),
     "vodhip_node_index_search_async": (_i32, [_vp, _vp, _i32, _i64, _i32, _i32, _vp, _vp, _vp]),
     "vodhip_node_index_search_finish": (_i32, [_vp]),
+    "vodhip_node_index_score_ids": (_i32, [_vp, _vp, _i32, _i64, _vp, _i64, _vp, _i32, _i32, _vp, _vp]),
+    "vodhip_node_index_search_ids": (_i32, [_vp, _vp, _i32, _i64, _vp, _i64, _i32, _vp, _i32, _i32, _vp, _vp, _vp]),
     "vodhip_merge_topk": (_i32, [_vp, _vp, _i32, _i64, _i32, _i32, _vp, _vp, _vp]),
     "vodhip_merge_topk_strided": (_i32, [_vp, _i64, _vp, _i64, _i32, _i64, _i32, _i32, _vp, _vp, _vp]),
     "vodhip_merge_hybrid": (

@@ -970,6 +970,79 @@ int vodhip_index_search(vodhip_index_t* ix, const void* queries, int q_dtype, in
     return vodhip_index_search_finish(ix, stream);
 }
 
+// ---- listed rows (kernels_listed.hip) -------------------------------------------------------------------------------------
+// Nothing here touches the index's search workspace, its FIFO or its query labels: the calls read the store (and the row labels)
+// only, so they may run beside searches in flight, on any stream, from several threads.
+static int listed_check(vodhip_index_t* ix, const void* queries, int q_dtype, int64_t nq, const int64_t* ids_dev, int64_t m,
+                        const int32_t* q_labels_dev, int n_per_query) {
+    if (!ix) return fail("index is NULL");
+    if (m < 1) return fail("m=%lld: a list holds at least one slot", (long long)m);
+    if (nq < 0 || (nq > 0 && (!queries || !ids_dev))) return fail("invalid query / id pointers");
+    if (q_dtype < 0 || q_dtype > 2) return fail("invalid q_dtype %d", q_dtype);
+    if (q_labels_dev && (n_per_query < 1 || n_per_query > 64)) return fail("n_per_query must be in [1, 64]");
+    if (q_labels_dev && !ix->row_label) return fail("set the row labels first (vodhip_index_set_row_labels)");
+    return 0;
+}
+
+static int listed_score(vodhip_index_t* ix, const void* queries, int q_dtype, int64_t nq, const int64_t* ids_dev, int64_t m,
+                        int64_t id_base, const int32_t* q_labels_dev, int n_per_query, float* out, hipStream_t stream) {
+    ListedArgs a;
+    a.plane = ix->exact ? (const void*)ix->data32 : (const void*)ix->data;
+    a.stride = ix->dim_pad;
+    a.dim = (int)ix->dim;
+    a.dim_pad = (int)ix->dim_pad;
+    a.store_dtype = ix->dtype;
+    a.exact = ix->exact ? 1 : 0;
+    a.q_src = queries;
+    a.q_dtype = q_dtype;
+    a.ids = ids_dev;
+    a.m = m;
+    a.id_base = id_base;
+    a.ntotal = ix->ntotal;
+    a.row_label = ix->row_label;
+    a.q_label = q_labels_dev;
+    a.n_qlab = q_labels_dev ? n_per_query : 0;
+    a.out = out;
+    HIP_OK(launch_score_listed(a, nq, stream));
+    return 0;
+}
+
+int vodhip_index_score_ids(vodhip_index_t* ix, const void* queries, int q_dtype, int64_t nq, const int64_t* ids_dev, int64_t m,
+                           int64_t id_base, const int32_t* q_labels_dev, int n_per_query, float* out_scores, void* stream_) {
+    if (listed_check(ix, queries, q_dtype, nq, ids_dev, m, q_labels_dev, n_per_query)) return -1;
+    if (nq > 0 && !out_scores) return fail("out_scores is NULL");
+    if (nq == 0) return 0;
+    HIP_OK(hipSetDevice(ix->device));
+    return listed_score(ix, queries, q_dtype, nq, ids_dev, m, id_base, q_labels_dev, n_per_query, out_scores, (hipStream_t)stream_);
+}
+
+int vodhip_index_search_ids(vodhip_index_t* ix, const void* queries, int q_dtype, int64_t nq, const int64_t* ids_dev, int64_t m, int k,
+                            int64_t id_base, const int32_t* q_labels_dev, int n_per_query, float* out_scores, int64_t* out_ids,
+                            void* stream_) {
+    if (listed_check(ix, queries, q_dtype, nq, ids_dev, m, q_labels_dev, n_per_query)) return -1;
+    if (m > VODHIP_MAX_LISTED) return fail("m=%lld exceeds VODHIP_MAX_LISTED=%d for the top-k form", (long long)m, VODHIP_MAX_LISTED);
+    if (k < 1 || k > VODHIP_MAX_K) return fail("k=%d out of range [1, %d]", k, VODHIP_MAX_K);
+    if (nq > 0 && (!out_scores || !out_ids)) return fail("invalid output pointers");
+    if (nq == 0) return 0;
+    HIP_OK(hipSetDevice(ix->device));
+    hipStream_t stream = (hipStream_t)stream_;
+    float* aligned = nullptr;  // stream-ordered temporary: the aligned scores the select reads
+    HIP_OK(hipMallocAsync((void**)&aligned, (size_t)nq * (size_t)m * sizeof(float), stream));
+    int rc = listed_score(ix, queries, q_dtype, nq, ids_dev, m, id_base, q_labels_dev, n_per_query, aligned, stream);
+    if (!rc) {
+        const hipError_t e = launch_select_listed(aligned, ids_dev, nq, m, k, id_base, out_scores, out_ids, stream);
+        if (e != hipSuccess) {
+            (void)hipGetLastError();
+            rc = fail("select of the listed scores failed: %s", hipGetErrorString(e));
+        }
+    }
+    const std::string keep = rc ? g_last_error : std::string();
+    const hipError_t fe = hipFreeAsync(aligned, stream);
+    if (rc) return fail("%s", keep.c_str());
+    HIP_OK(fe);
+    return 0;
+}
+
 int vodhip_debug_schedule(int64_t ntotal, int k, int64_t nq, int64_t cand_cap, int64_t dense_rows, int64_t sample_div,
                           int64_t growth_x100, int tile, int recovery_pass, int n_cu, int64_t* out, int max_stages) {
     PlanTunables t;

@@ -186,6 +186,32 @@ hipError_t launch_ingest_exact(const void* src, int src_dtype, int64_t n_rows, i
 hipError_t launch_exact_stats(const float* row_n2, const float* row_d2, int64_t n_rows, unsigned int* stats, hipStream_t stream);
 hipError_t launch_exact_rescore(const ExactArgs& a, int64_t nq, hipStream_t stream);
 
+// ---- launchers (kernels_listed.hip): scores of listed rows, top-k over a list -------------------
+struct ListedArgs {
+    const void* plane = nullptr;      // [rows][stride] fp16 / bf16 rows, or the float32 plane of an exact store (`exact`)
+    int64_t stride = 0;
+    int dim = 0, dim_pad = 0;
+    int store_dtype = 0;              // 0 = f16, 1 = bf16: what the query is rounded to (not with `exact`)
+    int exact = 0;                    // 1: float32 plane, unrounded query, exact_dot (exact_dot.h)
+    const void* q_src = nullptr;      // [nq, dim] of q_dtype
+    int q_dtype = 0;
+    const int64_t* ids = nullptr;     // [nq, m] listed ids (global: id_base is subtracted)
+    int64_t m = 0, id_base = 0, ntotal = 0;
+    const int* row_label = nullptr;   // the store's subset labels; read only with q_label
+    const int* q_label = nullptr;     // [nq, n_qlab] or NULL = unrestricted
+    int n_qlab = 0;
+    float* out = nullptr;             // [nq, m]
+    int spb = 0;                      // set by the launcher: slots per workgroup, workgroups per query
+    int64_t chunks = 0;
+};
+hipError_t launch_score_listed(ListedArgs a, int64_t nq, hipStream_t stream);
+// out[i] = parts[owner(ids[i])][i], owner = id / rows_per_shard; -inf where no shard owns the id.  parts: [n_shards][n]
+hipError_t launch_combine_listed(const float* parts, const int64_t* ids, int64_t n, int n_shards, int64_t rows_per_shard, float* out,
+                                 hipStream_t stream);
+// the k best distinct entries of every row of scores / ids [nq, m] (m <= 8192) by (score desc, id asc); NaN and -inf never enter
+hipError_t launch_select_listed(const float* scores, const int64_t* ids, int64_t nq, int64_t m, int k, int64_t id_base, float* out_scores,
+                                int64_t* out_ids, hipStream_t stream);
+
 // ---- launchers (kernels_hybrid.hip) -----------------------------------------------------------
 struct HybridArgs {
     const int64_t* lookup_idx;

@@ -665,6 +665,149 @@ int vodhip_node_index_search(vodhip_node_index_t* nx, const void* queries, int q
     return vodhip_node_index_search_finish(nx);
 }
 
+// Listed rows behind the one handle (include/vodhip.h, H2i).  The batch (queries, ids, labels) is brought to host memory once and
+// replicated from there; shard g scores the WHOLE list with id_base = g * R - rows of the other shards are out of its range and score
+// -inf - and its aligned buffer returns through host memory to devices[0], where the buffers are combined by ownership and, for the
+// top-k form, selected once.  Host-synchronous on purpose: a listed request is small, and the route works with or without peer access.
+static int node_listed(vodhip_node_index* nx, const void* queries, int q_dtype, int64_t nq, const int64_t* ids, int64_t m, int k,
+                       const int32_t* q_labels, int n_per_query, int location, float* out_scores, int64_t* out_ids, void* stream_) {
+    if (!nx) return nfail("index is NULL");
+    if (m < 1) return nfail("m=%lld: a list holds at least one slot", (long long)m);
+    if (k >= 0 && m > VODHIP_MAX_LISTED) return nfail("m=%lld exceeds VODHIP_MAX_LISTED=%d for the top-k form", (long long)m, VODHIP_MAX_LISTED);
+    if (k >= 0 && (k < 1 || k > VODHIP_MAX_K)) return nfail("k=%d out of range [1, %d]", k, VODHIP_MAX_K);
+    if (nq < 0 || (nq > 0 && (!queries || !ids || !out_scores || (k >= 0 && !out_ids)))) return nfail("invalid query / id / output pointers");
+    if (q_dtype < 0 || q_dtype > 2) return nfail("invalid q_dtype %d", q_dtype);
+    if (location != VODHIP_HOST && location != VODHIP_DEVICE) return nfail("invalid location %d", location);
+    if (q_labels && (n_per_query < 1 || n_per_query > 64)) return nfail("n_per_query must be in [1, 64]");
+    std::lock_guard<std::mutex> guard(nx->mu);
+    if (q_labels && !nx->has_row_labels) return nfail("set the row labels first (vodhip_node_index_set_row_labels)");
+    if (nq == 0) return 0;
+    const int G = nx->n, dev0 = nx->device[0];
+    hipStream_t user = location == VODHIP_DEVICE ? (hipStream_t)stream_ : nx->merge_stream;
+    const size_t q_bytes = (size_t)nq * (size_t)nx->dim * elem_bytes(q_dtype), n = (size_t)nq * (size_t)m;
+    const size_t lab_bytes = q_labels ? (size_t)nq * (size_t)n_per_query * sizeof(int32_t) : 0;
+    // 1. the batch in host memory
+    std::vector<char> hq, hl;
+    std::vector<int64_t> hi;
+    const void* q_host = queries;
+    const int64_t* ids_host = ids;
+    const int32_t* lab_host = q_labels;
+    NODE_HIP_OK(hipSetDevice(dev0));
+    if (location == VODHIP_DEVICE) {
+        hq.resize(q_bytes);
+        hi.resize(n);
+        hl.resize(lab_bytes);
+        NODE_HIP_OK(hipMemcpyAsync(hq.data(), queries, q_bytes, hipMemcpyDeviceToHost, user));
+        NODE_HIP_OK(hipMemcpyAsync(hi.data(), ids, n * sizeof(int64_t), hipMemcpyDeviceToHost, user));
+        if (q_labels) NODE_HIP_OK(hipMemcpyAsync(hl.data(), q_labels, lab_bytes, hipMemcpyDeviceToHost, user));
+        NODE_HIP_OK(hipStreamSynchronize(user));
+        q_host = hq.data();
+        ids_host = hi.data();
+        lab_host = q_labels ? (const int32_t*)hl.data() : nullptr;
+    }
+    // 2. every shard scores the whole list (the devices run side by side: nothing is waited for until every shard is enqueued)
+    std::vector<float> parts((size_t)G * n);
+    struct Tmp { void* q = nullptr; int64_t* ids = nullptr; int32_t* lab = nullptr; float* out = nullptr; };
+    std::vector<Tmp> tmp((size_t)G);
+    int rc = 0;
+    std::string err;
+    auto hip_step = [&](hipError_t e, const char* what) {
+        if (e != hipSuccess && !rc) {
+            (void)hipGetLastError();
+            err = std::string(what) + " failed: " + hipGetErrorString(e);
+            rc = -1;
+        }
+        return e == hipSuccess;
+    };
+    for (int g = 0; g < G && !rc; ++g) {
+        hipStream_t st = nx->stream[g];
+        Tmp& t = tmp[(size_t)g];
+        if (!hip_step(hipSetDevice(nx->device[g]), "hipSetDevice")) break;
+        if (!hip_step(hipMallocAsync(&t.q, q_bytes, st), "hipMallocAsync")) break;
+        if (!hip_step(hipMallocAsync((void**)&t.ids, n * sizeof(int64_t), st), "hipMallocAsync")) break;
+        if (!hip_step(hipMallocAsync((void**)&t.out, n * sizeof(float), st), "hipMallocAsync")) break;
+        if (lab_host && !hip_step(hipMallocAsync((void**)&t.lab, lab_bytes, st), "hipMallocAsync")) break;
+        if (!hip_step(hipMemcpyAsync(t.q, q_host, q_bytes, hipMemcpyHostToDevice, st), "hipMemcpyAsync")) break;
+        if (!hip_step(hipMemcpyAsync(t.ids, ids_host, n * sizeof(int64_t), hipMemcpyHostToDevice, st), "hipMemcpyAsync")) break;
+        if (lab_host && !hip_step(hipMemcpyAsync(t.lab, lab_host, lab_bytes, hipMemcpyHostToDevice, st), "hipMemcpyAsync")) break;
+        if (vodhip_index_score_ids(nx->shard[g], t.q, q_dtype, nq, t.ids, m, g * nx->rows_per_shard, t.lab, n_per_query, t.out, st)) {
+            err = std::string("shard ") + std::to_string(g) + ": " + vodhip_last_error();
+            rc = -1;
+            break;
+        }
+        hip_step(hipMemcpyAsync(parts.data() + (size_t)g * n, t.out, n * sizeof(float), hipMemcpyDeviceToHost, st), "hipMemcpyAsync");
+    }
+    for (int g = 0; g < G; ++g) {  // (also after a failure: what was enqueued reads the host vectors of this frame)
+        Tmp& t = tmp[(size_t)g];
+        if (hipSetDevice(nx->device[g]) != hipSuccess) continue;
+        if (t.q) (void)hipFreeAsync(t.q, nx->stream[g]);
+        if (t.ids) (void)hipFreeAsync(t.ids, nx->stream[g]);
+        if (t.lab) (void)hipFreeAsync(t.lab, nx->stream[g]);
+        if (t.out) (void)hipFreeAsync(t.out, nx->stream[g]);
+        hip_step(hipStreamSynchronize(nx->stream[g]), "hipStreamSynchronize");
+    }
+    (void)hipSetDevice(dev0);
+    if (rc) return nfail("%s", err.c_str());
+    // 3. on devices[0]: combine by ownership, select once
+    float *d_parts = nullptr, *d_aligned = nullptr, *d_s = nullptr;
+    int64_t *d_ids = nullptr, *d_i = nullptr;
+    const size_t res = k >= 0 ? (size_t)nq * (size_t)k : 0;
+    auto steps = [&]() -> int {
+        NODE_HIP_OK(hipMallocAsync((void**)&d_parts, (size_t)G * n * sizeof(float), user));
+        NODE_HIP_OK(hipMemcpyAsync(d_parts, parts.data(), (size_t)G * n * sizeof(float), hipMemcpyHostToDevice, user));
+        const int64_t* ids0 = ids;
+        if (location == VODHIP_HOST) {
+            NODE_HIP_OK(hipMallocAsync((void**)&d_ids, n * sizeof(int64_t), user));
+            NODE_HIP_OK(hipMemcpyAsync(d_ids, ids_host, n * sizeof(int64_t), hipMemcpyHostToDevice, user));
+            ids0 = d_ids;
+        }
+        float* aligned = out_scores;
+        if (k >= 0 || location == VODHIP_HOST) {
+            NODE_HIP_OK(hipMallocAsync((void**)&d_aligned, n * sizeof(float), user));
+            aligned = d_aligned;
+        }
+        NODE_HIP_OK(vodhip::launch_combine_listed(d_parts, ids0, (int64_t)n, G, nx->rows_per_shard, aligned, user));
+        if (k < 0) {
+            if (location == VODHIP_HOST) NODE_HIP_OK(hipMemcpyAsync(out_scores, aligned, n * sizeof(float), hipMemcpyDeviceToHost, user));
+        } else {
+            float* fs = out_scores;
+            int64_t* fi = out_ids;
+            if (location == VODHIP_HOST) {
+                NODE_HIP_OK(hipMallocAsync((void**)&d_s, res * sizeof(float), user));
+                NODE_HIP_OK(hipMallocAsync((void**)&d_i, res * sizeof(int64_t), user));
+                fs = d_s;
+                fi = d_i;
+            }
+            NODE_HIP_OK(vodhip::launch_select_listed(aligned, ids0, nq, m, k, 0, fs, fi, user));
+            if (location == VODHIP_HOST) {
+                NODE_HIP_OK(hipMemcpyAsync(out_scores, fs, res * sizeof(float), hipMemcpyDeviceToHost, user));
+                NODE_HIP_OK(hipMemcpyAsync(out_ids, fi, res * sizeof(int64_t), hipMemcpyDeviceToHost, user));
+            }
+        }
+        return 0;
+    };
+    rc = steps();
+    const std::string keep = rc ? vodhip_last_error() : "";
+    for (void* p : {(void*)d_parts, (void*)d_aligned, (void*)d_s, (void*)d_ids, (void*)d_i})
+        if (p) (void)hipFreeAsync(p, user);
+    const hipError_t se = hipStreamSynchronize(user);  // (`parts` and the host copies of this frame were sources of copies on `user`)
+    if (rc) return nfail("%s", keep.c_str());
+    NODE_HIP_OK(se);
+    return 0;
+}
+
+int vodhip_node_index_score_ids(vodhip_node_index_t* nx, const void* queries, int q_dtype, int64_t nq, const int64_t* ids, int64_t m,
+                                const int32_t* q_labels, int n_per_query, int location, float* out_scores, void* stream) {
+    return node_listed(nx, queries, q_dtype, nq, ids, m, -1, q_labels, n_per_query, location, out_scores, nullptr, stream);
+}
+
+int vodhip_node_index_search_ids(vodhip_node_index_t* nx, const void* queries, int q_dtype, int64_t nq, const int64_t* ids, int64_t m,
+                                 int k, const int32_t* q_labels, int n_per_query, int location, float* out_scores, int64_t* out_ids,
+                                 void* stream) {
+    if (k < 0) return nfail("k=%d out of range [1, %d]", k, VODHIP_MAX_K);
+    return node_listed(nx, queries, q_dtype, nq, ids, m, k, q_labels, n_per_query, location, out_scores, out_ids, stream);
+}
+
 int vodhip_node_index_get_stat(vodhip_node_index_t* nx, const char* key, int64_t* out) {
     if (!nx || !key || !out) return nfail("NULL argument");
     std::lock_guard<std::mutex> guard(nx->mu);

@@ -17,6 +17,22 @@ import torch
 from vod_amd import _native
 
 
+def pad_listed_ids(ids, nq: int | None = None) -> np.ndarray:
+    """`ids` of `score_ids` as a C-contiguous int64 [nq, m] NumPy array: an array is taken as it is, a ragged list of lists is padded
+    with -1 (an empty slot) to its longest row - at least one column, so that a batch of empty lists is still a list."""
+    if isinstance(ids, np.ndarray):
+        arr = ids
+    else:
+        rows = [np.asarray(r, dtype=np.int64).reshape(-1) for r in ids]
+        arr = np.full((len(rows), max(1, max((len(r) for r in rows), default=0))), -1, dtype=np.int64)
+        for i, r in enumerate(rows):
+            arr[i, : len(r)] = r
+    arr = np.ascontiguousarray(arr, dtype=np.int64)
+    if arr.ndim != 2 or (nq is not None and arr.shape[0] != nq):
+        raise ValueError(f"expected ids of shape [{'nq' if nq is None else nq}, m], got {tuple(arr.shape)}")
+    return arr
+
+
 class HipFlatIndex:
     """Exact MIPS index: row-major fp16/bf16 rows in HBM, searched by the fused MFMA + top-k kernels.
 
@@ -250,6 +266,56 @@ class HipFlatIndex:
             self.finish()
         return res
 
+    def score_ids(self, queries, ids, k: int | None = None, *, subset=None, id_base: int = 0, out=None):
+        """Scores of LISTED rows - the dense counterpart of `ids` in the reference's `SearchClient.search`, which its Elasticsearch client
+        honours with a `terms` filter and its faiss client drops (/root/reference/src/vod_search/es_search/client.py:145,177-183,
+        faiss_search/client.py:70).
+
+        `ids`: int64 [nq, m] tensor / array, or a ragged list of lists (padded with -1).  A slot that is empty (id < 0), out of range
+        (id - id_base outside [0, ntotal)) or whose row carries none of the query's `subset` labels scores -inf.
+        `k=None`: float32 [nq, m] aligned to `ids` (`out`: that tensor).  `k=int`: (scores [nq, k], ids [nq, k]) - the k best distinct
+        listed rows by (score desc, id asc), pads (-inf, -1); m <= 8192 (`out`: the pair).
+        Enqueued on the current stream; nothing to finish, and safe beside searches of this index that are in flight."""
+        q = self._prep_queries(queries)
+        nq = q.shape[0]
+        if isinstance(ids, torch.Tensor):
+            lst = ids.to(self.device, torch.int64).contiguous()
+            if lst.ndim != 2 or lst.shape[0] != nq:
+                raise ValueError(f"expected ids of shape [{nq}, m], got {tuple(lst.shape)}")
+        else:
+            lst = torch.from_numpy(pad_listed_ids(ids, nq)).to(self.device)
+        m = int(lst.shape[1])
+        sub, n_sub = None, 0
+        if subset is not None:
+            sub = subset if isinstance(subset, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(subset))
+            sub = sub.to(self.device, torch.int32).contiguous()
+            if sub.ndim != 2 or sub.shape[0] != nq:
+                raise ValueError(f"expected subset labels of shape [{nq}, S], got {tuple(sub.shape)}")
+            n_sub = int(sub.shape[1])
+        sub_ptr = None if sub is None else sub.data_ptr()
+        with torch.cuda.device(self.device):
+            stream = _native.current_stream_ptr(self.device)
+            if k is None:
+                scores = torch.empty((nq, m), dtype=torch.float32, device=self.device) if out is None else out
+                _native.check(self._lib.vodhip_index_score_ids(self._h, q.data_ptr(), _native.torch_dtype_code(q.dtype), nq, lst.data_ptr(), m,
+                                                               int(id_base), sub_ptr, n_sub, scores.data_ptr(), stream))
+                res = scores
+            else:
+                if out is None:
+                    scores = torch.empty((nq, int(k)), dtype=torch.float32, device=self.device)
+                    top = torch.empty((nq, int(k)), dtype=torch.int64, device=self.device)
+                else:
+                    scores, top = out
+                _native.check(self._lib.vodhip_index_search_ids(self._h, q.data_ptr(), _native.torch_dtype_code(q.dtype), nq, lst.data_ptr(), m,
+                                                                int(k), int(id_base), sub_ptr, n_sub, scores.data_ptr(), top.data_ptr(), stream))
+                res = (scores, top)
+        # inputs this call built itself (converted / uploaded copies) must outlive the launch: the caching allocator hands their blocks
+        # out again in the order of the stream they were allocated on, which need not be the current one
+        for t, given in ((q, queries), (lst, ids), (sub, subset)):
+            if t is not None and t is not given:
+                t.record_stream(torch.cuda.current_stream(self.device))
+        return res
+
 
 def merge_topk(scores: torch.Tensor, ids: torch.Tensor, k_out: int | None = None) -> tuple[torch.Tensor, torch.Tensor]:
     """Merge per-shard top-k lists [n_shards, nq, k] (global ids, pads -1) into [nq, k_out] on the GPU."""
@@ -478,3 +544,55 @@ class HipNodeIndex:
         _native.check(self._lib.vodhip_node_index_search(self._h, q.ctypes.data, 2 if q.dtype == np.float32 else 0, q.shape[0], int(k), 0,
                                                          out_s.ctypes.data, out_i.ctypes.data, None))
         return out_s, out_i
+
+    def score_ids(self, queries, ids, k: int | None = None, *, subset=None, out=None):
+        """`HipFlatIndex.score_ids` over every shard: `ids` are global row ids; results equal one index holding all the rows.
+        NumPy queries -> NumPy results (host buffers); a tensor on `devices[0]` -> tensors there, complete on the current stream.
+        `ids` / `subset` may be host arrays, ragged lists (ids) or tensors on `devices[0]` whatever the queries are."""
+        nq = int(queries.shape[0])
+        on_device = isinstance(queries, torch.Tensor)
+        if on_device:
+            if queries.device != self.device:
+                raise ValueError(f"queries live on {queries.device}, the merge device is {self.device}")
+            q = queries.contiguous()
+            if q.dtype not in (torch.float16, torch.bfloat16, torch.float32):
+                q = q.float()
+            code = _native.torch_dtype_code(q.dtype)
+        else:
+            q = np.ascontiguousarray(queries)
+            if q.dtype not in (np.float32, np.float16):
+                q = q.astype(np.float32)
+            code = 2 if q.dtype == np.float32 else 0
+        if q.ndim != 2 or q.shape[1] != self.dim:
+            raise ValueError(f"expected [nq, {self.dim}] queries, got {tuple(q.shape)}")
+        if on_device:
+            lst = ids.to(self.device, torch.int64).contiguous() if isinstance(ids, torch.Tensor) else torch.from_numpy(pad_listed_ids(ids, nq)).to(self.device)
+            sub = None if subset is None else (subset if isinstance(subset, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(subset))).to(self.device, torch.int32).contiguous()
+        else:
+            lst = pad_listed_ids(ids.cpu().numpy() if isinstance(ids, torch.Tensor) else ids, nq)
+            sub = None if subset is None else np.ascontiguousarray(subset.cpu().numpy() if isinstance(subset, torch.Tensor) else subset, dtype=np.int32)
+        if lst.ndim != 2 or lst.shape[0] != nq:
+            raise ValueError(f"expected ids of shape [{nq}, m], got {tuple(lst.shape)}")
+        if sub is not None and (sub.ndim != 2 or sub.shape[0] != nq):
+            raise ValueError(f"subset must be int32 [nq, n_per_query], got {tuple(sub.shape)}")
+        m = int(lst.shape[1])
+        n_sub = 0 if sub is None else int(sub.shape[1])
+        ptr = (lambda t: None if t is None else t.data_ptr()) if on_device else (lambda a: None if a is None else a.ctypes.data)
+        shape = (nq, m) if k is None else (nq, int(k))
+        if out is not None:
+            scores, top = (out, None) if k is None else out
+        elif on_device:
+            scores = torch.empty(shape, dtype=torch.float32, device=self.device)
+            top = None if k is None else torch.empty(shape, dtype=torch.int64, device=self.device)
+        else:
+            scores = np.empty(shape, dtype=np.float32)
+            top = None if k is None else np.empty(shape, dtype=np.int64)
+        loc = _native.DEVICE if on_device else _native.HOST
+        with torch.cuda.device(self.device):
+            stream = _native.current_stream_ptr(self.device) if on_device else None
+            if k is None:
+                _native.check(self._lib.vodhip_node_index_score_ids(self._h, ptr(q), code, nq, ptr(lst), m, ptr(sub), n_sub, loc, ptr(scores), stream))
+                return scores
+            _native.check(self._lib.vodhip_node_index_search_ids(self._h, ptr(q), code, nq, ptr(lst), m, int(k), ptr(sub), n_sub, loc,
+                                                                 ptr(scores), ptr(top), stream))
+        return scores, top

@@ -155,7 +155,7 @@ class HipMipsClient(base.SearchClient):
     requires_vectors = True
 
     def __init__(self, host: str = "http://localhost", port: int = 7678, binary: bool = False, forward_subset_ids: bool = False,
-                 wire_dtype: str | None = None, uds: str | None = None, native: bool = True):
+                 wire_dtype: str | None = None, uds: str | None = None, native: bool = True, forward_ids: bool = False):
         self.host = host
         # the exchange itself (request document, framing, reply parsing) runs in libvodhip's client (`vodhip_client_*`, one call with the
         # GIL released) when the library can be loaded in this process and the address is plain http / a Unix socket; anything it cannot do
@@ -169,6 +169,11 @@ class HipMipsClient(base.SearchClient):
         # The reference's faiss client drops `subset_ids`; set this to let the GPU index honour them (the server must
         # have been started with `--subset-ids-path`).
         self.forward_subset_ids = forward_subset_ids
+        # The reference's faiss client drops `ids` too (faiss_search/client.py:70); its Elasticsearch client restricts the hits to the
+        # listed sections and labels them `scores > -inf` (es_search/client.py:145,177-183).  Set this and a request that carries `ids`
+        # is answered that way by the GPU index (`score_ids`): the client can then serve as the `lookup_engine_name` of a hybrid search.
+        # Off (the default) the bytes on the wire are what they were.
+        self.forward_ids = forward_ids
         # "float16": send the queries as float16 (half the bytes on the wire).  Exact for a float16 store - the library rounds
         # float32 queries to the store dtype anyway (round to nearest even, like NumPy) - so only set it for such a store.
         self.wire_dtype = wire_dtype
@@ -187,6 +192,7 @@ class HipMipsClient(base.SearchClient):
         self.__dict__.setdefault("wire_dtype", None)
         self.__dict__.setdefault("uds", None)
         self.__dict__.setdefault("native", True)
+        self.__dict__.setdefault("forward_ids", False)
         self._local = threading.local()
 
     @property
@@ -325,13 +331,14 @@ class HipMipsClient(base.SearchClient):
         vector: np.ndarray,
         text: None | list[str] = None,  # noqa: ARG002
         subset_ids: None | list[list[base.SubsetId]] = None,
-        ids: None | list[list[base.SectionId]] = None,  # noqa: ARG002
+        ids: None | list[list[base.SectionId]] = None,
         shard: None | list[base.ShardName] = None,  # noqa: ARG002
         top_k: int = 3,
         timeout: float = 120,
     ) -> vt.RetrievalBatch:
         start = time.time()
-        filtered = self.forward_subset_ids and subset_ids is not None
+        listed = self.forward_ids and ids is not None
+        filtered = (self.forward_subset_ids and subset_ids is not None) or listed
         if self.native and not filtered:
             out = self._search_native(vector, top_k, timeout)
             if out is not None:
@@ -341,13 +348,18 @@ class HipMipsClient(base.SearchClient):
         extra: dict = {"top_k": top_k}
         if self.forward_subset_ids and subset_ids is not None:
             extra["subset_ids"] = [list(map(str, s)) for s in subset_ids]
+        if listed:
+            extra["ids"] = [list(map(str, s)) for s in ids]
         # the same JSON document `requests.post(json=...)` would send: the base64 text is written straight into the body buffer
         body = io.json_body_with_arrays({"vectors": self._wire(vector)}, extra)
         status, _, content = self._post("/fast-search", body, "application/json", timeout)
         self._raise_for_status(status, content, f"{self.url}/fast-search")
         small, spans = io.find_payload_spans(content, ("scores", "indices"))
         take = lambda key: io.deserialize_np_array_span(content, *spans[key]) if key in spans else io.deserialize_np_array(small[key])  # noqa: E731
-        return vt.RetrievalBatch.cast(indices=take("indices"), scores=take("scores"), labels=None, meta={"time": time.time() - start})
+        scores = take("scores")
+        # a listed request: `labels = scores > -inf`, what the Elasticsearch client returns (es_search/client.py:145)
+        labels = (np.asarray(scores) > -np.inf).astype(np.int64) if listed else None
+        return vt.RetrievalBatch.cast(indices=take("indices"), scores=scores, labels=labels, meta={"time": time.time() - start})
 
 
     def _native_handle(self):
@@ -458,6 +470,8 @@ class HipMipsMaster(base.SearchMaster[HipMipsClient]):
         batcher_params: None | dict[str, int] = None,  # vodhip_batcher_set_param on the server (max_queries, grace_us, grace_pct, flat_queries, depth)
         uds: bool | str = False,  # also listen on a Unix-domain socket (True = a path in a private directory); `get_client()` then uses it
         exact_f32: bool = False,  # the server keeps the float32 rows and answers with the float32 brute-force result (HipFlatIndex)
+        subset_ids_path: None | str | pathlib.Path = None,  # `.npy`, one subset id per vector: what `forward_subset_ids` clients filter by
+        section_ids_path: None | str | pathlib.Path = None,  # `.npy`, one unique section id per vector: what `forward_ids` clients list
     ):
         super().__init__(skip_setup=skip_setup, free_resources=free_resources)
         self.vectors_path = vectors_path if str(vectors_path).startswith("synthetic:") else pathlib.Path(vectors_path)
@@ -466,6 +480,8 @@ class HipMipsMaster(base.SearchMaster[HipMipsClient]):
         self.port = find_available_port() if port < 0 else port
         self.dtype = dtype
         self.exact_f32 = bool(exact_f32)
+        self.subset_ids_path = subset_ids_path
+        self.section_ids_path = section_ids_path
         self.device = device
         # `devices=[...]`: the store is row-sharded over these GPUs behind the SAME host:port (one worker process per
         # GPU on an RCCL group; what `FaissMaster(serve_on_gpu=True)` gets from faiss's index_cpu_to_all_gpus,
@@ -498,6 +514,8 @@ class HipMipsMaster(base.SearchMaster[HipMipsClient]):
             "--logging-level", str(self.logging_level),
             "--dtype", self.dtype,
             *(["--exact-f32"] if self.exact_f32 else []),
+            *(["--subset-ids-path", str(self.subset_ids_path)] if self.subset_ids_path else []),
+            *(["--section-ids-path", str(self.section_ids_path)] if self.section_ids_path else []),
             "--http", self.http,
             *(["--micro-batch-wait-ms", str(self.micro_batch_wait_ms)] if self.micro_batch_wait_ms > 0 else []),
             *(["--uds", str(self.uds)] if self.uds else []),

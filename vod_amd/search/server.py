@@ -39,6 +39,9 @@ class FastSearchQuery(pydantic.BaseModel):
     top_k: int = 3
     # extension (absent in the reference's model, whose faiss client drops `subset_ids`): per-query allowed subset ids
     subset_ids: None | list[list[str]] = None
+    # extension (the reference's faiss client drops `ids` as well, faiss_search/client.py:70): per-query section ids - only the listed
+    # sections can be hits, as with its Elasticsearch client (es_search/client.py:177-183); `[]` for a query = no hit
+    ids: None | list[list[str]] = None
 
 
 class SearchResponse(pydantic.BaseModel):
@@ -51,6 +54,38 @@ class FastSearchResponse(pydantic.BaseModel):
     model_config = pydantic.ConfigDict(extra="forbid")
     scores: str
     indices: str
+
+
+def load_section_rows(path, n_rows: int) -> dict[str, int]:
+    """`--section-ids-path`: a `.npy` with one UNIQUE section id per stored row -> the `str -> row` map of listed requests."""
+    ids = np.load(path, allow_pickle=False)
+    if len(ids) != n_rows:
+        raise ValueError(f"{path}: {len(ids)} section ids for {n_rows} vectors")
+    names = ids.astype(str)
+    uniq, counts = np.unique(names, return_counts=True)
+    if len(uniq) != len(names):
+        dup = uniq[counts > 1][:5].tolist()
+        raise ValueError(f"{path}: section ids must be unique, {int((counts > 1).sum())} are not (e.g. {dup})")
+    return {str(nm): r for r, nm in enumerate(names)}
+
+
+def encode_listed_ids(ids: list[list[str]], section_rows: dict[str, int] | None) -> np.ndarray:
+    """The `ids` of a request as global rows, int64 [nq, m], ragged lists padded with -1 (an empty slot; m >= 1).  With a section-id
+    map an id is looked up; without one it is taken as a decimal row number.  An unknown or unparsable id matches nothing (-1), and so
+    does `[]`: a query that lists nothing has no hit (the Elasticsearch client's behaviour, es_search/client.py:178-180)."""
+    rows = np.full((len(ids), max(1, max((len(r) for r in ids), default=0))), -1, dtype=np.int64)
+    for i, names in enumerate(ids):
+        for j, nm in enumerate(names):
+            if section_rows is not None:
+                rows[i, j] = section_rows.get(str(nm), -1)
+            else:
+                try:
+                    v = int(str(nm))
+                except ValueError:
+                    continue
+                if 0 <= v < (1 << 62):
+                    rows[i, j] = v
+    return rows
 
 
 class _CallbackEngine:
@@ -115,7 +150,7 @@ class Endpoints:
         self._generic.clear()
 
     # -- the search itself --------------------------------------------------------------------------------------------
-    def search(self, query_vec: np.ndarray, top_k: int, subset_ids=None, client: int = 0) -> tuple[np.ndarray, np.ndarray]:
+    def search(self, query_vec: np.ndarray, top_k: int, subset_ids=None, client: int = 0, ids=None) -> tuple[np.ndarray, np.ndarray]:
         if query_vec.ndim != 2:
             raise ValueError(f"Expected 2D array, got {query_vec.ndim}D array")
         subset = None
@@ -123,6 +158,16 @@ class Endpoints:
             if len(subset_ids) != len(query_vec):
                 raise ValueError("`subset_ids` must have one list per query")
             subset = self.engine.encode_subset(subset_ids)
+        if ids is not None:
+            # a listed request: only the listed sections can be hits (AND the subset filter, as Elasticsearch combines the two).  It is
+            # a gather of the listed rows, not a scan: it goes straight to the engine, not through the batcher that fuses scans
+            if len(ids) != len(query_vec):
+                raise ValueError("`ids` must have one list per query")
+            if not hasattr(self.engine, "search_listed"):
+                raise ValueError("this engine cannot score listed ids")
+            rows = encode_listed_ids(ids, getattr(self.engine, "section_rows", None))
+            scores, indices = self.engine.search_listed(query_vec, top_k, rows, subset)
+            return np.asarray(scores, dtype=np.float32), np.asarray(indices, dtype=np.int64)
         scores, indices = self._batcher_for(int(query_vec.shape[1])).search(query_vec, top_k, subset=subset, client=client)
         return np.asarray(scores, dtype=np.float32), np.asarray(indices, dtype=np.int64)
 
@@ -146,7 +191,7 @@ class Endpoints:
         query = FastSearchQuery(**small)  # raises pydantic.ValidationError -> 422
         try:
             vectors = io.deserialize_np_array_span(body, *spans["vectors"]) if "vectors" in spans else io.deserialize_np_array(query.vectors)
-            scores, indices = self.search(vectors, query.top_k, query.subset_ids, client=client)
+            scores, indices = self.search(vectors, query.top_k, query.subset_ids, client=client, ids=query.ids)
             return io.json_body_with_arrays({"scores": scores, "indices": indices})
         except Exception as exc:
             raise _SearchFailed(traceback.format_exc()) from exc
@@ -256,9 +301,11 @@ class HipEngine:
     `row_range=(lo, hi)`: hold only rows [lo, hi) of the store (one shard of a multi-GPU group); ids stay global."""
 
     def __init__(self, vectors_path: str, dtype: str = "float16", device: int = 0, subset_ids_path: str | None = None,
-                 row_range: tuple[int, int] | None = None, exact_f32: bool = False):
+                 row_range: tuple[int, int] | None = None, exact_f32: bool = False, section_ids_path: str | None = None):
         import torch
 
+        self.section_rows: dict[str, int] | None = None  # `--section-ids-path`: section id -> global row (None: ids are row numbers)
+        self._section_ids_path = section_ids_path
         self.exact_f32 = bool(exact_f32)  # keep the float32 rows too: results of a float32 brute force (HipFlatIndex)
 
         from vod_amd import store
@@ -271,6 +318,8 @@ class HipEngine:
             return self._init_synthetic(str(vectors_path), dtype, device, row_range)
         vectors = store.open_vectors(vectors_path)
         n, d = vectors.shape
+        if section_ids_path:
+            self.section_rows = load_section_rows(section_ids_path, n)  # (before the ingest: a bad file fails the start at once)
         lo, hi = (0, n) if row_range is None else (int(row_range[0]), int(row_range[1]))
         self.n_store, self.row_lo, self.row_hi = n, lo, hi
         self.index = HipFlatIndex(d, max(hi - lo, 1), dtype=getattr(torch, dtype), device=device, exact_f32=self.exact_f32)
@@ -305,6 +354,8 @@ class HipEngine:
         n, d = (int(v) for v in shape.lower().split("x"))
         lo, hi = (0, n) if row_range is None else (int(row_range[0]), int(row_range[1]))
         self.n_store, self.row_lo, self.row_hi = n, lo, hi
+        if self._section_ids_path:
+            self.section_rows = load_section_rows(self._section_ids_path, n)
         self.index = HipFlatIndex(d, max(hi - lo, 1), dtype=getattr(torch, dtype), device=device, exact_f32=self.exact_f32)
         self.vocab = {}
         for rows in synthetic_rows(torch, torch.device("cuda", device), lo, hi, d, int(seed or 0)):
@@ -357,6 +408,14 @@ class HipEngine:
     def search(self, query_vec: np.ndarray, top_k: int, subset_ids: list[list[str]] | None = None) -> tuple[np.ndarray, np.ndarray]:
         return self.search_encoded(query_vec, top_k, self.encode_subset(subset_ids))
 
+    def search_listed(self, query_vec: np.ndarray, top_k: int, rows: np.ndarray, subset: np.ndarray | None = None):
+        """The `top_k` best of the listed global `rows` (int64 [nq, m], -1 = empty slot) per query, restricted to `subset` when given
+        (`HipFlatIndex.score_ids`).  Runs on the calling thread's stream, beside whatever the batcher has in flight."""
+        if query_vec.ndim != 2 or query_vec.shape[1] != self.index.dim:
+            raise ValueError(f"query dimension {query_vec.shape[-1]} != index dimension {self.index.dim}")
+        scores, indices = self.index.score_ids(query_vec, rows, int(top_k), subset=subset, id_base=self.row_lo)
+        return scores.cpu().numpy(), indices.cpu().numpy()
+
     def close(self) -> None:
         b = getattr(self, "_batcher", None)
         if b is not None:
@@ -373,16 +432,19 @@ class NodeHipEngine:
     Same `.ntotal` / `.search` as `HipEngine`."""
 
     def __init__(self, vectors_path: str, devices: list[int], dtype: str = "float16", subset_ids_path: str | None = None,
-                 exact_f32: bool = False):
+                 exact_f32: bool = False, section_ids_path: str | None = None):
         import torch
 
         from vod_amd import store
         from vod_amd.index import HipNodeIndex
 
         self.vocab: dict[str, int] = {}
+        self.section_rows: dict[str, int] | None = None
         if str(vectors_path).startswith("synthetic:"):
             shape, _, seed = str(vectors_path)[len("synthetic:"):].partition(":")
             n, d = (int(v) for v in shape.lower().split("x"))
+            if section_ids_path:
+                self.section_rows = load_section_rows(section_ids_path, n)
             self.index = HipNodeIndex(d, max(n, 1), devices, dtype=getattr(torch, dtype), exact_f32=exact_f32)
             for rows in synthetic_rows(torch, torch.device("cuda", devices[0]), 0, n, d, int(seed or 0)):
                 self.index.add((rows if exact_f32 else rows.to(torch.float16)).cpu().numpy())
@@ -392,6 +454,8 @@ class NodeHipEngine:
         vectors = store.open_vectors(vectors_path)
         n, d = vectors.shape
         self.n_store = n
+        if section_ids_path:
+            self.section_rows = load_section_rows(section_ids_path, n)
         self.index = HipNodeIndex(d, max(n, 1), devices, dtype=getattr(torch, dtype), exact_f32=exact_f32)
         if hasattr(vectors, "iter_row_blocks"):
             for _lo, rows in vectors.iter_row_blocks():
@@ -447,6 +511,12 @@ class NodeHipEngine:
     def search(self, query_vec: np.ndarray, top_k: int, subset_ids: list[list[str]] | None = None) -> tuple[np.ndarray, np.ndarray]:
         return self.search_encoded(query_vec, top_k, self.encode_subset(subset_ids))
 
+    def search_listed(self, query_vec: np.ndarray, top_k: int, rows: np.ndarray, subset: np.ndarray | None = None):
+        """`HipEngine.search_listed` over every shard (`HipNodeIndex.score_ids`: host arrays in and out)."""
+        if query_vec.ndim != 2 or query_vec.shape[1] != self.index.dim:
+            raise ValueError(f"query dimension {query_vec.shape[-1]} != index dimension {self.index.dim}")
+        return self.index.score_ids(np.asarray(query_vec), rows, int(top_k), subset=subset)
+
     def close(self) -> None:
         b = getattr(self, "_batcher", None)
         if b is not None:
@@ -482,6 +552,10 @@ class GroupHipEngine:
     def search(self, query_vec: np.ndarray, top_k: int, subset_ids: list[list[str]] | None = None) -> tuple[np.ndarray, np.ndarray]:
         return self.search_encoded(query_vec, top_k, self.local.encode_subset(subset_ids))
 
+    def search_listed(self, query_vec, top_k, rows, subset=None):
+        # every rank would have to score its rows of every list and rank 0 combine them: not built (`--group-backend node` scores listed ids)
+        raise ValueError("this engine cannot score listed ids")
+
 
 def parse_args(argv=None) -> argparse.Namespace:
     p = argparse.ArgumentParser()
@@ -499,6 +573,9 @@ def parse_args(argv=None) -> argparse.Namespace:
                    help="comma-separated GPU ids: the store is row-sharded over them, one worker process per GPU on an RCCL "
                         "group, rank 0 answers HTTP (the reference's `--serve-on-gpu` = faiss index_cpu_to_all_gpus, server.py:51-54)")
     p.add_argument("--subset-ids-path", type=str, default=None, help=".npy with one subset id (string) per vector")
+    p.add_argument("--section-ids-path", type=str, default=None,
+                   help=".npy with one UNIQUE section id (string) per vector: requests that carry `ids` list sections by these ids "
+                        "(without it a listed id is a decimal row number)")
     p.add_argument("--http", type=str, default="native", choices=["native", "uvicorn"],
                    help="HTTP shell: libvodhip's native front (default: the hot routes never enter the interpreter), or uvicorn + FastAPI "
                         "(fallback: ASGI hosting; every route runs in the interpreter)")
@@ -668,13 +745,15 @@ def main(argv=None) -> None:
         limit_cpu_threads(max(1, usable_cpus() // max(1, n_workers)))  # the workers of a group share the grant
     if args.devices is not None and args.group_backend == "node":
         devices = [int(x) for x in args.devices.split(",") if x.strip() != ""]
-        engine = NodeHipEngine(args.vectors_path, devices, dtype=args.dtype, subset_ids_path=args.subset_ids_path, exact_f32=args.exact_f32)
+        engine = NodeHipEngine(args.vectors_path, devices, dtype=args.dtype, subset_ids_path=args.subset_ids_path, exact_f32=args.exact_f32,
+                               section_ids_path=args.section_ids_path)
         return _serve(engine, args, re.sub(r"^(http|https)://", "", args.host))
     if args.devices is not None and args.rank is None:
         raise SystemExit(run_owner(args, argv))
     if args.devices is not None:
         return run_worker(args)
-    engine = HipEngine(args.vectors_path, dtype=args.dtype, device=args.device, subset_ids_path=args.subset_ids_path, exact_f32=args.exact_f32)
+    engine = HipEngine(args.vectors_path, dtype=args.dtype, device=args.device, subset_ids_path=args.subset_ids_path, exact_f32=args.exact_f32,
+                       section_ids_path=args.section_ids_path)
     host = re.sub(r"^(http|https)://", "", args.host)
     _serve(engine, args, host)
 
