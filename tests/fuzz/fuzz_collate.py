@@ -32,10 +32,12 @@ def fuzz_merge(rng):
 
     nq = int(rng.choice([1, 2, 7, 64, 130]))
     kl = int(rng.choice([0, 1, 5, 32, 128, 600]))
-    ks = [int(rng.choice([0, 1, 3, 16, 128, 700])) for _ in range(int(rng.integers(0, 5)))]
-    if kl + sum(ks) > 4000:
-        ks = ks[:1]
-    n_ids = int(rng.choice([5, 40, 300, 100_000]))
+    ks = [int(rng.choice([0, 1, 3, 16, 128, 700, 2000])) for _ in range(int(rng.integers(0, 5)))]
+    while kl + sum(ks) > 4096:  # the kernel's limit: the last engine is cut so that the row is exactly that wide
+        ks[-1] -= min(ks[-1], kl + sum(ks) - 4096)
+        ks = ks if ks[-1] else ks[:-1]
+    # (pool size, 64-bit): the wide pool is 2^33 * j + small - ids that differ in the high word and share the low one
+    n_ids, wide = [(5, False), (40, False), (300, False), (100_000, False), (300, True)][int(rng.integers(0, 5))]
     pad_frac = float(rng.choice([0.0, 0.2, 0.9]))
     dup = bool(rng.random() < 0.3)
 
@@ -49,13 +51,15 @@ def fuzz_merge(rng):
             scr[r, :nv] = rng.normal(size=nv).astype(np.float32) * 5
             if nv and rng.random() < 0.2:
                 scr[r, int(rng.integers(0, nv))] = np.nan
+        if wide:
+            idx = np.where(idx >= 0, (idx << 33) + idx % 3, idx)
         return idx, scr
 
-    LAST.clear(); LAST.update(kind="merge", nq=nq, kl=kl, ks=ks, n_ids=n_ids, pad=pad_frac, dup=dup)
+    LAST.clear(); LAST.update(kind="merge", nq=nq, kl=kl, ks=ks, n_ids=n_ids, wide=wide, pad=pad_frac, dup=dup)
     l_idx, l_scr = eng(kl)
     l_lbl = (l_scr > -np.inf).astype(np.int64) * rng.integers(1, 3, size=l_scr.shape)
     engs = {f"e{i}": eng(k) for i, k in enumerate(ks)}
-    weights = {n: float(rng.choice([0.0, 0.5, 1.0, 1.7])) for n in engs}
+    weights = {n: float(rng.choice([0.0, 0.5, 1.0, 1.7, -1.5])) for n in engs}
     idx, scr, lbl, raw = merge_hybrid(l_idx, l_lbl, engs, weights)
     o_idx, o_scr, o_lbl, o_raw = oracle_merge((l_idx, np.zeros(l_idx.shape, np.float32), l_lbl), engs, weights)
     _eq(idx, o_idx, "merge idx")
@@ -63,7 +67,7 @@ def fuzz_merge(rng):
     _eq(lbl, o_lbl, "merge labels")
     for n in engs:
         _eq(raw[n], o_raw[n], f"merge raw {n}")
-    return dict(kind="merge", nq=nq, kl=kl, ks=ks, n_ids=n_ids, pad=pad_frac, dup=dup)
+    return dict(LAST)
 
 
 def fuzz_sampling(rng):

@@ -197,6 +197,107 @@ def gen_merge_corners() -> None:
     _save("merge_corners", {"cases": cases}, **arrays)
 
 
+def gen_merge_edges() -> None:
+    """Input classes the reference defines and no other fixture feeds, with 1, 2 and 4 scored engines (tests/test_hybrid_edges_gpu.py):
+    64-bit ids that differ only in the high word (x, x + 2^32, x + 2^40, 2^62 + 1: spread over the segments in row 0, inside one list
+    in row 1), ids -2 and -7 among real ones (row 2; merge.py:93 skips every index < 0), a -1 at an INTERIOR position of the lookup
+    (non-zero label) and of every engine (finite score) followed by real ids (row 3: that score enters the row minimum, and label and
+    raw score are what the pad columns report), +inf / -inf / NaN scores (row 4: `inf * 0.0` is NaN), an id repeated in the lookup
+    with different labels (row 5), one id in every segment and repeated inside two of them (row 6), an ordinary row (row 7);
+    weights 0.0, -1.5 and 2.0."""
+    x, hi32, hi40, big = 5, 5 + 2**32, 5 + 2**40, 2**62 + 1
+    inf, nan = np.inf, np.nan
+    lookup_idx = np.array([
+        [x, 11, 12, -1, -1, -1],
+        [hi40, x, 13, -1, -1, -1],
+        [21, -2, 22, -7, 23, -1],
+        [31, -1, 32, 33, -1, -1],
+        [41, 42, 43, -1, -1, -1],
+        [51, 52, 51, 53, 52, 51],
+        [61, 62, 63, -1, -1, -1],
+        [71, 72, 73, 74, -1, -1],
+    ], dtype=np.int64)
+    lookup_lbl = np.array([
+        [1, 2, 1, 0, 0, 0],
+        [1, 2, 3, 0, 0, 0],
+        [1, 5, 2, 6, 1, 0],
+        [1, 7, 2, 1, 0, 0],
+        [1, 1, 2, 0, 0, 0],
+        [1, 2, 3, 1, 4, 5],
+        [2, 1, 1, 0, 0, 0],
+        [1, 2, 1, 3, 0, 0],
+    ], dtype=np.int64)
+    lookup_scr = np.where(lookup_idx >= 0, 7.0, -inf).astype(np.float32)   # discarded by the reference (search.py:92)
+    e_idx = [
+        np.array([
+            [hi32, 14, 11, 15, -1, -1, -1, -1],
+            [x, hi32, hi40, big, hi32, 13, x, -1],
+            [-7, 24, 21, -2, 25, -1, -1, -1],
+            [34, 31, -1, 35, 32, -1, -1, -1],
+            [44, 41, 45, 46, 42, 47, -1, -1],
+            [52, 54, 51, 55, -1, -1, -1, -1],
+            [64, 61, 65, 61, 66, -1, -1, -1],
+            [75, 71, 76, 77, 78, 72, 79, 80],
+        ], dtype=np.int64),
+        np.array([
+            [hi40, 16, 14, x, 17, 12, -1, -1, -1, -1, -1, -1],
+            [big, 18, hi40, 19, hi32, -1, -1, -1, -1, -1, -1, -1],
+            [26, -2, -2, 24, 22, -7, 27, -1, -1, -1, -1, -1],
+            [-1, 36, 34, 33, 37, -1, -1, -1, -1, -1, -1, -1],
+            [48, 44, 43, 49, 40, 41, -1, -1, -1, -1, -1, -1],
+            [56, 51, 57, 52, 58, 59, 53, 50, 54, -1, -1, -1],
+            [61, 67, 64, 68, -1, -1, -1, -1, -1, -1, -1, -1],
+            [81, 82, 75, 83, 73, 84, 85, 86, 87, 88, 89, 90],
+        ], dtype=np.int64),
+        np.array([
+            [big, hi32, 18, -1, -1],
+            [hi32, x, -1, -1, -1],
+            [28, -7, 21, 26, -1],
+            [38, -1, 36, 31, -1],
+            [43, 39, 48, -1, -1],
+            [59, 52, -1, -1, -1],
+            [69, 61, 61, 61, 60],
+            [91, 81, 71, 92, 93],
+        ], dtype=np.int64),
+        np.array([
+            [x, hi32, big, 19, hi40, -1, -1],
+            [big, 13, hi40, -1, -1, -1, -1],
+            [-2, 29, 28, 25, -1, -1, -1],
+            [39, 38, 35, -1, 30, 32, -1],
+            [45, 49, 41, 20, -1, -1, -1],
+            [51, 50, -1, -1, -1, -1, -1],
+            [61, 69, 64, -1, -1, -1, -1],
+            [94, 93, 82, 72, 95, -1, -1],
+        ], dtype=np.int64),
+    ]
+    rng = np.random.default_rng(5150)
+    e_scr = []
+    for idx in e_idx:
+        scr = (rng.normal(size=idx.shape) * 3).astype(np.float32)
+        scr[idx == -1] = -inf            # pads, as an engine returns them ...
+        e_scr.append(scr)
+    e_scr[0][3, 2], e_scr[1][3, 0], e_scr[2][3, 1], e_scr[3][3, 3] = 0.25, -9.5, 1.5, -4.0   # ... but row 3: interior -1 with a FINITE score
+    e_scr[0][4, :6] = [inf, 1.0, -inf, nan, 2.5, inf]
+    e_scr[1][4, :6] = [nan, inf, 3.0, -inf, -1.0, nan]
+    e_scr[2][4, :3] = [inf, inf, nan]       # no finite score at all: the row minimum is +inf
+    e_scr[3][4, :4] = [-inf, 0.5, inf, nan]
+    names = ["e0", "e1", "e2", "e3"]
+    arrays = dict(lookup_idx=lookup_idx, lookup_scr=lookup_scr, lookup_lbl=lookup_lbl)
+    for n, i, sc in zip(names, e_idx, e_scr):
+        arrays[f"{n}_idx"], arrays[f"{n}_scr"] = i, sc
+    cases = {"one_engine": {"e1": -1.5}, "two_engines": {"e0": 2.0, "e2": 0.0}, "four_engines": {"e0": 0.0, "e1": -1.5, "e2": 2.0, "e3": 1.0}}
+    for name, w in cases.items():
+        res = {"lookup": RB(scores=lookup_scr.copy(), indices=lookup_idx.copy(), labels=lookup_lbl.copy())}
+        for n in w:
+            res[n] = RB(scores=arrays[f"{n}_scr"].copy(), indices=arrays[f"{n}_idx"].copy())
+        with np.errstate(all="ignore"):
+            merged, raw = M["search"]._merge_search_results(res, dict(w))
+        arrays[f"{name}_out_idx"], arrays[f"{name}_out_scr"], arrays[f"{name}_out_lbl"] = merged.indices, merged.scores, merged.labels
+        for e, r in raw.items():
+            arrays[f"{name}_raw_{e}"] = r
+    _save("merge_edges", {"cases": cases}, **arrays)
+
+
 # ----------------------------------------------------------------------------------------
 def gen_normalize() -> None:
     arrays = {}
@@ -633,8 +734,14 @@ if __name__ == "__main__":
         gen_merge_corners()
         (HERE / "manifest.json").write_text(json.dumps(manifest, indent=1, sort_keys=True))
         raise SystemExit(0)
+    if sys.argv[1:] == ["merge_edges"]:
+        manifest.update(json.loads((HERE / "manifest.json").read_text()))
+        gen_merge_edges()
+        (HERE / "manifest.json").write_text(json.dumps(manifest, indent=1, sort_keys=True))
+        raise SystemExit(0)
     gen_merge()
     gen_merge_corners()
+    gen_merge_edges()
     gen_normalize()
     gen_gather()
     gen_sampling()

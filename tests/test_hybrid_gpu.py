@@ -1,5 +1,6 @@
 """GPU parity tests for the hybrid score merge (H4): bit-exact against the golden vectors captured from
-the reference's own modules and against the CPU oracle on seeded random cases, through the C-ABI."""
+the reference's own modules and against the CPU oracle on seeded random cases, through the C-ABI.
+Exact widths, 64-bit ids, degenerate rows, the cursor-maxima path and raw ABI shapes: tests/test_hybrid_edges_gpu.py."""
 import json
 
 import numpy as np

@@ -86,6 +86,27 @@ def test_hybrid_merge_corner_cases_match_reference(case):
         _eq(raw[n], g[f"{case}_raw_{n}"])
 
 
+@pytest.mark.parametrize("case", ["one_engine", "two_engines", "four_engines"])
+def test_hybrid_merge_edge_inputs_match_reference(case):
+    """64-bit ids that differ only in the high word, ids -2 / -7, a -1 INSIDE a list with a label / a finite score (what the pad
+    columns then report, and part of the row minimum), +inf / -inf / NaN scores, zero and negative weights, a lookup id repeated with
+    different labels, one id in every segment: `merge_edges.npz`, from the reference's own `_merge_search_results`."""
+    g = _load("merge_edges")
+    w = MANIFEST["merge_edges"]["params"]["cases"][case]
+    engines = {n: (g[f"{n}_idx"], g[f"{n}_scr"]) for n in w}
+    idx, scr, lbl, raw = ohyb.merge_hybrid((g["lookup_idx"], g["lookup_scr"], g["lookup_lbl"]), engines, dict(w))
+    for got, name in ((idx, "out_idx"), (scr, "out_scr"), (lbl, "out_lbl")):
+        assert got.dtype == g[f"{case}_{name}"].dtype
+        _eq(got, g[f"{case}_{name}"])
+    assert set(raw) == set(w)
+    for n in w:
+        assert raw[n].dtype == np.float32
+        _eq(raw[n], g[f"{case}_raw_{n}"])
+    # the fixture is only worth its name if the ids it is about survived into the reference's output
+    assert {5, 5 + 2**32, 5 + 2**40, 2**62 + 1} <= set(g[f"{case}_out_idx"][1].tolist())
+    assert not (g[f"{case}_out_idx"] < -1).any()
+
+
 def test_normalize_matches_reference():
     g = _load("normalize")
     p = MANIFEST["normalize"]["params"]

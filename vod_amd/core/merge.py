@@ -59,10 +59,15 @@ def merge_hybrid_device(
     lookup_lbl: torch.Tensor | None,
     engines: dict[str, tuple[torch.Tensor, torch.Tensor]],
     weights: dict[str, float],
+    cursors: str = "auto",
 ) -> MergedOnDevice:
     """Device-tensor API without any host synchronisation: ONE launch, outputs left at full stride.
 
-    lookup_idx int64 [nq, kl]; engines[name] = (idx int64 [nq, k], scores f32 [nq, k])."""
+    lookup_idx int64 [nq, kl]; engines[name] = (idx int64 [nq, k], scores f32 [nq, k]).
+    `cursors`: how the per-stage cursors that fix the cut width are returned - "per_row" (`row_cursor` [nq, MAX_ENGINES], plain
+    stores), "max" (`stage_max` [MAX_ENGINES], cleared on the stream + atomics) or "auto": per row up to 4096 rows, maxima above."""
+    if cursors not in ("auto", "per_row", "max"):
+        raise ValueError(f"cursors must be 'auto', 'per_row' or 'max', got {cursors!r}")
     lib = _native.load_library()
     dev = lookup_idx.device
     if dev.type != "cuda":
@@ -91,8 +96,8 @@ def merge_hybrid_device(
     out_raw = [torch.empty((nq, stride), dtype=torch.float32, device=dev) for _ in names]
     # the per-stage cursors that fix the reference's cut width: per row (plain stores, ONE launch; the sampling kernel takes
     # the maximum) - or, for very tall batches, the maxima themselves (cleared by the library on the stream + atomics)
-    per_row = nq <= 4096
-    cursors = torch.empty((nq, _native.MAX_ENGINES) if per_row else (_native.MAX_ENGINES,), dtype=torch.int32, device=dev)
+    per_row = nq <= 4096 if cursors == "auto" else cursors == "per_row"
+    cur = torch.empty((nq, _native.MAX_ENGINES) if per_row else (_native.MAX_ENGINES,), dtype=torch.int32, device=dev)
 
     n_e = len(names)
     VP = ctypes.c_void_p
@@ -107,12 +112,12 @@ def merge_hybrid_device(
                 lookup_idx.data_ptr(), lookup_lbl.data_ptr() if lookup_lbl is not None else None, kl, n_e,
                 arr_idx, arr_scr, arr_k, arr_w, nq,
                 out_idx.data_ptr(), out_scr.data_ptr(), out_lbl.data_ptr() if out_lbl is not None else None,
-                arr_raw, stride, None if per_row else cursors.data_ptr(), cursors.data_ptr() if per_row else None,
+                arr_raw, stride, None if per_row else cur.data_ptr(), cur.data_ptr() if per_row else None,
                 _native.current_stream_ptr(dev),
             )
         )
-    return MergedOnDevice(out_idx, out_scr, out_lbl, dict(zip(names, out_raw)), None if per_row else cursors, int(kl), ks,
-                          cursors if per_row else None)
+    return MergedOnDevice(out_idx, out_scr, out_lbl, dict(zip(names, out_raw)), None if per_row else cur, int(kl), ks,
+                          cur if per_row else None)
 
 
 def merge_hybrid_tensors(

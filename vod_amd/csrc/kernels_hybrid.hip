@@ -29,6 +29,7 @@
 // (< 1 MB per batch); it is deliberately not shaped into a GEMM.
 #include <cstdlib>
 
+#include "hybrid_plan.h"
 #include "vodhip_internal.h"
 
 namespace vodhip {
@@ -46,8 +47,7 @@ __device__ long long g_probe_hybrid[256];
 #define HY_PROBE(i) VODHIP_PROBE(g_probe_hybrid, i)
 #endif
 
-constexpr int HY_THREADS = 512;  // 8 wavefronts: one entry per thread up to W = 512 (the probes are latency chains: width beats depth)
-constexpr int HY_WAVES = HY_THREADS / 64;
+// HY_THREADS, HY_WAVES: hybrid_plan.h (the LDS footprint depends on them)
 constexpr int HY_MAX_SEG = 5;  // lookup + VODHIP_MAX_ENGINES
 typedef unsigned long long hy_u64;
 constexpr hy_u64 HY_EMPTY = ~0ull;
@@ -350,12 +350,10 @@ hipError_t launch_merge_hybrid(const HybridArgs& a, hipStream_t stream) {
     if (a.nq == 0) return hipSuccess;
     int W = a.k_lookup;
     for (int i = 0; i < a.n_engines; ++i) W += a.engine_k[i];
-    // load factor <= 1/4 where LDS allows it (short probe chains: a wavefront waits for its longest one), never above 1/2
-    int T = 64;
-    while (T < 4 * W) T <<= 1;
-    const size_t fixed = (size_t)W * (8 + 4 + 4) + (size_t)(W + 1) * 4 + HY_WAVES * 4 * 4 + (HY_WAVES + 1) * 4 + 16;
-    while (fixed + (size_t)T * 9 > 150 * 1024 && T > 2 * W) T >>= 1;
-    const size_t lds = fixed + (size_t)T * 9;
+    // table size and LDS footprint: hybrid_plan.h (load factor <= 1/4 where that fits its cap, never above 1/2)
+    const HybridPlan plan = hybrid_plan(W);
+    const int T = plan.T;
+    const size_t lds = plan.lds;
     if (lds > 64 * 1024) {
         hipError_t e = allow_dynamic_lds((const void*)merge_hybrid_kernel, (int)lds);
         if (e != hipSuccess) return e;
