@@ -32,6 +32,8 @@ def parse_args() -> argparse.Namespace:
     p.add_argument("--n_trials", type=int, default=10)
     # extensions of this engine (absent in the reference's script)
     p.add_argument("--devices", type=str, default=None, help="comma-separated GPU ids: row-shard the store over them behind one address")
+    p.add_argument("--metric", type=str, default="inner_product", choices=["inner_product", "l2"],
+                   help="the reference's FaissFactoryConfig.metric: l2 = squared L2 distances, ascending (single device)")
     p.add_argument("--binary", action="store_true", help="use the raw-bytes route instead of the reference's base64-in-JSON")
     return p.parse_args()
 
@@ -41,7 +43,7 @@ def run(args: argparse.Namespace) -> None:
     with tempfile.TemporaryDirectory() as tmpdir:
         # Build the index: the store file the server streams into HBM (the reference builds, writes and re-reads a faiss file here)
         devices = None if args.devices is None else [int(d) for d in args.devices.split(",")]
-        master = factory.build_hip_mips_index(vectors, config={"logging_level": "warning"}, cache_dir=tmpdir, devices=devices)
+        master = factory.build_hip_mips_index(vectors, config={"logging_level": "warning", "metric": args.metric}, cache_dir=tmpdir, devices=devices)
         # Spin up the server
         with master:
             client = master.get_client()

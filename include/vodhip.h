@@ -17,6 +17,7 @@
  *   - result layout everywhere: scores float32 [nq,k] sorted descending, ids int64 [nq,k],
  *     ties -> smaller id first, missing entries padded with score -inf / id -1
  *     (the repo-wide padding convention, src/vod_types/retrieval.py:284-285).
+ *     A VODHIP_L2 index returns squared L2 distances instead: sorted ASCENDING, ties -> smaller id, pads +inf / -1 (see VODHIP_L2).
  */
 #ifndef VODHIP_H
 #define VODHIP_H
@@ -38,6 +39,24 @@ enum { VODHIP_F16 = 0, VODHIP_BF16 = 1, VODHIP_F32 = 2 };
  * during re-scoring: 64 KB at the limit); vodhip_index_create refuses a wider one ("VODHIP_EXACT_F32 stores take dim <= 16384").
  * A plain store has no width limit of its own (tested up to dim 16384). */
 #define VODHIP_EXACT_F32 0x100
+/* OR-ed into the store dtype at create: the index ranks by SQUARED L2 DISTANCE (faiss.index_factory(D, "Flat", METRIC_L2): the
+ * reference's FaissFactoryConfig.metric = "l2", src/vod_configs/search.py:21-27,143-149, faiss_search/build.py:60).
+ * |q - x|^2 = |q|^2 - 2 (q.x - |x|^2 / 2): every row keeps c = -|x~|^2 / 2 behind its `dim` values, split into three store-dtype
+ * terms; the queries are staged with three power-of-two constants behind theirs; the inner-product scan over dim + 3 columns then
+ * searches L2 unchanged and one launch turns its scores into distances ("L2 metric").
+ *   - the store keeps rows of dim + 3 columns, padded to a multiple of 64: vodhip_index_data's stride includes the bias columns;
+ *     vodhip_index_dim, vodhip_index_get_rows and vodhip_index_add speak the user's `dim`;
+ *   - SEARCH CONTRACT: out_scores are squared L2 distances of the stored (rounded) rows and the rounded queries, sorted ASCENDING,
+ *     ties -> smaller id, clamped at 0; pads are (+inf, -1).  faiss pads L2 results with +FLT_MAX: a documented deviation, like the
+ *     -inf pad of the inner-product side.  id_base, the subset labels, "lanes", four searches in flight and the overflow recovery
+ *     passes work as for inner product.  Two rows whose float32 similarity scores differ may round to the same distance: inside
+ *     such a tie the order is that of the similarity score;
+ *   - a row with |x~|^2 beyond the split's limit (fp16: 33538048, just under 2^25; bf16: 2^121) cannot carry its bias: the bias
+ *     saturates at the limit - the row ranks behind every row within the limit unless q.x~ alone reaches the limit (|q~| |x~| >=
+ *     1.6e7 for fp16) - and stat "l2_saturated_rows" counts it: a store that reports 0 has no such row;
+ *   - REFUSED, each with its own vodhip_last_error: VODHIP_L2 | VODHIP_EXACT_F32, vodhip_index_score_ids / _search_ids on an L2
+ *     index, vodhip_node_index_create with the flag. */
+#define VODHIP_L2 0x200
 /* where a caller buffer lives */
 enum { VODHIP_HOST = 0, VODHIP_DEVICE = 1 };
 
@@ -48,13 +67,13 @@ int vodhip_version(void);
 
 /* ---------------------------------------------------------------------------------------------
  * H1  corpus vector store.
- * Replaces: faiss.index_factory(D, "Flat", METRIC_INNER_PRODUCT) + index.add(float32 batch)
+ * Replaces: faiss.index_factory(D, "Flat", METRIC_INNER_PRODUCT | METRIC_L2 with VODHIP_L2) + index.add(float32 batch)
  *           (src/vod_search/faiss_search/build.py:51-81) and the faiss.write_index/read_index
  *           round trip (src/vod_search/factory.py:167, src/vod_search/faiss_search/server.py:42).
  * The store is a row-major [capacity, dim_padded] fp16/bf16 matrix in HBM on `device`
  * (dim padded with zeros to a multiple of 64).  Rows get ids 0,1,2,... in insertion order.
  * ------------------------------------------------------------------------------------------- */
-int vodhip_index_create(int device, int64_t dim, int store_dtype /* VODHIP_F16 | VODHIP_BF16, optionally | VODHIP_EXACT_F32 */,
+int vodhip_index_create(int device, int64_t dim, int store_dtype /* VODHIP_F16 | VODHIP_BF16, optionally | VODHIP_EXACT_F32 or | VODHIP_L2 */,
                         int64_t capacity_rows, vodhip_index_t** out);
 int vodhip_index_destroy(vodhip_index_t* index);
 
@@ -70,7 +89,8 @@ int vodhip_index_reset(vodhip_index_t* index);               /* ntotal := 0 (cap
 int vodhip_index_ntotal(const vodhip_index_t* index, int64_t* out);
 int vodhip_index_dim(const vodhip_index_t* index, int64_t* out);
 int vodhip_index_capacity(const vodhip_index_t* index, int64_t* out);
-/* raw view of the store (device pointer, row stride in elements) for persistence / tests */
+/* raw view of the store (device pointer, row stride in elements) for persistence / tests; the stride of a VODHIP_L2 store
+ * includes its three bias columns (columns [dim, dim + 3) of every row), then the zero padding */
 int vodhip_index_data(const vodhip_index_t* index, void** dev_ptr, int64_t* row_stride_elems, int* store_dtype);
 /* copy rows [row_begin, row_begin + n_rows) of the store, as stored (fp16/bf16, unpadded [n_rows, dim]),
  * to `dst` in host or device memory; async on `stream` for device destinations. */
@@ -189,7 +209,9 @@ int vodhip_index_set_query_labels(vodhip_index_t* index, const int32_t* q_labels
  *   with survivors that did not fit into those rings and took the in-loop path, first pass), "last_filter_launches", "last_filter_ns" (with "profile"), "last_recovery_launches",
  *   "last_recovery_ns" (the filter launches of the recovery passes, accounted separately); "exact" (1 for a VODHIP_EXACT_F32 store),
  *   "last_exact_kx" (k' of the last search), "last_exact_band_queries" (queries whose list did not prove complete and ran a band
- *   pass), "last_exact_band_passes". */
+ *   pass), "last_exact_band_passes"; "l2" (1 for a VODHIP_L2 store), "l2_saturated_rows" (rows ingested since create / reset whose
+ *   bias saturated; reading it waits for the device), "last_l2_stage_ns" / "last_l2_finish_ns" (with "profile": HIP events around the
+ *   query staging launch and the finish launch of the first pass). */
 int vodhip_index_set_param(vodhip_index_t* index, const char* key, int64_t value);
 /* Host-side planning only (no device and no HIP runtime call): the stage list a search of `nq` queries for the top `k` of
  * `ntotal` rows would run on a device with `n_cu` compute units (<= 0 = 256, the MI355X), with the given tunables (<= 0 =
@@ -200,6 +222,12 @@ int vodhip_index_set_param(vodhip_index_t* index, const char* key, int64_t value
 int vodhip_debug_schedule(int64_t ntotal, int k, int64_t nq, int64_t cand_cap, int64_t dense_rows, int64_t sample_div,
                           int64_t growth_x100, int tile, int recovery_pass, int n_cu, int64_t* out, int max_stages);
 int vodhip_index_get_stat(const vodhip_index_t* index, const char* key, int64_t* out);
+/* Host-side arithmetic only (no HIP call): the bias split of a VODHIP_L2 store (vod_amd/csrc/l2_bias.h).  c = -|x~|^2 / 2 as a
+ * float32 -> terms[3] = the store-dtype bits kept in the row's bias columns, consts[3] = the query constants (powers of two) they
+ * meet: sum_i consts[i] * value(terms[i]) = c within 2^-28 (fp16) / 2^-126 (bf16), exactly for every half-integer within the limit;
+ * no term and no constant is subnormal in the store dtype.  Returns 1 when the bias saturated (|c| beyond the limit, or not
+ * finite), 0 otherwise, -1 for invalid arguments. */
+int vodhip_debug_l2_split(float c, int dtype, uint16_t terms[3], float consts[3]);
 /* Host-side planning only: the order in which a search's FILTER stages walk the 256-row tiles of a store of `ntotal` rows - position p
  * (stages are runs of consecutive positions) is tile (p * perm_mul) mod perm_mod; perm_mul <= 1 = positions are tiles (small stores). */
 int vodhip_debug_tile_order(int64_t ntotal, int64_t* perm_mul, int64_t* perm_mod);

@@ -15,6 +15,14 @@ _lib: ctypes.CDLL | None = None
 
 F16, BF16, F32 = 0, 1, 2
 EXACT_F32 = 0x100  # VODHIP_EXACT_F32: OR-ed into the store dtype at create
+L2 = 0x200  # VODHIP_L2: OR-ed into the store dtype at create - the index ranks by squared L2 distance
+METRICS = {"inner_product": 0, "l2": L2}  # `metric=` of the Python indexes -> the flag
+
+
+def metric_flag(metric: str) -> int:
+    if metric not in METRICS:
+        raise ValueError(f"metric must be one of {sorted(METRICS)}, got {metric!r}")
+    return METRICS[metric]
 HOST, DEVICE = 0, 1
 MAX_K = 2048
 MAX_LISTED = 8192  # VODHIP_MAX_LISTED: slots per query of the top-k form of `score_ids`
@@ -62,6 +70,7 @@ SIGNATURES: dict[str, tuple] = {
     "vodhip_index_set_param": (_i32, [_vp, _c.c_char_p, _i64]),
     "vodhip_debug_schedule": (_i32, [_i64, _i32, _i64, _i64, _i64, _i64, _i64, _i32, _i32, _i32, _c.POINTER(_i64), _i32]),
     "vodhip_index_get_stat": (_i32, [_vp, _c.c_char_p, _c.POINTER(_i64)]),
+    "vodhip_debug_l2_split": (_i32, [_c.c_float, _i32, _c.POINTER(_c.c_uint16), _c.POINTER(_c.c_float)]),
     "vodhip_debug_tile_order": (_i32, [_i64, _c.POINTER(_i64), _c.POINTER(_i64)]),
     "vodhip_debug_read_probe": (_i32, [_i32, _c.POINTER(_i64), _i32]),
     "vodhip_node_index_create": (_i32, [_i32, _c.POINTER(_i32), _i64, _i32, _i64, _c.POINTER(_vp)]),

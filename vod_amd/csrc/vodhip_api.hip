@@ -15,6 +15,7 @@
 #include <thread>
 #include <vector>
 
+#include "l2_bias.h"
 #include "search_plan.h"
 #include "vodhip_internal.h"
 
@@ -71,6 +72,7 @@ struct PendingSearch {
     bool band = false;             // exact mode: a BAND pass - candidates are re-scored into the caller's rows (kernels_exact.hip)
     bool defer_flags = false;      // exact mode: the flag words are fetched (and the slot's event recorded) behind the re-scoring launch
     int lane = 0;                  // which of the index's two workspaces / streams this search runs on (1 = the index's own stream)
+    float* l2_out = nullptr;       // L2 store: the caller's out_scores (out_scores above is the slot's similarity-form buffer, queries its staged copy)
 };
 
 constexpr int FLAG_WORDS = 4;     // flag words of a workspace / of a slot's host copy ([3]: blocks that missed the survivor rings)
@@ -82,6 +84,7 @@ constexpr int64_t OVF_ROWS = 65536;  // per-query overflow flags are kept for ba
 struct vodhip_index {
     int device = 0;
     int64_t dim = 0, dim_pad = 0;
+    int64_t dim_s = 0;               // columns a search contracts over: dim, or dim + 3 for an L2 store (the bias columns, l2_bias.h)
     int64_t capacity = 0, capacity_pad = 0;
     int64_t ntotal = 0;
     int dtype = VODHIP_F16;
@@ -114,6 +117,16 @@ struct vodhip_index {
     unsigned int* x_flag_q = nullptr;        // device [MAX_IN_FLIGHT][OVF_ROWS]: the queries whose list did not prove complete
     int64_t exact_expand_x100 = 0;           // k' = k * this / 100 (+ 16); 0 = by store dtype (fp16: 110, bf16: 200)
     int64_t last_exact_kx = 0, last_exact_band_queries = 0, last_exact_band_passes = 0;
+    // VODHIP_L2 (kernels_l2.hip): rows carry three bias columns behind the user's dim; per in-flight slot the staged queries
+    // [nq][dim + 3], their squared norms and the search's similarity-form scores [nq][k] (the recovery passes seed from them)
+    bool l2 = false;
+    unsigned int* l2_sat = nullptr;          // device word: rows whose bias saturated since create / reset
+    uint16_t* l2_q[4] = {nullptr, nullptr, nullptr, nullptr};
+    float* l2_qn[4] = {nullptr, nullptr, nullptr, nullptr};
+    float* l2_sim[4] = {nullptr, nullptr, nullptr, nullptr};
+    size_t l2_q_cap[4] = {0, 0, 0, 0}, l2_qn_cap[4] = {0, 0, 0, 0}, l2_sim_cap[4] = {0, 0, 0, 0};  // elements
+    hipEvent_t l2_ev[4][4] = {};             // with "profile": per slot, (start, stop) around the staging and around the finish launch
+    int64_t last_l2_stage_ns = 0, last_l2_finish_ns = 0;
     // Two LANES: workspace 0 is used on the caller's stream; workspace 1 on a stream of the index's own, so that two consecutive searches
     // of a caller that runs one search ahead (the bench, the batcher) overlap on the device: while one search's select / prepare launches
     // and the partly filled last round of its stage leave CUs idle, the other search's FILTER workgroups take them.  Used for batches of
@@ -338,7 +351,7 @@ int enqueue_search_impl(vodhip_index* ix, const PendingSearch& ps, bool safe, in
         const int64_t row0 = ps.q_map ? 0 : qb;
         W.ovf_q = track_ovf ? ix->ovf_q + (size_t)ps.slot * OVF_ROWS + qb : nullptr;
         const float* margin = ps.band ? ix->x_eps + (size_t)ps.slot * OVF_ROWS + row0 : nullptr;  // BAND pass: seeded k-th exact score - eps
-        HIP_OK(launch_search_prepare(ws, (const char*)ps.queries + (size_t)row0 * ix->dim * q_es, ps.q_dtype, nq, ix->dim,
+        HIP_OK(launch_search_prepare(ws, (const char*)ps.queries + (size_t)row0 * ix->dim_s * q_es, ps.q_dtype, nq, ix->dim_s,
                                      ix->dtype, nq_pad, ix->dim_pad, qb == 0, recovery > 0 ? ps.out_scores + row0 * k : nullptr,
                                      recovery > 0 ? ps.out_ids + row0 * k : nullptr, k, q_map, stream, margin));
         W.extra.q_label = ps.q_label ? ps.q_label + (size_t)row0 * ps.n_qlab : nullptr;
@@ -447,6 +460,33 @@ int exact_reserve_lists(vodhip_index* ix, int slot, size_t elems) {
     return 0;
 }
 
+// ---- L2 stores (kernels_l2.hip) --------------------------------------------------------------------------------------------
+// grow-only; a slot's buffers are idle when it is handed out again (its previous search was finished)
+template <typename T>
+int l2_reserve(T*& buf, size_t& cap, size_t elems) {
+    if (cap >= elems) return 0;
+    (void)hipFree(buf);
+    buf = nullptr;
+    cap = 0;
+    HIP_OK(hipMalloc((void**)&buf, elems * sizeof(T)));
+    cap = elems;
+    return 0;
+}
+
+// with "profile": the event `which` of the slot (0 / 1 around the staging launch, 2 / 3 around the first finish launch), recorded now
+int l2_profile_mark(vodhip_index* ix, int slot, int which, hipStream_t stream) {
+    if (!ix->profile) return 0;
+    if (!ix->l2_ev[slot][which]) HIP_OK(hipEventCreate(&ix->l2_ev[slot][which]));
+    HIP_OK(hipEventRecord(ix->l2_ev[slot][which], stream));
+    return 0;
+}
+
+// similarity form -> squared distances in the caller's rows, from the slot's buffers: behind the first pass, and again after recovery
+int enqueue_l2_finish(vodhip_index* ix, const PendingSearch& ps, hipStream_t stream) {
+    HIP_OK(launch_l2_finish(ix->l2_sim[ps.slot], ix->l2_qn[ps.slot], ps.nq, ps.k, ps.l2_out, stream));
+    return 0;
+}
+
 }  // namespace
 
 extern "C" {
@@ -458,15 +498,19 @@ int vodhip_index_create(int device, int64_t dim, int store_dtype, int64_t capaci
     if (!out) return fail("out is NULL");
     if (dim <= 0 || capacity_rows < 0) return fail("invalid dim=%lld / capacity=%lld", (long long)dim, (long long)capacity_rows);
     const bool exact = (store_dtype & VODHIP_EXACT_F32) != 0;
-    store_dtype &= ~VODHIP_EXACT_F32;
-    if (store_dtype != VODHIP_F16 && store_dtype != VODHIP_BF16) return fail("store dtype must be F16 or BF16 (optionally | VODHIP_EXACT_F32)");
+    const bool l2 = (store_dtype & VODHIP_L2) != 0;
+    store_dtype &= ~(VODHIP_EXACT_F32 | VODHIP_L2);
+    if (store_dtype != VODHIP_F16 && store_dtype != VODHIP_BF16) return fail("store dtype must be F16 or BF16 (optionally | VODHIP_EXACT_F32 or | VODHIP_L2)");
+    if (l2 && exact) return fail("VODHIP_L2 | VODHIP_EXACT_F32 is not supported: an L2 store scores the rounded rows (DESIGN.md 8)");
     if (exact && (dim + 63) / 64 * 64 > 16384) return fail("VODHIP_EXACT_F32 stores take dim <= 16384");
     if (capacity_rows >= (1ll << 31) - 2 * ROW_ALIGN) return fail("capacity must be < 2^31 rows per device");
     HIP_OK(hipSetDevice(device));
     vodhip_index* ix = new vodhip_index();
     ix->device = device;
     ix->dim = dim;
-    ix->dim_pad = round_up(dim, 64);
+    ix->l2 = l2;
+    ix->dim_s = l2 ? dim + L2_BIAS_COLS : dim;
+    ix->dim_pad = round_up(ix->dim_s, 64);
     ix->capacity = capacity_rows;
     ix->capacity_pad = round_up(capacity_rows, ROW_ALIGN) + 2 * ROW_ALIGN;  // the last tile (up to 384 rows from a 256-aligned start) never reads past the allocation
     ix->dtype = store_dtype;
@@ -489,6 +533,9 @@ int vodhip_index_create(int device, int64_t dim, int store_dtype, int64_t capaci
     for (int i = 0; i < MAX_IN_FLIGHT && e == hipSuccess; ++i) e = hipEventCreateWithFlags(&ix->done[i], hipEventDisableTiming);
     for (int i = 0; i < MAX_IN_FLIGHT && e == hipSuccess; ++i) e = hipEventCreateWithFlags(&ix->lane_in[i], hipEventDisableTiming);
     if (e == hipSuccess) e = hipStreamCreateWithFlags(&ix->lane_stream, hipStreamNonBlocking);
+    if (l2 && e == hipSuccess) e = hipMalloc((void**)&ix->l2_sat, sizeof(unsigned int));
+    if (l2 && e == hipSuccess) e = hipMemset(ix->l2_sat, 0, sizeof(unsigned int));
+    if (l2 && e == hipSuccess) e = hipStreamSynchronize(nullptr);
     if (exact && e == hipSuccess) {
         // the float32 plane (rows are written whole, zero padded columns included: no fill needed) + the bound's bookkeeping
         const size_t bytes32 = ((size_t)capacity_rows + 1) * ix->dim_pad * sizeof(float);
@@ -514,6 +561,7 @@ int vodhip_index_create(int device, int64_t dim, int store_dtype, int64_t capaci
         (void)hipGetLastError();
         (void)hipFree(ix->data);
         (void)hipFree(ix->data32);
+        (void)hipFree(ix->l2_sat);
         delete ix;
         return fail("store initialisation failed: %s", hipGetErrorString(e));
     }
@@ -550,6 +598,15 @@ int vodhip_index_destroy(vodhip_index_t* ix) {
         (void)hipFree(ix->x_list_s[i]);
         (void)hipFree(ix->x_list_i[i]);
     }
+    (void)hipFree(ix->l2_sat);
+    for (int i = 0; i < MAX_IN_FLIGHT; ++i)
+        for (hipEvent_t e : ix->l2_ev[i])
+            if (e) (void)hipEventDestroy(e);
+    for (int i = 0; i < MAX_IN_FLIGHT; ++i) {
+        (void)hipFree(ix->l2_q[i]);
+        (void)hipFree(ix->l2_qn[i]);
+        (void)hipFree(ix->l2_sim[i]);
+    }
     (void)hipFree(ix->row_label);
     (void)hipFree(ix->ovf_q);
     (void)hipFree(ix->q_map);
@@ -575,7 +632,11 @@ int vodhip_index_add(vodhip_index_t* ix, const void* rows, int64_t n_rows, int s
             return launch_ingest_exact(dev_src, src_dtype, n, ix->dim, ix->data + (size_t)first_row * ix->dim_pad, ix->dtype,
                                        ix->data32 + (size_t)first_row * ix->dim_pad, ix->dim_pad, ix->norm_stats, ix->row_n2 + first_row,
                                        ix->row_d2 + first_row, stream);
-        return launch_convert_rows(dev_src, src_dtype, n, ix->dim, ix->data + (size_t)first_row * ix->dim_pad, ix->dtype, ix->dim_pad, stream);
+        hipError_t e = launch_convert_rows(dev_src, src_dtype, n, ix->dim, ix->data + (size_t)first_row * ix->dim_pad, ix->dtype, ix->dim_pad, stream);
+        // L2 store: the bias columns, from the values as stored (one more launch per slice, behind the conversion)
+        if (e == hipSuccess && ix->l2)
+            e = launch_l2_bias(ix->data + (size_t)first_row * ix->dim_pad, ix->dtype, n, ix->dim, ix->dim_pad, ix->l2_sat, stream);
+        return e;
     };
     if (src_location == VODHIP_DEVICE) {
         HIP_OK(ingest(rows, n_rows, ix->ntotal));
@@ -647,6 +708,12 @@ int vodhip_index_reset(vodhip_index_t* ix) {
         HIP_OK(hipStreamSynchronize(nullptr));
         ix->stats_dirty = true;
         ix->adapt_k = ix->adapt_kx = 0;
+    }
+    if (ix->l2) {  // the saturation count starts over with the store
+        HIP_OK(hipSetDevice(ix->device));
+        HIP_OK(hipDeviceSynchronize());
+        HIP_OK(hipMemset(ix->l2_sat, 0, sizeof(unsigned int)));
+        HIP_OK(hipStreamSynchronize(nullptr));
     }
     ix->ntotal = 0;
     return 0;
@@ -792,7 +859,31 @@ int vodhip_index_search_async(vodhip_index_t* ix, const void* queries, int q_dty
     }
     if (ix->inflight.empty() && ix->unfinished == 0) ix->ev_used = 0;  // profile events are recycled once nothing refers to them
     ps.ev_begin = ix->ev_used;
-    if (ix->exact && nq > 0) {
+    if (ix->l2 && nq > 0) {
+        // L2 store: ONE staging launch (rounded queries + the three constants, |q~|^2), the unchanged search over dim + 3 columns
+        // into the slot's similarity-form buffer, ONE finish launch into the caller's scores, then the flag words: no host round trip
+        if (l2_reserve(ix->l2_q[ps.slot], ix->l2_q_cap[ps.slot], (size_t)nq * ix->dim_s)) return -1;
+        if (l2_reserve(ix->l2_qn[ps.slot], ix->l2_qn_cap[ps.slot], (size_t)nq)) return -1;
+        if (l2_reserve(ix->l2_sim[ps.slot], ix->l2_sim_cap[ps.slot], (size_t)nq * k)) return -1;
+        if (l2_profile_mark(ix, ps.slot, 0, stream)) return -1;
+        HIP_OK(launch_l2_stage_queries(queries, q_dtype, nq, ix->dim, ix->dtype, ix->l2_q[ps.slot], ix->l2_qn[ps.slot], stream));
+        if (l2_profile_mark(ix, ps.slot, 1, stream)) return -1;
+        ps.queries = ix->l2_q[ps.slot];
+        ps.q_dtype = ix->dtype;
+        ps.l2_out = out_scores;
+        ps.out_scores = ix->l2_sim[ps.slot];
+        PendingSearch first = ps;
+        first.defer_flags = true;  // the flag words travel behind the finish launch
+        if (enqueue_search(ix, first, ix->force_safe != 0, 0, stream)) return -1;
+        const SearchWorkspace& ws = ix->ws_lane[ps.lane];
+        if (l2_profile_mark(ix, ps.slot, 2, stream) || enqueue_l2_finish(ix, ps, stream) || l2_profile_mark(ix, ps.slot, 3, stream) ||
+            hipMemcpyAsync(ix->overflow_host + FLAG_WORDS * ps.slot, ws.overflow, FLAG_WORDS * sizeof(unsigned int), hipMemcpyDeviceToHost, stream) != hipSuccess ||
+            hipEventRecord(ix->done[ps.slot], stream) != hipSuccess) {
+            (void)hipGetLastError();
+            (void)hipStreamSynchronize(stream);
+            return fail("enqueueing the L2 finish failed");
+        }
+    } else if (ix->exact && nq > 0) {
         // exact mode: the scan fills the slot's top-k' list, the re-scoring kernel behind it writes the caller's rows (no host round
         // trip in between: the list is re-scored even if it later turns out that a candidate list overflowed - finish repeats it then)
         const int kx_formula = exact_kx(ix, k);
@@ -910,7 +1001,14 @@ int vodhip_index_search_finish(vodhip_index_t* ix, void* stream_) {
         if (ix->adapt_kx < target) ix->adapt_kx = target;
     }
     if (ps.nq > 0 && ps.kx == 0) {
-        if (recover_overflow(ix, ps, stream) < 0) return -1;
+        const int passes = recover_overflow(ix, ps, stream);
+        if (passes < 0) return -1;
+        if (passes > 0 && ps.l2_out) {
+            // L2 store: the recovery passes seeded from, and rewrote, the similarity-form buffer; the caller's rows are converted
+            // from it again, whole (never from the distances the first conversion wrote)
+            if (enqueue_l2_finish(ix, ps, stream)) return -1;
+            HIP_OK(hipStreamSynchronize(stream));
+        }
     } else if (ps.nq > 0) {
         // exact mode.  (1) the scan's own exactness: a recovered list is re-scored again (the first re-scoring saw the incomplete one)
         const int passes = recover_overflow(ix, exact_inner(ix, ps), stream);
@@ -954,6 +1052,14 @@ int vodhip_index_search_finish(vodhip_index_t* ix, void* stream_) {
             }
         }
     }
+    ix->last_l2_stage_ns = ix->last_l2_finish_ns = 0;
+    if (ps.l2_out && ps.nq > 0 && ix->profile && ix->l2_ev[ps.slot][0] && ix->l2_ev[ps.slot][3]) {
+        float ms = 0.f;
+        HIP_OK(hipEventElapsedTime(&ms, ix->l2_ev[ps.slot][0], ix->l2_ev[ps.slot][1]));
+        ix->last_l2_stage_ns = (int64_t)((double)ms * 1e6);
+        HIP_OK(hipEventElapsedTime(&ms, ix->l2_ev[ps.slot][2], ix->l2_ev[ps.slot][3]));
+        ix->last_l2_finish_ns = (int64_t)((double)ms * 1e6);
+    }
     ix->last_filter_launches = (int64_t)((ps.ev_end - ps.ev_begin) / 2);
     ix->last_filter_ns = 0;
     for (size_t e = ps.ev_begin; e + 1 < ps.ev_end; e += 2) {
@@ -976,6 +1082,7 @@ int vodhip_index_search(vodhip_index_t* ix, const void* queries, int q_dtype, in
 static int listed_check(vodhip_index_t* ix, const void* queries, int q_dtype, int64_t nq, const int64_t* ids_dev, int64_t m,
                         const int32_t* q_labels_dev, int n_per_query) {
     if (!ix) return fail("index is NULL");
+    if (ix->l2) return fail("listed ids are not supported on an L2 index (VODHIP_L2): score_ids / search_ids need an inner-product store");
     if (m < 1) return fail("m=%lld: a list holds at least one slot", (long long)m);
     if (nq < 0 || (nq > 0 && (!queries || !ids_dev))) return fail("invalid query / id pointers");
     if (q_dtype < 0 || q_dtype > 2) return fail("invalid q_dtype %d", q_dtype);
@@ -1147,7 +1254,21 @@ int vodhip_index_get_stat(const vodhip_index_t* ix, const char* key, int64_t* ou
         *out = ix->last_recovery_ns;
     else if (!strcmp(key, "exact"))
         *out = ix->exact ? 1 : 0;
-    else if (!strcmp(key, "last_exact_kx"))
+    else if (!strcmp(key, "l2"))
+        *out = ix->l2 ? 1 : 0;
+    else if (!strcmp(key, "last_l2_stage_ns"))
+        *out = ix->last_l2_stage_ns;
+    else if (!strcmp(key, "last_l2_finish_ns"))
+        *out = ix->last_l2_finish_ns;
+    else if (!strcmp(key, "l2_saturated_rows")) {  // (waits for the device: ingests on any stream have counted)
+        unsigned int w = 0;
+        if (ix->l2) {
+            HIP_OK(hipSetDevice(ix->device));
+            HIP_OK(hipDeviceSynchronize());
+            HIP_OK(hipMemcpy(&w, ix->l2_sat, sizeof(w), hipMemcpyDeviceToHost));
+        }
+        *out = (int64_t)w;
+    } else if (!strcmp(key, "last_exact_kx"))
         *out = ix->last_exact_kx;
     else if (!strcmp(key, "last_exact_need"))
         *out = ix->last_exact_need;

@@ -212,6 +212,17 @@ hipError_t launch_combine_listed(const float* parts, const int64_t* ids, int64_t
 hipError_t launch_select_listed(const float* scores, const int64_t* ids, int64_t nq, int64_t m, int k, int64_t id_base, float* out_scores,
                                 int64_t* out_ids, hipStream_t stream);
 
+// ---- launchers (kernels_l2.hip): the L2 metric around the inner-product scan (VODHIP_L2 stores) ---
+// rows: the first of n_rows freshly converted rows [.., stride] (columns >= dim zero); writes the three bias terms of every row
+// into columns [dim, dim + 3) and counts rows whose bias saturated into *saturated (l2_bias.h)
+hipError_t launch_l2_bias(void* rows, int store_dtype, int64_t n_rows, int64_t dim, int64_t stride, unsigned int* saturated,
+                          hipStream_t stream);
+// q_src [nq, dim] of q_dtype -> staged [nq, dim + 3] of the store dtype (rounded, saturating; then the three constants), qn [nq] = |q~|^2
+hipError_t launch_l2_stage_queries(const void* q_src, int q_dtype, int64_t nq, int64_t dim, int store_dtype, void* staged, float* qn,
+                                   hipStream_t stream);
+// sim [nq, k] similarity-form scores (pads -inf) -> dist [nq, k] = max(0, qn - 2 sim), pads +inf
+hipError_t launch_l2_finish(const float* sim, const float* qn, int64_t nq, int k, float* dist, hipStream_t stream);
+
 // ---- launchers (kernels_hybrid.hip) -----------------------------------------------------------
 struct HybridArgs {
     const int64_t* lookup_idx;

@@ -136,6 +136,7 @@ int vodhip_node_index_create(int n_devices, const int* devices, int64_t dim, int
     if (!out) return nfail("out is NULL");
     if (n_devices < 1 || n_devices > 64 || !devices) return nfail("n_devices=%d out of range [1, 64]", n_devices);
     if (capacity_rows < 0) return nfail("invalid capacity=%lld", (long long)capacity_rows);
+    if (store_dtype & VODHIP_L2) return nfail("VODHIP_L2 is not supported by the node index: the merge of the shards' lists orders by inner product (DESIGN.md 8)");
     vodhip_node_index* nx = new vodhip_node_index();
     nx->n = n_devices;
     nx->dim = dim;

@@ -24,7 +24,8 @@ class HipMipsFactoryConfig:
     """The few fields of the reference's `FaissFactoryConfig` (src/vod_configs/search.py:124-154) this path needs."""
 
     factory: str = "Flat"           # only the exact index exists here
-    metric: str = "inner_product"   # src/vod_configs/search.py:130
+    metric: str = "inner_product"   # src/vod_configs/search.py:130; "l2" = squared L2 distances, ascending: the single-device engine
+                                    # only, scored on the values rounded to `dtype` (exact_f32 must be off or undecided)
     dtype: str = "float16"          # HBM storage type of the SCAN copy (float16 | bfloat16)
     exact_f32: bool | None = None   # also keep the float32 rows and return the float32 brute-force result on the unrounded vectors and
                                     # queries - what the reference's faiss IndexFlat computes (build.py:65-73); the vector file handed
@@ -118,6 +119,15 @@ def build_hip_mips_index(
         config = resolve_port(config, broadcast_fn)
     if devices is None and config.devices is not None:
         devices = list(config.devices)
+    if config.factory != "Flat" or config.metric not in ("inner_product", "l2"):
+        raise ValueError(f"the HIP engine is an exact flat index: factory='Flat' with metric='inner_product' or 'l2' "
+                         f"(got factory={config.factory!r}, metric={config.metric!r})")
+    if config.metric == "l2":
+        if devices is not None:
+            raise ValueError("metric='l2' needs the single-device engine: `devices` (the node and group engines) serve inner_product only")
+        if config.exact_f32:
+            raise ValueError("metric='l2' scores the vectors as rounded to `dtype`: exact_f32=True is not supported with it")
+        config = dataclasses.replace(config, exact_f32=False)  # (also settles the auto choice: no float32 plane)
     if config.exact_f32 is None:  # auto: float32 / float64 vectors are served exactly, float16 vectors as they are
         try:
             vec_dtype = np.dtype(getattr(vectors, "dtype", None) or np.asarray(vectors[0]).dtype) if len(vectors) else np.dtype(np.float16)
@@ -139,8 +149,6 @@ def build_hip_mips_index(
                 logger.info("exact_f32 (auto): float32 vectors are served exactly - %.1f GB per device instead of %.1f GB (exact_f32=False)",
                             need / 1e9, plain / 1e9)
         config = dataclasses.replace(config, exact_f32=want_exact)
-    if config.factory != "Flat" or config.metric != "inner_product":
-        raise ValueError("the HIP MIPS engine is an exact inner-product index (factory='Flat', metric='inner_product')")
     from vod_amd.zarr_store import ZarrVectors
 
     if isinstance(vectors, ZarrVectors):
@@ -168,6 +176,7 @@ def build_hip_mips_index(
         free_resources=free_resources,
         dtype=config.dtype,
         exact_f32=bool(config.exact_f32),
+        metric=config.metric,
         device=config.device,
         devices=None if devices is None else list(devices),
         group_backend=config.group_backend,

@@ -39,10 +39,14 @@ class HipFlatIndex:
     `exact_f32=True` (VODHIP_EXACT_F32): the store also keeps the float32 rows and every search returns what a float32 brute force
     over the UNROUNDED rows and queries returns - the reference's own arithmetic (faiss IndexFlat holds float32,
     /root/reference/src/vod_search/faiss_search/build.py:65-73) - with the fp16 / bf16 scan as the filter.  Without it scores are
-    dot products of the values as rounded to `dtype`."""
+    dot products of the values as rounded to `dtype`.
+
+    `metric="l2"` (VODHIP_L2; faiss `index_factory(D, "Flat", METRIC_L2)`): searches return SQUARED L2 distances of the stored
+    (rounded) rows and the rounded queries, ascending.  The store keeps three bias columns per row behind the user's `dim` (they
+    show in `dim_pad` only: `add`, `stored_rows` and `save` speak `dim`).  Not combined with `exact_f32`; `score_ids` raises."""
 
     def __init__(self, dim: int, capacity: int, dtype: torch.dtype = torch.float16, device: int | torch.device = 0,
-                 exact_f32: bool = False):
+                 exact_f32: bool = False, metric: str = "inner_product"):
         self._lib = _native.load_library()
         if not torch.cuda.is_available():
             raise _native.NativeLibraryError("HipFlatIndex needs a ROCm device (torch.cuda.is_available() is False)")
@@ -53,10 +57,12 @@ class HipFlatIndex:
         self.capacity = int(capacity)
         self.dtype = dtype
         self.exact_f32 = bool(exact_f32)
+        self.metric = metric
+        flags = _native.metric_flag(metric) | (_native.EXACT_F32 if self.exact_f32 else 0)
         handle = ctypes.c_void_p()
         _native.check(
             self._lib.vodhip_index_create(
-                self.device.index or 0, self.dim, _native.torch_dtype_code(dtype) | (_native.EXACT_F32 if self.exact_f32 else 0),
+                self.device.index or 0, self.dim, _native.torch_dtype_code(dtype) | flags,
                 self.capacity, ctypes.byref(handle)
             )
         )
@@ -124,7 +130,8 @@ class HipFlatIndex:
             )
 
     def stored_rows(self, begin: int = 0, n: int | None = None) -> torch.Tensor:
-        """Copy of the stored (rounded) rows [begin, begin+n) as a device tensor -- tests / persistence."""
+        """Copy of the stored (rounded) rows [begin, begin+n) as a device tensor [n, dim] (an L2 store's bias columns are not part of
+        it) -- tests / persistence."""
         n = self.ntotal - begin if n is None else int(n)
         out = torch.empty((n, self.dim), dtype=self.dtype, device=self.device)
         with torch.cuda.device(self.device):
@@ -164,7 +171,8 @@ class HipFlatIndex:
     # -- persistence (the store itself is the on-disk format, no faiss file round trip) -----------
     def save(self, path, chunk: int = 1 << 20) -> None:
         """Write the stored rows (as stored: fp16, or bf16 widened to fp32; the float32 rows of an `exact_f32` store - what
-        `faiss.write_index` persists for the reference, factory.py:167) to a `.npy`, slice by slice."""
+        `faiss.write_index` persists for the reference, factory.py:167) to a `.npy`, slice by slice.  An L2 store writes the user's
+        columns only: `load(..., metric="l2")` derives the bias columns again."""
         n = self.ntotal
         np_dtype = np.float16 if (self.dtype == torch.float16 and not self.exact_f32) else np.float32
         out = np.lib.format.open_memmap(path, mode="w+", dtype=np_dtype, shape=(n, self.dim))
@@ -180,12 +188,12 @@ class HipFlatIndex:
 
     @classmethod
     def load(cls, path, dtype: torch.dtype = torch.float16, device: int | torch.device = 0, capacity: int | None = None,
-             chunk: int = 1 << 18, exact_f32: bool = False) -> "HipFlatIndex":
-        """Build an index from a 2-D float16/float32 `.npy` (memory-mapped, streamed to HBM in slices)."""
+             chunk: int = 1 << 18, exact_f32: bool = False, metric: str = "inner_product") -> "HipFlatIndex":
+        """Build an index of `metric` from a 2-D float16/float32 `.npy` (memory-mapped, streamed to HBM in slices)."""
         arr = np.load(path, mmap_mode="r", allow_pickle=False)
         if arr.ndim != 2:
             raise ValueError(f"expected a 2-D vector file, got shape {arr.shape}")
-        ix = cls(arr.shape[1], max(capacity or arr.shape[0], 1), dtype=dtype, device=device, exact_f32=exact_f32)
+        ix = cls(arr.shape[1], max(capacity or arr.shape[0], 1), dtype=dtype, device=device, exact_f32=exact_f32, metric=metric)
         if arr.flags.c_contiguous:
             ix.add(arr)  # ONE call: the library pipelines page-cache reads, pinned staging and DMA itself (64 MB slices)
         else:
@@ -222,7 +230,10 @@ class HipFlatIndex:
                      subset: np.ndarray | torch.Tensor | None = None):
         """Enqueue a search on the current stream; call `finish()` before trusting the outputs.
 
-        `subset`: optional int32 [nq, S] allowed row labels per query (-1 = empty slot, all -1 = unrestricted)."""
+        `subset`: optional int32 [nq, S] allowed row labels per query (-1 = empty slot, all -1 = unrestricted).
+
+        On a `metric="l2"` index the scores are squared L2 distances, ascending, ties -> smaller id, clamped at 0, pads (+inf, -1);
+        `id_base`, `subset`, the lanes and up to 4 searches in flight work as for inner product."""
         q = self._prep_queries(queries)
         nq = q.shape[0]
         if subset is not None:
@@ -260,7 +271,10 @@ class HipFlatIndex:
             self._keep.popleft()
 
     def search(self, queries, k: int, id_base: int = 0, out=None, subset=None) -> tuple[torch.Tensor, torch.Tensor]:
-        """Exact top-k by inner product: (scores f32 [nq,k] desc, ids i64 [nq,k]); ties -> smaller id; pad -inf/-1."""
+        """Exact top-k by inner product: (scores f32 [nq,k] desc, ids i64 [nq,k]); ties -> smaller id; pad -inf/-1.
+
+        `metric="l2"`: exact top-k by squared L2 distance of the rounded rows and queries: (distances f32 [nq,k] ASCENDING, ids);
+        ties -> smaller id; distances are clamped at 0; pad +inf/-1 (faiss pads with +FLT_MAX)."""
         with torch.cuda.device(self.device):
             res = self.search_async(queries, k, id_base, out, subset)
             self.finish()
@@ -275,7 +289,8 @@ class HipFlatIndex:
         (id - id_base outside [0, ntotal)) or whose row carries none of the query's `subset` labels scores -inf.
         `k=None`: float32 [nq, m] aligned to `ids` (`out`: that tensor).  `k=int`: (scores [nq, k], ids [nq, k]) - the k best distinct
         listed rows by (score desc, id asc), pads (-inf, -1); m <= 8192 (`out`: the pair).
-        Enqueued on the current stream; nothing to finish, and safe beside searches of this index that are in flight."""
+        Enqueued on the current stream; nothing to finish, and safe beside searches of this index that are in flight.
+        An L2 index refuses (the library's message: listed ids need an inner-product store)."""
         q = self._prep_queries(queries)
         nq = q.shape[0]
         if isinstance(ids, torch.Tensor):
@@ -376,7 +391,8 @@ class HipNodeIndex:
     C / C++ consumer of the library gets, and what a single-process Python host can use without `torch.distributed`.
     """
 
-    def __init__(self, dim: int, capacity: int, devices: list[int], dtype: torch.dtype = torch.float16, exact_f32: bool = False):
+    def __init__(self, dim: int, capacity: int, devices: list[int], dtype: torch.dtype = torch.float16, exact_f32: bool = False,
+                 metric: str = "inner_product"):
         self._lib = _native.load_library()
         if not torch.cuda.is_available():
             raise _native.NativeLibraryError("HipNodeIndex needs a ROCm device (torch.cuda.is_available() is False)")
@@ -389,7 +405,8 @@ class HipNodeIndex:
         self.exact_f32 = bool(exact_f32)  # every shard keeps its float32 rows (HipFlatIndex): the merged result is the float32 brute force
         handle = ctypes.c_void_p()
         arr = (ctypes.c_int32 * len(self.devices))(*self.devices)
-        code = _native.torch_dtype_code(dtype) | (_native.EXACT_F32 if self.exact_f32 else 0)
+        self.metric = metric  # (the library refuses VODHIP_L2 here: the shards' lists are merged by inner product)
+        code = _native.torch_dtype_code(dtype) | (_native.EXACT_F32 if self.exact_f32 else 0) | _native.metric_flag(metric)
         _native.check(self._lib.vodhip_node_index_create(len(self.devices), arr, self.dim, code, self.capacity, ctypes.byref(handle)))
         self._h = handle
 

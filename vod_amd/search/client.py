@@ -472,6 +472,7 @@ class HipMipsMaster(base.SearchMaster[HipMipsClient]):
         exact_f32: bool = False,  # the server keeps the float32 rows and answers with the float32 brute-force result (HipFlatIndex)
         subset_ids_path: None | str | pathlib.Path = None,  # `.npy`, one subset id per vector: what `forward_subset_ids` clients filter by
         section_ids_path: None | str | pathlib.Path = None,  # `.npy`, one unique section id per vector: what `forward_ids` clients list
+        metric: str = "inner_product",  # "l2": the server ranks by squared L2 distance, ascending (single device; not with exact_f32 / `ids`)
     ):
         super().__init__(skip_setup=skip_setup, free_resources=free_resources)
         self.vectors_path = vectors_path if str(vectors_path).startswith("synthetic:") else pathlib.Path(vectors_path)
@@ -480,6 +481,7 @@ class HipMipsMaster(base.SearchMaster[HipMipsClient]):
         self.port = find_available_port() if port < 0 else port
         self.dtype = dtype
         self.exact_f32 = bool(exact_f32)
+        self.metric = metric
         self.subset_ids_path = subset_ids_path
         self.section_ids_path = section_ids_path
         self.device = device
@@ -514,6 +516,7 @@ class HipMipsMaster(base.SearchMaster[HipMipsClient]):
             "--logging-level", str(self.logging_level),
             "--dtype", self.dtype,
             *(["--exact-f32"] if self.exact_f32 else []),
+            *(["--metric", self.metric] if self.metric != "inner_product" else []),
             *(["--subset-ids-path", str(self.subset_ids_path)] if self.subset_ids_path else []),
             *(["--section-ids-path", str(self.section_ids_path)] if self.section_ids_path else []),
             "--http", self.http,

@@ -301,9 +301,11 @@ class HipEngine:
     `row_range=(lo, hi)`: hold only rows [lo, hi) of the store (one shard of a multi-GPU group); ids stay global."""
 
     def __init__(self, vectors_path: str, dtype: str = "float16", device: int = 0, subset_ids_path: str | None = None,
-                 row_range: tuple[int, int] | None = None, exact_f32: bool = False, section_ids_path: str | None = None):
+                 row_range: tuple[int, int] | None = None, exact_f32: bool = False, section_ids_path: str | None = None,
+                 metric: str = "inner_product"):
         import torch
 
+        self.metric = metric  # "l2": squared L2 distances, ascending (HipFlatIndex); requests that list `ids` are refused by the library
         self.section_rows: dict[str, int] | None = None  # `--section-ids-path`: section id -> global row (None: ids are row numbers)
         self._section_ids_path = section_ids_path
         self.exact_f32 = bool(exact_f32)  # keep the float32 rows too: results of a float32 brute force (HipFlatIndex)
@@ -322,7 +324,7 @@ class HipEngine:
             self.section_rows = load_section_rows(section_ids_path, n)  # (before the ingest: a bad file fails the start at once)
         lo, hi = (0, n) if row_range is None else (int(row_range[0]), int(row_range[1]))
         self.n_store, self.row_lo, self.row_hi = n, lo, hi
-        self.index = HipFlatIndex(d, max(hi - lo, 1), dtype=getattr(torch, dtype), device=device, exact_f32=self.exact_f32)
+        self.index = HipFlatIndex(d, max(hi - lo, 1), dtype=getattr(torch, dtype), device=device, exact_f32=self.exact_f32, metric=self.metric)
         step = 262144
         if hasattr(vectors, "iter_row_blocks") and row_range is None:
             # zarr store: blocks aligned to its chunk grid, each chunk decoded once, on a thread pool running ahead of the ingest
@@ -356,7 +358,7 @@ class HipEngine:
         self.n_store, self.row_lo, self.row_hi = n, lo, hi
         if self._section_ids_path:
             self.section_rows = load_section_rows(self._section_ids_path, n)
-        self.index = HipFlatIndex(d, max(hi - lo, 1), dtype=getattr(torch, dtype), device=device, exact_f32=self.exact_f32)
+        self.index = HipFlatIndex(d, max(hi - lo, 1), dtype=getattr(torch, dtype), device=device, exact_f32=self.exact_f32, metric=self.metric)
         self.vocab = {}
         for rows in synthetic_rows(torch, torch.device("cuda", device), lo, hi, d, int(seed or 0)):
             self.index.add(rows if self.exact_f32 else rows.to(getattr(torch, dtype)))
@@ -568,6 +570,9 @@ def parse_args(argv=None) -> argparse.Namespace:
                    help="keep the float32 rows next to the fp16 / bf16 scan copy and answer with the float32 brute-force result on the "
                         "unrounded vectors and queries - the reference's arithmetic (faiss IndexFlat holds float32, build.py:65-73); "
                         "+4 bytes per element of HBM, ~1-3 %% of search time")
+    p.add_argument("--metric", type=str, default="inner_product", choices=["inner_product", "l2"],
+                   help="l2: rank by squared L2 distance (ascending; pads +inf / -1) - the single-device engine only; not with --exact-f32, "
+                        "--devices or requests that list `ids`")
     p.add_argument("--device", type=int, default=0)
     p.add_argument("--devices", type=str, default=None,
                    help="comma-separated GPU ids: the store is row-sharded over them, one worker process per GPU on an RCCL "
@@ -743,6 +748,9 @@ def main(argv=None) -> None:
 
         n_workers = len([x for x in args.devices.split(",") if x.strip() != ""]) if (args.devices and args.rank is not None) else 1
         limit_cpu_threads(max(1, usable_cpus() // max(1, n_workers)))  # the workers of a group share the grant
+    if args.metric != "inner_product" and args.devices is not None:
+        # the node index and the process group merge their shards' lists by inner product: refuse at start-up, before any ingest
+        raise SystemExit(f"--metric {args.metric} needs the single-device engine: --devices (node and group engines) serve inner_product only")
     if args.devices is not None and args.group_backend == "node":
         devices = [int(x) for x in args.devices.split(",") if x.strip() != ""]
         engine = NodeHipEngine(args.vectors_path, devices, dtype=args.dtype, subset_ids_path=args.subset_ids_path, exact_f32=args.exact_f32,
@@ -753,7 +761,7 @@ def main(argv=None) -> None:
     if args.devices is not None:
         return run_worker(args)
     engine = HipEngine(args.vectors_path, dtype=args.dtype, device=args.device, subset_ids_path=args.subset_ids_path, exact_f32=args.exact_f32,
-                       section_ids_path=args.section_ids_path)
+                       section_ids_path=args.section_ids_path, metric=args.metric)
     host = re.sub(r"^(http|https)://", "", args.host)
     _serve(engine, args, host)
 
