@@ -164,6 +164,28 @@ int vodhip_index_search_ids(vodhip_index_t* index, const void* queries, int q_dt
                             int k, int64_t id_base, const int32_t* q_labels_dev, int n_per_query, float* out_scores,
                             int64_t* out_ids, void* stream);
 
+/* H2p. The exact softmax normaliser of the retriever over the WHOLE store (kernels_partition.hip):
+ *     log Z_beta(q) = log sum_{z < ntotal, eligible} exp(beta * <q~, x~_z>) = beta * out_max[q] + out_log_rel[q]
+ * with out_max[q] = the largest score (the bits vodhip_index_search returns at k = 1) and out_log_rel[q] = log sum exp(beta (s - max))
+ * >= 0.  Two words, not one: beta * max can be tens of thousands, where the float32 spacing would swallow log_rel; callers who want one
+ * number add them.  Replaces: nothing in the reference - it never normalises over the store; this is the denominator its truncated
+ * objectives (top-k + samples) approximate, so logsumexp(beta * topk) - log Z is the posterior mass a result list covers.
+ * Queries as in H2 (rounded to the store dtype, saturating).  A row counts when it is below ntotal, its score is not NaN (a search
+ * leaves NaN out too) and `q_labels_dev` (DEVICE int32 [nq, n_per_query], NULL = unrestricted; the rule of
+ * vodhip_index_set_query_labels; an ARGUMENT, not index state) allows it.  No eligible row (an empty index included): (-inf, -inf).
+ * A +inf score: (+inf, +inf).  One scan of the store on the MFMA path with an online log-sum-exp in place of the top-k; the score
+ * matrix is never materialised.  ONE summation order per query, fixed by ntotal and the padded width alone: a query's two words are
+ * the same bits whatever the batch around it, and on every repeat.
+ * out_max / out_log_rel: DEVICE float32 [nq], complete on `stream`; the call only enqueues work and uses neither the index's search
+ * workspace nor its query labels (its temporaries are hipMallocAsync on `stream`): it may run beside searches in flight; it must not
+ * overlap add / reset / set_row_labels.  nq == 0 returns 0 and writes nothing.
+ * REFUSED, each with its own vodhip_last_error: NULL index / pointers with nq > 0, q_dtype outside 0..2, beta not finite or <= 0,
+ * n_per_query outside 1..64, labels without row labels, a VODHIP_L2 store (its scores are not similarities), a VODHIP_EXACT_F32 store
+ * (this pass scores the rounded plane). */
+int vodhip_index_log_partition(vodhip_index_t* index, const void* queries, int q_dtype, int64_t nq, float beta,
+                               const int32_t* q_labels_dev /* NULL = unrestricted */, int n_per_query,
+                               float* out_max /* DEVICE [nq] */, float* out_log_rel /* DEVICE [nq] */, void* stream);
+
 /* Optional subset filter.  The reference's SearchClient.search carries `subset_ids`; its Elasticsearch and
  * Qdrant engines restrict hits to sections whose subset id is listed (src/vod_search/es_search/client.py:185-191,
  * qdrant_search/client.py:124-136) while its faiss client ignores it (faiss_search/client.py:67-72).  Here every stored
@@ -312,6 +334,14 @@ int vodhip_node_index_score_ids(vodhip_node_index_t* index, const void* queries,
 int vodhip_node_index_search_ids(vodhip_node_index_t* index, const void* queries, int q_dtype, int64_t nq, const int64_t* ids, int64_t m,
                                  int k, const int32_t* q_labels, int n_per_query, int location, float* out_scores, int64_t* out_ids,
                                  void* stream);
+/* H2p behind the one handle: queries, `q_labels` (may be NULL) and both outputs are HOST buffers.  Every shard runs
+ * vodhip_index_log_partition on its own device and stream; the 2 * nq floats per shard return through host memory and are folded in
+ * increasing shard order: max = max_g max_g, log_rel = log sum_g exp(beta (max_g - max) + log_rel_g); a shard with no eligible row
+ * contributes nothing.  out_max equals one index holding all the rows bit for bit; out_log_rel within the rounding of the fold.
+ * Host-synchronous; serialised with the other calls on the handle; refusals as for the flat call. */
+int vodhip_node_index_log_partition(vodhip_node_index_t* index, const void* queries, int q_dtype, int64_t nq, float beta,
+                                    const int32_t* q_labels /* HOST or NULL */, int n_per_query,
+                                    float* out_max, float* out_log_rel /* HOST [nq] */);
 /* With param "profile" = 1 (also set on every shard: their filter launches are bracketed, read per shard through vodhip_index_get_stat on
  * the handle vodhip_node_index_shard returns): "last_merge_ns" = the merge launch on devices[0], from the moment every shard's list had
  * arrived; "last_copy_ns_max" = the slowest shard's copy of its list towards devices[0] (peer copy over xGMI, or the down-leg to pinned

@@ -16,6 +16,7 @@
 #include <vector>
 
 #include "l2_bias.h"
+#include "partition_fold.h"
 #include "search_plan.h"
 #include "vodhip_internal.h"
 
@@ -1147,6 +1148,56 @@ int vodhip_index_search_ids(vodhip_index_t* ix, const void* queries, int q_dtype
     const hipError_t fe = hipFreeAsync(aligned, stream);
     if (rc) return fail("%s", keep.c_str());
     HIP_OK(fe);
+    return 0;
+}
+
+// ---- log-partition scan (kernels_partition.hip) ---------------------------------------------------------------------------
+// Like the listed calls: reads the store (and the row labels) only; staged queries and partials are stream-ordered temporaries.
+int vodhip_index_log_partition(vodhip_index_t* ix, const void* queries, int q_dtype, int64_t nq, float beta, const int32_t* q_labels_dev,
+                               int n_per_query, float* out_max, float* out_log_rel, void* stream_) {
+    if (!ix) return fail("index is NULL");
+    if (const char* msg = log_partition_args_error(queries, q_dtype, nq, beta, q_labels_dev, n_per_query, out_max, out_log_rel)) {
+        if (!strcmp(msg, "invalid q_dtype")) return fail("invalid q_dtype %d", q_dtype);
+        if (!strncmp(msg, "beta", 4)) return fail("beta=%g: %s", (double)beta, msg);
+        return fail("%s", msg);
+    }
+    if (ix->l2) return fail("log_partition is not supported on an L2 index (VODHIP_L2): its scores are distances, not similarities");
+    if (ix->exact) return fail("log_partition is not supported on a VODHIP_EXACT_F32 store: the scan scores the rounded rows, that store's contract is the float32 rows");
+    if (q_labels_dev && !ix->row_label) return fail("set the row labels first (vodhip_index_set_row_labels)");
+    if (nq == 0) return 0;
+    HIP_OK(hipSetDevice(ix->device));
+    hipStream_t stream = (hipStream_t)stream_;
+    constexpr int64_t Q_CHUNK = 1024;  // queries per scan launch (a multiple of the query tile): bounds the partials' size
+    PartitionArgs a;
+    a.store = ix->data;
+    a.dim = ix->dim;
+    a.dim_pad = ix->dim_pad;
+    a.ntotal = ix->ntotal;
+    a.store_dtype = ix->dtype;
+    a.q_src = queries;
+    a.q_dtype = q_dtype;
+    a.row_label = ix->row_label;
+    a.q_label = q_labels_dev;
+    a.n_qlab = q_labels_dev ? n_per_query : 0;
+    a.beta = beta;
+    a.out_max = out_max;
+    a.out_log_rel = out_log_rel;
+    const int64_t nq_pad = log_partition_nq_pad(std::min(nq, Q_CHUNK));
+    const size_t stage_bytes = (size_t)nq_pad * (size_t)ix->dim_pad * 2;
+    const size_t part_bytes = std::max<size_t>(8, (size_t)log_partition_tiles(a.ntotal) * (size_t)nq_pad * 8);
+    HIP_OK(hipMallocAsync(&a.q_stage, stage_bytes, stream));
+    if (hipError_t e = hipMallocAsync(&a.part, part_bytes, stream); e != hipSuccess) {
+        (void)hipGetLastError();
+        (void)hipFreeAsync(a.q_stage, stream);
+        return fail("hipMallocAsync of the %zu-byte partials failed: %s", part_bytes, hipGetErrorString(e));
+    }
+    hipError_t le = hipSuccess;
+    for (int64_t q0 = 0; q0 < nq && le == hipSuccess; q0 += Q_CHUNK) le = launch_log_partition(a, q0, std::min(Q_CHUNK, nq - q0), stream);
+    if (le != hipSuccess) (void)hipGetLastError();
+    const hipError_t f1 = hipFreeAsync(a.q_stage, stream), f2 = hipFreeAsync(a.part, stream);
+    if (le != hipSuccess) return fail("log-partition launch failed: %s", hipGetErrorString(le));
+    HIP_OK(f1);
+    HIP_OK(f2);
     return 0;
 }
 

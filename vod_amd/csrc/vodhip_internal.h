@@ -223,6 +223,27 @@ hipError_t launch_l2_stage_queries(const void* q_src, int q_dtype, int64_t nq, i
 // sim [nq, k] similarity-form scores (pads -inf) -> dist [nq, k] = max(0, qn - 2 sim), pads +inf
 hipError_t launch_l2_finish(const float* sim, const float* qn, int64_t nq, int k, float* dist, hipStream_t stream);
 
+// ---- launchers (kernels_partition.hip): log sum exp(beta * score) over the whole store -----------
+struct PartitionArgs {
+    const void* store = nullptr;      // [>= round_up(ntotal, 256) rows][dim_pad] fp16 / bf16 rows
+    int64_t dim = 0, dim_pad = 0, ntotal = 0;
+    int store_dtype = 0;              // 0 = f16, 1 = bf16
+    const void* q_src = nullptr;      // the caller's queries [.., dim] of q_dtype
+    int q_dtype = 0;
+    const int* row_label = nullptr;   // the store's subset labels; read only with q_label
+    const int* q_label = nullptr;     // [.., n_qlab] rows of the caller's batch, or NULL = unrestricted
+    int n_qlab = 0;
+    float beta = 1.f;
+    void* q_stage = nullptr;          // temporary: log_partition_nq_pad(nq) * dim_pad 16-bit words
+    void* part = nullptr;             // temporary: log_partition_tiles(ntotal) * log_partition_nq_pad(nq) float2
+    float* out_max = nullptr;         // [rows of the caller's batch]
+    float* out_log_rel = nullptr;
+};
+int64_t log_partition_nq_pad(int64_t nq);
+int64_t log_partition_tiles(int64_t ntotal);
+// queries [q_first, q_first + nq) of the caller's batch -> out_max / out_log_rel [q_first ..); a query's bits do not depend on the split
+hipError_t launch_log_partition(const PartitionArgs& a, int64_t q_first, int64_t nq, hipStream_t stream);
+
 // ---- launchers (kernels_hybrid.hip) -----------------------------------------------------------
 struct HybridArgs {
     const int64_t* lookup_idx;

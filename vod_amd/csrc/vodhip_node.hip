@@ -17,6 +17,7 @@
 #include <thread>
 #include <vector>
 
+#include "partition_fold.h"
 #include "vodhip_internal.h"
 
 namespace {
@@ -807,6 +808,68 @@ int vodhip_node_index_search_ids(vodhip_node_index_t* nx, const void* queries, i
                                  void* stream) {
     if (k < 0) return nfail("k=%d out of range [1, %d]", k, VODHIP_MAX_K);
     return node_listed(nx, queries, q_dtype, nq, ids, m, k, q_labels, n_per_query, location, out_scores, out_ids, stream);
+}
+
+// The log-partition scan behind the one handle (include/vodhip.h, H2p): host queries and labels are replicated to every shard, every
+// shard runs the flat call on its own device and stream, the 2 * nq floats per shard return through host memory and are folded there in
+// increasing shard order (partition_fold.h).  No peer copies, no streams beyond the shards' own.
+int vodhip_node_index_log_partition(vodhip_node_index_t* nx, const void* queries, int q_dtype, int64_t nq, float beta, const int32_t* q_labels,
+                                    int n_per_query, float* out_max, float* out_log_rel) {
+    if (!nx) return nfail("index is NULL");
+    if (const char* msg = vodhip::log_partition_args_error(queries, q_dtype, nq, beta, q_labels, n_per_query, out_max, out_log_rel)) {
+        if (!strcmp(msg, "invalid q_dtype")) return nfail("invalid q_dtype %d", q_dtype);
+        if (!strncmp(msg, "beta", 4)) return nfail("beta=%g: %s", (double)beta, msg);
+        return nfail("%s", msg);
+    }
+    if (nx->dtype & VODHIP_L2) return nfail("log_partition is not supported on an L2 index (VODHIP_L2): its scores are distances, not similarities");
+    if (nx->dtype & VODHIP_EXACT_F32) return nfail("log_partition is not supported on a VODHIP_EXACT_F32 store: the scan scores the rounded rows, that store's contract is the float32 rows");
+    std::lock_guard<std::mutex> guard(nx->mu);
+    if (q_labels && !nx->has_row_labels) return nfail("set the row labels first (vodhip_node_index_set_row_labels)");
+    if (nq == 0) return 0;
+    const int G = nx->n;
+    const size_t q_bytes = (size_t)nq * (size_t)nx->dim * elem_bytes(q_dtype);
+    const size_t lab_bytes = q_labels ? (size_t)nq * (size_t)n_per_query * sizeof(int32_t) : 0;
+    std::vector<float> parts((size_t)G * 2 * (size_t)nq);  // shard g: [max | log_rel] at g * 2 nq
+    struct Tmp { void* q = nullptr; int32_t* lab = nullptr; float* out = nullptr; };
+    std::vector<Tmp> tmp((size_t)G);
+    int rc = 0;
+    std::string err;
+    auto hip_step = [&](hipError_t e, const char* what) {
+        if (e != hipSuccess && !rc) {
+            (void)hipGetLastError();
+            err = std::string(what) + " failed: " + hipGetErrorString(e);
+            rc = -1;
+        }
+        return e == hipSuccess;
+    };
+    for (int g = 0; g < G && !rc; ++g) {  // (the devices run side by side: nothing is waited for until every shard is enqueued)
+        hipStream_t st = nx->stream[g];
+        Tmp& t = tmp[(size_t)g];
+        if (!hip_step(hipSetDevice(nx->device[g]), "hipSetDevice")) break;
+        if (!hip_step(hipMallocAsync(&t.q, q_bytes, st), "hipMallocAsync")) break;
+        if (!hip_step(hipMallocAsync((void**)&t.out, 2 * (size_t)nq * sizeof(float), st), "hipMallocAsync")) break;
+        if (q_labels && !hip_step(hipMallocAsync((void**)&t.lab, lab_bytes, st), "hipMallocAsync")) break;
+        if (!hip_step(hipMemcpyAsync(t.q, queries, q_bytes, hipMemcpyHostToDevice, st), "hipMemcpyAsync")) break;
+        if (q_labels && !hip_step(hipMemcpyAsync(t.lab, q_labels, lab_bytes, hipMemcpyHostToDevice, st), "hipMemcpyAsync")) break;
+        if (vodhip_index_log_partition(nx->shard[g], t.q, q_dtype, nq, beta, t.lab, n_per_query, t.out, t.out + nq, st)) {
+            err = std::string("shard ") + std::to_string(g) + ": " + vodhip_last_error();
+            rc = -1;
+            break;
+        }
+        hip_step(hipMemcpyAsync(parts.data() + (size_t)g * 2 * (size_t)nq, t.out, 2 * (size_t)nq * sizeof(float), hipMemcpyDeviceToHost, st), "hipMemcpyAsync");
+    }
+    for (int g = 0; g < G; ++g) {  // (also after a failure: what was enqueued reads the caller's host buffers)
+        Tmp& t = tmp[(size_t)g];
+        if (hipSetDevice(nx->device[g]) != hipSuccess) continue;
+        if (t.q) (void)hipFreeAsync(t.q, nx->stream[g]);
+        if (t.lab) (void)hipFreeAsync(t.lab, nx->stream[g]);
+        if (t.out) (void)hipFreeAsync(t.out, nx->stream[g]);
+        hip_step(hipStreamSynchronize(nx->stream[g]), "hipStreamSynchronize");
+    }
+    (void)hipSetDevice(nx->device[0]);
+    if (rc) return nfail("%s", err.c_str());
+    vodhip::fold_log_partition(parts.data(), parts.data() + nq, G, 2 * nq, nq, beta, out_max, out_log_rel);
+    return 0;
 }
 
 int vodhip_node_index_get_stat(vodhip_node_index_t* nx, const char* key, int64_t* out) {

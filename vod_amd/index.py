@@ -10,6 +10,7 @@ from __future__ import annotations
 
 import collections
 import ctypes
+from typing import Any, NamedTuple
 
 import numpy as np
 import torch
@@ -332,6 +333,58 @@ class HipFlatIndex:
         return res
 
 
+    def log_partition(self, queries, temperature: float = 1.0, subset=None, out=None) -> LogPartition:
+        """The exact softmax normaliser over the WHOLE store, `log Z(q) = log sum_z exp(<q~, x~_z> / temperature)`, from one scan on
+        the MFMA path (no `[nq, N]` score matrix): `LogPartition(log_z, max_score, log_rel)`, float32 device tensors `[nq]` with
+        `log_z = max_score / temperature + log_rel`.  `max_score` is the bits `search(q, 1)` returns; `log_rel >= 0` carries what the
+        float32 spacing at `max_score / temperature` would swallow.  No eligible row: all three -inf.
+
+        `queries` as in `search`, `subset` as in `score_ids` (an argument, not index state).  `out`: a (max_score, log_rel) pair to
+        write into.  Enqueued on the current stream; nothing to finish, and safe beside searches of this index that are in flight.
+        L2 and `exact_f32` indexes refuse (the library's message)."""
+        q = self._prep_queries(queries)
+        nq = q.shape[0]
+        beta = 1.0 / float(temperature) if temperature else float("nan")
+        sub, n_sub = None, 0
+        if subset is not None:
+            sub = subset if isinstance(subset, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(subset))
+            sub = sub.to(self.device, torch.int32).contiguous()
+            if sub.ndim != 2 or sub.shape[0] != nq:
+                raise ValueError(f"expected subset labels of shape [{nq}, S], got {tuple(sub.shape)}")
+            n_sub = int(sub.shape[1])
+        if out is None:
+            max_score = torch.empty((nq,), dtype=torch.float32, device=self.device)
+            log_rel = torch.empty((nq,), dtype=torch.float32, device=self.device)
+        else:
+            max_score, log_rel = out
+        with torch.cuda.device(self.device):
+            _native.check(self._lib.vodhip_index_log_partition(
+                self._h, q.data_ptr(), _native.torch_dtype_code(q.dtype), nq, beta, None if sub is None else sub.data_ptr(), n_sub,
+                max_score.data_ptr(), log_rel.data_ptr(), _native.current_stream_ptr(self.device)))
+        for t, given in ((q, queries), (sub, subset)):
+            if t is not None and t is not given:
+                t.record_stream(torch.cuda.current_stream(self.device))
+        return LogPartition(max_score * beta + log_rel, max_score, log_rel)  # (-inf + -inf and +inf + +inf: never NaN)
+
+
+class LogPartition(NamedTuple):
+    """`log_z = max_score / temperature + log_rel` of `HipFlatIndex.log_partition` / `HipNodeIndex.log_partition`, each `[nq]`."""
+
+    log_z: Any
+    max_score: Any
+    log_rel: Any
+
+
+def topk_log_coverage(scores: torch.Tensor, log_partition: LogPartition, temperature: float = 1.0) -> torch.Tensor:
+    """Log of the posterior mass a returned top-k list covers: `logsumexp(scores / T - max_score / T) - log_rel`, `[nq]`, <= 0 up to
+    rounding.  `scores`: `[nq, k]` as `search` returns them (pads -inf drop out); `log_partition`: what `log_partition` returned for the
+    same queries and temperature.  Plain torch on the device of `scores`; a query with no eligible row gives NaN (0 / 0)."""
+    s = torch.as_tensor(scores).float()
+    m = torch.as_tensor(log_partition.max_score).to(s.device).float()
+    r = torch.as_tensor(log_partition.log_rel).to(s.device).float()
+    return torch.logsumexp((s - m[:, None]) / float(temperature), dim=1) - r
+
+
 def merge_topk(scores: torch.Tensor, ids: torch.Tensor, k_out: int | None = None) -> tuple[torch.Tensor, torch.Tensor]:
     """Merge per-shard top-k lists [n_shards, nq, k] (global ids, pads -1) into [nq, k_out] on the GPU."""
     lib = _native.load_library()
@@ -561,6 +614,35 @@ class HipNodeIndex:
         _native.check(self._lib.vodhip_node_index_search(self._h, q.ctypes.data, 2 if q.dtype == np.float32 else 0, q.shape[0], int(k), 0,
                                                          out_s.ctypes.data, out_i.ctypes.data, None))
         return out_s, out_i
+
+    def log_partition(self, queries, temperature: float = 1.0, subset: np.ndarray | None = None) -> LogPartition:
+        """`HipFlatIndex.log_partition` over every shard: each shard scans its rows on its own device, the per-shard pairs are folded on
+        the host in shard order.  Host queries (NumPy, or a tensor that is copied to the host) -> `LogPartition` of float32 NumPy arrays
+        `[nq]`; `max_score` equals one index holding all the rows bit for bit."""
+        if isinstance(queries, torch.Tensor):
+            queries = queries.detach().float().cpu().numpy()
+        q = np.ascontiguousarray(queries)
+        if q.dtype not in (np.float32, np.float16):
+            q = q.astype(np.float32)
+        if q.ndim != 2 or q.shape[1] != self.dim:
+            raise ValueError(f"expected [nq, {self.dim}] queries, got {tuple(q.shape)}")
+        nq = int(q.shape[0])
+        beta = 1.0 / float(temperature) if temperature else float("nan")
+        sub, n_sub = None, 0
+        if subset is not None:
+            sub = np.ascontiguousarray(subset.cpu().numpy() if isinstance(subset, torch.Tensor) else subset, dtype=np.int32)
+            if sub.ndim != 2 or sub.shape[0] != nq:
+                raise ValueError(f"subset must be int32 [nq, n_per_query], got {tuple(sub.shape)}")
+            n_sub = int(sub.shape[1])
+        max_score = np.empty((nq,), dtype=np.float32)
+        log_rel = np.empty((nq,), dtype=np.float32)
+        with torch.cuda.device(self.device):
+            _native.check(self._lib.vodhip_node_index_log_partition(
+                self._h, q.ctypes.data, 2 if q.dtype == np.float32 else 0, nq, beta, None if sub is None else sub.ctypes.data, n_sub,
+                max_score.ctypes.data, log_rel.ctypes.data))
+        with np.errstate(invalid="ignore"):
+            log_z = (max_score * np.float32(beta) + log_rel).astype(np.float32)
+        return LogPartition(log_z, max_score, log_rel)
 
     def score_ids(self, queries, ids, k: int | None = None, *, subset=None, out=None):
         """`HipFlatIndex.score_ids` over every shard: `ids` are global row ids; results equal one index holding all the rows.
