@@ -186,6 +186,32 @@ int vodhip_index_log_partition(vodhip_index_t* index, const void* queries, int q
                                const int32_t* q_labels_dev /* NULL = unrestricted */, int n_per_query,
                                float* out_max /* DEVICE [nq] */, float* out_log_rel /* DEVICE [nq] */, void* stream);
 
+/* H2m. The posterior mean of the stored rows under that softmax (kernels_posterior.hip) = the gradient of log Z with respect to q:
+ *     out_mean[q, :] = sum_{z < ntotal, eligible} p(z | q) x~_z,   p(z | q) = exp(beta <q~, x~_z> - log Z_beta(q)),
+ *     d log Z_beta / d q = beta * out_mean[q, :].
+ * out_max / out_log_rel are the bits vodhip_index_log_partition returns for the same query (its three launches run first, unchanged);
+ * eligibility, queries, labels, stream and concurrency rules are H2p's.  A second scan turns each 256-row tile's scores into weights
+ * exp(beta (s - m_ref)), rounded ONCE to the store dtype, and contracts them with the tile's rows on the MFMA (float32 accumulate);
+ * m_ref is the largest score of the tile's group of VODHIP_POSTERIOR_GROUP_ROWS consecutive rows, so a group's largest weight is
+ * exactly 1.  fp16 stores: weights are kept as normal fp16 numbers down to 2^-29 of the group's largest; smaller ones may be flushed
+ * to zero (an absolute error below rows-per-group * 2^-29 * max |x| of the column, before the group's own weight <= 1).  The groups are
+ * folded in increasing order with the weights exp(beta (m_g - max) - log_rel).  ONE order per (query, column), fixed by ntotal and the
+ * padded width alone: a mean row is the same bits whatever the batch around it and on every repeat; there are no atomics.
+ * No eligible row, or a +inf score: the two words as in H2p, the mean row all zeros.
+ * NON-FINITE STORED VALUES: an excluded row has weight 0, and 0 * NaN is NaN on the MFMA.  A column in which any row of a scanned
+ * 256-row tile holds a NaN or an infinity - an excluded row, a row past ntotal inside the last tile or a stale row behind a reset
+ * included - is NaN in every query's mean; the other columns and the two scalar words are unaffected.  There is no sanitising pass.
+ * out_mean: DEVICE float32 [nq, dim].  Temporaries are hipMallocAsync on `stream`: the staged queries and partials of H2p, and the
+ * group accumulators, groups * slice * dim_pad * 4 bytes; batches run in slices of 64 .. 1024 queries chosen so that the accumulators
+ * stay at or below VODHIP_POSTERIOR_TEMP_BYTES (256 MiB) unless a 64-query slice alone needs more.
+ * nq == 0 returns 0 and writes nothing; a refused call writes nothing.  REFUSED as H2p (same messages), and a NULL out_mean. */
+#define VODHIP_POSTERIOR_GROUP_ROWS 16384
+#define VODHIP_POSTERIOR_TEMP_BYTES (256ll << 20)
+int vodhip_index_posterior_mean(vodhip_index_t* index, const void* queries, int q_dtype, int64_t nq, float beta,
+                                const int32_t* q_labels_dev /* NULL = unrestricted */, int n_per_query,
+                                float* out_max /* DEVICE [nq] */, float* out_log_rel /* DEVICE [nq] */,
+                                float* out_mean /* DEVICE [nq][dim] */, void* stream);
+
 /* Optional subset filter.  The reference's SearchClient.search carries `subset_ids`; its Elasticsearch and
  * Qdrant engines restrict hits to sections whose subset id is listed (src/vod_search/es_search/client.py:185-191,
  * qdrant_search/client.py:124-136) while its faiss client ignores it (faiss_search/client.py:67-72).  Here every stored
@@ -342,6 +368,12 @@ int vodhip_node_index_search_ids(vodhip_node_index_t* index, const void* queries
 int vodhip_node_index_log_partition(vodhip_node_index_t* index, const void* queries, int q_dtype, int64_t nq, float beta,
                                     const int32_t* q_labels /* HOST or NULL */, int n_per_query,
                                     float* out_max, float* out_log_rel /* HOST [nq] */);
+/* H2m behind the one handle: HOST buffers, as above.  Every shard runs vodhip_index_posterior_mean; the shards are folded on the host
+ * in increasing shard order, in double: the pair as above, mean = sum_g w_g mean_g with w_g = exp(beta (max_g - max) + log_rel_g -
+ * log_rel); a shard with no eligible row carries weight 0 (its row is not read).  No eligible row anywhere, or a +inf score: zeros. */
+int vodhip_node_index_posterior_mean(vodhip_node_index_t* index, const void* queries, int q_dtype, int64_t nq, float beta,
+                                     const int32_t* q_labels /* HOST or NULL */, int n_per_query,
+                                     float* out_max, float* out_log_rel /* HOST [nq] */, float* out_mean /* HOST [nq][dim] */);
 /* With param "profile" = 1 (also set on every shard: their filter launches are bracketed, read per shard through vodhip_index_get_stat on
  * the handle vodhip_node_index_shard returns): "last_merge_ns" = the merge launch on devices[0], from the moment every shard's list had
  * arrived; "last_copy_ns_max" = the slowest shard's copy of its list towards devices[0] (peer copy over xGMI, or the down-leg to pinned

@@ -2,9 +2,11 @@
 // point, and the fold of per-shard (max, log_rel) pairs of a node index.  Plain C++ (no HIP): tests/sanitize/partition_fold_check.cpp
 // compiles this header alone under the sanitizers.
 #pragma once
+#include <algorithm>
 #include <cmath>
 #include <cstdint>
 #include <limits>
+#include <vector>
 
 namespace vodhip {
 
@@ -44,6 +46,34 @@ inline void fold_log_partition(const float* max_g, const float* log_rel_g, int n
         }
         out_max[q] = m;
         out_log_rel[q] = (float)std::log(sum);
+    }
+}
+
+// The posterior means of `n_shards` shards (kernels_posterior.hip), shard g's row of query q at mean_g[g * mean_stride + q * dim], with
+// the shard pairs as above and the FOLDED pair (out_max, out_log_rel) of fold_log_partition: in increasing shard order, in double,
+//   mean[q, :] = sum_g w_g mean_g[q, :],  w_g = exp(beta (max_g - max) + log_rel_g - log_rel).
+// A shard with no eligible row carries weight 0 and its row is not read; a query whose folded maximum is not finite gets the zero row.
+inline void fold_posterior_mean(const float* max_g, const float* log_rel_g, const float* mean_g, int n_shards, int64_t stride,
+                                int64_t mean_stride, int64_t nq, int64_t dim, float beta, const float* out_max, const float* out_log_rel,
+                                float* out_mean) {
+    const float inf = std::numeric_limits<float>::infinity();
+    std::vector<double> sum((size_t)(dim > 0 ? dim : 0));
+    for (int64_t q = 0; q < nq; ++q) {
+        float* row = out_mean + q * dim;
+        const float m = out_max[q], lr = out_log_rel[q];
+        if (m == inf || m == -inf || !(m == m)) {
+            for (int64_t d = 0; d < dim; ++d) row[d] = 0.f;
+            continue;
+        }
+        std::fill(sum.begin(), sum.end(), 0.0);
+        for (int g = 0; g < n_shards; ++g) {
+            const float mg = max_g[(int64_t)g * stride + q], lg = log_rel_g[(int64_t)g * stride + q];
+            if (mg == -inf || lg == -inf) continue;
+            const double w = std::exp((double)beta * ((double)mg - (double)m) + (double)lg - (double)lr);
+            const float* src = mean_g + (int64_t)g * mean_stride + q * dim;
+            for (int64_t d = 0; d < dim; ++d) sum[(size_t)d] += w * (double)src[d];
+        }
+        for (int64_t d = 0; d < dim; ++d) row[d] = (float)sum[(size_t)d];
     }
 }
 

@@ -1201,6 +1201,68 @@ int vodhip_index_log_partition(vodhip_index_t* ix, const void* queries, int q_dt
     return 0;
 }
 
+// ---- posterior mean (kernels_posterior.hip): the log-partition launches, then the second scan and its finish -------------------
+int vodhip_index_posterior_mean(vodhip_index_t* ix, const void* queries, int q_dtype, int64_t nq, float beta, const int32_t* q_labels_dev,
+                                int n_per_query, float* out_max, float* out_log_rel, float* out_mean, void* stream_) {
+    if (!ix) return fail("index is NULL");
+    if (const char* msg = log_partition_args_error(queries, q_dtype, nq, beta, q_labels_dev, n_per_query, out_max, out_log_rel)) {
+        if (!strcmp(msg, "invalid q_dtype")) return fail("invalid q_dtype %d", q_dtype);
+        if (!strncmp(msg, "beta", 4)) return fail("beta=%g: %s", (double)beta, msg);
+        return fail("%s", msg);
+    }
+    if (nq > 0 && !out_mean) return fail("invalid query / output pointers");
+    if (ix->l2) return fail("log_partition is not supported on an L2 index (VODHIP_L2): its scores are distances, not similarities");
+    if (ix->exact) return fail("log_partition is not supported on a VODHIP_EXACT_F32 store: the scan scores the rounded rows, that store's contract is the float32 rows");
+    if (q_labels_dev && !ix->row_label) return fail("set the row labels first (vodhip_index_set_row_labels)");
+    if (nq == 0) return 0;
+    HIP_OK(hipSetDevice(ix->device));
+    hipStream_t stream = (hipStream_t)stream_;
+    PosteriorArgs a;
+    a.p.store = ix->data;
+    a.p.dim = ix->dim;
+    a.p.dim_pad = ix->dim_pad;
+    a.p.ntotal = ix->ntotal;
+    a.p.store_dtype = ix->dtype;
+    a.p.q_src = queries;
+    a.p.q_dtype = q_dtype;
+    a.p.row_label = ix->row_label;
+    a.p.q_label = q_labels_dev;
+    a.p.n_qlab = q_labels_dev ? n_per_query : 0;
+    a.p.beta = beta;
+    a.p.out_max = out_max;
+    a.p.out_log_rel = out_log_rel;
+    a.out_mean = out_mean;
+    // queries per slice: a multiple of 128 (or 64) up to 1024 that keeps the group accumulators under VODHIP_POSTERIOR_TEMP_BYTES
+    const size_t per_query = std::max<size_t>(1, (size_t)posterior_mean_groups(a.p.ntotal)) * (size_t)ix->dim_pad * sizeof(float);
+    int64_t slice = (int64_t)((size_t)VODHIP_POSTERIOR_TEMP_BYTES / per_query) / 128 * 128;
+    slice = std::min<int64_t>(1024, std::max<int64_t>(64, slice));
+    const int64_t nq_pad = log_partition_nq_pad(std::min(nq, slice));
+    const size_t stage_bytes = (size_t)nq_pad * (size_t)ix->dim_pad * 2;
+    const size_t part_bytes = std::max<size_t>(8, (size_t)log_partition_tiles(a.p.ntotal) * (size_t)nq_pad * 8);
+    const size_t acc_bytes = per_query * (size_t)nq_pad;
+    void* tmp[3] = {nullptr, nullptr, nullptr};
+    const size_t bytes[3] = {stage_bytes, part_bytes, acc_bytes};
+    for (int i = 0; i < 3; ++i) {
+        if (hipError_t e = hipMallocAsync(&tmp[i], bytes[i], stream); e != hipSuccess) {
+            (void)hipGetLastError();
+            for (int j = 0; j < i; ++j) (void)hipFreeAsync(tmp[j], stream);
+            return fail("hipMallocAsync of a %zu-byte temporary failed: %s", bytes[i], hipGetErrorString(e));
+        }
+    }
+    a.p.q_stage = tmp[0];
+    a.p.part = tmp[1];
+    a.acc = (float*)tmp[2];
+    hipError_t le = hipSuccess;
+    for (int64_t q0 = 0; q0 < nq && le == hipSuccess; q0 += slice) le = launch_posterior_mean(a, q0, std::min(slice, nq - q0), stream);
+    if (le != hipSuccess) (void)hipGetLastError();
+    hipError_t fe = hipSuccess;
+    for (int i = 0; i < 3; ++i)
+        if (hipError_t e = hipFreeAsync(tmp[i], stream); e != hipSuccess) fe = e;
+    if (le != hipSuccess) return fail("posterior-mean launch failed: %s", hipGetErrorString(le));
+    HIP_OK(fe);
+    return 0;
+}
+
 int vodhip_debug_schedule(int64_t ntotal, int k, int64_t nq, int64_t cand_cap, int64_t dense_rows, int64_t sample_div,
                           int64_t growth_x100, int tile, int recovery_pass, int n_cu, int64_t* out, int max_stages) {
     PlanTunables t;

@@ -244,6 +244,17 @@ int64_t log_partition_tiles(int64_t ntotal);
 // queries [q_first, q_first + nq) of the caller's batch -> out_max / out_log_rel [q_first ..); a query's bits do not depend on the split
 hipError_t launch_log_partition(const PartitionArgs& a, int64_t q_first, int64_t nq, hipStream_t stream);
 
+// ---- launchers (kernels_posterior.hip): the posterior mean of the rows, sum_z p(z | q) x_z, behind the log-partition launches ----
+struct PosteriorArgs {
+    PartitionArgs p;                  // the log-partition call of the same batch: its launches run first, unchanged
+    float* acc = nullptr;             // temporary: posterior_mean_groups(ntotal) * log_partition_nq_pad(nq) * dim_pad floats
+    float* out_mean = nullptr;        // [rows of the caller's batch][dim]
+};
+int64_t posterior_mean_groups(int64_t ntotal);
+// queries [q_first, q_first + nq) of the caller's batch -> out_max / out_log_rel (the bits of launch_log_partition) and out_mean rows
+// [q_first ..); a query's bits do not depend on the split
+hipError_t launch_posterior_mean(const PosteriorArgs& a, int64_t q_first, int64_t nq, hipStream_t stream);
+
 // ---- launchers (kernels_hybrid.hip) -----------------------------------------------------------
 struct HybridArgs {
     const int64_t* lookup_idx;

@@ -366,6 +366,47 @@ class HipFlatIndex:
                 t.record_stream(torch.cuda.current_stream(self.device))
         return LogPartition(max_score * beta + log_rel, max_score, log_rel)  # (-inf + -inf and +inf + +inf: never NaN)
 
+    def posterior_mean(self, queries, temperature: float = 1.0, subset=None, out=None) -> "PosteriorMean":
+        """The posterior mean of the stored rows under the softmax over the WHOLE store, `mean[q] = sum_z p(z | q) x~_z` with
+        `p(z | q) = exp(<q~, x~_z> / temperature - log Z(q))`: `PosteriorMean(mean, log_partition)`, `mean` a float32 device tensor
+        `[nq, dim]`, `log_partition` the `LogPartition` that `log_partition` returns for the same call, bit for bit.  `mean / temperature`
+        is the gradient of `log Z` with respect to the query (`log_z` wraps it for autograd).  Two scans on the MFMA path, no `[nq, N]`
+        matrix; a `mean` row is the same bits whatever the batch around it.  A query with no eligible row (or a +inf score) gets the zero
+        row.  A stored NaN / infinity in column d makes column d of every mean NaN (the library's contract, `vodhip.h` H2m).
+
+        Arguments as `log_partition`; `out`: a (max_score, log_rel, mean) triple to write into."""
+        q = self._prep_queries(queries)
+        nq = q.shape[0]
+        beta = 1.0 / float(temperature) if temperature else float("nan")
+        sub, n_sub = None, 0
+        if subset is not None:
+            sub = subset if isinstance(subset, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(subset))
+            sub = sub.to(self.device, torch.int32).contiguous()
+            if sub.ndim != 2 or sub.shape[0] != nq:
+                raise ValueError(f"expected subset labels of shape [{nq}, S], got {tuple(sub.shape)}")
+            n_sub = int(sub.shape[1])
+        if out is None:
+            max_score = torch.empty((nq,), dtype=torch.float32, device=self.device)
+            log_rel = torch.empty((nq,), dtype=torch.float32, device=self.device)
+            mean = torch.empty((nq, self.dim), dtype=torch.float32, device=self.device)
+        else:
+            max_score, log_rel, mean = out
+        with torch.cuda.device(self.device):
+            _native.check(self._lib.vodhip_index_posterior_mean(
+                self._h, q.data_ptr(), _native.torch_dtype_code(q.dtype), nq, beta, None if sub is None else sub.data_ptr(), n_sub,
+                max_score.data_ptr(), log_rel.data_ptr(), mean.data_ptr(), _native.current_stream_ptr(self.device)))
+        for t, given in ((q, queries), (sub, subset)):
+            if t is not None and t is not given:
+                t.record_stream(torch.cuda.current_stream(self.device))
+        return PosteriorMean(mean, LogPartition(max_score * beta + log_rel, max_score, log_rel))
+
+    def log_z(self, queries: torch.Tensor, temperature: float = 1.0, subset=None) -> torch.Tensor:
+        """`log Z(q)` over the whole store as a float32 `[nq]` tensor that is differentiable with respect to `queries`: forward is
+        `posterior_mean`, backward `grad_q = grad_out[:, None] * mean / temperature`, cast to the dtype of `queries` (straight through
+        the rounding of the queries to the store dtype).  No gradient flows to the store; rows of `grad_q` whose `log_z` is not finite
+        are zero.  The exact retrieval NLL of a positive row: `-(<q, x_pos> / T - index.log_z(q, T))`."""
+        return _LogZ.apply(queries, self, float(temperature), subset)
+
 
 class LogPartition(NamedTuple):
     """`log_z = max_score / temperature + log_rel` of `HipFlatIndex.log_partition` / `HipNodeIndex.log_partition`, each `[nq]`."""
@@ -373,6 +414,39 @@ class LogPartition(NamedTuple):
     log_z: Any
     max_score: Any
     log_rel: Any
+
+
+class PosteriorMean(NamedTuple):
+    """`mean[q] = sum_z p(z | q) x_z` (`[nq, dim]`) of `posterior_mean`, with the `LogPartition` of the same call."""
+
+    mean: Any
+    log_partition: LogPartition
+
+
+def log_z_backward(grad_out: torch.Tensor, mean: torch.Tensor, log_z: torch.Tensor, beta: float, dtype: torch.dtype) -> torch.Tensor:
+    """The backward of `log_z`: `grad_out[:, None] * beta * mean` in float32, zero where `log_z` is not finite, cast to `dtype`."""
+    g = grad_out.to(torch.float32)[:, None] * (float(beta) * mean.to(torch.float32))
+    g = torch.where(torch.isfinite(log_z)[:, None], g, torch.zeros_like(g))
+    return g.to(dtype)
+
+
+class _LogZ(torch.autograd.Function):
+    """`index.log_z`: `index` is anything with `posterior_mean(queries, temperature, subset)`."""
+
+    @staticmethod
+    def forward(ctx, queries, index, temperature, subset):
+        pm = index.posterior_mean(queries.detach(), temperature, subset)
+        log_z = torch.as_tensor(pm.log_partition.log_z)
+        ctx.save_for_backward(torch.as_tensor(pm.mean), log_z)
+        ctx.beta = 1.0 / temperature
+        ctx.q_dtype, ctx.q_device = queries.dtype, queries.device
+        return log_z.clone()
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        mean, log_z = ctx.saved_tensors
+        g = log_z_backward(grad_out.to(mean.device), mean, log_z, ctx.beta, ctx.q_dtype)
+        return g.to(ctx.q_device), None, None, None
 
 
 def topk_log_coverage(scores: torch.Tensor, log_partition: LogPartition, temperature: float = 1.0) -> torch.Tensor:
@@ -643,6 +717,36 @@ class HipNodeIndex:
         with np.errstate(invalid="ignore"):
             log_z = (max_score * np.float32(beta) + log_rel).astype(np.float32)
         return LogPartition(log_z, max_score, log_rel)
+
+    def posterior_mean(self, queries, temperature: float = 1.0, subset: np.ndarray | None = None) -> "PosteriorMean":
+        """`HipFlatIndex.posterior_mean` over every shard: each shard runs the flat call on its own device, the shards are folded on the
+        host in shard order, in double (`mean = sum_g w_g mean_g`).  Host queries -> `PosteriorMean` of float32 NumPy arrays;
+        `max_score` equals one index holding all the rows bit for bit."""
+        if isinstance(queries, torch.Tensor):
+            queries = queries.detach().float().cpu().numpy()
+        q = np.ascontiguousarray(queries)
+        if q.dtype not in (np.float32, np.float16):
+            q = q.astype(np.float32)
+        if q.ndim != 2 or q.shape[1] != self.dim:
+            raise ValueError(f"expected [nq, {self.dim}] queries, got {tuple(q.shape)}")
+        nq = int(q.shape[0])
+        beta = 1.0 / float(temperature) if temperature else float("nan")
+        sub, n_sub = None, 0
+        if subset is not None:
+            sub = np.ascontiguousarray(subset.cpu().numpy() if isinstance(subset, torch.Tensor) else subset, dtype=np.int32)
+            if sub.ndim != 2 or sub.shape[0] != nq:
+                raise ValueError(f"subset must be int32 [nq, n_per_query], got {tuple(sub.shape)}")
+            n_sub = int(sub.shape[1])
+        max_score = np.empty((nq,), dtype=np.float32)
+        log_rel = np.empty((nq,), dtype=np.float32)
+        mean = np.empty((nq, self.dim), dtype=np.float32)
+        with torch.cuda.device(self.device):
+            _native.check(self._lib.vodhip_node_index_posterior_mean(
+                self._h, q.ctypes.data, 2 if q.dtype == np.float32 else 0, nq, beta, None if sub is None else sub.ctypes.data, n_sub,
+                max_score.ctypes.data, log_rel.ctypes.data, mean.ctypes.data))
+        with np.errstate(invalid="ignore"):
+            log_z = (max_score * np.float32(beta) + log_rel).astype(np.float32)
+        return PosteriorMean(mean, LogPartition(log_z, max_score, log_rel))
 
     def score_ids(self, queries, ids, k: int | None = None, *, subset=None, out=None):
         """`HipFlatIndex.score_ids` over every shard: `ids` are global row ids; results equal one index holding all the rows.
