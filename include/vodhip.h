@@ -212,6 +212,43 @@ int vodhip_index_posterior_mean(vodhip_index_t* index, const void* queries, int 
                                 float* out_max /* DEVICE [nq] */, float* out_log_rel /* DEVICE [nq] */,
                                 float* out_mean /* DEVICE [nq][dim] */, void* stream);
 
+/* H2s. k rows drawn WITHOUT replacement from that softmax over the whole store, with priority-sampling weights
+ * (kernels_sample_posterior.hip).  Gumbel-top-k: the k eligible rows with the largest keys
+ *     key(q, z) = fl(fl(beta * s(q, z)) - logf(E)),   E = -log1pf(-v),   by (key desc, id asc),
+ * s the float32 score of H2p's scan, and with key_{k+1} the (k+1)-th largest key
+ *     log_p = beta (s - max_score) - log_rel,   log_tau = (key_{k+1} - beta max_score) - log_rel,
+ *     log_weight = log_p - log(-expm1(-exp(log_p - log_tau)))   (double arithmetic on the float32 words; log_tau = -inf: log_p).
+ * sum_S exp(log_weight) f(z) is an unbiased estimate of E_p[f].  NOISE: Philox4x32-10 with key (seed & 0xffffffff, seed >> 32) and
+ * counter (low word of g >> 2, g >> 34, qs, j), g = id_base + row, qs = query_offset + q: output word g & 3 at j = 0 is w_hi of row g,
+ * at j = 1 its w_lo; v = float32((w_hi 2^32 + w_lo + 1/2) 2^-64), at most 1 - 2^-24.  A draw depends on (seed, qs, g) alone: not on
+ * the batch, the sharding or the launch geometry.  query_offset >= 0, query_offset + nq <= 2^32, id_base >= 0.
+ * out_max / out_log_rel are H2p's bits for the same query (its launches run first, unchanged); eligibility, queries, labels and
+ * stream rules are H2p's; a row with a -inf score is never drawn.  Behind them: a key-max scan (one float per query and 256-row
+ * tile), a threshold launch (theta = the (k+1)-th largest tile maximum: a lower bound of key_{k+1}), an emit scan that skips the
+ * K loop of every tile without a key >= theta and appends the others' to per-query lists of 256 (k + 1 +
+ * VODHIP_SAMPLE_SLACK_TILES) slots (at most the padded store), and a select launch.  The result is exact: there is no fallback pass.
+ * A list can only overflow when more than VODHIP_SAMPLE_SLACK_TILES further tile maxima tie EXACTLY with theta; a slot past the
+ * list is not written, the call fails ("candidate list overflow") and its outputs are undefined.
+ * Outputs, DEVICE: out_ids int64 [nq][k] (pads -1), out_scores / out_log_p / out_log_weight float32 [nq][k] (pads -inf), out_keys
+ * float32 [nq][k + 1] (unnormalised keys, descending, pads -inf).  Fewer than k eligible rows: pads; a query whose log Z is not
+ * finite (no eligible row, a +inf score): all pads.  Batches run in slices of 64 .. 1024 queries so that the temporaries (12 bytes
+ * per list slot, 12 per query and tile) stay at or below VODHIP_POSTERIOR_TEMP_BYTES unless a 64-query slice alone needs more.  The
+ * call WAITS for `stream` before it returns (it reads its status words).  Its temporaries are one grow-only block that the index
+ * keeps until it is destroyed (a stream-ordered pool hands its memory back at every such wait); the block is held for the length of
+ * a call, so two calls on one index run one after the other, whatever their streams - searches and the other calls of this header
+ * are not held up.  Stats "last_sample_overflow", "last_sample_selfcheck" (queries with fewer
+ * candidates than hit tiles: never, the two scans compute a key with the same instructions), "last_sample_candidates" /
+ * "last_sample_max_candidates", "last_sample_emit_groups" / "last_sample_emit_skipped", and with param "profile" = 1
+ * "last_sample_ns_partition" / "_keymax" / "_threshold" / "_emit" / "_select".
+ * nq == 0 returns 0 and writes nothing; a refused call writes nothing.  REFUSED as H2p (L2 and VODHIP_EXACT_F32 stores with messages
+ * of their own), k outside [1, 255], a bad query_offset / id_base, a NULL output. */
+#define VODHIP_SAMPLE_SLACK_TILES 2
+int vodhip_index_sample_posterior(vodhip_index_t* index, const void* queries, int q_dtype, int64_t nq, int k, float beta, uint64_t seed,
+                                  int64_t query_offset, int64_t id_base, const int32_t* q_labels_dev /* NULL = unrestricted */,
+                                  int n_per_query, float* out_max /* DEVICE [nq] */, float* out_log_rel /* DEVICE [nq] */,
+                                  int64_t* out_ids /* DEVICE [nq][k] */, float* out_scores, float* out_log_p,
+                                  float* out_log_weight /* DEVICE [nq][k] */, float* out_keys /* DEVICE [nq][k + 1] */, void* stream);
+
 /* Optional subset filter.  The reference's SearchClient.search carries `subset_ids`; its Elasticsearch and
  * Qdrant engines restrict hits to sections whose subset id is listed (src/vod_search/es_search/client.py:185-191,
  * qdrant_search/client.py:124-136) while its faiss client ignores it (faiss_search/client.py:67-72).  Here every stored
@@ -374,6 +411,15 @@ int vodhip_node_index_log_partition(vodhip_node_index_t* index, const void* quer
 int vodhip_node_index_posterior_mean(vodhip_node_index_t* index, const void* queries, int q_dtype, int64_t nq, float beta,
                                      const int32_t* q_labels /* HOST or NULL */, int n_per_query,
                                      float* out_max, float* out_log_rel /* HOST [nq] */, float* out_mean /* HOST [nq][dim] */);
+/* H2s behind the one handle: HOST buffers, host-synchronous.  Every shard runs vodhip_index_sample_posterior with id_base = its first
+ * global row; keys are unnormalised and the noise is a function of the global row, so the k + 1 best of the union of the shards'
+ * lists ARE the k + 1 best of the whole store: ids, scores and keys equal one index holding all the rows bit for bit.  The pairs are
+ * folded as above, the lists merged by (key desc, id asc) and log_p / log_weight recomputed in double from the folded pair
+ * (sample_fold.h). */
+int vodhip_node_index_sample_posterior(vodhip_node_index_t* index, const void* queries, int q_dtype, int64_t nq, int k, float beta,
+                                       uint64_t seed, int64_t query_offset, const int32_t* q_labels /* HOST or NULL */, int n_per_query,
+                                       float* out_max, float* out_log_rel /* HOST [nq] */, int64_t* out_ids, float* out_scores,
+                                       float* out_log_p, float* out_log_weight /* HOST [nq][k] */, float* out_keys /* HOST [nq][k + 1] */);
 /* With param "profile" = 1 (also set on every shard: their filter launches are bracketed, read per shard through vodhip_index_get_stat on
  * the handle vodhip_node_index_shard returns): "last_merge_ns" = the merge launch on devices[0], from the moment every shard's list had
  * arrived; "last_copy_ns_max" = the slowest shard's copy of its list towards devices[0] (peer copy over xGMI, or the down-leg to pinned

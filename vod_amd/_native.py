@@ -67,6 +67,8 @@ SIGNATURES: dict[str, tuple] = {
     "vodhip_index_search_ids": (_i32, [_vp, _vp, _i32, _i64, _vp, _i64, _i32, _i64, _vp, _i32, _vp, _vp, _vp]),
     "vodhip_index_log_partition": (_i32, [_vp, _vp, _i32, _i64, _c.c_float, _vp, _i32, _vp, _vp, _vp]),
     "vodhip_index_posterior_mean": (_i32, [_vp, _vp, _i32, _i64, _c.c_float, _vp, _i32, _vp, _vp, _vp, _vp]),
+    "vodhip_index_sample_posterior": (
+        _i32, [_vp, _vp, _i32, _i64, _i32, _c.c_float, _c.c_uint64, _i64, _i64, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "vodhip_index_set_row_labels": (_i32, [_vp, _vp, _i64, _i32, _vp]),
     "vodhip_index_set_query_labels": (_i32, [_vp, _vp, _i32]),
     "vodhip_index_set_param": (_i32, [_vp, _c.c_char_p, _i64]),
@@ -94,6 +96,8 @@ SIGNATURES: dict[str, tuple] = {
     "vodhip_node_index_search_ids": (_i32, [_vp, _vp, _i32, _i64, _vp, _i64, _i32, _vp, _i32, _i32, _vp, _vp, _vp]),
     "vodhip_node_index_log_partition": (_i32, [_vp, _vp, _i32, _i64, _c.c_float, _vp, _i32, _vp, _vp]),
     "vodhip_node_index_posterior_mean": (_i32, [_vp, _vp, _i32, _i64, _c.c_float, _vp, _i32, _vp, _vp, _vp]),
+    "vodhip_node_index_sample_posterior": (
+        _i32, [_vp, _vp, _i32, _i64, _i32, _c.c_float, _c.c_uint64, _i64, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "vodhip_merge_topk": (_i32, [_vp, _vp, _i32, _i64, _i32, _i32, _vp, _vp, _vp]),
     "vodhip_merge_topk_strided": (_i32, [_vp, _i64, _vp, _i64, _i32, _i64, _i32, _i32, _vp, _vp, _vp]),
     "vodhip_merge_hybrid": (

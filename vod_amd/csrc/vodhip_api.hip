@@ -4,6 +4,7 @@
 #include "../../include/vodhip.h"
 
 #include <algorithm>
+#include <atomic>
 #include <cmath>
 #include <cstdarg>
 #include <cstdio>
@@ -17,6 +18,7 @@
 
 #include "l2_bias.h"
 #include "partition_fold.h"
+#include "sample_fold.h"
 #include "search_plan.h"
 #include "vodhip_internal.h"
 
@@ -152,6 +154,15 @@ struct vodhip_index {
     int64_t last_overflow = 0, last_chunks = 0, last_survivor_ring = 0, last_ring_fallbacks = 0, last_safe_reruns = 0, last_recovered_queries = 0;
     int64_t last_filter_launches = 0, last_filter_ns = 0;
     int64_t last_recovery_launches = 0, last_recovery_ns = 0;  // filter launches of the recovery passes (with "profile")
+    // the last vodhip_index_sample_posterior: its status words, the emit launches' workgroups, with "profile" the ns per launch
+    std::atomic<int64_t> last_sample[6] = {};      // overflow, selfcheck, max candidates, emit skipped, candidates, emit groups
+    std::atomic<int64_t> last_sample_ns[5] = {};   // partition, keymax, threshold, emit, select
+    // its temporaries: one grow-only block, kept between calls (the call waits for its stream at its end, and a stream-ordered pool
+    // hands its memory back at every such wait: allocating per call cost 1.1 ms of a 3.8 ms call at 256 queries); held by
+    // sample_mu for the length of a call, so two calls on one index run one after the other
+    void* sample_ws = nullptr;
+    size_t sample_ws_bytes = 0;
+    std::mutex sample_mu;
     std::vector<hipEvent_t> ev_pool;  // pairs (start, stop), reused across searches
     size_t ev_used = 0;
     // Every entry point that touches `inflight`, the shared workspace (`ws`, incl. its host-side `extra`) or the event pool holds
@@ -609,6 +620,7 @@ int vodhip_index_destroy(vodhip_index_t* ix) {
         (void)hipFree(ix->l2_sim[i]);
     }
     (void)hipFree(ix->row_label);
+    (void)hipFree(ix->sample_ws);
     (void)hipFree(ix->ovf_q);
     (void)hipFree(ix->q_map);
     (void)hipHostFree(ix->overflow_host);
@@ -1263,6 +1275,126 @@ int vodhip_index_posterior_mean(vodhip_index_t* ix, const void* queries, int q_d
     return 0;
 }
 
+// ---- posterior sampling (kernels_sample_posterior.hip): the log-partition launches, key-max scan, threshold, emit scan, select ------
+int vodhip_index_sample_posterior(vodhip_index_t* ix, const void* queries, int q_dtype, int64_t nq, int k, float beta, uint64_t seed,
+                                  int64_t query_offset, int64_t id_base, const int32_t* q_labels_dev, int n_per_query, float* out_max,
+                                  float* out_log_rel, int64_t* out_ids, float* out_scores, float* out_log_p, float* out_log_weight,
+                                  float* out_keys, void* stream_) {
+    if (!ix) return fail("index is NULL");
+    if (const char* msg = log_partition_args_error(queries, q_dtype, nq, beta, q_labels_dev, n_per_query, out_max, out_log_rel)) {
+        if (!strcmp(msg, "invalid q_dtype")) return fail("invalid q_dtype %d", q_dtype);
+        if (!strncmp(msg, "beta", 4)) return fail("beta=%g: %s", (double)beta, msg);
+        return fail("%s", msg);
+    }
+    if (const char* msg = sample_posterior_args_error(nq, k, query_offset, id_base, out_ids, out_scores, out_log_p, out_log_weight, out_keys)) {
+        if (msg[0] == 'k') return fail("k=%d: %s", k, msg);
+        return fail("%s", msg);
+    }
+    if (ix->l2) return fail("sample_posterior is not supported on an L2 index (VODHIP_L2): its scores are distances, not similarities");
+    if (ix->exact) return fail("sample_posterior is not supported on a VODHIP_EXACT_F32 store: the scan scores the rounded rows, that store's contract is the float32 rows");
+    if (q_labels_dev && !ix->row_label) return fail("set the row labels first (vodhip_index_set_row_labels)");
+    if (nq == 0) return 0;
+    HIP_OK(hipSetDevice(ix->device));
+    hipStream_t stream = (hipStream_t)stream_;
+    PosteriorSampleArgs a;
+    a.p.store = ix->data;
+    a.p.dim = ix->dim;
+    a.p.dim_pad = ix->dim_pad;
+    a.p.ntotal = ix->ntotal;
+    a.p.store_dtype = ix->dtype;
+    a.p.q_src = queries;
+    a.p.q_dtype = q_dtype;
+    a.p.row_label = ix->row_label;
+    a.p.q_label = q_labels_dev;
+    a.p.n_qlab = q_labels_dev ? n_per_query : 0;
+    a.p.beta = beta;
+    a.p.out_max = out_max;
+    a.p.out_log_rel = out_log_rel;
+    a.k = k;
+    a.seed = seed;
+    a.query_offset = query_offset;
+    a.id_base = id_base;
+    a.stride = sample_posterior_stride(a.p.ntotal, k);
+    a.out_ids = out_ids;
+    a.out_scores = out_scores;
+    a.out_log_p = out_log_p;
+    a.out_log_weight = out_log_weight;
+    a.out_keys = out_keys;
+    // queries per slice: a multiple of 128 (or 64) up to 1024 that keeps the candidate lists and the tile words under VODHIP_POSTERIOR_TEMP_BYTES
+    const size_t n_tiles = std::max<size_t>(1, (size_t)log_partition_tiles(a.p.ntotal));
+    const size_t per_query = (size_t)a.stride * 12 + n_tiles * 12;
+    int64_t slice = (int64_t)((size_t)VODHIP_POSTERIOR_TEMP_BYTES / per_query) / 128 * 128;
+    slice = std::min<int64_t>(1024, std::max<int64_t>(64, slice));
+    const int64_t nq_pad = log_partition_nq_pad(std::min(nq, slice));
+    constexpr int NT = 7;
+    const size_t bytes[NT] = {(size_t)nq_pad * (size_t)ix->dim_pad * 2, n_tiles * (size_t)nq_pad * 8, n_tiles * (size_t)nq_pad * 4,
+                              (size_t)nq_pad * (size_t)a.stride * 8, (size_t)nq_pad * (size_t)a.stride * 4,
+                              (size_t)sample_posterior_ctl_words(nq_pad) * 4, 8 * sizeof(unsigned int)};
+    size_t off[NT + 1] = {0};
+    for (int i = 0; i < NT; ++i) off[i + 1] = off[i] + (bytes[i] + 255) / 256 * 256;
+    std::lock_guard<std::mutex> guard(ix->sample_mu);
+    if (ix->sample_ws_bytes < off[NT]) {  // (the previous call has waited for its stream: nothing reads the old block)
+        (void)hipFree(ix->sample_ws);
+        ix->sample_ws = nullptr;
+        ix->sample_ws_bytes = 0;
+        if (hipError_t e = hipMalloc(&ix->sample_ws, off[NT]); e != hipSuccess) {
+            (void)hipGetLastError();
+            ix->sample_ws = nullptr;
+            return fail("hipMalloc of the %zu-byte sampling workspace failed: %s", off[NT], hipGetErrorString(e));
+        }
+        ix->sample_ws_bytes = off[NT];
+    }
+    char* tmp[NT];
+    for (int i = 0; i < NT; ++i) tmp[i] = (char*)ix->sample_ws + off[i];
+    a.p.q_stage = tmp[0];
+    a.p.part = tmp[1];
+    a.keymax = (float*)tmp[2];
+    a.cand_key = tmp[3];
+    a.cand_score = (float*)tmp[4];
+    a.ctl = (unsigned int*)tmp[5];
+    a.status = (unsigned int*)tmp[6];
+    hipEvent_t ev[6] = {};
+    const bool profile = ix->profile != 0;
+    hipError_t le = hipMemsetAsync(a.status, 0, 8 * sizeof(unsigned int), stream);
+    if (profile) {
+        for (int i = 0; i < 6 && le == hipSuccess; ++i) le = hipEventCreate(&ev[i]);
+        a.ev = ev;
+    }
+    double ns[5] = {0, 0, 0, 0, 0};
+    int64_t emit_groups = 0;
+    for (int64_t q0 = 0; q0 < nq && le == hipSuccess; q0 += slice) {
+        const int64_t n = std::min(slice, nq - q0);
+        if (profile) le = hipEventRecord(ev[0], stream);
+        if (le == hipSuccess) le = launch_sample_posterior(a, q0, n, stream);
+        emit_groups += log_partition_tiles(a.p.ntotal) * (log_partition_nq_pad(n) / (n <= 64 ? 64 : 128));
+        if (profile && le == hipSuccess) {  // (one slice at a time: the events are reused)
+            le = hipEventSynchronize(ev[5]);
+            for (int i = 0; i < 5 && le == hipSuccess; ++i) {
+                float ms = 0.f;
+                le = hipEventElapsedTime(&ms, ev[i], ev[i + 1]);
+                ns[i] += (double)ms * 1e6;
+            }
+        }
+    }
+    unsigned int st[8] = {};
+    if (le == hipSuccess) le = hipMemcpyAsync(st, a.status, sizeof(st), hipMemcpyDeviceToHost, stream);
+    if (le != hipSuccess) (void)hipGetLastError();
+    const hipError_t se = hipStreamSynchronize(stream);  // the status words have arrived; the workspace is free for the next call
+    for (int i = 0; i < 6; ++i)
+        if (ev[i]) (void)hipEventDestroy(ev[i]);
+    if (le != hipSuccess) return fail("sample-posterior launch failed: %s", hipGetErrorString(le));
+    HIP_OK(se);
+    ix->last_sample[0] = st[0];
+    ix->last_sample[1] = st[1];
+    ix->last_sample[2] = st[2];
+    ix->last_sample[3] = st[3];
+    ix->last_sample[4] = (int64_t)(((uint64_t)st[5] << 32) | st[4]);
+    ix->last_sample[5] = emit_groups;
+    for (int i = 0; i < 5; ++i) ix->last_sample_ns[i] = (int64_t)ns[i];
+    if (st[0]) return fail("candidate list overflow: %u queries met more than %d tile maxima tied with their threshold", st[0], VODHIP_SAMPLE_SLACK_TILES);
+    return 0;
+}
+
 int vodhip_debug_schedule(int64_t ntotal, int k, int64_t nq, int64_t cand_cap, int64_t dense_rows, int64_t sample_div,
                           int64_t growth_x100, int tile, int recovery_pass, int n_cu, int64_t* out, int max_stages) {
     PlanTunables t;
@@ -1365,6 +1497,28 @@ int vodhip_index_get_stat(const vodhip_index_t* ix, const char* key, int64_t* ou
         *out = ix->last_recovery_launches;
     else if (!strcmp(key, "last_recovery_ns"))
         *out = ix->last_recovery_ns;
+    else if (!strcmp(key, "last_sample_overflow"))
+        *out = ix->last_sample[0];
+    else if (!strcmp(key, "last_sample_selfcheck"))
+        *out = ix->last_sample[1];
+    else if (!strcmp(key, "last_sample_max_candidates"))
+        *out = ix->last_sample[2];
+    else if (!strcmp(key, "last_sample_emit_skipped"))
+        *out = ix->last_sample[3];
+    else if (!strcmp(key, "last_sample_candidates"))
+        *out = ix->last_sample[4];
+    else if (!strcmp(key, "last_sample_emit_groups"))
+        *out = ix->last_sample[5];
+    else if (!strcmp(key, "last_sample_ns_partition"))
+        *out = ix->last_sample_ns[0];
+    else if (!strcmp(key, "last_sample_ns_keymax"))
+        *out = ix->last_sample_ns[1];
+    else if (!strcmp(key, "last_sample_ns_threshold"))
+        *out = ix->last_sample_ns[2];
+    else if (!strcmp(key, "last_sample_ns_emit"))
+        *out = ix->last_sample_ns[3];
+    else if (!strcmp(key, "last_sample_ns_select"))
+        *out = ix->last_sample_ns[4];
     else if (!strcmp(key, "exact"))
         *out = ix->exact ? 1 : 0;
     else if (!strcmp(key, "l2"))

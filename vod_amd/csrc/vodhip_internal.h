@@ -255,6 +255,35 @@ int64_t posterior_mean_groups(int64_t ntotal);
 // [q_first ..); a query's bits do not depend on the split
 hipError_t launch_posterior_mean(const PosteriorArgs& a, int64_t q_first, int64_t nq, hipStream_t stream);
 
+// ---- launchers (kernels_sample_posterior.hip): k rows without replacement from p(z | q) over the whole store --------------------
+struct PosteriorSampleArgs {
+    PartitionArgs p;                  // the log-partition call of the same batch: its launches run first, unchanged
+    int k = 0;                        // 1 .. 255
+    uint64_t seed = 0;
+    int64_t query_offset = 0;         // stream index of query 0 of the caller's batch
+    int64_t id_base = 0;              // global id of row 0
+    int64_t stride = 0;               // candidate slots per query: sample_posterior_stride(ntotal, k)
+    // temporaries, sized for P = log_partition_nq_pad(queries of a launch)
+    float* keymax = nullptr;          // P * log_partition_tiles(ntotal) floats
+    void* cand_key = nullptr;         // P * stride 64-bit keys
+    float* cand_score = nullptr;      // P * stride floats
+    unsigned int* ctl = nullptr;      // sample_posterior_ctl_words(P) words: counters, hit tiles, thresholds (cleared by every launch)
+    unsigned int* status = nullptr;   // 8 words, cleared by the caller once per call: [0] queries whose list overflowed, [1] queries with
+                                      // fewer candidates than hit tiles, [2] largest list, [3] emit workgroups that skipped their K loop,
+                                      // [4..5] candidates in all (64 bits)
+    int64_t* out_ids = nullptr;       // [rows of the caller's batch][k]
+    float* out_scores = nullptr;
+    float* out_log_p = nullptr;
+    float* out_log_weight = nullptr;
+    float* out_keys = nullptr;        // [..][k + 1]
+    hipEvent_t* ev = nullptr;         // NULL, or 6 events: [1] .. [5] are recorded behind the log-partition launches, the key-max scan,
+                                      // the threshold, the emit scan and the select ([0] is the caller's, in front)
+};
+int64_t sample_posterior_stride(int64_t ntotal, int k);
+int64_t sample_posterior_ctl_words(int64_t nq_pad);
+// queries [q_first, q_first + nq) of the caller's batch; a query's bits do not depend on the split
+hipError_t launch_sample_posterior(const PosteriorSampleArgs& a, int64_t q_first, int64_t nq, hipStream_t stream);
+
 // ---- launchers (kernels_hybrid.hip) -----------------------------------------------------------
 struct HybridArgs {
     const int64_t* lookup_idx;

@@ -18,6 +18,7 @@
 #include <vector>
 
 #include "partition_fold.h"
+#include "sample_fold.h"
 #include "vodhip_internal.h"
 
 namespace {
@@ -934,6 +935,83 @@ int vodhip_node_index_posterior_mean(vodhip_node_index_t* nx, const void* querie
     vodhip::fold_log_partition(parts.data(), parts.data() + nq, G, (int64_t)per_shard, nq, beta, out_max, out_log_rel);
     vodhip::fold_posterior_mean(parts.data(), parts.data() + nq, parts.data() + 2 * nq, G, (int64_t)per_shard, (int64_t)per_shard, nq, (int64_t)dim, beta,
                                 out_max, out_log_rel, out_mean);
+    return 0;
+}
+
+// Posterior sampling behind the one handle (H2s): as above; every shard draws with id_base = its first global row, the lists are
+// merged on the host (sample_fold.h).
+int vodhip_node_index_sample_posterior(vodhip_node_index_t* nx, const void* queries, int q_dtype, int64_t nq, int k, float beta, uint64_t seed,
+                                       int64_t query_offset, const int32_t* q_labels, int n_per_query, float* out_max, float* out_log_rel,
+                                       int64_t* out_ids, float* out_scores, float* out_log_p, float* out_log_weight, float* out_keys) {
+    if (!nx) return nfail("index is NULL");
+    if (const char* msg = vodhip::log_partition_args_error(queries, q_dtype, nq, beta, q_labels, n_per_query, out_max, out_log_rel)) {
+        if (!strcmp(msg, "invalid q_dtype")) return nfail("invalid q_dtype %d", q_dtype);
+        if (!strncmp(msg, "beta", 4)) return nfail("beta=%g: %s", (double)beta, msg);
+        return nfail("%s", msg);
+    }
+    if (const char* msg = vodhip::sample_posterior_args_error(nq, k, query_offset, 0, out_ids, out_scores, out_log_p, out_log_weight, out_keys)) {
+        if (msg[0] == 'k') return nfail("k=%d: %s", k, msg);
+        return nfail("%s", msg);
+    }
+    if (nx->dtype & VODHIP_L2) return nfail("sample_posterior is not supported on an L2 index (VODHIP_L2): its scores are distances, not similarities");
+    if (nx->dtype & VODHIP_EXACT_F32) return nfail("sample_posterior is not supported on a VODHIP_EXACT_F32 store: the scan scores the rounded rows, that store's contract is the float32 rows");
+    std::lock_guard<std::mutex> guard(nx->mu);
+    if (q_labels && !nx->has_row_labels) return nfail("set the row labels first (vodhip_node_index_set_row_labels)");
+    if (nq == 0) return 0;
+    const int G = nx->n;
+    const size_t q_bytes = (size_t)nq * (size_t)nx->dim * elem_bytes(q_dtype);
+    const size_t lab_bytes = q_labels ? (size_t)nq * (size_t)n_per_query * sizeof(int32_t) : 0;
+    // shard g, floats: [max | log_rel | scores nq k | log_p | log_weight | keys nq (k + 1)] at g * per_f; ids at g * nq k
+    const size_t rows = (size_t)nq * (size_t)k;
+    const size_t per_f = 2 * (size_t)nq + 3 * rows + (size_t)nq * (size_t)(k + 1);
+    std::vector<float> parts((size_t)G * per_f);
+    std::vector<int64_t> ids((size_t)G * rows);
+    struct Tmp { void* q = nullptr; int32_t* lab = nullptr; float* out = nullptr; int64_t* ids = nullptr; };
+    std::vector<Tmp> tmp((size_t)G);
+    int rc = 0;
+    std::string err;
+    auto hip_step = [&](hipError_t e, const char* what) {
+        if (e != hipSuccess && !rc) {
+            (void)hipGetLastError();
+            err = std::string(what) + " failed: " + hipGetErrorString(e);
+            rc = -1;
+        }
+        return e == hipSuccess;
+    };
+    for (int g = 0; g < G && !rc; ++g) {  // (the flat call waits for its stream: the shards run one after the other)
+        hipStream_t st = nx->stream[g];
+        Tmp& t = tmp[(size_t)g];
+        if (!hip_step(hipSetDevice(nx->device[g]), "hipSetDevice")) break;
+        if (!hip_step(hipMallocAsync(&t.q, q_bytes, st), "hipMallocAsync")) break;
+        if (!hip_step(hipMallocAsync((void**)&t.out, per_f * sizeof(float), st), "hipMallocAsync")) break;
+        if (!hip_step(hipMallocAsync((void**)&t.ids, rows * sizeof(int64_t), st), "hipMallocAsync")) break;
+        if (q_labels && !hip_step(hipMallocAsync((void**)&t.lab, lab_bytes, st), "hipMallocAsync")) break;
+        if (!hip_step(hipMemcpyAsync(t.q, queries, q_bytes, hipMemcpyHostToDevice, st), "hipMemcpyAsync")) break;
+        if (q_labels && !hip_step(hipMemcpyAsync(t.lab, q_labels, lab_bytes, hipMemcpyHostToDevice, st), "hipMemcpyAsync")) break;
+        float* f = t.out;
+        if (vodhip_index_sample_posterior(nx->shard[g], t.q, q_dtype, nq, k, beta, seed, query_offset, g * nx->rows_per_shard, t.lab, n_per_query, f,
+                                          f + nq, t.ids, f + 2 * nq, f + 2 * nq + rows, f + 2 * nq + 2 * rows, f + 2 * nq + 3 * rows, st)) {
+            err = std::string("shard ") + std::to_string(g) + ": " + vodhip_last_error();
+            rc = -1;
+            break;
+        }
+        hip_step(hipMemcpyAsync(parts.data() + (size_t)g * per_f, t.out, per_f * sizeof(float), hipMemcpyDeviceToHost, st), "hipMemcpyAsync");
+        hip_step(hipMemcpyAsync(ids.data() + (size_t)g * rows, t.ids, rows * sizeof(int64_t), hipMemcpyDeviceToHost, st), "hipMemcpyAsync");
+    }
+    for (int g = 0; g < G; ++g) {  // (also after a failure: what was enqueued reads the caller's host buffers)
+        Tmp& t = tmp[(size_t)g];
+        if (hipSetDevice(nx->device[g]) != hipSuccess) continue;
+        if (t.q) (void)hipFreeAsync(t.q, nx->stream[g]);
+        if (t.lab) (void)hipFreeAsync(t.lab, nx->stream[g]);
+        if (t.out) (void)hipFreeAsync(t.out, nx->stream[g]);
+        if (t.ids) (void)hipFreeAsync(t.ids, nx->stream[g]);
+        hip_step(hipStreamSynchronize(nx->stream[g]), "hipStreamSynchronize");
+    }
+    (void)hipSetDevice(nx->device[0]);
+    if (rc) return nfail("%s", err.c_str());
+    vodhip::fold_log_partition(parts.data(), parts.data() + nq, G, (int64_t)per_f, nq, beta, out_max, out_log_rel);
+    vodhip::fold_sample_posterior(parts.data() + 2 * nq + 3 * rows, ids.data(), parts.data() + 2 * nq, G, (int64_t)per_f, (int64_t)rows, (int64_t)per_f, nq, k, beta,
+                                  out_max, out_log_rel, out_ids, out_scores, out_log_p, out_log_weight, out_keys);
     return 0;
 }
 

@@ -400,6 +400,58 @@ class HipFlatIndex:
                 t.record_stream(torch.cuda.current_stream(self.device))
         return PosteriorMean(mean, LogPartition(max_score * beta + log_rel, max_score, log_rel))
 
+    def sample_posterior(self, queries, k: int, temperature: float = 1.0, *, seed: int, query_offset: int = 0, subset=None,
+                         id_base: int = 0, out=None) -> "PosteriorSample":
+        """`k` rows drawn WITHOUT replacement from the softmax over the WHOLE store, `p(z | q) = exp(<q~, x~_z> / temperature - log Z(q))`,
+        with their priority-sampling weights: `PosteriorSample(ids, scores, log_p, log_weight, log_tau, keys, log_partition)`.  `ids`
+        int64 `[nq, k]` (pads -1), `scores` / `log_p` / `log_weight` float32 `[nq, k]` (pads -inf), `keys` float32 `[nq, k + 1]` the
+        unnormalised Gumbel keys `score / temperature - log E` in descending order (pads -inf), `log_tau` `[nq]` the (k+1)-th key minus
+        `log Z` (-inf when every eligible row was returned), `log_partition` the `LogPartition` that `log_partition` returns for the same
+        call, bit for bit.  `sum_j exp(log_weight[q, j]) f(ids[q, j])` is an unbiased estimate of `E_{p(. | q)}[f]`; with
+        `log_tau = -inf` the weights are the probabilities themselves.  Exact over every stored row (no top-K proposal, no `[nq, N]`
+        matrix): three scans on the MFMA path, `1 <= k <= 255`.
+
+        The noise is counter-based (Philox4x32-10): the draw of row `id_base + z` for query `query_offset + i` depends on `seed`, that
+        row id and that query index alone, so a query's result is the same bits alone, inside any batch (give it its `query_offset`),
+        on every repeat, and over shards that pass their own `id_base`.  A query with no eligible row (or a +inf score) is all pads.
+        The call waits for the current stream before it returns (it reads its overflow word).
+
+        Arguments as `log_partition`; `out`: a (max_score, log_rel, ids, scores, log_p, log_weight, keys) tuple to write into."""
+        q = self._prep_queries(queries)
+        nq = q.shape[0]
+        k = int(k)
+        if not 1 <= k <= 255:
+            raise ValueError(f"k must be in [1, 255], got {k}")
+        if not 0 <= int(seed) < 2 ** 64:
+            raise ValueError(f"seed must be in [0, 2^64), got {seed}")
+        beta = 1.0 / float(temperature) if temperature else float("nan")
+        sub, n_sub = None, 0
+        if subset is not None:
+            sub = subset if isinstance(subset, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(subset))
+            sub = sub.to(self.device, torch.int32).contiguous()
+            if sub.ndim != 2 or sub.shape[0] != nq:
+                raise ValueError(f"expected subset labels of shape [{nq}, S], got {tuple(sub.shape)}")
+            n_sub = int(sub.shape[1])
+        if out is None:
+            f32 = dict(dtype=torch.float32, device=self.device)
+            max_score, log_rel = torch.empty((nq,), **f32), torch.empty((nq,), **f32)
+            ids = torch.empty((nq, k), dtype=torch.int64, device=self.device)
+            scores, log_p, log_weight = torch.empty((nq, k), **f32), torch.empty((nq, k), **f32), torch.empty((nq, k), **f32)
+            keys = torch.empty((nq, k + 1), **f32)
+        else:
+            max_score, log_rel, ids, scores, log_p, log_weight, keys = out
+        with torch.cuda.device(self.device):
+            _native.check(self._lib.vodhip_index_sample_posterior(
+                self._h, q.data_ptr(), _native.torch_dtype_code(q.dtype), nq, k, beta, int(seed), int(query_offset), int(id_base),
+                None if sub is None else sub.data_ptr(), n_sub, max_score.data_ptr(), log_rel.data_ptr(), ids.data_ptr(), scores.data_ptr(),
+                log_p.data_ptr(), log_weight.data_ptr(), keys.data_ptr(), _native.current_stream_ptr(self.device)))
+        for t, given in ((q, queries), (sub, subset)):
+            if t is not None and t is not given:
+                t.record_stream(torch.cuda.current_stream(self.device))
+        log_tau = (keys[:, k] - max_score * beta) - log_rel  # (a pad key -inf stays -inf; a query without a finite log Z: NaN -> -inf)
+        log_tau = torch.where(torch.isnan(log_tau), torch.full_like(log_tau, float("-inf")), log_tau)
+        return PosteriorSample(ids, scores, log_p, log_weight, log_tau, keys, LogPartition(max_score * beta + log_rel, max_score, log_rel))
+
     def log_z(self, queries: torch.Tensor, temperature: float = 1.0, subset=None) -> torch.Tensor:
         """`log Z(q)` over the whole store as a float32 `[nq]` tensor that is differentiable with respect to `queries`: forward is
         `posterior_mean`, backward `grad_q = grad_out[:, None] * mean / temperature`, cast to the dtype of `queries` (straight through
@@ -420,6 +472,19 @@ class PosteriorMean(NamedTuple):
     """`mean[q] = sum_z p(z | q) x_z` (`[nq, dim]`) of `posterior_mean`, with the `LogPartition` of the same call."""
 
     mean: Any
+    log_partition: LogPartition
+
+
+class PosteriorSample(NamedTuple):
+    """`k` rows without replacement from `p(z | q)` over the whole store (`sample_posterior`): `ids`, `scores`, `log_p`, `log_weight`
+    `[nq, k]`, `log_tau` `[nq]`, `keys` `[nq, k + 1]`, with the `LogPartition` of the same call."""
+
+    ids: Any
+    scores: Any
+    log_p: Any
+    log_weight: Any
+    log_tau: Any
+    keys: Any
     log_partition: LogPartition
 
 
@@ -747,6 +812,46 @@ class HipNodeIndex:
         with np.errstate(invalid="ignore"):
             log_z = (max_score * np.float32(beta) + log_rel).astype(np.float32)
         return PosteriorMean(mean, LogPartition(log_z, max_score, log_rel))
+
+    def sample_posterior(self, queries, k: int, temperature: float = 1.0, *, seed: int, query_offset: int = 0,
+                         subset: np.ndarray | None = None) -> "PosteriorSample":
+        """`HipFlatIndex.sample_posterior` over every shard: each shard draws with `id_base` = its first global row, the lists are merged
+        on the host by (key desc, id asc) and `log_p` / `log_weight` recomputed in double from the folded `LogPartition`.  Host queries
+        -> `PosteriorSample` of NumPy arrays; `ids`, `scores` and `keys` equal one index holding all the rows bit for bit."""
+        if isinstance(queries, torch.Tensor):
+            queries = queries.detach().float().cpu().numpy()
+        q = np.ascontiguousarray(queries)
+        if q.dtype not in (np.float32, np.float16):
+            q = q.astype(np.float32)
+        if q.ndim != 2 or q.shape[1] != self.dim:
+            raise ValueError(f"expected [nq, {self.dim}] queries, got {tuple(q.shape)}")
+        nq = int(q.shape[0])
+        k = int(k)
+        if not 1 <= k <= 255:
+            raise ValueError(f"k must be in [1, 255], got {k}")
+        if not 0 <= int(seed) < 2 ** 64:
+            raise ValueError(f"seed must be in [0, 2^64), got {seed}")
+        beta = 1.0 / float(temperature) if temperature else float("nan")
+        sub, n_sub = None, 0
+        if subset is not None:
+            sub = np.ascontiguousarray(subset.cpu().numpy() if isinstance(subset, torch.Tensor) else subset, dtype=np.int32)
+            if sub.ndim != 2 or sub.shape[0] != nq:
+                raise ValueError(f"subset must be int32 [nq, n_per_query], got {tuple(sub.shape)}")
+            n_sub = int(sub.shape[1])
+        max_score, log_rel = np.empty((nq,), dtype=np.float32), np.empty((nq,), dtype=np.float32)
+        ids = np.empty((nq, k), dtype=np.int64)
+        scores, log_p, log_weight = (np.empty((nq, k), dtype=np.float32) for _ in range(3))
+        keys = np.empty((nq, k + 1), dtype=np.float32)
+        with torch.cuda.device(self.device):
+            _native.check(self._lib.vodhip_node_index_sample_posterior(
+                self._h, q.ctypes.data, 2 if q.dtype == np.float32 else 0, nq, k, beta, int(seed), int(query_offset),
+                None if sub is None else sub.ctypes.data, n_sub, max_score.ctypes.data, log_rel.ctypes.data, ids.ctypes.data,
+                scores.ctypes.data, log_p.ctypes.data, log_weight.ctypes.data, keys.ctypes.data))
+        with np.errstate(invalid="ignore"):
+            log_z = (max_score * np.float32(beta) + log_rel).astype(np.float32)
+            log_tau = ((keys[:, k] - max_score * np.float32(beta)) - log_rel).astype(np.float32)
+        log_tau[np.isnan(log_tau)] = -np.inf
+        return PosteriorSample(ids, scores, log_p, log_weight, log_tau, keys, LogPartition(log_z, max_score, log_rel))
 
     def score_ids(self, queries, ids, k: int | None = None, *, subset=None, out=None):
         """`HipFlatIndex.score_ids` over every shard: `ids` are global row ids; results equal one index holding all the rows.
