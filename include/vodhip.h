@@ -164,6 +164,31 @@ int vodhip_index_search_ids(vodhip_index_t* index, const void* queries, int q_dt
                             int k, int64_t id_base, const int32_t* q_labels_dev, int n_per_query, float* out_scores,
                             int64_t* out_ids, void* stream);
 
+/* H2w  the WEIGHTED SUM of listed rows (kernels_listed.hip): the backward of H2i's scores with respect to the query, and by itself the
+ * priority-sampling estimate of the posterior mean (ids and exp(log_weight) of H2s), a truncated posterior mean, or a float32 row fetch.
+ *     out[q, d] = sum over the PRESENT slots j with weights[q, j] != 0 of weights[q, j] * x~[ids[q, j] - id_base, d]
+ * `ids_dev` DEVICE int64 [nq, m], `weights_dev` DEVICE float32 [nq, m], `out` DEVICE float32 [nq, dim], dense; any m >= 1.
+ * PRESENCE is H2i's rule (the same device function decides it): id >= 0, id - id_base in [0, ntotal), and the row's label among the
+ * query's `q_labels_dev` (an argument; NULL or all -1 = unrestricted).  An ABSENT slot contributes nothing WHATEVER its weight, NaN and
+ * +-inf included (an upstream gradient at a -inf score is often NaN).  A present slot whose weight is exactly 0.0 (either sign) is
+ * skipped too: its row is not read and cannot contribute NaN or inf.  A query whose slots are all skipped gets the zero row.  A
+ * duplicate id contributes once per slot.  A NaN weight on a present slot makes that query's row NaN, and no other's.
+ * PLANE: fp16 / bf16 stores sum the stored 16-bit rows, widened exactly to float32; VODHIP_EXACT_F32 stores sum the float32 plane -
+ * the plane their H2i scores come from.  Products and sums are float32, each product fused into its add, subnormals kept.
+ * ORDER: one summation order per (query, column), fixed by that query's own ids / weights row and the store's width: it does not
+ * depend on nq, on the query's place in the batch or on the launch; no atomics.  (Slots in runs of 8 in increasing order, the 4 runs of
+ * a 32-slot chunk as ((0 + 1) + 2) + 3, the chunks in increasing order.)
+ * The call only enqueues work on `stream` and never synchronises with the host; lists longer than one chunk keep their partial sums
+ * in a hipMallocAsync temporary on `stream` of at most VODHIP_SUM_IDS_TEMP_BYTES (or one query's), a slice of the batch at a time.
+ * Like H2i it reads the store and the row labels only: it may run on any stream beside searches in flight and from several threads,
+ * and must not overlap add / reset / set_row_labels.  REFUSED (< 0, vodhip_last_error): m < 1, labels without row labels, n_per_query
+ * outside [1, 64], NULL buffers with nq > 0, and an L2 index (its rows carry bias columns and its scores are distances).  nq == 0
+ * returns 0 and writes nothing. */
+#define VODHIP_SUM_IDS_TEMP_BYTES (256ll << 20)
+int vodhip_index_sum_ids(vodhip_index_t* index, const int64_t* ids_dev, const float* weights_dev, int64_t nq, int64_t m, int64_t id_base,
+                         const int32_t* q_labels_dev /* NULL = unrestricted */, int n_per_query, float* out /* DEVICE [nq, dim] */,
+                         void* stream);
+
 /* H2p. The exact softmax normaliser of the retriever over the WHOLE store (kernels_partition.hip):
  *     log Z_beta(q) = log sum_{z < ntotal, eligible} exp(beta * <q~, x~_z>) = beta * out_max[q] + out_log_rel[q]
  * with out_max[q] = the largest score (the bits vodhip_index_search returns at k = 1) and out_log_rel[q] = log sum exp(beta (s - max))
@@ -397,6 +422,15 @@ int vodhip_node_index_score_ids(vodhip_node_index_t* index, const void* queries,
 int vodhip_node_index_search_ids(vodhip_node_index_t* index, const void* queries, int q_dtype, int64_t nq, const int64_t* ids, int64_t m,
                                  int k, const int32_t* q_labels, int n_per_query, int location, float* out_scores, int64_t* out_ids,
                                  void* stream);
+/* H2w behind the one handle: `ids` ([nq, m], GLOBAL row ids), `weights` ([nq, m]), `q_labels` (may be NULL) and `out` ([nq, dim]) are
+ * host buffers (location = VODHIP_HOST) or live on devices[0], under the rule of vodhip_node_index_score_ids.  The batch is replicated
+ * to every shard; shard g runs vodhip_index_sum_ids with id_base = g * R, so that it sums the rows it owns (rows of other shards are
+ * out of its range); the per-shard [nq, dim] sums meet on devices[0] and are added there in INCREASING SHARD ORDER.  The result is
+ * deterministic for a given sharding; it need not be the flat index's bits (the association differs) and is where every sum is exact.
+ * Host-synchronous (the batch travels through host memory); DEVICE outputs are complete on `stream` on return, HOST outputs in place.
+ * Serialised with the other calls on the handle; refusals as for the flat call, and an invalid location. */
+int vodhip_node_index_sum_ids(vodhip_node_index_t* index, const int64_t* ids, const float* weights, int64_t nq, int64_t m,
+                              const int32_t* q_labels, int n_per_query, int location, float* out, void* stream);
 /* H2p behind the one handle: queries, `q_labels` (may be NULL) and both outputs are HOST buffers.  Every shard runs
  * vodhip_index_log_partition on its own device and stream; the 2 * nq floats per shard return through host memory and are folded in
  * increasing shard order: max = max_g max_g, log_rel = log sum_g exp(beta (max_g - max) + log_rel_g); a shard with no eligible row

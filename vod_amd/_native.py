@@ -65,6 +65,7 @@ SIGNATURES: dict[str, tuple] = {
     "vodhip_index_search_finish": (_i32, [_vp, _vp]),
     "vodhip_index_score_ids": (_i32, [_vp, _vp, _i32, _i64, _vp, _i64, _i64, _vp, _i32, _vp, _vp]),
     "vodhip_index_search_ids": (_i32, [_vp, _vp, _i32, _i64, _vp, _i64, _i32, _i64, _vp, _i32, _vp, _vp, _vp]),
+    "vodhip_index_sum_ids": (_i32, [_vp, _vp, _vp, _i64, _i64, _i64, _vp, _i32, _vp, _vp]),
     "vodhip_index_log_partition": (_i32, [_vp, _vp, _i32, _i64, _c.c_float, _vp, _i32, _vp, _vp, _vp]),
     "vodhip_index_posterior_mean": (_i32, [_vp, _vp, _i32, _i64, _c.c_float, _vp, _i32, _vp, _vp, _vp, _vp]),
     "vodhip_index_sample_posterior": (
@@ -94,6 +95,7 @@ SIGNATURES: dict[str, tuple] = {
     "vodhip_node_index_search_finish": (_i32, [_vp]),
     "vodhip_node_index_score_ids": (_i32, [_vp, _vp, _i32, _i64, _vp, _i64, _vp, _i32, _i32, _vp, _vp]),
     "vodhip_node_index_search_ids": (_i32, [_vp, _vp, _i32, _i64, _vp, _i64, _i32, _vp, _i32, _i32, _vp, _vp, _vp]),
+    "vodhip_node_index_sum_ids": (_i32, [_vp, _vp, _vp, _i64, _i64, _vp, _i32, _i32, _vp, _vp]),
     "vodhip_node_index_log_partition": (_i32, [_vp, _vp, _i32, _i64, _c.c_float, _vp, _i32, _vp, _vp]),
     "vodhip_node_index_posterior_mean": (_i32, [_vp, _vp, _i32, _i64, _c.c_float, _vp, _i32, _vp, _vp, _vp]),
     "vodhip_node_index_sample_posterior": (

@@ -1163,6 +1163,55 @@ int vodhip_index_search_ids(vodhip_index_t* ix, const void* queries, int q_dtype
     return 0;
 }
 
+// the weighted sum of listed rows (H2w): the partials of lists longer than one chunk are a stream-ordered temporary of at most
+// VODHIP_SUM_IDS_TEMP_BYTES (or one query's), filled and folded a slice of the batch at a time - a query's bits do not depend on the slice
+int vodhip_index_sum_ids(vodhip_index_t* ix, const int64_t* ids_dev, const float* weights_dev, int64_t nq, int64_t m, int64_t id_base,
+                         const int32_t* q_labels_dev, int n_per_query, float* out, void* stream_) {
+    if (!ix) return fail("index is NULL");
+    if (ix->l2) return fail("listed ids are not supported on an L2 index (VODHIP_L2): sum_ids needs an inner-product store");
+    if (m < 1) return fail("m=%lld: a list holds at least one slot", (long long)m);
+    if (nq < 0 || (nq > 0 && (!ids_dev || !weights_dev || !out))) return fail("invalid id / weight / output pointers");
+    if (q_labels_dev && (n_per_query < 1 || n_per_query > 64)) return fail("n_per_query must be in [1, 64]");
+    if (q_labels_dev && !ix->row_label) return fail("set the row labels first (vodhip_index_set_row_labels)");
+    if (nq == 0) return 0;
+    HIP_OK(hipSetDevice(ix->device));
+    hipStream_t stream = (hipStream_t)stream_;
+    ListedArgs a;
+    a.plane = ix->exact ? (const void*)ix->data32 : (const void*)ix->data;
+    a.stride = ix->dim_pad;
+    a.dim = (int)ix->dim;
+    a.dim_pad = (int)ix->dim_pad;
+    a.store_dtype = ix->dtype;
+    a.exact = ix->exact ? 1 : 0;
+    a.m = m;
+    a.id_base = id_base;
+    a.ntotal = ix->ntotal;
+    a.row_label = ix->row_label;
+    a.n_qlab = q_labels_dev ? n_per_query : 0;
+    const int64_t chunks = listed_sum_chunks(m);
+    const size_t per_query = (size_t)chunks * (size_t)ix->dim * sizeof(float);
+    const int64_t slice = chunks == 1 ? nq : std::min<int64_t>(nq, std::max<int64_t>(1, (int64_t)((size_t)VODHIP_SUM_IDS_TEMP_BYTES / per_query)));
+    if (chunks > 1) {
+        if (hipError_t e = hipMallocAsync((void**)&a.part, per_query * (size_t)slice, stream); e != hipSuccess) {
+            (void)hipGetLastError();
+            return fail("hipMallocAsync of the %zu-byte partial sums failed: %s", per_query * (size_t)slice, hipGetErrorString(e));
+        }
+    }
+    hipError_t le = hipSuccess;
+    for (int64_t q0 = 0; q0 < nq && le == hipSuccess; q0 += slice) {
+        a.ids = ids_dev + q0 * m;
+        a.weights = weights_dev + q0 * m;
+        a.q_label = q_labels_dev ? q_labels_dev + q0 * n_per_query : nullptr;
+        a.out = out + q0 * ix->dim;
+        le = launch_sum_listed(a, std::min(slice, nq - q0), stream);
+    }
+    if (le != hipSuccess) (void)hipGetLastError();
+    const hipError_t fe = a.part ? hipFreeAsync(a.part, stream) : hipSuccess;
+    if (le != hipSuccess) return fail("launch of the listed-row sum failed: %s", hipGetErrorString(le));
+    HIP_OK(fe);
+    return 0;
+}
+
 // ---- log-partition scan (kernels_partition.hip) ---------------------------------------------------------------------------
 // Like the listed calls: reads the store (and the row labels) only; staged queries and partials are stream-ordered temporaries.
 int vodhip_index_log_partition(vodhip_index_t* ix, const void* queries, int q_dtype, int64_t nq, float beta, const int32_t* q_labels_dev,

@@ -200,11 +200,21 @@ struct ListedArgs {
     const int* row_label = nullptr;   // the store's subset labels; read only with q_label
     const int* q_label = nullptr;     // [nq, n_qlab] or NULL = unrestricted
     int n_qlab = 0;
-    float* out = nullptr;             // [nq, m]
+    float* out = nullptr;             // [nq, m]; the weighted sum: [nq, dim]
     int spb = 0;                      // set by the launcher: slots per workgroup, workgroups per query
     int64_t chunks = 0;
+    // the weighted sum of listed rows only (q_src / q_dtype are not read there)
+    const float* weights = nullptr;   // [nq, m]
+    float* part = nullptr;            // temporary: nq * listed_sum_chunks(m) * dim floats; not read when a list is one chunk
 };
 hipError_t launch_score_listed(ListedArgs a, int64_t nq, hipStream_t stream);
+// out[q, :] = sum over the present slots j with weights[q, j] != 0 of weights[q, j] * row(ids[q, j]) (float32 [nq, dim]); one summation
+// order per (query, column), fixed by the query's own list and the store's width
+int64_t listed_sum_chunks(int64_t m);
+hipError_t launch_sum_listed(ListedArgs a, int64_t nq, hipStream_t stream);
+// out[q, d] = parts[0][q, d] + parts[1][q, d] + ... in increasing part order; part p of query q starts at parts + p * part_stride + q * q_stride
+hipError_t launch_fold_listed_sum(const float* parts, int64_t n_parts, int64_t part_stride, int64_t q_stride, int64_t nq, int dim, float* out,
+                                  hipStream_t stream);
 // out[i] = parts[owner(ids[i])][i], owner = id / rows_per_shard; -inf where no shard owns the id.  parts: [n_shards][n]
 hipError_t launch_combine_listed(const float* parts, const int64_t* ids, int64_t n, int n_shards, int64_t rows_per_shard, float* out,
                                  hipStream_t stream);

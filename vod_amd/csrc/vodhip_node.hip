@@ -811,6 +811,111 @@ int vodhip_node_index_search_ids(vodhip_node_index_t* nx, const void* queries, i
     return node_listed(nx, queries, q_dtype, nq, ids, m, k, q_labels, n_per_query, location, out_scores, out_ids, stream);
 }
 
+// The weighted sum of listed rows behind the one handle (include/vodhip.h, H2w).  The route of node_listed: the batch through host
+// memory to every shard, shard g sums the rows it owns (id_base = g * R), the [nq, dim] sums return through host memory to devices[0]
+// and are added there in increasing shard order by the kernel that adds a list's chunks.
+int vodhip_node_index_sum_ids(vodhip_node_index_t* nx, const int64_t* ids, const float* weights, int64_t nq, int64_t m, const int32_t* q_labels,
+                              int n_per_query, int location, float* out, void* stream_) {
+    if (!nx) return nfail("index is NULL");
+    if (nx->dtype & VODHIP_L2) return nfail("listed ids are not supported on an L2 index (VODHIP_L2): sum_ids needs an inner-product store");
+    if (m < 1) return nfail("m=%lld: a list holds at least one slot", (long long)m);
+    if (nq < 0 || (nq > 0 && (!ids || !weights || !out))) return nfail("invalid id / weight / output pointers");
+    if (location != VODHIP_HOST && location != VODHIP_DEVICE) return nfail("invalid location %d", location);
+    if (q_labels && (n_per_query < 1 || n_per_query > 64)) return nfail("n_per_query must be in [1, 64]");
+    std::lock_guard<std::mutex> guard(nx->mu);
+    if (q_labels && !nx->has_row_labels) return nfail("set the row labels first (vodhip_node_index_set_row_labels)");
+    if (nq == 0) return 0;
+    const int G = nx->n, dev0 = nx->device[0];
+    hipStream_t user = location == VODHIP_DEVICE ? (hipStream_t)stream_ : nx->merge_stream;
+    const size_t n = (size_t)nq * (size_t)m, n_out = (size_t)nq * (size_t)nx->dim;
+    const size_t lab_bytes = q_labels ? (size_t)nq * (size_t)n_per_query * sizeof(int32_t) : 0;
+    // 1. the batch in host memory
+    std::vector<int64_t> hi;
+    std::vector<float> hw;
+    std::vector<char> hl;
+    const int64_t* ids_host = ids;
+    const float* w_host = weights;
+    const int32_t* lab_host = q_labels;
+    NODE_HIP_OK(hipSetDevice(dev0));
+    if (location == VODHIP_DEVICE) {
+        hi.resize(n);
+        hw.resize(n);
+        hl.resize(lab_bytes);
+        NODE_HIP_OK(hipMemcpyAsync(hi.data(), ids, n * sizeof(int64_t), hipMemcpyDeviceToHost, user));
+        NODE_HIP_OK(hipMemcpyAsync(hw.data(), weights, n * sizeof(float), hipMemcpyDeviceToHost, user));
+        if (q_labels) NODE_HIP_OK(hipMemcpyAsync(hl.data(), q_labels, lab_bytes, hipMemcpyDeviceToHost, user));
+        NODE_HIP_OK(hipStreamSynchronize(user));
+        ids_host = hi.data();
+        w_host = hw.data();
+        lab_host = q_labels ? (const int32_t*)hl.data() : nullptr;
+    }
+    // 2. every shard sums its own rows (the devices run side by side: nothing is waited for until every shard is enqueued)
+    std::vector<float> parts((size_t)G * n_out);
+    struct Tmp { int64_t* ids = nullptr; float* w = nullptr; int32_t* lab = nullptr; float* out = nullptr; };
+    std::vector<Tmp> tmp((size_t)G);
+    int rc = 0;
+    std::string err;
+    auto hip_step = [&](hipError_t e, const char* what) {
+        if (e != hipSuccess && !rc) {
+            (void)hipGetLastError();
+            err = std::string(what) + " failed: " + hipGetErrorString(e);
+            rc = -1;
+        }
+        return e == hipSuccess;
+    };
+    for (int g = 0; g < G && !rc; ++g) {
+        hipStream_t st = nx->stream[g];
+        Tmp& t = tmp[(size_t)g];
+        if (!hip_step(hipSetDevice(nx->device[g]), "hipSetDevice")) break;
+        if (!hip_step(hipMallocAsync((void**)&t.ids, n * sizeof(int64_t), st), "hipMallocAsync")) break;
+        if (!hip_step(hipMallocAsync((void**)&t.w, n * sizeof(float), st), "hipMallocAsync")) break;
+        if (!hip_step(hipMallocAsync((void**)&t.out, n_out * sizeof(float), st), "hipMallocAsync")) break;
+        if (lab_host && !hip_step(hipMallocAsync((void**)&t.lab, lab_bytes, st), "hipMallocAsync")) break;
+        if (!hip_step(hipMemcpyAsync(t.ids, ids_host, n * sizeof(int64_t), hipMemcpyHostToDevice, st), "hipMemcpyAsync")) break;
+        if (!hip_step(hipMemcpyAsync(t.w, w_host, n * sizeof(float), hipMemcpyHostToDevice, st), "hipMemcpyAsync")) break;
+        if (lab_host && !hip_step(hipMemcpyAsync(t.lab, lab_host, lab_bytes, hipMemcpyHostToDevice, st), "hipMemcpyAsync")) break;
+        if (vodhip_index_sum_ids(nx->shard[g], t.ids, t.w, nq, m, g * nx->rows_per_shard, t.lab, n_per_query, t.out, st)) {
+            err = std::string("shard ") + std::to_string(g) + ": " + vodhip_last_error();
+            rc = -1;
+            break;
+        }
+        hip_step(hipMemcpyAsync(parts.data() + (size_t)g * n_out, t.out, n_out * sizeof(float), hipMemcpyDeviceToHost, st), "hipMemcpyAsync");
+    }
+    for (int g = 0; g < G; ++g) {  // (also after a failure: what was enqueued reads the host vectors of this frame)
+        Tmp& t = tmp[(size_t)g];
+        if (hipSetDevice(nx->device[g]) != hipSuccess) continue;
+        if (t.ids) (void)hipFreeAsync(t.ids, nx->stream[g]);
+        if (t.w) (void)hipFreeAsync(t.w, nx->stream[g]);
+        if (t.lab) (void)hipFreeAsync(t.lab, nx->stream[g]);
+        if (t.out) (void)hipFreeAsync(t.out, nx->stream[g]);
+        hip_step(hipStreamSynchronize(nx->stream[g]), "hipStreamSynchronize");
+    }
+    (void)hipSetDevice(dev0);
+    if (rc) return nfail("%s", err.c_str());
+    // 3. on devices[0]: the shards' sums added in increasing shard order
+    float *d_parts = nullptr, *d_out = nullptr;
+    auto steps = [&]() -> int {
+        NODE_HIP_OK(hipMallocAsync((void**)&d_parts, (size_t)G * n_out * sizeof(float), user));
+        NODE_HIP_OK(hipMemcpyAsync(d_parts, parts.data(), (size_t)G * n_out * sizeof(float), hipMemcpyHostToDevice, user));
+        float* sum = out;
+        if (location == VODHIP_HOST) {
+            NODE_HIP_OK(hipMallocAsync((void**)&d_out, n_out * sizeof(float), user));
+            sum = d_out;
+        }
+        NODE_HIP_OK(vodhip::launch_fold_listed_sum(d_parts, G, (int64_t)n_out, nx->dim, nq, (int)nx->dim, sum, user));
+        if (location == VODHIP_HOST) NODE_HIP_OK(hipMemcpyAsync(out, sum, n_out * sizeof(float), hipMemcpyDeviceToHost, user));
+        return 0;
+    };
+    rc = steps();
+    const std::string keep = rc ? vodhip_last_error() : "";
+    for (void* p : {(void*)d_parts, (void*)d_out})
+        if (p) (void)hipFreeAsync(p, user);
+    const hipError_t se = hipStreamSynchronize(user);  // (`parts` was the source of a copy on `user`)
+    if (rc) return nfail("%s", keep.c_str());
+    NODE_HIP_OK(se);
+    return 0;
+}
+
 // The log-partition scan behind the one handle (include/vodhip.h, H2p): host queries and labels are replicated to every shard, every
 // shard runs the flat call on its own device and stream, the 2 * nq floats per shard return through host memory and are folded there in
 // increasing shard order (partition_fold.h).  No peer copies, no streams beyond the shards' own.

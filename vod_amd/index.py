@@ -34,6 +34,24 @@ def pad_listed_ids(ids, nq: int | None = None) -> np.ndarray:
     return arr
 
 
+def pad_listed_weights(weights, shape: tuple[int, int]) -> np.ndarray:
+    """`weights` of `sum_ids` as a C-contiguous float32 NumPy array of `shape` = the shape of the padded ids: an array is taken as it is,
+    a ragged list of lists is padded with 0 (a zero weight skips its slot)."""
+    if isinstance(weights, np.ndarray):
+        arr = weights
+    else:
+        rows = [np.asarray(r, dtype=np.float32).reshape(-1) for r in weights]
+        if len(rows) != shape[0] or any(len(r) > shape[1] for r in rows):
+            raise ValueError(f"expected weights of shape {tuple(shape)}, got {len(rows)} rows of up to {max((len(r) for r in rows), default=0)}")
+        arr = np.zeros(shape, dtype=np.float32)
+        for i, r in enumerate(rows):
+            arr[i, : len(r)] = r
+    arr = np.ascontiguousarray(arr, dtype=np.float32)
+    if arr.shape != tuple(shape):
+        raise ValueError(f"expected weights of shape {tuple(shape)}, got {tuple(arr.shape)}")
+    return arr
+
+
 class HipFlatIndex:
     """Exact MIPS index: row-major fp16/bf16 rows in HBM, searched by the fused MFMA + top-k kernels.
 
@@ -332,6 +350,59 @@ class HipFlatIndex:
                 t.record_stream(torch.cuda.current_stream(self.device))
         return res
 
+    def sum_ids(self, ids, weights, *, subset=None, id_base: int = 0, out=None) -> torch.Tensor:
+        """The weighted sum of LISTED rows, `out[q] = sum_j weights[q, j] * x~[ids[q, j] - id_base]`: float32 `[nq, dim]` on the device
+        (`out`: that tensor).  It is the backward of `score_ids` with respect to the queries (`listed_scores` wires it); with `ids` and
+        `exp(log_weight)` of `sample_posterior` it is the priority-sampling estimate of `posterior_mean`, with top-k ids and softmax
+        weights the truncated posterior mean, with one-hot weights a row fetch in float32.
+
+        `ids` as in `score_ids`; `weights`: float32 `[nq, m]` tensor / array, or a ragged list of lists (padded with 0).  A slot that
+        `score_ids` scores -inf (empty, out of range, outside the query's `subset`) contributes nothing whatever its weight - NaN and inf
+        included; a present slot with weight 0.0 is skipped as well (its row is not read).  All slots skipped: the zero row.  Duplicates
+        add.  fp16 / bf16 stores sum the stored rows widened to float32, an `exact_f32` store its float32 rows.  One summation order per
+        query, fixed by its own list and the width of the store: the bits of a row do not depend on the batch around it.
+        Enqueued on the current stream; nothing to finish, and safe beside searches of this index that are in flight.
+        An L2 index refuses (the library's message)."""
+        if isinstance(ids, torch.Tensor):
+            lst = ids.to(self.device, torch.int64).contiguous()
+            if lst.ndim != 2:
+                raise ValueError(f"expected ids of shape [nq, m], got {tuple(lst.shape)}")
+        else:
+            lst = torch.from_numpy(pad_listed_ids(ids)).to(self.device)
+        nq, m = int(lst.shape[0]), int(lst.shape[1])
+        if isinstance(weights, torch.Tensor):
+            w = weights.to(self.device, torch.float32).contiguous()
+            if tuple(w.shape) != (nq, m):
+                raise ValueError(f"expected weights of shape {(nq, m)}, got {tuple(w.shape)}")
+        else:
+            w = torch.from_numpy(pad_listed_weights(weights, (nq, m))).to(self.device)
+        sub, n_sub = None, 0
+        if subset is not None:
+            sub = subset if isinstance(subset, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(subset))
+            sub = sub.to(self.device, torch.int32).contiguous()
+            if sub.ndim != 2 or sub.shape[0] != nq:
+                raise ValueError(f"expected subset labels of shape [{nq}, S], got {tuple(sub.shape)}")
+            n_sub = int(sub.shape[1])
+        res = torch.empty((nq, self.dim), dtype=torch.float32, device=self.device) if out is None else out
+        with torch.cuda.device(self.device):
+            _native.check(self._lib.vodhip_index_sum_ids(self._h, lst.data_ptr(), w.data_ptr(), nq, m, int(id_base),
+                                                         None if sub is None else sub.data_ptr(), n_sub, res.data_ptr(),
+                                                         _native.current_stream_ptr(self.device)))
+        for t, given in ((lst, ids), (w, weights), (sub, subset)):  # (the rule of score_ids: copies this call made outlive the launch)
+            if t is not None and t is not given:
+                t.record_stream(torch.cuda.current_stream(self.device))
+        return res
+
+    def listed_scores(self, queries: torch.Tensor, ids, *, subset=None, id_base: int = 0) -> torch.Tensor:
+        """`score_ids(queries, ids)` - the same bits, -inf at absent slots - as a float32 `[nq, m]` tensor that is differentiable (once)
+        with respect to `queries`: backward is `sum_ids(ids, grad_out)`, cast to the dtype and device of `queries` (straight through the
+        rounding of the queries to the store dtype, as `log_z`).  The gradient at absent slots vanishes by the presence rule of `sum_ids`,
+        whatever arrives there (NaN included); no gradient flows to the store.  With `sample_posterior`:
+        `s = index.sample_posterior(q, k, seed=...)`, `index.listed_scores(q, s.ids)` are the sampled scores as a function of `q`."""
+        if not isinstance(ids, torch.Tensor):
+            ids = torch.from_numpy(pad_listed_ids(ids, int(queries.shape[0]))).to(self.device)
+        return _ListedScores.apply(queries, self, ids, {"subset": subset, "id_base": id_base})
+
 
     def log_partition(self, queries, temperature: float = 1.0, subset=None, out=None) -> LogPartition:
         """The exact softmax normaliser over the WHOLE store, `log Z(q) = log sum_z exp(<q~, x~_z> / temperature)`, from one scan on
@@ -512,6 +583,31 @@ class _LogZ(torch.autograd.Function):
         mean, log_z = ctx.saved_tensors
         g = log_z_backward(grad_out.to(mean.device), mean, log_z, ctx.beta, ctx.q_dtype)
         return g.to(ctx.q_device), None, None, None
+
+
+def listed_scores_backward(index, ids, grad_out: torch.Tensor, dtype: torch.dtype, device: torch.device, **kw) -> torch.Tensor:
+    """The backward of `listed_scores`: `index.sum_ids(ids, grad_out, **kw)` cast to `dtype` on `device`.  Absent slots drop out inside
+    `sum_ids` whatever their gradient (NaN at a -inf score included): nothing is masked here."""
+    g = index.sum_ids(ids, grad_out, **kw)
+    if not isinstance(g, torch.Tensor):
+        g = torch.as_tensor(g)
+    return g if g.dtype == dtype and g.device == device else g.to(device=device, dtype=dtype)
+
+
+class _ListedScores(torch.autograd.Function):
+    """`index.listed_scores`: `index` is anything with `score_ids(queries, ids, **kw)` and `sum_ids(ids, weights, **kw)`."""
+
+    @staticmethod
+    def forward(ctx, queries, index, ids, kw):
+        scores = torch.as_tensor(index.score_ids(queries.detach(), ids, **kw))
+        ctx.index, ctx.ids, ctx.kw = index, ids, kw
+        ctx.q_dtype, ctx.q_device = queries.dtype, queries.device
+        return scores
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_out):
+        return listed_scores_backward(ctx.index, ctx.ids, grad_out, ctx.q_dtype, ctx.q_device, **ctx.kw), None, None, None
 
 
 def topk_log_coverage(scores: torch.Tensor, log_partition: LogPartition, temperature: float = 1.0) -> torch.Tensor:
@@ -904,3 +1000,48 @@ class HipNodeIndex:
             _native.check(self._lib.vodhip_node_index_search_ids(self._h, ptr(q), code, nq, ptr(lst), m, int(k), ptr(sub), n_sub, loc,
                                                                  ptr(scores), ptr(top), stream))
         return scores, top
+
+    def sum_ids(self, ids, weights, *, subset=None, out=None):
+        """`HipFlatIndex.sum_ids` over every shard: `ids` are global row ids; every shard sums the rows it owns, the per-shard sums are
+        added on `devices[0]` in increasing shard order - deterministic for a given sharding, the flat index's bits where every sum is
+        exact.  `weights` a tensor on `devices[0]` -> a tensor there, complete on the current stream; host weights (NumPy, a CPU tensor,
+        ragged lists) -> a NumPy array.  `ids` / `subset` may be host arrays, ragged lists (ids) or tensors whatever the weights are."""
+        on_device = isinstance(weights, torch.Tensor) and weights.is_cuda
+        if on_device:
+            if weights.device != self.device:
+                raise ValueError(f"weights live on {weights.device}, the merge device is {self.device}")
+            lst = ids.to(self.device, torch.int64).contiguous() if isinstance(ids, torch.Tensor) else torch.from_numpy(pad_listed_ids(ids)).to(self.device)
+            w = weights.to(torch.float32).contiguous()
+            sub = None if subset is None else (subset if isinstance(subset, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(subset))).to(self.device, torch.int32).contiguous()
+        else:
+            lst = pad_listed_ids(ids.cpu().numpy() if isinstance(ids, torch.Tensor) else ids)
+            w = pad_listed_weights(weights.detach().float().numpy() if isinstance(weights, torch.Tensor) else weights, lst.shape)
+            sub = None if subset is None else np.ascontiguousarray(subset.cpu().numpy() if isinstance(subset, torch.Tensor) else subset, dtype=np.int32)
+        if lst.ndim != 2:
+            raise ValueError(f"expected ids of shape [nq, m], got {tuple(lst.shape)}")
+        nq, m = int(lst.shape[0]), int(lst.shape[1])
+        if tuple(w.shape) != (nq, m):
+            raise ValueError(f"expected weights of shape {(nq, m)}, got {tuple(w.shape)}")
+        if sub is not None and (sub.ndim != 2 or sub.shape[0] != nq):
+            raise ValueError(f"subset must be int32 [nq, n_per_query], got {tuple(sub.shape)}")
+        n_sub = 0 if sub is None else int(sub.shape[1])
+        ptr = (lambda t: None if t is None else t.data_ptr()) if on_device else (lambda a: None if a is None else a.ctypes.data)
+        if out is not None:
+            res = out
+        elif on_device:
+            res = torch.empty((nq, self.dim), dtype=torch.float32, device=self.device)
+        else:
+            res = np.empty((nq, self.dim), dtype=np.float32)
+        with torch.cuda.device(self.device):
+            stream = _native.current_stream_ptr(self.device) if on_device else None
+            _native.check(self._lib.vodhip_node_index_sum_ids(self._h, ptr(lst), ptr(w), nq, m, ptr(sub), n_sub,
+                                                              _native.DEVICE if on_device else _native.HOST, ptr(res), stream))
+        return res
+
+    def listed_scores(self, queries: torch.Tensor, ids, *, subset=None) -> torch.Tensor:
+        """`HipFlatIndex.listed_scores` over every shard: the bits of `score_ids`, differentiable (once) with respect to `queries`;
+        backward is this index's `sum_ids`.  The scores live on `devices[0]` (queries elsewhere are copied there); the gradient arrives
+        in the dtype and on the device of `queries`."""
+        if not isinstance(ids, torch.Tensor):
+            ids = torch.from_numpy(pad_listed_ids(ids, int(queries.shape[0]))).to(self.device)
+        return _ListedScores.apply(queries.to(self.device), self, ids, {"subset": subset})
