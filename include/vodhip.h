@@ -274,6 +274,42 @@ int vodhip_index_sample_posterior(vodhip_index_t* index, const void* queries, in
                                   int64_t* out_ids /* DEVICE [nq][k] */, float* out_scores, float* out_log_p,
                                   float* out_log_weight /* DEVICE [nq][k] */, float* out_keys /* DEVICE [nq][k + 1] */, void* stream);
 
+/* H2r. Exact RANKS over the whole store (kernels_rank.hip): at what position would a search return a given row, however deep - and how
+ * many rows score above a threshold.  Replaces: nothing in the reference - its metrics see ranks only inside the truncated result
+ * list, so MRR / hit@k / mean rank treat "rank 2049" and "rank 9 million" as the same miss.
+ * ELIGIBLE rows are H2p's: below ntotal, scan score not NaN, allowed by `q_labels_dev`.  ORDER is the search's: scores compare by
+ * their result key (-0.0 == +0.0), ties go to the smaller id.  For a threshold t and a tie id r
+ *     C(q; t, r) = #{ eligible rows z : s(q, z) > t  or  (s(q, z) == t and id_base + z < r) }.
+ *   vodhip_index_count_above     out_counts[q, j] = C(q; thresholds[q, j], tie_ids[q, j]); tie_ids_dev NULL: the strict count.  A NaN
+ *                                threshold gives -1.
+ *   vodhip_index_rank_ids        out_scores[q, j] = the SCAN's score of row ids[q, j] - the bits vodhip_index_search returns for the
+ *                                pair (H2i's order of summation is another one) - and out_ranks[q, j] = C(q; that score, ids[q, j]):
+ *                                the 0-based position at which a search over the eligible rows returns the row.  PRESENT is H2i's rule;
+ *                                an absent slot gives (-1, -inf), a NaN score rank -1 with the score as computed.  Duplicate ids are
+ *                                independent slots.
+ *   vodhip_index_scan_score_ids  the scores alone (no scan of the store: the listed rows are gathered and multiplied on the MFMA with
+ *                                the scan's K loop); out_rows (may be NULL): DEVICE int32 [nq, m], the local row of a present slot, -1
+ *                                of an absent one - a present row with a -inf score and an absent slot both score -inf.
+ * 1 <= m <= VODHIP_RANK_MAX_LISTED; the cost of the scan's epilogue is linear in m.  One scan of the store on the MFMA path with integer
+ * compares in place of the top-k; nothing of size [nq, N].  Counts are integer sums: the same on every repeat and whatever the batch.
+ * Temporaries are hipMallocAsync on `stream` (staged queries, the gathered rows, 12 bytes per slot), batches run in slices of 64 .. 1024
+ * queries so that they stay at or below VODHIP_POSTERIOR_TEMP_BYTES unless a 64-query slice alone needs more.  The calls only enqueue
+ * work and never synchronise with the host; they use neither the search workspace nor the index's query labels: they may run beside
+ * searches in flight; they must not overlap add / reset / set_row_labels.  nq == 0 returns 0 and writes nothing.
+ * REFUSED, each with its own vodhip_last_error: NULL index / pointers with nq > 0, q_dtype outside 0..2, m outside [1, 64], n_per_query
+ * outside [1, 64], labels without row labels, VODHIP_L2 and VODHIP_EXACT_F32 stores (H2p's reasons). */
+#define VODHIP_RANK_MAX_LISTED 64
+int vodhip_index_count_above(vodhip_index_t* index, const void* queries, int q_dtype, int64_t nq, const float* thresholds_dev,
+                             const int64_t* tie_ids_dev /* NULL = strict */, int64_t m, int64_t id_base,
+                             const int32_t* q_labels_dev /* NULL = unrestricted */, int n_per_query,
+                             int64_t* out_counts /* DEVICE [nq][m] */, void* stream);
+int vodhip_index_rank_ids(vodhip_index_t* index, const void* queries, int q_dtype, int64_t nq, const int64_t* ids_dev, int64_t m,
+                          int64_t id_base, const int32_t* q_labels_dev /* NULL = unrestricted */, int n_per_query,
+                          int64_t* out_ranks /* DEVICE [nq][m] */, float* out_scores /* DEVICE [nq][m] */, void* stream);
+int vodhip_index_scan_score_ids(vodhip_index_t* index, const void* queries, int q_dtype, int64_t nq, const int64_t* ids_dev, int64_t m,
+                                int64_t id_base, const int32_t* q_labels_dev /* NULL = unrestricted */, int n_per_query,
+                                float* out_scores /* DEVICE [nq][m] */, int32_t* out_rows /* DEVICE [nq][m], or NULL */, void* stream);
+
 /* Optional subset filter.  The reference's SearchClient.search carries `subset_ids`; its Elasticsearch and
  * Qdrant engines restrict hits to sections whose subset id is listed (src/vod_search/es_search/client.py:185-191,
  * qdrant_search/client.py:124-136) while its faiss client ignores it (faiss_search/client.py:67-72).  Here every stored
@@ -439,6 +475,18 @@ int vodhip_node_index_sum_ids(vodhip_node_index_t* index, const int64_t* ids, co
 int vodhip_node_index_log_partition(vodhip_node_index_t* index, const void* queries, int q_dtype, int64_t nq, float beta,
                                     const int32_t* q_labels /* HOST or NULL */, int n_per_query,
                                     float* out_max, float* out_log_rel /* HOST [nq] */);
+/* H2r behind the one handle: queries, ids / thresholds / tie ids, `q_labels` (may be NULL) and the outputs are HOST buffers; ids are
+ * GLOBAL row ids.  rank_ids: every shard picks the scan scores of the ids it owns (vodhip_index_scan_score_ids with id_base = its
+ * first global row), the host combines them by ownership - no values are compared -, every shard counts its rows against the combined
+ * (score, global id) pairs (vodhip_index_count_above), and the host adds the counts in int64 (rank_fold.h).  count_above: the last two
+ * steps alone.  Ranks, counts and scores equal one index holding all the rows bit for bit.  Host-synchronous; serialised with the
+ * other calls on the handle; refusals as for the flat calls. */
+int vodhip_node_index_rank_ids(vodhip_node_index_t* index, const void* queries, int q_dtype, int64_t nq, const int64_t* ids, int64_t m,
+                               const int32_t* q_labels /* HOST or NULL */, int n_per_query,
+                               int64_t* out_ranks, float* out_scores /* HOST [nq][m] */);
+int vodhip_node_index_count_above(vodhip_node_index_t* index, const void* queries, int q_dtype, int64_t nq, const float* thresholds,
+                                  const int64_t* tie_ids /* HOST or NULL = strict */, int64_t m,
+                                  const int32_t* q_labels /* HOST or NULL */, int n_per_query, int64_t* out_counts /* HOST [nq][m] */);
 /* H2m behind the one handle: HOST buffers, as above.  Every shard runs vodhip_index_posterior_mean; the shards are folded on the host
  * in increasing shard order, in double: the pair as above, mean = sum_g w_g mean_g with w_g = exp(beta (max_g - max) + log_rel_g -
  * log_rel); a shard with no eligible row carries weight 0 (its row is not read).  No eligible row anywhere, or a +inf score: zeros. */

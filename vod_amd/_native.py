@@ -68,6 +68,9 @@ SIGNATURES: dict[str, tuple] = {
     "vodhip_index_sum_ids": (_i32, [_vp, _vp, _vp, _i64, _i64, _i64, _vp, _i32, _vp, _vp]),
     "vodhip_index_log_partition": (_i32, [_vp, _vp, _i32, _i64, _c.c_float, _vp, _i32, _vp, _vp, _vp]),
     "vodhip_index_posterior_mean": (_i32, [_vp, _vp, _i32, _i64, _c.c_float, _vp, _i32, _vp, _vp, _vp, _vp]),
+    "vodhip_index_count_above": (_i32, [_vp, _vp, _i32, _i64, _vp, _vp, _i64, _i64, _vp, _i32, _vp, _vp]),
+    "vodhip_index_rank_ids": (_i32, [_vp, _vp, _i32, _i64, _vp, _i64, _i64, _vp, _i32, _vp, _vp, _vp]),
+    "vodhip_index_scan_score_ids": (_i32, [_vp, _vp, _i32, _i64, _vp, _i64, _i64, _vp, _i32, _vp, _vp, _vp]),
     "vodhip_index_sample_posterior": (
         _i32, [_vp, _vp, _i32, _i64, _i32, _c.c_float, _c.c_uint64, _i64, _i64, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "vodhip_index_set_row_labels": (_i32, [_vp, _vp, _i64, _i32, _vp]),
@@ -98,6 +101,8 @@ SIGNATURES: dict[str, tuple] = {
     "vodhip_node_index_sum_ids": (_i32, [_vp, _vp, _vp, _i64, _i64, _vp, _i32, _i32, _vp, _vp]),
     "vodhip_node_index_log_partition": (_i32, [_vp, _vp, _i32, _i64, _c.c_float, _vp, _i32, _vp, _vp]),
     "vodhip_node_index_posterior_mean": (_i32, [_vp, _vp, _i32, _i64, _c.c_float, _vp, _i32, _vp, _vp, _vp]),
+    "vodhip_node_index_rank_ids": (_i32, [_vp, _vp, _i32, _i64, _vp, _i64, _vp, _i32, _vp, _vp]),
+    "vodhip_node_index_count_above": (_i32, [_vp, _vp, _i32, _i64, _vp, _vp, _i64, _vp, _i32, _vp]),
     "vodhip_node_index_sample_posterior": (
         _i32, [_vp, _vp, _i32, _i64, _i32, _c.c_float, _c.c_uint64, _i64, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "vodhip_merge_topk": (_i32, [_vp, _vp, _i32, _i64, _i32, _i32, _vp, _vp, _vp]),

@@ -19,6 +19,7 @@
 #include "l2_bias.h"
 #include "partition_fold.h"
 #include "sample_fold.h"
+#include "rank_fold.h"
 #include "search_plan.h"
 #include "vodhip_internal.h"
 
@@ -1260,6 +1261,103 @@ int vodhip_index_log_partition(vodhip_index_t* ix, const void* queries, int q_dt
     HIP_OK(f1);
     HIP_OK(f2);
     return 0;
+}
+
+// ---- exact ranks (kernels_rank.hip): pick the listed pairs' scan scores, count the store against them -----------------------------
+// Like the log-partition call: reads the store (and the row labels) only; every temporary is stream-ordered.
+static int rank_call(vodhip_index_t* ix, int mode, const char* what, const void* queries, int q_dtype, int64_t nq, const int64_t* ids_dev,
+                     const float* thresholds_dev, const int64_t* tie_ids_dev, int64_t m, int64_t id_base, const int32_t* q_labels_dev,
+                     int n_per_query, int64_t* out_counts, float* out_scores, int32_t* out_rows, hipStream_t stream) {
+    if (!ix) return fail("index is NULL");
+    if (const char* msg = rank_args_error(queries, q_dtype, nq, m, q_labels_dev, n_per_query)) {
+        if (!strcmp(msg, "invalid q_dtype")) return fail("invalid q_dtype %d", q_dtype);
+        if (msg[0] == 'm') return fail("m=%lld: %s", (long long)m, msg + 2);
+        return fail("%s", msg);
+    }
+    if (nq > 0) {
+        if (mode != RANK_MODE_THRESHOLDS && !ids_dev) return fail("ids is NULL");
+        if (mode == RANK_MODE_THRESHOLDS && !thresholds_dev) return fail("thresholds is NULL");
+        if (mode != RANK_MODE_PICK && !out_counts) return fail(mode == RANK_MODE_RANK ? "out_ranks is NULL" : "out_counts is NULL");
+        if (mode != RANK_MODE_THRESHOLDS && !out_scores) return fail("out_scores is NULL");
+    }
+    if (ix->l2) return fail("%s is not supported on an L2 index (VODHIP_L2): its scores are distances, not similarities", what);
+    if (ix->exact) return fail("%s is not supported on a VODHIP_EXACT_F32 store: the scan scores the rounded rows, that store's contract is the float32 rows", what);
+    if (q_labels_dev && !ix->row_label) return fail("set the row labels first (vodhip_index_set_row_labels)");
+    if (nq == 0) return 0;
+    HIP_OK(hipSetDevice(ix->device));
+    RankArgs a;
+    a.store = ix->data;
+    a.dim = ix->dim;
+    a.dim_pad = ix->dim_pad;
+    a.ntotal = ix->ntotal;
+    a.store_dtype = ix->dtype;
+    a.q_src = queries;
+    a.q_dtype = q_dtype;
+    a.row_label = ix->row_label;
+    a.q_label = q_labels_dev;
+    a.n_qlab = q_labels_dev ? n_per_query : 0;
+    a.m = m;
+    a.id_base = id_base;
+    a.ids = ids_dev;
+    a.thresholds = thresholds_dev;
+    a.tie_ids = tie_ids_dev;
+    a.out_score = out_scores;
+    a.out_rows = out_rows;
+    a.out_count = out_counts;
+    const bool pick = mode != RANK_MODE_THRESHOLDS, count = mode != RANK_MODE_PICK;
+    // queries per slice: a multiple of 128 (or 64) up to 1024 that keeps the temporaries under VODHIP_POSTERIOR_TEMP_BYTES (the rule of
+    // posterior_mean); a query's gathered rows are at most m + 3 rows of the mini-store
+    const size_t row_bytes = (size_t)ix->dim_pad * 2;
+    const size_t per_query = row_bytes * (size_t)(1 + (pick ? m + 3 : 0)) + (size_t)m * 16;
+    int64_t slice = (int64_t)((size_t)VODHIP_POSTERIOR_TEMP_BYTES / per_query) / 128 * 128;
+    slice = std::min<int64_t>(1024, std::max<int64_t>(64, slice));
+    const int64_t nq_pad = rank_nq_pad(std::min(nq, slice));
+    void* tmp[4] = {nullptr, nullptr, nullptr, nullptr};
+    const size_t bytes[4] = {(size_t)nq_pad * row_bytes, pick ? (size_t)rank_mini_rows(nq_pad, m) * row_bytes : 0, pick ? (size_t)nq_pad * (size_t)m * 4 : 0,
+                             count ? (size_t)nq_pad * (size_t)m * 12 : 0};
+    for (int i = 0; i < 4; ++i) {
+        if (bytes[i] == 0) continue;
+        if (hipError_t e = hipMallocAsync(&tmp[i], bytes[i], stream); e != hipSuccess) {
+            (void)hipGetLastError();
+            for (int j = 0; j < i; ++j)
+                if (tmp[j]) (void)hipFreeAsync(tmp[j], stream);
+            return fail("hipMallocAsync of a %zu-byte temporary failed: %s", bytes[i], hipGetErrorString(e));
+        }
+    }
+    a.q_stage = tmp[0];
+    a.mini = tmp[1];
+    a.slot_row = (int*)tmp[2];
+    a.table = (unsigned int*)tmp[3];
+    hipError_t le = hipSuccess;
+    for (int64_t q0 = 0; q0 < nq && le == hipSuccess; q0 += slice) le = launch_rank(a, mode, q0, std::min(slice, nq - q0), stream);
+    if (le != hipSuccess) (void)hipGetLastError();
+    hipError_t fe = hipSuccess;
+    for (int i = 0; i < 4; ++i)
+        if (tmp[i])
+            if (hipError_t e = hipFreeAsync(tmp[i], stream); e != hipSuccess) fe = e;
+    if (le != hipSuccess) return fail("%s launch failed: %s", what, hipGetErrorString(le));
+    HIP_OK(fe);
+    return 0;
+}
+
+int vodhip_index_count_above(vodhip_index_t* ix, const void* queries, int q_dtype, int64_t nq, const float* thresholds_dev,
+                             const int64_t* tie_ids_dev, int64_t m, int64_t id_base, const int32_t* q_labels_dev, int n_per_query,
+                             int64_t* out_counts, void* stream_) {
+    return rank_call(ix, RANK_MODE_THRESHOLDS, "count_above", queries, q_dtype, nq, nullptr, thresholds_dev, tie_ids_dev, m, id_base, q_labels_dev,
+                     n_per_query, out_counts, nullptr, nullptr, (hipStream_t)stream_);
+}
+
+int vodhip_index_rank_ids(vodhip_index_t* ix, const void* queries, int q_dtype, int64_t nq, const int64_t* ids_dev, int64_t m, int64_t id_base,
+                          const int32_t* q_labels_dev, int n_per_query, int64_t* out_ranks, float* out_scores, void* stream_) {
+    return rank_call(ix, RANK_MODE_RANK, "rank_ids", queries, q_dtype, nq, ids_dev, nullptr, nullptr, m, id_base, q_labels_dev, n_per_query, out_ranks,
+                     out_scores, nullptr, (hipStream_t)stream_);
+}
+
+int vodhip_index_scan_score_ids(vodhip_index_t* ix, const void* queries, int q_dtype, int64_t nq, const int64_t* ids_dev, int64_t m,
+                                int64_t id_base, const int32_t* q_labels_dev, int n_per_query, float* out_scores, int32_t* out_rows,
+                                void* stream_) {
+    return rank_call(ix, RANK_MODE_PICK, "scan_score_ids", queries, q_dtype, nq, ids_dev, nullptr, nullptr, m, id_base, q_labels_dev, n_per_query,
+                     nullptr, out_scores, out_rows, (hipStream_t)stream_);
 }
 
 // ---- posterior mean (kernels_posterior.hip): the log-partition launches, then the second scan and its finish -------------------

@@ -254,6 +254,35 @@ int64_t log_partition_tiles(int64_t ntotal);
 // queries [q_first, q_first + nq) of the caller's batch -> out_max / out_log_rel [q_first ..); a query's bits do not depend on the split
 hipError_t launch_log_partition(const PartitionArgs& a, int64_t q_first, int64_t nq, hipStream_t stream);
 
+// ---- launchers (kernels_rank.hip): exact ranks of listed rows / counts above thresholds over the whole store ----
+struct RankArgs {
+    const void* store = nullptr;      // [>= round_up(ntotal, 256) rows][dim_pad] fp16 / bf16 rows
+    int64_t dim = 0, dim_pad = 0, ntotal = 0;
+    int store_dtype = 0;              // 0 = f16, 1 = bf16
+    const void* q_src = nullptr;      // the caller's queries [.., dim] of q_dtype
+    int q_dtype = 0;
+    const int* row_label = nullptr;   // the store's subset labels; read only with q_label
+    const int* q_label = nullptr;     // [.., n_qlab] rows of the caller's batch, or NULL = unrestricted
+    int n_qlab = 0;
+    int64_t m = 0, id_base = 0;       // slots per query (1 .. VODHIP_RANK_MAX_LISTED), global id of row 0
+    const int64_t* ids = nullptr;     // PICK / RANK: [.., m] listed ids
+    const float* thresholds = nullptr;  // THRESHOLDS: [.., m]
+    const int64_t* tie_ids = nullptr;   // THRESHOLDS: [.., m], or NULL = strict counts
+    // temporaries, sized for P = rank_nq_pad(queries of a launch)
+    void* q_stage = nullptr;          // P * dim_pad 16-bit words
+    void* mini = nullptr;             // PICK / RANK: rank_mini_rows(P, m) * dim_pad 16-bit words
+    int* slot_row = nullptr;          // PICK / RANK: P * m words
+    unsigned int* table = nullptr;    // RANK / THRESHOLDS: 3 * P * m words (keys, tie rows, counts)
+    float* out_score = nullptr;       // PICK / RANK: [rows of the caller's batch][m]
+    int* out_rows = nullptr;          // PICK / RANK: the same shape, or NULL
+    int64_t* out_count = nullptr;     // RANK / THRESHOLDS: the same shape
+};
+enum : int { RANK_MODE_PICK = 0, RANK_MODE_RANK = 1, RANK_MODE_THRESHOLDS = 2 };
+int64_t rank_nq_pad(int64_t nq);
+int64_t rank_mini_rows(int64_t nq_pad, int64_t m);
+// queries [q_first, q_first + nq) of the caller's batch; a query's results do not depend on the split
+hipError_t launch_rank(const RankArgs& a, int mode, int64_t q_first, int64_t nq, hipStream_t stream);
+
 // ---- launchers (kernels_posterior.hip): the posterior mean of the rows, sum_z p(z | q) x_z, behind the log-partition launches ----
 struct PosteriorArgs {
     PartitionArgs p;                  // the log-partition call of the same batch: its launches run first, unchanged

@@ -19,6 +19,7 @@
 
 #include "partition_fold.h"
 #include "sample_fold.h"
+#include "rank_fold.h"
 #include "vodhip_internal.h"
 
 namespace {
@@ -975,6 +976,130 @@ int vodhip_node_index_log_partition(vodhip_node_index_t* nx, const void* queries
     (void)hipSetDevice(nx->device[0]);
     if (rc) return nfail("%s", err.c_str());
     vodhip::fold_log_partition(parts.data(), parts.data() + nq, G, 2 * nq, nq, beta, out_max, out_log_rel);
+    return 0;
+}
+
+// The rank calls behind the one handle (include/vodhip.h, H2r).  One PASS = the same flat call on every shard, on its own device and
+// stream, with id_base = the shard's first global row: host inputs are replicated, the per-shard outputs return through host memory.
+//   thresholds == NULL  vodhip_index_scan_score_ids of `ids`     -> score_g / row_g  [G][n]
+//   else                vodhip_index_count_above (`ids` = the tie ids, may be NULL)  -> count_g [G][n]
+// The caller holds nx->mu.
+static int node_rank_pass(vodhip_node_index_t* nx, const void* queries, int q_dtype, int64_t nq, int64_t m, const int64_t* ids, const float* thresholds,
+                          const int32_t* q_labels, int n_per_query, float* score_g, int32_t* row_g, int64_t* count_g) {
+    const int G = nx->n;
+    const size_t n = (size_t)nq * (size_t)m;
+    const size_t q_bytes = (size_t)nq * (size_t)nx->dim * elem_bytes(q_dtype);
+    const size_t lab_bytes = q_labels ? (size_t)nq * (size_t)n_per_query * sizeof(int32_t) : 0;
+    struct Tmp { void* q = nullptr; int64_t* ids = nullptr; float* thr = nullptr; int32_t* lab = nullptr; float* score = nullptr; int32_t* row = nullptr; int64_t* cnt = nullptr; };
+    std::vector<Tmp> tmp((size_t)G);
+    int rc = 0;
+    std::string err;
+    auto hip_step = [&](hipError_t e, const char* what) {
+        if (e != hipSuccess && !rc) {
+            (void)hipGetLastError();
+            err = std::string(what) + " failed: " + hipGetErrorString(e);
+            rc = -1;
+        }
+        return e == hipSuccess;
+    };
+    for (int g = 0; g < G && !rc; ++g) {  // (the devices run side by side: nothing is waited for until every shard is enqueued)
+        hipStream_t st = nx->stream[g];
+        Tmp& t = tmp[(size_t)g];
+        if (!hip_step(hipSetDevice(nx->device[g]), "hipSetDevice")) break;
+        if (!hip_step(hipMallocAsync(&t.q, q_bytes, st), "hipMallocAsync")) break;
+        if (!hip_step(hipMemcpyAsync(t.q, queries, q_bytes, hipMemcpyHostToDevice, st), "hipMemcpyAsync")) break;
+        if (ids) {
+            if (!hip_step(hipMallocAsync((void**)&t.ids, n * sizeof(int64_t), st), "hipMallocAsync")) break;
+            if (!hip_step(hipMemcpyAsync(t.ids, ids, n * sizeof(int64_t), hipMemcpyHostToDevice, st), "hipMemcpyAsync")) break;
+        }
+        if (q_labels) {
+            if (!hip_step(hipMallocAsync((void**)&t.lab, lab_bytes, st), "hipMallocAsync")) break;
+            if (!hip_step(hipMemcpyAsync(t.lab, q_labels, lab_bytes, hipMemcpyHostToDevice, st), "hipMemcpyAsync")) break;
+        }
+        const int64_t base = (int64_t)g * nx->rows_per_shard;
+        int call;
+        if (!thresholds) {
+            if (!hip_step(hipMallocAsync((void**)&t.score, n * sizeof(float), st), "hipMallocAsync")) break;
+            if (!hip_step(hipMallocAsync((void**)&t.row, n * sizeof(int32_t), st), "hipMallocAsync")) break;
+            call = vodhip_index_scan_score_ids(nx->shard[g], t.q, q_dtype, nq, t.ids, m, base, t.lab, n_per_query, t.score, t.row, st);
+        } else {
+            if (!hip_step(hipMallocAsync((void**)&t.thr, n * sizeof(float), st), "hipMallocAsync")) break;
+            if (!hip_step(hipMemcpyAsync(t.thr, thresholds, n * sizeof(float), hipMemcpyHostToDevice, st), "hipMemcpyAsync")) break;
+            if (!hip_step(hipMallocAsync((void**)&t.cnt, n * sizeof(int64_t), st), "hipMallocAsync")) break;
+            call = vodhip_index_count_above(nx->shard[g], t.q, q_dtype, nq, t.thr, t.ids, m, base, t.lab, n_per_query, t.cnt, st);
+        }
+        if (call) {
+            err = std::string("shard ") + std::to_string(g) + ": " + vodhip_last_error();
+            rc = -1;
+            break;
+        }
+        if (!thresholds) {
+            hip_step(hipMemcpyAsync(score_g + (size_t)g * n, t.score, n * sizeof(float), hipMemcpyDeviceToHost, st), "hipMemcpyAsync");
+            hip_step(hipMemcpyAsync(row_g + (size_t)g * n, t.row, n * sizeof(int32_t), hipMemcpyDeviceToHost, st), "hipMemcpyAsync");
+        } else {
+            hip_step(hipMemcpyAsync(count_g + (size_t)g * n, t.cnt, n * sizeof(int64_t), hipMemcpyDeviceToHost, st), "hipMemcpyAsync");
+        }
+    }
+    for (int g = 0; g < G; ++g) {  // (also after a failure: what was enqueued reads the caller's host buffers)
+        Tmp& t = tmp[(size_t)g];
+        if (hipSetDevice(nx->device[g]) != hipSuccess) continue;
+        for (void* p : {t.q, (void*)t.ids, (void*)t.thr, (void*)t.lab, (void*)t.score, (void*)t.row, (void*)t.cnt})
+            if (p) (void)hipFreeAsync(p, nx->stream[g]);
+        hip_step(hipStreamSynchronize(nx->stream[g]), "hipStreamSynchronize");
+    }
+    (void)hipSetDevice(nx->device[0]);
+    if (rc) return nfail("%s", err.c_str());
+    return 0;
+}
+
+static int node_rank_check(vodhip_node_index_t* nx, const char* what, const void* queries, int q_dtype, int64_t nq, int64_t m, const void* q_labels,
+                           int n_per_query) {
+    if (!nx) return nfail("index is NULL");
+    if (const char* msg = vodhip::rank_args_error(queries, q_dtype, nq, m, q_labels, n_per_query)) {
+        if (!strcmp(msg, "invalid q_dtype")) return nfail("invalid q_dtype %d", q_dtype);
+        if (msg[0] == 'm') return nfail("m=%lld: %s", (long long)m, msg + 2);
+        return nfail("%s", msg);
+    }
+    if (nx->dtype & VODHIP_L2) return nfail("%s is not supported on an L2 index (VODHIP_L2): its scores are distances, not similarities", what);
+    if (nx->dtype & VODHIP_EXACT_F32) return nfail("%s is not supported on a VODHIP_EXACT_F32 store: the scan scores the rounded rows, that store's contract is the float32 rows", what);
+    return 0;
+}
+
+int vodhip_node_index_count_above(vodhip_node_index_t* nx, const void* queries, int q_dtype, int64_t nq, const float* thresholds, const int64_t* tie_ids,
+                                  int64_t m, const int32_t* q_labels, int n_per_query, int64_t* out_counts) {
+    if (node_rank_check(nx, "count_above", queries, q_dtype, nq, m, q_labels, n_per_query)) return -1;
+    if (nq > 0 && !thresholds) return nfail("thresholds is NULL");
+    if (nq > 0 && !out_counts) return nfail("out_counts is NULL");
+    std::lock_guard<std::mutex> guard(nx->mu);
+    if (q_labels && !nx->has_row_labels) return nfail("set the row labels first (vodhip_node_index_set_row_labels)");
+    if (nq == 0) return 0;
+    const size_t n = (size_t)nq * (size_t)m;
+    std::vector<int64_t> count_g((size_t)nx->n * n);
+    if (node_rank_pass(nx, queries, q_dtype, nq, m, tie_ids, thresholds, q_labels, n_per_query, nullptr, nullptr, count_g.data())) return -1;
+    vodhip::sum_counts(count_g.data(), (int64_t)n, nx->n, out_counts);
+    return 0;
+}
+
+int vodhip_node_index_rank_ids(vodhip_node_index_t* nx, const void* queries, int q_dtype, int64_t nq, const int64_t* ids, int64_t m,
+                               const int32_t* q_labels, int n_per_query, int64_t* out_ranks, float* out_scores) {
+    if (node_rank_check(nx, "rank_ids", queries, q_dtype, nq, m, q_labels, n_per_query)) return -1;
+    if (nq > 0 && !ids) return nfail("ids is NULL");
+    if (nq > 0 && !out_ranks) return nfail("out_ranks is NULL");
+    if (nq > 0 && !out_scores) return nfail("out_scores is NULL");
+    std::lock_guard<std::mutex> guard(nx->mu);
+    if (q_labels && !nx->has_row_labels) return nfail("set the row labels first (vodhip_node_index_set_row_labels)");
+    if (nq == 0) return 0;
+    const int G = nx->n;
+    const size_t n = (size_t)nq * (size_t)m;
+    std::vector<float> score_g((size_t)G * n), thr(n);
+    std::vector<int32_t> row_g((size_t)G * n);
+    std::vector<uint8_t> present(n);
+    std::vector<int64_t> count_g((size_t)G * n);
+    if (node_rank_pass(nx, queries, q_dtype, nq, m, ids, nullptr, q_labels, n_per_query, score_g.data(), row_g.data(), nullptr)) return -1;
+    vodhip::combine_scan_scores(score_g.data(), row_g.data(), ids, (int64_t)n, G, nx->rows_per_shard, out_scores, present.data());
+    vodhip::rank_thresholds(out_scores, present.data(), (int64_t)n, thr.data());
+    if (node_rank_pass(nx, queries, q_dtype, nq, m, ids, thr.data(), q_labels, n_per_query, nullptr, nullptr, count_g.data())) return -1;
+    vodhip::sum_counts(count_g.data(), (int64_t)n, G, out_ranks);
     return 0;
 }
 

@@ -403,6 +403,77 @@ class HipFlatIndex:
             ids = torch.from_numpy(pad_listed_ids(ids, int(queries.shape[0]))).to(self.device)
         return _ListedScores.apply(queries, self, ids, {"subset": subset, "id_base": id_base})
 
+    def _subset_labels(self, subset, nq: int):
+        """`subset` -> (int32 device tensor `[nq, S]` or None, S)."""
+        if subset is None:
+            return None, 0
+        sub = subset if isinstance(subset, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(subset))
+        sub = sub.to(self.device, torch.int32).contiguous()
+        if sub.ndim != 2 or sub.shape[0] != nq:
+            raise ValueError(f"expected subset labels of shape [{nq}, S], got {tuple(sub.shape)}")
+        return sub, int(sub.shape[1])
+
+    def rank_ids(self, queries, ids, *, subset=None, id_base: int = 0) -> "ListedRanks":
+        """The exact rank of LISTED rows over the WHOLE store, however deep: `ListedRanks(rank, score)`, int64 / float32 device tensors
+        `[nq, m]`.  `score[q, j]` is the scan's score of row `ids[q, j] - id_base` - the bits `search` returns for that pair - and
+        `rank[q, j]` the 0-based position at which a search over the query's eligible rows returns it: the number of eligible rows
+        with a larger score, or an equal score (`-0.0 == +0.0`) and a smaller id.  For every finite hit of `search(q, k)` at position
+        `p`, `rank_ids(q, ids_of_search)[q, p]` is `(p, the same score bits)`.
+
+        `ids` as in `score_ids` with `m <= 64`; a slot that `score_ids` calls absent (empty, out of range, outside the query's `subset`)
+        gives `(-1, -inf)`, a NaN score rank -1 with the score as computed; duplicates are independent slots.  One scan of the store on
+        the MFMA path with integer compares in place of the top-k (cost linear in `m`), no `[nq, N]` matrix.  Enqueued on the current
+        stream; nothing to finish, and safe beside searches of this index that are in flight.  L2 and `exact_f32` indexes refuse."""
+        q = self._prep_queries(queries)
+        nq = q.shape[0]
+        if isinstance(ids, torch.Tensor):
+            lst = ids.to(self.device, torch.int64).contiguous()
+            if lst.ndim != 2 or lst.shape[0] != nq:
+                raise ValueError(f"expected ids of shape [{nq}, m], got {tuple(lst.shape)}")
+        else:
+            lst = torch.from_numpy(pad_listed_ids(ids, nq)).to(self.device)
+        m = int(lst.shape[1])
+        sub, n_sub = self._subset_labels(subset, nq)
+        rank = torch.empty((nq, m), dtype=torch.int64, device=self.device)
+        score = torch.empty((nq, m), dtype=torch.float32, device=self.device)
+        with torch.cuda.device(self.device):
+            _native.check(self._lib.vodhip_index_rank_ids(
+                self._h, q.data_ptr(), _native.torch_dtype_code(q.dtype), nq, lst.data_ptr(), m, int(id_base),
+                None if sub is None else sub.data_ptr(), n_sub, rank.data_ptr(), score.data_ptr(), _native.current_stream_ptr(self.device)))
+        for t, given in ((q, queries), (lst, ids), (sub, subset)):  # (the rule of score_ids: copies this call made outlive the launch)
+            if t is not None and t is not given:
+                t.record_stream(torch.cuda.current_stream(self.device))
+        return ListedRanks(rank, score)
+
+    def count_above(self, queries, thresholds, *, tie_ids=None, subset=None, id_base: int = 0) -> torch.Tensor:
+        """How many eligible rows of the WHOLE store score above a threshold: int64 device tensor `[nq, m]`, entry `[q, j]` the number
+        of rows `z` with `score(q, z) > thresholds[q, j]`, or - with `tie_ids` - with an equal score and `id_base + z < tie_ids[q, j]`
+        (the order of `search`; `-0.0 == +0.0`).  It is the score CDF: choose `k`, size a candidate list, find a quantile.  A NaN
+        threshold gives -1.  `count_above(q, score, tie_ids=ids)` is `rank_ids(q, ids).rank`.  `thresholds`: float32 `[nq, m]`,
+        `m <= 64`; `tie_ids`: int64 of the same shape.  Eligibility, queries, `subset`, stream rules and refusals as `rank_ids`."""
+        q = self._prep_queries(queries)
+        nq = q.shape[0]
+        thr = thresholds if isinstance(thresholds, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(thresholds, dtype=np.float32))
+        thr = thr.to(self.device, torch.float32).contiguous()
+        if thr.ndim != 2 or thr.shape[0] != nq:
+            raise ValueError(f"expected thresholds of shape [{nq}, m], got {tuple(thr.shape)}")
+        m = int(thr.shape[1])
+        tie = None
+        if tie_ids is not None:
+            tie = tie_ids if isinstance(tie_ids, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(tie_ids, dtype=np.int64))
+            tie = tie.to(self.device, torch.int64).contiguous()
+            if tuple(tie.shape) != (nq, m):
+                raise ValueError(f"expected tie_ids of shape {(nq, m)}, got {tuple(tie.shape)}")
+        sub, n_sub = self._subset_labels(subset, nq)
+        out = torch.empty((nq, m), dtype=torch.int64, device=self.device)
+        with torch.cuda.device(self.device):
+            _native.check(self._lib.vodhip_index_count_above(
+                self._h, q.data_ptr(), _native.torch_dtype_code(q.dtype), nq, thr.data_ptr(), None if tie is None else tie.data_ptr(), m,
+                int(id_base), None if sub is None else sub.data_ptr(), n_sub, out.data_ptr(), _native.current_stream_ptr(self.device)))
+        for t, given in ((q, queries), (thr, thresholds), (tie, tie_ids), (sub, subset)):
+            if t is not None and t is not given:
+                t.record_stream(torch.cuda.current_stream(self.device))
+        return out
 
     def log_partition(self, queries, temperature: float = 1.0, subset=None, out=None) -> LogPartition:
         """The exact softmax normaliser over the WHOLE store, `log Z(q) = log sum_z exp(<q~, x~_z> / temperature)`, from one scan on
@@ -539,6 +610,13 @@ class LogPartition(NamedTuple):
     log_rel: Any
 
 
+class ListedRanks(NamedTuple):
+    """`rank` (int64, -1 = absent or NaN) and `score` (float32, the scan's bits; -inf = absent) of `rank_ids`, each `[nq, m]`."""
+
+    rank: Any
+    score: Any
+
+
 class PosteriorMean(NamedTuple):
     """`mean[q] = sum_z p(z | q) x_z` (`[nq, dim]`) of `posterior_mean`, with the `LogPartition` of the same call."""
 
@@ -618,6 +696,31 @@ def topk_log_coverage(scores: torch.Tensor, log_partition: LogPartition, tempera
     m = torch.as_tensor(log_partition.max_score).to(s.device).float()
     r = torch.as_tensor(log_partition.log_rel).to(s.device).float()
     return torch.logsumexp((s - m[:, None]) / float(temperature), dim=1) - r
+
+
+def rank_metrics(rank, ks=(1, 5, 20, 100)) -> dict[str, float]:
+    """Retrieval metrics from exact ranks (`rank_ids(...).rank`, `[nq, m]` or `[nq]`, 0-based, -1 = not ranked): `mrr`, `hit@k` for
+    every `k` of `ks`, `mean_rank` and `median_rank`.  Slots with rank -1 are left out everywhere.  For `mrr` and `hit@k` a query's BEST
+    present slot counts (one reciprocal rank per query, averaged over the queries that have a present slot); `mean_rank` / `median_rank`
+    are over all present slots, 0-based.  No present slot at all: every value NaN.  Plain torch on the device of `rank`."""
+    r = torch.as_tensor(rank)
+    if r.ndim == 1:
+        r = r[:, None]
+    present = r >= 0
+    out: dict[str, float] = {}
+    if not bool(present.any()):
+        nan = float("nan")
+        return {"mrr": nan, **{f"hit@{int(k)}": nan for k in ks}, "mean_rank": nan, "median_rank": nan}
+    big = torch.iinfo(torch.int64).max
+    best = torch.where(present, r, torch.full_like(r, big)).min(dim=1).values
+    best = best[present.any(dim=1)].to(torch.float64)
+    out["mrr"] = float((1.0 / (best + 1.0)).mean())
+    for k in ks:
+        out[f"hit@{int(k)}"] = float((best < int(k)).to(torch.float64).mean())
+    flat = r[present].to(torch.float64)
+    out["mean_rank"] = float(flat.mean())
+    out["median_rank"] = float(flat.median())  # (the lower of the two middle values of an even count)
+    return out
 
 
 def merge_topk(scores: torch.Tensor, ids: torch.Tensor, k_out: int | None = None) -> tuple[torch.Tensor, torch.Tensor]:
@@ -878,6 +981,72 @@ class HipNodeIndex:
         with np.errstate(invalid="ignore"):
             log_z = (max_score * np.float32(beta) + log_rel).astype(np.float32)
         return LogPartition(log_z, max_score, log_rel)
+
+    def _host_queries(self, queries) -> np.ndarray:
+        if isinstance(queries, torch.Tensor):
+            queries = queries.detach().float().cpu().numpy()
+        q = np.ascontiguousarray(queries)
+        if q.dtype not in (np.float32, np.float16):
+            q = q.astype(np.float32)
+        if q.ndim != 2 or q.shape[1] != self.dim:
+            raise ValueError(f"expected [nq, {self.dim}] queries, got {tuple(q.shape)}")
+        return q
+
+    @staticmethod
+    def _host_subset(subset, nq: int):
+        if subset is None:
+            return None, 0
+        sub = np.ascontiguousarray(subset.cpu().numpy() if isinstance(subset, torch.Tensor) else subset, dtype=np.int32)
+        if sub.ndim != 2 or sub.shape[0] != nq:
+            raise ValueError(f"subset must be int32 [nq, n_per_query], got {tuple(sub.shape)}")
+        return sub, int(sub.shape[1])
+
+    def rank_ids(self, queries, ids, *, subset=None) -> "ListedRanks":
+        """`HipFlatIndex.rank_ids` over every shard, `ids` GLOBAL row ids: each shard picks the scan scores of the ids it owns, the
+        host combines them by ownership, each shard counts its rows against the combined (score, id) pairs and the host adds the
+        counts.  Host inputs -> `ListedRanks` of NumPy arrays `[nq, m]` that equal one index holding all the rows bit for bit."""
+        q = self._host_queries(queries)
+        nq = int(q.shape[0])
+        if isinstance(ids, torch.Tensor):
+            ids = ids.detach().cpu().numpy()
+        lst = np.ascontiguousarray(ids, dtype=np.int64) if isinstance(ids, np.ndarray) else pad_listed_ids(ids, nq)
+        if lst.ndim != 2 or lst.shape[0] != nq:
+            raise ValueError(f"expected ids of shape [{nq}, m], got {tuple(lst.shape)}")
+        m = int(lst.shape[1])
+        sub, n_sub = self._host_subset(subset, nq)
+        rank = np.empty((nq, m), dtype=np.int64)
+        score = np.empty((nq, m), dtype=np.float32)
+        with torch.cuda.device(self.device):
+            _native.check(self._lib.vodhip_node_index_rank_ids(
+                self._h, q.ctypes.data, 2 if q.dtype == np.float32 else 0, nq, lst.ctypes.data, m, None if sub is None else sub.ctypes.data,
+                n_sub, rank.ctypes.data, score.ctypes.data))
+        return ListedRanks(rank, score)
+
+    def count_above(self, queries, thresholds, *, tie_ids=None, subset=None) -> np.ndarray:
+        """`HipFlatIndex.count_above` over every shard (`tie_ids` GLOBAL row ids): the shards' counts added on the host in int64.  Host
+        inputs -> int64 NumPy array `[nq, m]` that equals one index holding all the rows."""
+        q = self._host_queries(queries)
+        nq = int(q.shape[0])
+        if isinstance(thresholds, torch.Tensor):
+            thresholds = thresholds.detach().cpu().numpy()
+        thr = np.ascontiguousarray(thresholds, dtype=np.float32)
+        if thr.ndim != 2 or thr.shape[0] != nq:
+            raise ValueError(f"expected thresholds of shape [{nq}, m], got {tuple(thr.shape)}")
+        m = int(thr.shape[1])
+        tie = None
+        if tie_ids is not None:
+            if isinstance(tie_ids, torch.Tensor):
+                tie_ids = tie_ids.detach().cpu().numpy()
+            tie = np.ascontiguousarray(tie_ids, dtype=np.int64)
+            if tie.shape != (nq, m):
+                raise ValueError(f"expected tie_ids of shape {(nq, m)}, got {tuple(tie.shape)}")
+        sub, n_sub = self._host_subset(subset, nq)
+        out = np.empty((nq, m), dtype=np.int64)
+        with torch.cuda.device(self.device):
+            _native.check(self._lib.vodhip_node_index_count_above(
+                self._h, q.ctypes.data, 2 if q.dtype == np.float32 else 0, nq, thr.ctypes.data, None if tie is None else tie.ctypes.data, m,
+                None if sub is None else sub.ctypes.data, n_sub, out.ctypes.data))
+        return out
 
     def posterior_mean(self, queries, temperature: float = 1.0, subset: np.ndarray | None = None) -> "PosteriorMean":
         """`HipFlatIndex.posterior_mean` over every shard: each shard runs the flat call on its own device, the shards are folded on the
