@@ -2,18 +2,15 @@
 //   log Z_beta(q) = log sum_{rows z < ntotal, eligible} exp(beta <q~, x~_z>) = beta * max_score + log_rel,
 //   max_score = max_z <q~, x~_z>,  log_rel = log sum_z exp(beta (<q~, x~_z> - max_score)) >= 0.
 // Three kernels:
-//   stage    queries -> [nq_pad][dim_pad] of the store dtype, rounded as a search rounds them (store_bits: saturating), zero padded
-//   scan     the K loop of mips_filter_kernel (LDS-DMA with the source-side XOR swizzle, 3-slot ring, v_mfma_f32_32x32x16 with the
-//            corpus as A and the queries as B: a lane's accumulator column is ONE query, its registers are corpus rows) over a
-//            256-row corpus tile x 64 | 128 queries; the epilogue replaces the top-k filter with a max-stabilised sum of exponentials
-//            and writes ONE partial (m, l) per (tile, query): m = the tile's maximum, l = sum exp(beta (s - m))
+//   stage    queries -> [nq_pad][dim_pad] of the store dtype (launch_scan_stage: the one staging kernel of every whole-store scan)
+//   scan     the shared scan core (store_scan.h: K loop, C layout and eligibility rule) over a 256-row tile x 64 | 128 queries with a
+//            max-stabilised sum of exponentials as its epilogue: ONE partial (m, l) per (tile, query), m = the tile's maximum,
+//            l = sum exp(beta (s - m))
 //   finish   folds a query's partials into (max_score, log_rel)
-// A row counts when row < ntotal (rows past it are zero or stale, tile padding reaches past the capacity), its score is not NaN (a
-// search leaves NaN out too) and the query's subset labels allow it (subset_allows, mips_common.h).
 //
 // ONE summation order per query, fixed by ntotal (and dim_pad, the length of the K loop) alone - not by nq, by the other queries of the
 // batch, by the query tile width or by the grid:
-//   score   the MFMA's own order over the dim_pad / 16 k-steps, the same for every column of the B operand;
+//   score   the scan core's (store_scan.h);
 //   tile t  holds rows [256 t, 256 t + 256).  Wave w of its 4 row waves holds rows 64 w .. 64 w + 63: lane half h (lane >> 5) of the
 //           query's two lanes holds, in register order (block i = 0, 1; register r = 0 .. 15), the rows 64 w + 32 i + 4 h + (r & 3) +
 //           8 (r >> 2).  m = the maximum over the tile's eligible rows (a maximum has no order).  Each lane adds its terms
@@ -25,20 +22,14 @@
 // query's two words are the same bits alone, as row 217 of 300, and on every repeat (there are no atomics).
 // expf and logf are the library functions (1 ulp each in the HIP math accuracy table), not the native approximations.
 // No eligible row: (-inf, -inf).  A +inf score: (+inf, +inf).  Scores that are all -inf count as no row.
-#include "mips_common.h"
-
-#include <type_traits>
+#include "store_scan.h"
 
 namespace vodhip {
 
 namespace {
 
-constexpr int PT_BM = 256;     // corpus rows of a tile = rows of one partial
-constexpr int PT_WM = 4;       // row waves
-constexpr int PT_NSTAGE = 3;   // LDS ring depth
-
-__global__ void __launch_bounds__(256) partition_stage_kernel(const void* __restrict__ q_src, int q_dtype, int64_t q_first, int64_t nq, int64_t dim,
-                                                              uint16_t* __restrict__ q_pad, int store_dtype, int64_t nq_pad, int64_t dim_pad) {
+__global__ void __launch_bounds__(256) scan_stage_kernel(const void* __restrict__ q_src, int q_dtype, int64_t q_first, int64_t nq, int64_t dim,
+                                                         uint16_t* __restrict__ q_pad, int store_dtype, int64_t nq_pad, int64_t dim_pad) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     const int64_t chunks_per_row = dim_pad / 8;
     if (i >= nq_pad * chunks_per_row) return;
@@ -65,135 +56,29 @@ __global__ void __launch_bounds__(256) partition_stage_kernel(const void* __rest
 
 // X: the store [>= n_xtiles * 256 rows][dim_pad]; Q: the staged queries [n_qtiles * BN][dim_pad]; part: [n_qtiles * BN][n_xtiles] (m, l)
 template <int DT, int BN, int WN, bool SUBSET>
-__global__ __launch_bounds__(PT_WM* WN * 64, 1)
+__global__ __launch_bounds__(scan_threads(WN), 1)
 void partition_scan_kernel(const uint16_t* __restrict__ X, const uint16_t* __restrict__ Q, int dim_pad, int ntotal, int n_xtiles, int n_qtiles,
                            int nq, float beta, float2* __restrict__ part, FilterExtra ex) {
-    constexpr int BM = PT_BM, WM = PT_WM, NSTAGE = PT_NSTAGE;
-    constexpr int BK = 64;
-    constexpr int NWAVES = WM * WN;
-    constexpr int TM = BM / WM, TN = BN / WN;
+    constexpr int WM = SCAN_WM;
+    constexpr int TM = SCAN_BM / WM, TN = BN / WN;
     constexpr int MI = TM / 32, NJ = TN / 32;
-    constexpr int ROW_BYTES = BK * 2;
-    constexpr int RPI = 8;
-    constexpr int KK = BK / 16;
-    constexpr int A_BYTES = BM * ROW_BYTES, B_BYTES = BN * ROW_BYTES;
-    constexpr int STAGE_BYTES = A_BYTES + B_BYTES;
-    constexpr int NA = BM / RPI / NWAVES;
-    constexpr int NB = BN / RPI / NWAVES;
-    constexpr int G = NA + NB;
-    static_assert(BM % (RPI * NWAVES) == 0 && BN % (RPI * NWAVES) == 0, "tile/wave mismatch");
-    static_assert(MI == 2, "the eligibility mask holds 2 x 16 rows per lane");
-    static_assert(2 * WM * BN * (int)sizeof(float) <= STAGE_BYTES, "the reduction arrays reuse the first ring slot");
+    static_assert(2 * WM * BN * (int)sizeof(float) <= scan_ring_bytes(BN) / SCAN_NSTAGE, "the reduction arrays reuse the first ring slot");
 
     extern __shared__ __attribute__((aligned(16))) char smem[];
-
-    // XCD-aware tile order (as mips_filter_kernel): the n_qtiles workgroups that re-read one corpus tile land on one XCD back to back
-    const int bid = blockIdx.x;
-    const int xcd = bid & 7, jj = bid >> 3;
-    const int qt = jj % n_qtiles;
-    const int xt = (jj / n_qtiles) * 8 + xcd;
-    if (xt >= n_xtiles) return;
-
-    const int tid = threadIdx.x;
-    const int lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int wm = wave / WN, wn = wave % WN;
-    const int x0 = xt * BM;
+    int qt, xt;
+    if (!scan_block_tile(blockIdx.x, n_qtiles, n_xtiles, &qt, &xt)) return;
+    const int x0 = xt * SCAN_BM;
     const int q0 = qt * BN;
 
-    // per-lane LDS-DMA sources: lane -> (row = base + lane / 8, 16-B slot = lane % 8); slot s of row r holds chunk s ^ ((r >> 1) & 7)
-    const int st_row = lane >> 3, st_slot = lane & 7;
-    const char* a_src[NA];
-    const char* b_src[NB];
-#pragma unroll
-    for (int t = 0; t < NA; ++t) {
-        const int r = (wave * NA + t) * RPI + st_row;
-        const int c = st_slot ^ ((r >> 1) & 7);
-        a_src[t] = (const char*)X + ((size_t)(x0 + r) * dim_pad + c * 8) * 2;
-    }
-#pragma unroll
-    for (int t = 0; t < NB; ++t) {
-        const int r = (wave * NB + t) * RPI + st_row;
-        const int c = st_slot ^ ((r >> 1) & 7);
-        b_src[t] = (const char*)Q + ((size_t)(q0 + r) * dim_pad + c * 8) * 2;
-    }
-    auto stage_part = [&](int ks, int p, int nparts) {
-        char* sa = smem + (ks % NSTAGE) * STAGE_BYTES;
-        char* sb = sa + A_BYTES;
-        const int kbyte = ks * ROW_BYTES;
-#pragma unroll
-        for (int u = 0; u < G; ++u) {
-            if ((u * nparts) / G != p) continue;
-            if (u < NA)
-                glds16(a_src[u] + kbyte, sa + (wave * NA + u) * RPI * ROW_BYTES);
-            else
-                glds16(b_src[u - NA] + kbyte, sb + (wave * NB + (u - NA)) * RPI * ROW_BYTES);
-        }
-    };
-
-    const int fr = lane & 31, fh = lane >> 5;
-    const int swz = (fr >> 1) & 7;
-    const int a_row_off = (wm * TM + fr) * ROW_BYTES;
-    const int b_row_off = A_BYTES + (wn * TN + fr) * ROW_BYTES;
-
     f32x16 acc[MI][NJ];
-#pragma unroll
-    for (int i = 0; i < MI; ++i)
-#pragma unroll
-        for (int j = 0; j < NJ; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+    scan_k_loop<DT, BN, WN>(X + (size_t)x0 * dim_pad, Q + (size_t)q0 * dim_pad, dim_pad, smem, acc);
 
-    const int nk = dim_pad / BK;
-#pragma unroll
-    for (int s = 0; s < NSTAGE - 1; ++s)
-        if (s < nk) stage_part(s, 0, 1);
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int wm = wave / WN, wn = wave % WN;
+    const int fr = lane & 31, fh = lane >> 5;
 
-    auto load_frags = [&](const char* base, int kk, u32x4(&af)[MI], u32x4(&bf)[NJ]) {
-        const int slot_off = ((2 * kk + fh) ^ swz) << 4;
-#pragma unroll
-        for (int i = 0; i < MI; ++i) af[i] = *(const u32x4*)(base + a_row_off + i * 32 * ROW_BYTES + slot_off);
-#pragma unroll
-        for (int j = 0; j < NJ; ++j) bf[j] = *(const u32x4*)(base + b_row_off + j * 32 * ROW_BYTES + slot_off);
-    };
-    auto mfma_group = [&](u32x4(&af)[MI], u32x4(&bf)[NJ]) {
-#pragma unroll
-        for (int i = 0; i < MI; ++i)
-#pragma unroll
-            for (int j = 0; j < NJ; ++j) acc[i][j] = mfma32<DT>(af[i], bf[j], acc[i][j]);
-    };
-    auto kslice = [&](int t, auto pre_tag) {
-        constexpr bool PRE = decltype(pre_tag)::value;
-        const char* base = smem + (t % NSTAGE) * STAGE_BYTES;
-        const int ks = t + NSTAGE - 1;
-        u32x4 af0[MI], bf0[NJ], af1[MI], bf1[NJ];
-        load_frags(base, 0, af0, bf0);
-        if constexpr (PRE) stage_part(ks, 0, KK);
-        load_frags(base, 1, af1, bf1);
-        mfma_group(af0, bf0);
-        if constexpr (PRE) stage_part(ks, 1, KK);
-        load_frags(base, 2, af0, bf0);
-        mfma_group(af1, bf1);
-        if constexpr (PRE) stage_part(ks, 2, KK);
-        load_frags(base, 3, af1, bf1);
-        mfma_group(af0, bf0);
-        if constexpr (PRE) stage_part(ks, 3, KK);
-        mfma_group(af1, bf1);
-    };
-    int t = 0;
-    for (; t + NSTAGE - 1 < nk; ++t) {
-        wait_vmcnt<(NSTAGE - 2) * G>();
-        __builtin_amdgcn_s_barrier();
-        kslice(t, std::true_type{});
-    }
-    for (; t < nk; ++t) {  // tail: the ring drains
-        if (nk - 1 - t >= 1) wait_vmcnt<G>();
-        else wait_vmcnt<0>();
-        __builtin_amdgcn_s_barrier();
-        kslice(t, std::false_type{});
-    }
-
-    // ---- epilogue.  C layout: col = lane & 31 (query), row = (reg & 3) + 8 (reg >> 2) + 4 (lane >> 5).
+    // ---- epilogue
     __syncthreads();  // every wave has read its last fragments: the first ring slot becomes the two reduction arrays
     float* red_m = reinterpret_cast<float*>(smem);  // [WM][BN]
     float* red_l = red_m + WM * BN;                 // [WM][BN]
@@ -204,26 +89,7 @@ void partition_scan_kernel(const uint16_t* __restrict__ X, const uint16_t* __res
     for (int j = 0; j < NJ; ++j) {
         const int col = wn * TN + j * 32 + fr;
         const int q = q0 + col;
-        unsigned mask = 0u;
-        if (q < nq) {
-#pragma unroll
-            for (int i = 0; i < MI; ++i)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    const int row = rlane + i * 32 + (r & 3) + 8 * (r >> 2);
-                    const float s = acc[i][j][r];
-                    mask |= (row < ntotal && s == s) ? (1u << (i * 16 + r)) : 0u;
-                }
-            if constexpr (SUBSET) {  // rolled: one label test per row that is still in
-                unsigned m2 = mask;
-                while (m2) {
-                    const int b = __builtin_ctz(m2);
-                    m2 &= m2 - 1;
-                    const int row = rlane + (b >> 4) * 32 + (b & 3) + 8 * ((b & 15) >> 2);
-                    if (!subset_allows(ex, q, row)) mask &= ~(1u << b);
-                }
-            }
-        }
+        const unsigned mask = q < nq ? scan_eligible_mask<SUBSET>(acc[0][j], acc[1][j], rlane, ntotal, q, ex) : 0u;
         float mx = -inf;
 #pragma unroll
         for (int i = 0; i < MI; ++i)
@@ -312,51 +178,42 @@ __global__ void __launch_bounds__(FIN_T) partition_finish_kernel(const float2* _
     }
 }
 
-template <int DT, int BN, int WN, bool SUBSET>
-hipError_t launch_scan(const PartitionArgs& a, int64_t nq, int64_t nq_pad, int n_tiles, const FilterExtra& ex, hipStream_t stream) {
-    const int n_qtiles = (int)(nq_pad / BN);
-    const int64_t grid = (int64_t)((n_tiles + 7) / 8) * 8 * n_qtiles;
-    if (grid > 0x7fffffffll) return hipErrorInvalidValue;
-    constexpr int threads = PT_WM * WN * 64;
-    constexpr size_t lds = (size_t)PT_NSTAGE * (PT_BM + BN) * 128;
-    auto kern = partition_scan_kernel<DT, BN, WN, SUBSET>;
-    if (hipError_t e = allow_dynamic_lds((const void*)kern, (int)lds); e != hipSuccess) return e;
-    hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(threads), lds, stream, (const uint16_t*)a.store, (const uint16_t*)a.q_stage, (int)a.dim_pad,
-                       (int)a.ntotal, n_tiles, n_qtiles, (int)nq, a.beta, (float2*)a.part, ex);
+}  // namespace
+
+int64_t scan_nq_pad(int64_t nq) { return nq <= 64 ? 64 : (nq + 127) / 128 * 128; }
+int64_t scan_tiles(int64_t ntotal) { return (ntotal + SCAN_BM - 1) / SCAN_BM; }
+
+hipError_t launch_scan_stage(const ScanInputs& s, int64_t q_first, int64_t nq, int64_t nq_pad, hipStream_t stream) {
+    const int64_t n = nq_pad * (s.dim_pad / 8);
+    hipLaunchKernelGGL(scan_stage_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, s.q_src, s.q_dtype, q_first, nq, s.dim,
+                       (uint16_t*)s.q_stage, s.store_dtype, nq_pad, s.dim_pad);
     return hipGetLastError();
 }
 
-template <int DT>
-hipError_t launch_scan_dt(const PartitionArgs& a, int64_t nq, int64_t nq_pad, int n_tiles, const FilterExtra& ex, hipStream_t stream) {
-    const bool subset = ex.row_label != nullptr;
-    if (nq_pad == 64)
-        return subset ? launch_scan<DT, 64, 1, true>(a, nq, nq_pad, n_tiles, ex, stream) : launch_scan<DT, 64, 1, false>(a, nq, nq_pad, n_tiles, ex, stream);
-    return subset ? launch_scan<DT, 128, 2, true>(a, nq, nq_pad, n_tiles, ex, stream) : launch_scan<DT, 128, 2, false>(a, nq, nq_pad, n_tiles, ex, stream);
+FilterExtra scan_filter_extra(const ScanInputs& s, int64_t q_first) {
+    FilterExtra ex;
+    if (s.q_label != nullptr) {
+        ex.row_label = s.row_label;
+        ex.q_label = s.q_label + (size_t)q_first * s.n_qlab;
+        ex.n_qlab = s.n_qlab;
+    }
+    return ex;
 }
-
-}  // namespace
-
-int64_t log_partition_nq_pad(int64_t nq) { return nq <= 64 ? 64 : (nq + 127) / 128 * 128; }
-int64_t log_partition_tiles(int64_t ntotal) { return (ntotal + PT_BM - 1) / PT_BM; }
 
 hipError_t launch_log_partition(const PartitionArgs& a, int64_t q_first, int64_t nq, hipStream_t stream) {
     if (nq <= 0) return hipSuccess;
-    const int64_t nq_pad = log_partition_nq_pad(nq);
-    const int64_t n_tiles = log_partition_tiles(a.ntotal);
+    const int64_t nq_pad = scan_nq_pad(nq);
+    const int64_t n_tiles = scan_tiles(a.ntotal);
     if (a.dim_pad % 64 != 0 || a.dim_pad <= 0 || a.ntotal < 0 || a.ntotal >= (1ll << 31) - 512 || nq > (1 << 20)) return hipErrorInvalidValue;
     if (n_tiles > 0) {
-        const int64_t n = nq_pad * (a.dim_pad / 8);
-        hipLaunchKernelGGL(partition_stage_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, a.q_src, a.q_dtype, q_first, nq, a.dim,
-                           (uint16_t*)a.q_stage, a.store_dtype, nq_pad, a.dim_pad);
-        if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
-        FilterExtra ex;
-        if (a.q_label != nullptr) {
-            ex.row_label = a.row_label;
-            ex.q_label = a.q_label + (size_t)q_first * a.n_qlab;
-            ex.n_qlab = a.n_qlab;
-        }
-        const hipError_t e = a.store_dtype == 0 ? launch_scan_dt<0>(a, nq, nq_pad, (int)n_tiles, ex, stream)
-                                                : launch_scan_dt<1>(a, nq, nq_pad, (int)n_tiles, ex, stream);
+        if (hipError_t e = launch_scan_stage(a, q_first, nq, nq_pad, stream); e != hipSuccess) return e;
+        const FilterExtra ex = scan_filter_extra(a, q_first);
+        const hipError_t e = scan_dispatch(a.store_dtype, nq_pad, ex.row_label != nullptr, [&](auto dt, auto bn, auto wn, auto subset) {
+            const int n_qtiles = (int)(nq_pad / bn.value);
+            return scan_launch<bn.value, wn.value>(partition_scan_kernel<dt.value, bn.value, wn.value, subset.value>, scan_grid((int)n_tiles, n_qtiles), stream,
+                                                   (const uint16_t*)a.store, (const uint16_t*)a.q_stage, (int)a.dim_pad, (int)a.ntotal, (int)n_tiles,
+                                                   n_qtiles, (int)nq, a.beta, (float2*)a.part, ex);
+        });
         if (e != hipSuccess) return e;
     }
     hipLaunchKernelGGL(partition_finish_kernel, dim3((unsigned)nq), dim3(FIN_T), 0, stream, (const float2*)a.part, n_tiles, a.beta, a.out_max + q_first,

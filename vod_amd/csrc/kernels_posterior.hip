@@ -3,8 +3,8 @@
 //   mean[q, :] = sum_{rows z < ntotal, eligible} p(z | q) x~_z,   p(z | q) = exp(beta <q~, x~_z> - log Z_beta(q)).
 // The call first runs the three launches of kernels_partition.hip unchanged (stage, scan, finish): (max_score, log_rel) are that call's
 // bits, and its `part` array holds every 256-row tile's maximum.  Then two kernels of this file:
-//   scan     one workgroup per (group of PM_GT consecutive row tiles, 64 queries, chunk of PM_DC = 256 columns).  Per tile it repeats the
-//            K loop of partition_scan_kernel (the same instructions in the same order: the same score bits), turns the score accumulators
+//   scan     one workgroup per (group of PM_GT consecutive row tiles, 64 queries, chunk of PM_DC = 256 columns).  Per tile it runs the
+//            K loop of the shared scan core (scan_k_loop, store_scan.h: the same score bits as every other scan), turns the score accumulators
 //            into weights P'[row, q] = exp(beta (s - m_ref(q))) rounded to the store dtype, m_ref(q) = the maximum of the group's tile
 //            maxima (>= every score of the group, so the group's largest weight is exactly 1), and contracts them with the tile's rows
 //            on the MFMA: Y[d, q] += sum_row X[row, d] P'[row, q].  The first product has the corpus as A and the queries as B, so a
@@ -29,59 +29,50 @@
 //           and adds them into its own accumulator in k-step order (block i = 0, 1; step s = 0, 1; inside a step the MFMA's own order),
 //           tile after tile in increasing t; at the end of the group the four waves add as ((w0 + w1) + w2) + w3.
 //   finish  in increasing g, starting from 0.
-// There are no atomics.  A row is eligible by the rule of kernels_partition.hip (row < ntotal, score not NaN, subset_allows); an
+// There are no atomics.  A row is eligible by the rule of the scan core (store_scan.h: row < ntotal, score not NaN, subset_allows); an
 // ineligible row has weight +0 - and 0 * NaN is NaN on the MFMA: a stored NaN / infinity in column d of any scanned tile (rows past
 // ntotal up to the tile's end included) makes column d of every query's mean NaN.  No eligible row or a +inf score: the mean row is 0.
-#include "mips_common.h"
+#include "store_scan.h"
 
 #include "../../include/vodhip.h"
 
 #include <algorithm>
-#include <type_traits>
 
 namespace vodhip {
 
 namespace {
 
-constexpr int PM_BM = 256;     // corpus rows of a tile (= PT_BM of kernels_partition.hip: the part array is indexed by it)
-constexpr int PM_WM = 4;       // row waves
-constexpr int PM_NSTAGE = 3;   // LDS ring depth of the K loop
 constexpr int PM_BN = 64;      // queries of a workgroup
 constexpr int PM_DC = 256;     // columns of a workgroup's accumulator
 constexpr int PM_GT = 64;      // tiles of a group: VODHIP_POSTERIOR_GROUP_ROWS / 256
-constexpr int PM_A_BYTES = PM_BM * 128;
+constexpr int PM_A_BYTES = SCAN_BM * 128;
 constexpr int PM_LDS = (PM_DC / 64) * PM_A_BYTES;  // the 4 slices of the second product; >= the K loop's ring
-static_assert(PM_LDS >= PM_NSTAGE * (PM_BM + PM_BN) * 128, "the ring fits under the slices");
-static_assert(PM_GT * PM_BM == VODHIP_POSTERIOR_GROUP_ROWS, "the header states the group size");
+static_assert(PM_LDS >= scan_ring_bytes(PM_BN), "the ring fits under the slices");
+static_assert(PM_GT * SCAN_BM == VODHIP_POSTERIOR_GROUP_ROWS, "the header states the group size");
 
 typedef short s16x4 __attribute__((ext_vector_type(4)));
 
 // X, Q, part: as partition_scan_kernel (part [n_qtiles * 64][n_xtiles], already written); acc_out [n_groups][n_qtiles * 64][dim_pad]
 template <int DT, bool SUBSET, int NSL>
-__global__ __launch_bounds__(PM_WM * 64, 1)
+__global__ __launch_bounds__(scan_threads(1), 1)
 void posterior_scan_kernel(const uint16_t* __restrict__ X, const uint16_t* __restrict__ Q, int dim_pad, int ntotal, int n_xtiles, int n_qtiles,
                            int n_dchunks, int dc_first, int nq, float beta, const float2* __restrict__ part, float* __restrict__ acc_out, FilterExtra ex) {
-    constexpr int BM = PM_BM, WM = PM_WM, NSTAGE = PM_NSTAGE, BN = PM_BN;
-    constexpr int BK = 64;
-    constexpr int NWAVES = WM;
+    constexpr int BM = SCAN_BM, WM = SCAN_WM, BN = PM_BN;
     constexpr int TM = BM / WM;
     constexpr int MI = TM / 32, NJ = BN / 32;
-    constexpr int ROW_BYTES = BK * 2;
+    constexpr int ROW_BYTES = SCAN_BK * 2;
     constexpr int RPI = 8;
-    constexpr int KK = BK / 16;
-    constexpr int A_BYTES = BM * ROW_BYTES, B_BYTES = BN * ROW_BYTES;
-    constexpr int STAGE_BYTES = A_BYTES + B_BYTES;
-    constexpr int NA = BM / RPI / NWAVES;
-    constexpr int NB = BN / RPI / NWAVES;
-    constexpr int G = NA + NB;
+    constexpr int A_BYTES = PM_A_BYTES;
+    constexpr int NA = BM / RPI / WM;
     constexpr int NYB = 2 * NSL;      // 32-column blocks of the accumulator (NSL = the chunk's 64-column slices)
     static_assert(MI == 2 && NJ == 2, "the eligibility mask holds 2 x 16 rows per lane");
     static_assert(NYB * NJ * 16 * 64 * (int)sizeof(float) <= PM_LDS, "the wave reduction fits the LDS");
 
     extern __shared__ __attribute__((aligned(16))) char smem[];
 
-    // XCD-aware order (as partition_scan_kernel): the n_qtiles * n_dchunks workgroups that walk one group's tiles land on one XCD back
-    // to back and walk them together, so a tile comes from HBM once and from that XCD's L2 for the others
+    // XCD-aware order (scan_block_tile's, with a group for the tile and the chunk index below the query tile): the n_qtiles * n_dchunks
+    // workgroups that walk one group's tiles land on one XCD back to back and walk them together, so a tile comes from HBM once and from
+    // that XCD's L2 for the others
     const int bid = blockIdx.x;
     const int xcd = bid & 7, jj = bid >> 3;
     const int dc = dc_first + jj % n_dchunks;
@@ -97,27 +88,18 @@ void posterior_scan_kernel(const uint16_t* __restrict__ X, const uint16_t* __res
     const int wm = wave;
     const int q0 = qt * BN;
 
-    // per-lane LDS-DMA sources (tile 0): lane -> (row = base + lane / 8, 16-B slot = lane % 8); slot s of row r holds chunk s ^ ((r >> 1) & 7)
+    // per-lane LDS-DMA sources of the slices (tile 0), in the K loop's image: lane -> (row = base + lane / 8, 16-B slot = lane % 8); slot s
+    // of row r holds chunk s ^ ((r >> 1) & 7)
     const int st_row = lane >> 3, st_slot = lane & 7;
     const char* a_src0[NA];
-    const char* b_src[NB];
 #pragma unroll
     for (int t = 0; t < NA; ++t) {
         const int r = (wave * NA + t) * RPI + st_row;
         const int c = st_slot ^ ((r >> 1) & 7);
         a_src0[t] = (const char*)X + ((size_t)r * dim_pad + c * 8) * 2;
     }
-#pragma unroll
-    for (int t = 0; t < NB; ++t) {
-        const int r = (wave * NB + t) * RPI + st_row;
-        const int c = st_slot ^ ((r >> 1) & 7);
-        b_src[t] = (const char*)Q + ((size_t)(q0 + r) * dim_pad + c * 8) * 2;
-    }
 
     const int fr = lane & 31, fh = lane >> 5;
-    const int swz = (fr >> 1) & 7;
-    const int a_row_off = (wm * TM + fr) * ROW_BYTES;
-    const int b_row_off = A_BYTES + fr * ROW_BYTES;
 
     // transposed reads of a slice image (T10): the 16 lanes of group gq = lane >> 4 read a block of 4 rows x 16 columns, lane 4 q + p
     // of the group supplies row q, columns 4 p .. 4 p + 3, and receives column (lane & 15) of the 4 rows.  The group's columns are
@@ -147,81 +129,13 @@ void posterior_scan_kernel(const uint16_t* __restrict__ X, const uint16_t* __res
 #pragma unroll
             for (int r = 0; r < 16; ++r) yacc[b][j][r] = 0.f;
 
-    const int nk = dim_pad / BK;
     for (int xt = t_begin; xt < t_end; ++xt) {
         const int x0 = xt * BM;
         const size_t tile_off = (size_t)x0 * dim_pad * 2;
-        auto stage_part = [&](int ks, int p, int nparts) {
-            char* sa = smem + (ks % NSTAGE) * STAGE_BYTES;
-            char* sb = sa + A_BYTES;
-            const int kbyte = ks * ROW_BYTES;
-#pragma unroll
-            for (int u = 0; u < G; ++u) {
-                if ((u * nparts) / G != p) continue;
-                if (u < NA)
-                    glds16(a_src0[u] + tile_off + kbyte, sa + (wave * NA + u) * RPI * ROW_BYTES);
-                else
-                    glds16(b_src[u - NA] + kbyte, sb + (wave * NB + (u - NA)) * RPI * ROW_BYTES);
-            }
-        };
-
-        f32x16 acc[MI][NJ];
-#pragma unroll
-        for (int i = 0; i < MI; ++i)
-#pragma unroll
-            for (int j = 0; j < NJ; ++j)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
 
         __syncthreads();  // the previous tile's transposed reads are done: the ring may be written
-#pragma unroll
-        for (int s = 0; s < NSTAGE - 1; ++s)
-            if (s < nk) stage_part(s, 0, 1);
-
-        // ---- the K loop of partition_scan_kernel, instruction for instruction: the same score bits
-        auto load_frags = [&](const char* base, int kk, u32x4(&af)[MI], u32x4(&bf)[NJ]) {
-            const int slot_off = ((2 * kk + fh) ^ swz) << 4;
-#pragma unroll
-            for (int i = 0; i < MI; ++i) af[i] = *(const u32x4*)(base + a_row_off + i * 32 * ROW_BYTES + slot_off);
-#pragma unroll
-            for (int j = 0; j < NJ; ++j) bf[j] = *(const u32x4*)(base + b_row_off + j * 32 * ROW_BYTES + slot_off);
-        };
-        auto mfma_group = [&](u32x4(&af)[MI], u32x4(&bf)[NJ]) {
-#pragma unroll
-            for (int i = 0; i < MI; ++i)
-#pragma unroll
-                for (int j = 0; j < NJ; ++j) acc[i][j] = mfma32<DT>(af[i], bf[j], acc[i][j]);
-        };
-        auto kslice = [&](int t, auto pre_tag) {
-            constexpr bool PRE = decltype(pre_tag)::value;
-            const char* base = smem + (t % NSTAGE) * STAGE_BYTES;
-            const int ks = t + NSTAGE - 1;
-            u32x4 af0[MI], bf0[NJ], af1[MI], bf1[NJ];
-            load_frags(base, 0, af0, bf0);
-            if constexpr (PRE) stage_part(ks, 0, KK);
-            load_frags(base, 1, af1, bf1);
-            mfma_group(af0, bf0);
-            if constexpr (PRE) stage_part(ks, 1, KK);
-            load_frags(base, 2, af0, bf0);
-            mfma_group(af1, bf1);
-            if constexpr (PRE) stage_part(ks, 2, KK);
-            load_frags(base, 3, af1, bf1);
-            mfma_group(af0, bf0);
-            if constexpr (PRE) stage_part(ks, 3, KK);
-            mfma_group(af1, bf1);
-        };
-        int t = 0;
-        for (; t + NSTAGE - 1 < nk; ++t) {
-            wait_vmcnt<(NSTAGE - 2) * G>();
-            __builtin_amdgcn_s_barrier();
-            kslice(t, std::true_type{});
-        }
-        for (; t < nk; ++t) {  // tail: the ring drains
-            if (nk - 1 - t >= 1) wait_vmcnt<G>();
-            else wait_vmcnt<0>();
-            __builtin_amdgcn_s_barrier();
-            kslice(t, std::false_type{});
-        }
+        f32x16 acc[MI][NJ];
+        scan_k_loop<DT, BN, 1>(X + (size_t)x0 * dim_pad, Q + (size_t)q0 * dim_pad, dim_pad, smem, acc);
 
         __syncthreads();  // every wave has read its last fragments: the LDS becomes the slice images
         // slice sl of the chunk is the A half of K-loop step 4 dc + sl, in the same image
@@ -233,33 +147,13 @@ void posterior_scan_kernel(const uint16_t* __restrict__ X, const uint16_t* __res
             }
 
         // ---- scores -> weights, packed as the B fragments of the second product (while the slices arrive)
-        // C layout: col = lane & 31 (query), row = (reg & 3) + 8 (reg >> 2) + 4 (lane >> 5)
         const int rlane = x0 + wm * TM + 4 * fh;  // the lane's row of (block 0, register 0)
         u32x4 wf[MI][2][NJ];
 #pragma unroll
         for (int j = 0; j < NJ; ++j) {
             const int col = j * 32 + fr;
             const int q = q0 + col;
-            unsigned mask = 0u;
-            if (q < nq) {
-#pragma unroll
-                for (int i = 0; i < MI; ++i)
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) {
-                        const int row = rlane + i * 32 + (r & 3) + 8 * (r >> 2);
-                        const float s = acc[i][j][r];
-                        mask |= (row < ntotal && s == s) ? (1u << (i * 16 + r)) : 0u;
-                    }
-                if constexpr (SUBSET) {  // rolled: one label test per row that is still in
-                    unsigned m2 = mask;
-                    while (m2) {
-                        const int b = __builtin_ctz(m2);
-                        m2 &= m2 - 1;
-                        const int row = rlane + (b >> 4) * 32 + (b & 3) + 8 * ((b & 15) >> 2);
-                        if (!subset_allows(ex, q, row)) mask &= ~(1u << b);
-                    }
-                }
-            }
+            unsigned mask = q < nq ? scan_eligible_mask<SUBSET>(acc[0][j], acc[1][j], rlane, ntotal, q, ex) : 0u;
             const float m = mref[j];
             if (!(m > -inf && m < inf)) mask = 0u;  // no eligible row in the group, or a +inf score: the finish writes the zero row
 #pragma unroll
@@ -412,7 +306,7 @@ hipError_t launch_pm_scan_n(const PosteriorArgs& a, int64_t nq, int n_qtiles, in
     if (grid > 0x7fffffffll) return hipErrorInvalidValue;
     auto kern = posterior_scan_kernel<DT, SUBSET, NSL>;
     if (hipError_t e = allow_dynamic_lds((const void*)kern, PM_LDS); e != hipSuccess) return e;
-    hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(PM_WM * 64), PM_LDS, stream, (const uint16_t*)a.p.store, (const uint16_t*)a.p.q_stage, (int)a.p.dim_pad,
+    hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(scan_threads(1)), PM_LDS, stream, (const uint16_t*)a.p.store, (const uint16_t*)a.p.q_stage, (int)a.p.dim_pad,
                        (int)a.p.ntotal, n_tiles, n_qtiles, n_dchunks, dc_first, (int)nq, a.p.beta, (const float2*)a.p.part, a.acc, ex);
     return hipGetLastError();
 }
@@ -432,21 +326,16 @@ hipError_t launch_pm_scan(const PosteriorArgs& a, int64_t nq, int n_qtiles, int 
 
 }  // namespace
 
-int64_t posterior_mean_groups(int64_t ntotal) { return (log_partition_tiles(ntotal) + PM_GT - 1) / PM_GT; }
+int64_t posterior_mean_groups(int64_t ntotal) { return (scan_tiles(ntotal) + PM_GT - 1) / PM_GT; }
 
 hipError_t launch_posterior_mean(const PosteriorArgs& a, int64_t q_first, int64_t nq, hipStream_t stream) {
     if (nq <= 0) return hipSuccess;
     if (hipError_t e = launch_log_partition(a.p, q_first, nq, stream); e != hipSuccess) return e;  // (checks the shapes)
-    const int64_t nq_pad = log_partition_nq_pad(nq);
-    const int n_tiles = (int)log_partition_tiles(a.p.ntotal);
+    const int64_t nq_pad = scan_nq_pad(nq);
+    const int n_tiles = (int)scan_tiles(a.p.ntotal);
     const int n_groups = (int)posterior_mean_groups(a.p.ntotal);
     if (n_tiles > 0) {
-        FilterExtra ex;
-        if (a.p.q_label != nullptr) {
-            ex.row_label = a.p.row_label;
-            ex.q_label = a.p.q_label + (size_t)q_first * a.p.n_qlab;
-            ex.n_qlab = a.p.n_qlab;
-        }
+        const FilterExtra ex = scan_filter_extra(a.p, q_first);
         const int n_qtiles = (int)(nq_pad / PM_BN);
         const bool subset = ex.row_label != nullptr;
         hipError_t e;

@@ -5,9 +5,9 @@
 // The result is the k eligible rows with the largest keys by (key desc, id asc); log_tau = the (k+1)-th largest key - log Z.
 // The call first runs the three launches of kernels_partition.hip unchanged (stage, scan, finish): (max_score, log_rel) are that call's
 // bits.  Then four launches of this file:
-//   key-max   the K loop of partition_scan_kernel (the same instructions in the same order: the same score bits) over a 256-row tile x
-//             64 | 128 queries; the epilogue writes the tile's MAXIMUM finite key per query, keymax[q][tile] (-inf: none).  A maximum
-//             has no order: no atomics.
+//   key-max   the shared scan core (store_scan.h: the K loop, hence the score bits, and the eligibility rule of every whole-store scan)
+//             over a 256-row tile x 64 | 128 queries; the epilogue writes the tile's MAXIMUM finite key per query, keymax[q][tile]
+//             (-inf: none).  A maximum has no order: no atomics.
 //   threshold one workgroup per query: theta[q] = the (k+1)-th largest of the query's tile maxima by a radix select over the
 //             order-preserving image of the float (4 passes of 8 bits; the histogram counts do not depend on the order of the LDS
 //             atomics); fewer than k + 1 tiles with a finite maximum: -inf.  k + 1 DISTINCT rows have keys >= theta, so theta is a lower
@@ -37,21 +37,17 @@
 // >= theta.  A key that is USED - a tile maximum, a candidate - is always the bits of sample_key; a row that is skipped has a key
 // strictly below what it would be compared with.
 // A query whose log Z is not finite (no eligible row, a +inf score) is all pads; a -inf score has a -inf key and is never drawn.
-#include "mips_common.h"
+#include "store_scan.h"
 #include "wg_sort.h"
 
 #include "../../include/vodhip.h"
 
 #include <algorithm>
-#include <type_traits>
 
 namespace vodhip {
 
 namespace {
 
-constexpr int SP_BM = 256;     // corpus rows of a tile (= PT_BM of kernels_partition.hip)
-constexpr int SP_WM = 4;       // row waves
-constexpr int SP_NSTAGE = 3;   // LDS ring depth
 constexpr int SP_SLACK_TILES = VODHIP_SAMPLE_SLACK_TILES;
 constexpr int SP_SORT = 2048, SP_KEEP = 256;  // select: keys per sort, of which the running best
 
@@ -109,40 +105,24 @@ enum : int { SPS_OVERFLOW = 0, SPS_SELF = 1, SPS_MAX_CAND = 2, SPS_SKIPPED = 3, 
 
 // X: the store [>= n_xtiles * 256 rows][dim_pad]; Q: the staged queries [n_qtiles * BN][dim_pad]
 template <int DT, int BN, int WN, bool SUBSET>
-__global__ __launch_bounds__(SP_WM* WN * 64, 1)
+__global__ __launch_bounds__(scan_threads(WN), 1)
 void sample_scan_kernel(const uint16_t* __restrict__ X, const uint16_t* __restrict__ Q, int dim_pad, int ntotal, int n_xtiles, int n_qtiles,
                         int nq, float beta, SampleScan sp, FilterExtra ex) {
-    constexpr int BM = SP_BM, WM = SP_WM, NSTAGE = SP_NSTAGE;
-    constexpr int BK = 64;
-    constexpr int NWAVES = WM * WN;
-    constexpr int TM = BM / WM, TN = BN / WN;
+    constexpr int WM = SCAN_WM;
+    constexpr int TM = SCAN_BM / WM, TN = BN / WN;
     constexpr int MI = TM / 32, NJ = TN / 32;
-    constexpr int ROW_BYTES = BK * 2;
-    constexpr int RPI = 8;
-    constexpr int KK = BK / 16;
-    constexpr int A_BYTES = BM * ROW_BYTES, B_BYTES = BN * ROW_BYTES;
-    constexpr int STAGE_BYTES = A_BYTES + B_BYTES;
-    constexpr int NA = BM / RPI / NWAVES;
-    constexpr int NB = BN / RPI / NWAVES;
-    constexpr int G = NA + NB;
-    static_assert(BM % (RPI * NWAVES) == 0 && BN % (RPI * NWAVES) == 0, "tile/wave mismatch");
-    static_assert(MI == 2, "the eligibility mask holds 2 x 16 rows per lane");
-    static_assert(WM * BN * (int)sizeof(float) <= STAGE_BYTES, "the reduction array reuses the first ring slot");
+    static_assert(WM * BN * (int)sizeof(float) <= scan_ring_bytes(BN) / SCAN_NSTAGE, "the reduction array reuses the first ring slot");
 
     extern __shared__ __attribute__((aligned(16))) char smem[];
-
-    // XCD-aware tile order (as partition_scan_kernel)
-    const int bid = blockIdx.x;
-    const int xcd = bid & 7, jj = bid >> 3;
-    const int qt = jj % n_qtiles;
-    const int xt = (jj / n_qtiles) * 8 + xcd;
-    if (xt >= n_xtiles) return;
+    int qt, xt;
+    if (!scan_block_tile(blockIdx.x, n_qtiles, n_xtiles, &qt, &xt)) return;
 
     const int tid = threadIdx.x;
     const int lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wm = wave / WN, wn = wave % WN;
-    const int x0 = xt * BM;
+    const int fr = lane & 31, fh = lane >> 5;
+    const int x0 = xt * SCAN_BM;
     const int q0 = qt * BN;
     const float inf = __builtin_inff();
 
@@ -158,100 +138,10 @@ void sample_scan_kernel(const uint16_t* __restrict__ X, const uint16_t* __restri
         }
     }
 
-    // per-lane LDS-DMA sources: lane -> (row = base + lane / 8, 16-B slot = lane % 8); slot s of row r holds chunk s ^ ((r >> 1) & 7)
-    const int st_row = lane >> 3, st_slot = lane & 7;
-    const char* a_src[NA];
-    const char* b_src[NB];
-#pragma unroll
-    for (int t = 0; t < NA; ++t) {
-        const int r = (wave * NA + t) * RPI + st_row;
-        const int c = st_slot ^ ((r >> 1) & 7);
-        a_src[t] = (const char*)X + ((size_t)(x0 + r) * dim_pad + c * 8) * 2;
-    }
-#pragma unroll
-    for (int t = 0; t < NB; ++t) {
-        const int r = (wave * NB + t) * RPI + st_row;
-        const int c = st_slot ^ ((r >> 1) & 7);
-        b_src[t] = (const char*)Q + ((size_t)(q0 + r) * dim_pad + c * 8) * 2;
-    }
-    auto stage_part = [&](int ks, int p, int nparts) {
-        char* sa = smem + (ks % NSTAGE) * STAGE_BYTES;
-        char* sb = sa + A_BYTES;
-        const int kbyte = ks * ROW_BYTES;
-#pragma unroll
-        for (int u = 0; u < G; ++u) {
-            if ((u * nparts) / G != p) continue;
-            if (u < NA)
-                glds16(a_src[u] + kbyte, sa + (wave * NA + u) * RPI * ROW_BYTES);
-            else
-                glds16(b_src[u - NA] + kbyte, sb + (wave * NB + (u - NA)) * RPI * ROW_BYTES);
-        }
-    };
-
-    const int fr = lane & 31, fh = lane >> 5;
-    const int swz = (fr >> 1) & 7;
-    const int a_row_off = (wm * TM + fr) * ROW_BYTES;
-    const int b_row_off = A_BYTES + (wn * TN + fr) * ROW_BYTES;
-
     f32x16 acc[MI][NJ];
-#pragma unroll
-    for (int i = 0; i < MI; ++i)
-#pragma unroll
-        for (int j = 0; j < NJ; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+    scan_k_loop<DT, BN, WN>(X + (size_t)x0 * dim_pad, Q + (size_t)q0 * dim_pad, dim_pad, smem, acc);
 
-    const int nk = dim_pad / BK;
-#pragma unroll
-    for (int s = 0; s < NSTAGE - 1; ++s)
-        if (s < nk) stage_part(s, 0, 1);
-
-    // ---- the K loop of partition_scan_kernel, instruction for instruction: the same score bits
-    auto load_frags = [&](const char* base, int kk, u32x4(&af)[MI], u32x4(&bf)[NJ]) {
-        const int slot_off = ((2 * kk + fh) ^ swz) << 4;
-#pragma unroll
-        for (int i = 0; i < MI; ++i) af[i] = *(const u32x4*)(base + a_row_off + i * 32 * ROW_BYTES + slot_off);
-#pragma unroll
-        for (int j = 0; j < NJ; ++j) bf[j] = *(const u32x4*)(base + b_row_off + j * 32 * ROW_BYTES + slot_off);
-    };
-    auto mfma_group = [&](u32x4(&af)[MI], u32x4(&bf)[NJ]) {
-#pragma unroll
-        for (int i = 0; i < MI; ++i)
-#pragma unroll
-            for (int j = 0; j < NJ; ++j) acc[i][j] = mfma32<DT>(af[i], bf[j], acc[i][j]);
-    };
-    auto kslice = [&](int t, auto pre_tag) {
-        constexpr bool PRE = decltype(pre_tag)::value;
-        const char* base = smem + (t % NSTAGE) * STAGE_BYTES;
-        const int ks = t + NSTAGE - 1;
-        u32x4 af0[MI], bf0[NJ], af1[MI], bf1[NJ];
-        load_frags(base, 0, af0, bf0);
-        if constexpr (PRE) stage_part(ks, 0, KK);
-        load_frags(base, 1, af1, bf1);
-        mfma_group(af0, bf0);
-        if constexpr (PRE) stage_part(ks, 1, KK);
-        load_frags(base, 2, af0, bf0);
-        mfma_group(af1, bf1);
-        if constexpr (PRE) stage_part(ks, 2, KK);
-        load_frags(base, 3, af1, bf1);
-        mfma_group(af0, bf0);
-        if constexpr (PRE) stage_part(ks, 3, KK);
-        mfma_group(af1, bf1);
-    };
-    int t = 0;
-    for (; t + NSTAGE - 1 < nk; ++t) {
-        wait_vmcnt<(NSTAGE - 2) * G>();
-        __builtin_amdgcn_s_barrier();
-        kslice(t, std::true_type{});
-    }
-    for (; t < nk; ++t) {  // tail: the ring drains
-        if (nk - 1 - t >= 1) wait_vmcnt<G>();
-        else wait_vmcnt<0>();
-        __builtin_amdgcn_s_barrier();
-        kslice(t, std::false_type{});
-    }
-
-    // ---- epilogue.  C layout: col = lane & 31 (query), row = (reg & 3) + 8 (reg >> 2) + 4 (lane >> 5).
+    // ---- epilogue
     __syncthreads();  // every wave has read its last fragments: the first ring slot becomes the reduction array
     float* red_m = reinterpret_cast<float*>(smem);  // [WM][BN]
     const int rlane = x0 + wm * TM + 4 * fh;        // the lane's row of (block 0, register 0): a multiple of 4
@@ -270,26 +160,7 @@ void sample_scan_kernel(const uint16_t* __restrict__ X, const uint16_t* __restri
             th = sp.theta[q];
             act = km > -inf && km >= th;
         }
-        unsigned mask = 0u;
-        if (act) {
-#pragma unroll
-            for (int i = 0; i < MI; ++i)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    const int row = rlane + i * 32 + (r & 3) + 8 * (r >> 2);
-                    const float s = acc[i][j][r];
-                    mask |= (row < ntotal && s == s) ? (1u << (i * 16 + r)) : 0u;
-                }
-            if constexpr (SUBSET) {  // rolled: one label test per row that is still in
-                unsigned m2 = mask;
-                while (m2) {
-                    const int b = __builtin_ctz(m2);
-                    m2 &= m2 - 1;
-                    const int row = rlane + (b >> 4) * 32 + (b & 3) + 8 * ((b & 15) >> 2);
-                    if (!subset_allows(ex, q, row)) mask &= ~(1u << b);
-                }
-            }
-        }
+        const unsigned mask = act ? scan_eligible_mask<SUBSET>(acc[0][j], acc[1][j], rlane, ntotal, q, ex) : 0u;
         // Pass 1, every eligible row: an UPPER bound of its key from the high word alone (key_upper) - one generator call per four rows
         // and no library logarithm.  -inf: not eligible.
         float ub[MI * 16];
@@ -339,7 +210,7 @@ void sample_scan_kernel(const uint16_t* __restrict__ X, const uint16_t* __restri
             if (go) {
 #pragma unroll
                 for (int r = 0; r < MI * 16; ++r) ub[r] = r == rsel ? -inf : ub[r];
-                const int row = rlane + (rsel >> 4) * 32 + (rsel & 3) + 8 * ((rsel & 15) >> 2);
+                const int row = scan_lane_row(rlane, rsel);
                 const unsigned long long g = sp.id_base + (unsigned long long)row;
                 const unsigned long long c = g >> 2;
                 const uint4 h = philox4x32_10(make_uint4((unsigned)c, (unsigned)(c >> 32), qs, 0u), sp.seed_lo, sp.seed_hi);
@@ -515,47 +386,30 @@ __global__ void __launch_bounds__(256) sample_select_kernel(SampleSelect a) {
     }
 }
 
-template <int DT, int BN, int WN, bool SUBSET>
 hipError_t launch_sp_scan(const PosteriorSampleArgs& a, const SampleScan& sp, int64_t nq, int64_t nq_pad, int n_tiles, const FilterExtra& ex, hipStream_t stream) {
-    const int n_qtiles = (int)(nq_pad / BN);
-    const int64_t grid = (int64_t)((n_tiles + 7) / 8) * 8 * n_qtiles;
-    if (grid > 0x7fffffffll) return hipErrorInvalidValue;
-    constexpr int threads = SP_WM * WN * 64;
-    constexpr size_t lds = (size_t)SP_NSTAGE * (SP_BM + BN) * 128;
-    auto kern = sample_scan_kernel<DT, BN, WN, SUBSET>;
-    if (hipError_t e = allow_dynamic_lds((const void*)kern, (int)lds); e != hipSuccess) return e;
-    hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(threads), lds, stream, (const uint16_t*)a.p.store, (const uint16_t*)a.p.q_stage, (int)a.p.dim_pad,
-                       (int)a.p.ntotal, n_tiles, n_qtiles, (int)nq, a.p.beta, sp, ex);
-    return hipGetLastError();
-}
-
-hipError_t launch_sp_scan_any(const PosteriorSampleArgs& a, const SampleScan& sp, int64_t nq, int64_t nq_pad, int n_tiles, const FilterExtra& ex, hipStream_t stream) {
-    const bool subset = ex.row_label != nullptr;
-    if (a.p.store_dtype == 0) {
-        if (nq_pad == 64)
-            return subset ? launch_sp_scan<0, 64, 1, true>(a, sp, nq, nq_pad, n_tiles, ex, stream) : launch_sp_scan<0, 64, 1, false>(a, sp, nq, nq_pad, n_tiles, ex, stream);
-        return subset ? launch_sp_scan<0, 128, 2, true>(a, sp, nq, nq_pad, n_tiles, ex, stream) : launch_sp_scan<0, 128, 2, false>(a, sp, nq, nq_pad, n_tiles, ex, stream);
-    }
-    if (nq_pad == 64)
-        return subset ? launch_sp_scan<1, 64, 1, true>(a, sp, nq, nq_pad, n_tiles, ex, stream) : launch_sp_scan<1, 64, 1, false>(a, sp, nq, nq_pad, n_tiles, ex, stream);
-    return subset ? launch_sp_scan<1, 128, 2, true>(a, sp, nq, nq_pad, n_tiles, ex, stream) : launch_sp_scan<1, 128, 2, false>(a, sp, nq, nq_pad, n_tiles, ex, stream);
+    return scan_dispatch(a.p.store_dtype, nq_pad, ex.row_label != nullptr, [&](auto dt, auto bn, auto wn, auto subset) {
+        const int n_qtiles = (int)(nq_pad / bn.value);
+        return scan_launch<bn.value, wn.value>(sample_scan_kernel<dt.value, bn.value, wn.value, subset.value>, scan_grid(n_tiles, n_qtiles), stream,
+                                               (const uint16_t*)a.p.store, (const uint16_t*)a.p.q_stage, (int)a.p.dim_pad, (int)a.p.ntotal, n_tiles, n_qtiles,
+                                               (int)nq, a.p.beta, sp, ex);
+    });
 }
 
 }  // namespace
 
 int64_t sample_posterior_stride(int64_t ntotal, int k) {
-    const int64_t tiles = log_partition_tiles(ntotal);
-    return SP_BM * std::max<int64_t>(1, std::min<int64_t>(tiles, (int64_t)k + 1 + SP_SLACK_TILES));
+    const int64_t tiles = scan_tiles(ntotal);
+    return SCAN_BM * std::max<int64_t>(1, std::min<int64_t>(tiles, (int64_t)k + 1 + SP_SLACK_TILES));
 }
 int64_t sample_posterior_ctl_words(int64_t nq_pad) { return nq_pad * CNT_STRIDE + 2 * nq_pad; }
 
 hipError_t launch_sample_posterior(const PosteriorSampleArgs& a, int64_t q_first, int64_t nq, hipStream_t stream) {
     if (nq <= 0) return hipSuccess;
-    if (a.k < 1 || a.k > 255 || a.stride < SP_BM || a.stride > (1ll << 30)) return hipErrorInvalidValue;
+    if (a.k < 1 || a.k > 255 || a.stride < SCAN_BM || a.stride > (1ll << 30)) return hipErrorInvalidValue;
     if (hipError_t e = launch_log_partition(a.p, q_first, nq, stream); e != hipSuccess) return e;  // (checks the shapes)
     if (a.ev && hipEventRecord(a.ev[1], stream) != hipSuccess) return hipErrorUnknown;
-    const int64_t nq_pad = log_partition_nq_pad(nq);
-    const int n_tiles = (int)log_partition_tiles(a.p.ntotal);
+    const int64_t nq_pad = scan_nq_pad(nq);
+    const int n_tiles = (int)scan_tiles(a.p.ntotal);
     unsigned int* cnt = a.ctl;                                   // [nq_pad * CNT_STRIDE]
     unsigned int* n_hit = a.ctl + nq_pad * CNT_STRIDE;           // [nq_pad]
     float* theta = (float*)(a.ctl + nq_pad * CNT_STRIDE + nq_pad);  // [nq_pad]
@@ -574,19 +428,14 @@ hipError_t launch_sample_posterior(const PosteriorSampleArgs& a, int64_t q_first
     sp.qs0 = (unsigned)((unsigned long long)a.query_offset + (unsigned long long)q_first);
     sp.id_base = (unsigned long long)a.id_base;
     if (n_tiles > 0) {
-        FilterExtra ex;
-        if (a.p.q_label != nullptr) {
-            ex.row_label = a.p.row_label;
-            ex.q_label = a.p.q_label + (size_t)q_first * a.p.n_qlab;
-            ex.n_qlab = a.p.n_qlab;
-        }
-        if (hipError_t e = launch_sp_scan_any(a, sp, nq, nq_pad, n_tiles, ex, stream); e != hipSuccess) return e;
+        const FilterExtra ex = scan_filter_extra(a.p, q_first);
+        if (hipError_t e = launch_sp_scan(a, sp, nq, nq_pad, n_tiles, ex, stream); e != hipSuccess) return e;
         if (a.ev && hipEventRecord(a.ev[2], stream) != hipSuccess) return hipErrorUnknown;
         hipLaunchKernelGGL(sample_threshold_kernel, dim3((unsigned)nq), dim3(TH_T), 0, stream, (const float*)a.keymax, n_tiles, a.k, theta, n_hit);
         if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
         if (a.ev && hipEventRecord(a.ev[3], stream) != hipSuccess) return hipErrorUnknown;
         sp.emit = 1;
-        if (hipError_t e = launch_sp_scan_any(a, sp, nq, nq_pad, n_tiles, ex, stream); e != hipSuccess) return e;
+        if (hipError_t e = launch_sp_scan(a, sp, nq, nq_pad, n_tiles, ex, stream); e != hipSuccess) return e;
         if (a.ev && hipEventRecord(a.ev[4], stream) != hipSuccess) return hipErrorUnknown;
     } else if (a.ev) {
         for (int i = 2; i <= 4; ++i)

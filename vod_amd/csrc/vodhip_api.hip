@@ -12,6 +12,7 @@
 #include <cstring>
 #include <string>
 #include <deque>
+#include <initializer_list>
 #include <mutex>
 #include <thread>
 #include <vector>
@@ -1213,40 +1214,94 @@ int vodhip_index_sum_ids(vodhip_index_t* ix, const int64_t* ids_dev, const float
     return 0;
 }
 
-// ---- log-partition scan (kernels_partition.hip) ---------------------------------------------------------------------------
-// Like the listed calls: reads the store (and the row labels) only; staged queries and partials are stream-ordered temporaries.
+// ---- the whole-store scans (store_scan.h): log_partition, the rank calls, posterior_mean, sample_posterior ---------------------------
+// Like the listed calls they read the store (and the row labels) only.  What the four flat calls share:
+
+// a message of log_partition_args_error, as the flat calls report it
+static int partition_args_fail(const char* msg, int q_dtype, float beta) {
+    if (!strcmp(msg, "invalid q_dtype")) return fail("invalid q_dtype %d", q_dtype);
+    if (!strncmp(msg, "beta", 4)) return fail("beta=%g: %s", (double)beta, msg);
+    return fail("%s", msg);
+}
+
+// the indexes no scan accepts; `what` names the operation in the message
+static int scan_refusal(const vodhip_index_t* ix, const char* what, const void* q_labels_dev) {
+    if (ix->l2) return fail("%s is not supported on an L2 index (VODHIP_L2): its scores are distances, not similarities", what);
+    if (ix->exact) return fail("%s is not supported on a VODHIP_EXACT_F32 store: the scan scores the rounded rows, that store's contract is the float32 rows", what);
+    if (q_labels_dev && !ix->row_label) return fail("set the row labels first (vodhip_index_set_row_labels)");
+    return 0;
+}
+
+static void fill_scan_inputs(ScanInputs& s, const vodhip_index_t* ix, const void* queries, int q_dtype, const int32_t* q_labels_dev, int n_per_query) {
+    s.store = ix->data;
+    s.dim = ix->dim;
+    s.dim_pad = ix->dim_pad;
+    s.ntotal = ix->ntotal;
+    s.store_dtype = ix->dtype;
+    s.q_src = queries;
+    s.q_dtype = q_dtype;
+    s.row_label = ix->row_label;
+    s.q_label = q_labels_dev;
+    s.n_qlab = q_labels_dev ? n_per_query : 0;
+}
+
+// queries per slice of a batch: a multiple of 128 (or 64) up to 1024 that keeps temporaries of per_query bytes each under
+// VODHIP_POSTERIOR_TEMP_BYTES unless a 64-query slice alone needs more
+static int64_t scan_slice_queries(size_t per_query) {
+    const int64_t slice = (int64_t)((size_t)VODHIP_POSTERIOR_TEMP_BYTES / per_query) / 128 * 128;
+    return std::min<int64_t>(1024, std::max<int64_t>(64, slice));
+}
+
+// the stream-ordered temporaries of a call: one block per byte count, none (NULL) for a count of 0
+struct ScanTemps {
+    static constexpr int MAX = 4;
+    void* p[MAX] = {nullptr, nullptr, nullptr, nullptr};
+    hipStream_t stream = nullptr;
+    int alloc(std::initializer_list<size_t> bytes) {  // 0, or the failure reported with nothing left allocated
+        int i = 0;
+        for (const size_t n : bytes) {
+            if (n != 0) {
+                if (hipError_t e = hipMallocAsync(&p[i], n, stream); e != hipSuccess) {
+                    (void)hipGetLastError();
+                    p[i] = nullptr;
+                    (void)release();
+                    return fail("hipMallocAsync of a %zu-byte temporary failed: %s", n, hipGetErrorString(e));
+                }
+            }
+            ++i;
+        }
+        return 0;
+    }
+    hipError_t release() {  // frees every block behind the launches; the first error
+        hipError_t fe = hipSuccess;
+        for (void*& q : p) {
+            if (q)
+                if (hipError_t e = hipFreeAsync(q, stream); e != hipSuccess && fe == hipSuccess) fe = e;
+            q = nullptr;
+        }
+        return fe;
+    }
+};
+
+// ---- log-partition scan (kernels_partition.hip): staged queries and partials are stream-ordered temporaries ----------------------
 int vodhip_index_log_partition(vodhip_index_t* ix, const void* queries, int q_dtype, int64_t nq, float beta, const int32_t* q_labels_dev,
                                int n_per_query, float* out_max, float* out_log_rel, void* stream_) {
     if (!ix) return fail("index is NULL");
-    if (const char* msg = log_partition_args_error(queries, q_dtype, nq, beta, q_labels_dev, n_per_query, out_max, out_log_rel)) {
-        if (!strcmp(msg, "invalid q_dtype")) return fail("invalid q_dtype %d", q_dtype);
-        if (!strncmp(msg, "beta", 4)) return fail("beta=%g: %s", (double)beta, msg);
-        return fail("%s", msg);
-    }
-    if (ix->l2) return fail("log_partition is not supported on an L2 index (VODHIP_L2): its scores are distances, not similarities");
-    if (ix->exact) return fail("log_partition is not supported on a VODHIP_EXACT_F32 store: the scan scores the rounded rows, that store's contract is the float32 rows");
-    if (q_labels_dev && !ix->row_label) return fail("set the row labels first (vodhip_index_set_row_labels)");
+    if (const char* msg = log_partition_args_error(queries, q_dtype, nq, beta, q_labels_dev, n_per_query, out_max, out_log_rel))
+        return partition_args_fail(msg, q_dtype, beta);
+    if (scan_refusal(ix, "log_partition", q_labels_dev)) return -1;
     if (nq == 0) return 0;
     HIP_OK(hipSetDevice(ix->device));
     hipStream_t stream = (hipStream_t)stream_;
     constexpr int64_t Q_CHUNK = 1024;  // queries per scan launch (a multiple of the query tile): bounds the partials' size
     PartitionArgs a;
-    a.store = ix->data;
-    a.dim = ix->dim;
-    a.dim_pad = ix->dim_pad;
-    a.ntotal = ix->ntotal;
-    a.store_dtype = ix->dtype;
-    a.q_src = queries;
-    a.q_dtype = q_dtype;
-    a.row_label = ix->row_label;
-    a.q_label = q_labels_dev;
-    a.n_qlab = q_labels_dev ? n_per_query : 0;
+    fill_scan_inputs(a, ix, queries, q_dtype, q_labels_dev, n_per_query);
     a.beta = beta;
     a.out_max = out_max;
     a.out_log_rel = out_log_rel;
-    const int64_t nq_pad = log_partition_nq_pad(std::min(nq, Q_CHUNK));
+    const int64_t nq_pad = scan_nq_pad(std::min(nq, Q_CHUNK));
     const size_t stage_bytes = (size_t)nq_pad * (size_t)ix->dim_pad * 2;
-    const size_t part_bytes = std::max<size_t>(8, (size_t)log_partition_tiles(a.ntotal) * (size_t)nq_pad * 8);
+    const size_t part_bytes = std::max<size_t>(8, (size_t)scan_tiles(a.ntotal) * (size_t)nq_pad * 8);
     HIP_OK(hipMallocAsync(&a.q_stage, stage_bytes, stream));
     if (hipError_t e = hipMallocAsync(&a.part, part_bytes, stream); e != hipSuccess) {
         (void)hipGetLastError();
@@ -1264,7 +1319,6 @@ int vodhip_index_log_partition(vodhip_index_t* ix, const void* queries, int q_dt
 }
 
 // ---- exact ranks (kernels_rank.hip): pick the listed pairs' scan scores, count the store against them -----------------------------
-// Like the log-partition call: reads the store (and the row labels) only; every temporary is stream-ordered.
 static int rank_call(vodhip_index_t* ix, int mode, const char* what, const void* queries, int q_dtype, int64_t nq, const int64_t* ids_dev,
                      const float* thresholds_dev, const int64_t* tie_ids_dev, int64_t m, int64_t id_base, const int32_t* q_labels_dev,
                      int n_per_query, int64_t* out_counts, float* out_scores, int32_t* out_rows, hipStream_t stream) {
@@ -1280,22 +1334,11 @@ static int rank_call(vodhip_index_t* ix, int mode, const char* what, const void*
         if (mode != RANK_MODE_PICK && !out_counts) return fail(mode == RANK_MODE_RANK ? "out_ranks is NULL" : "out_counts is NULL");
         if (mode != RANK_MODE_THRESHOLDS && !out_scores) return fail("out_scores is NULL");
     }
-    if (ix->l2) return fail("%s is not supported on an L2 index (VODHIP_L2): its scores are distances, not similarities", what);
-    if (ix->exact) return fail("%s is not supported on a VODHIP_EXACT_F32 store: the scan scores the rounded rows, that store's contract is the float32 rows", what);
-    if (q_labels_dev && !ix->row_label) return fail("set the row labels first (vodhip_index_set_row_labels)");
+    if (scan_refusal(ix, what, q_labels_dev)) return -1;
     if (nq == 0) return 0;
     HIP_OK(hipSetDevice(ix->device));
     RankArgs a;
-    a.store = ix->data;
-    a.dim = ix->dim;
-    a.dim_pad = ix->dim_pad;
-    a.ntotal = ix->ntotal;
-    a.store_dtype = ix->dtype;
-    a.q_src = queries;
-    a.q_dtype = q_dtype;
-    a.row_label = ix->row_label;
-    a.q_label = q_labels_dev;
-    a.n_qlab = q_labels_dev ? n_per_query : 0;
+    fill_scan_inputs(a, ix, queries, q_dtype, q_labels_dev, n_per_query);
     a.m = m;
     a.id_base = id_base;
     a.ids = ids_dev;
@@ -1305,36 +1348,23 @@ static int rank_call(vodhip_index_t* ix, int mode, const char* what, const void*
     a.out_rows = out_rows;
     a.out_count = out_counts;
     const bool pick = mode != RANK_MODE_THRESHOLDS, count = mode != RANK_MODE_PICK;
-    // queries per slice: a multiple of 128 (or 64) up to 1024 that keeps the temporaries under VODHIP_POSTERIOR_TEMP_BYTES (the rule of
-    // posterior_mean); a query's gathered rows are at most m + 3 rows of the mini-store
+    // a query's gathered rows are at most m + 3 rows of the mini-store
     const size_t row_bytes = (size_t)ix->dim_pad * 2;
-    const size_t per_query = row_bytes * (size_t)(1 + (pick ? m + 3 : 0)) + (size_t)m * 16;
-    int64_t slice = (int64_t)((size_t)VODHIP_POSTERIOR_TEMP_BYTES / per_query) / 128 * 128;
-    slice = std::min<int64_t>(1024, std::max<int64_t>(64, slice));
-    const int64_t nq_pad = rank_nq_pad(std::min(nq, slice));
-    void* tmp[4] = {nullptr, nullptr, nullptr, nullptr};
-    const size_t bytes[4] = {(size_t)nq_pad * row_bytes, pick ? (size_t)rank_mini_rows(nq_pad, m) * row_bytes : 0, pick ? (size_t)nq_pad * (size_t)m * 4 : 0,
-                             count ? (size_t)nq_pad * (size_t)m * 12 : 0};
-    for (int i = 0; i < 4; ++i) {
-        if (bytes[i] == 0) continue;
-        if (hipError_t e = hipMallocAsync(&tmp[i], bytes[i], stream); e != hipSuccess) {
-            (void)hipGetLastError();
-            for (int j = 0; j < i; ++j)
-                if (tmp[j]) (void)hipFreeAsync(tmp[j], stream);
-            return fail("hipMallocAsync of a %zu-byte temporary failed: %s", bytes[i], hipGetErrorString(e));
-        }
-    }
-    a.q_stage = tmp[0];
-    a.mini = tmp[1];
-    a.slot_row = (int*)tmp[2];
-    a.table = (unsigned int*)tmp[3];
+    const int64_t slice = scan_slice_queries(row_bytes * (size_t)(1 + (pick ? m + 3 : 0)) + (size_t)m * 16);
+    const int64_t nq_pad = scan_nq_pad(std::min(nq, slice));
+    ScanTemps tmp;
+    tmp.stream = stream;
+    if (tmp.alloc({(size_t)nq_pad * row_bytes, pick ? (size_t)rank_mini_rows(nq_pad, m) * row_bytes : 0, pick ? (size_t)nq_pad * (size_t)m * 4 : 0,
+                   count ? (size_t)nq_pad * (size_t)m * 12 : 0}))
+        return -1;
+    a.q_stage = tmp.p[0];
+    a.mini = tmp.p[1];
+    a.slot_row = (int*)tmp.p[2];
+    a.table = (unsigned int*)tmp.p[3];
     hipError_t le = hipSuccess;
     for (int64_t q0 = 0; q0 < nq && le == hipSuccess; q0 += slice) le = launch_rank(a, mode, q0, std::min(slice, nq - q0), stream);
     if (le != hipSuccess) (void)hipGetLastError();
-    hipError_t fe = hipSuccess;
-    for (int i = 0; i < 4; ++i)
-        if (tmp[i])
-            if (hipError_t e = hipFreeAsync(tmp[i], stream); e != hipSuccess) fe = e;
+    const hipError_t fe = tmp.release();
     if (le != hipSuccess) return fail("%s launch failed: %s", what, hipGetErrorString(le));
     HIP_OK(fe);
     return 0;
@@ -1364,59 +1394,33 @@ int vodhip_index_scan_score_ids(vodhip_index_t* ix, const void* queries, int q_d
 int vodhip_index_posterior_mean(vodhip_index_t* ix, const void* queries, int q_dtype, int64_t nq, float beta, const int32_t* q_labels_dev,
                                 int n_per_query, float* out_max, float* out_log_rel, float* out_mean, void* stream_) {
     if (!ix) return fail("index is NULL");
-    if (const char* msg = log_partition_args_error(queries, q_dtype, nq, beta, q_labels_dev, n_per_query, out_max, out_log_rel)) {
-        if (!strcmp(msg, "invalid q_dtype")) return fail("invalid q_dtype %d", q_dtype);
-        if (!strncmp(msg, "beta", 4)) return fail("beta=%g: %s", (double)beta, msg);
-        return fail("%s", msg);
-    }
+    if (const char* msg = log_partition_args_error(queries, q_dtype, nq, beta, q_labels_dev, n_per_query, out_max, out_log_rel))
+        return partition_args_fail(msg, q_dtype, beta);
     if (nq > 0 && !out_mean) return fail("invalid query / output pointers");
-    if (ix->l2) return fail("log_partition is not supported on an L2 index (VODHIP_L2): its scores are distances, not similarities");
-    if (ix->exact) return fail("log_partition is not supported on a VODHIP_EXACT_F32 store: the scan scores the rounded rows, that store's contract is the float32 rows");
-    if (q_labels_dev && !ix->row_label) return fail("set the row labels first (vodhip_index_set_row_labels)");
+    if (scan_refusal(ix, "log_partition", q_labels_dev)) return -1;  // (the name these two refusals have always carried here)
     if (nq == 0) return 0;
     HIP_OK(hipSetDevice(ix->device));
     hipStream_t stream = (hipStream_t)stream_;
     PosteriorArgs a;
-    a.p.store = ix->data;
-    a.p.dim = ix->dim;
-    a.p.dim_pad = ix->dim_pad;
-    a.p.ntotal = ix->ntotal;
-    a.p.store_dtype = ix->dtype;
-    a.p.q_src = queries;
-    a.p.q_dtype = q_dtype;
-    a.p.row_label = ix->row_label;
-    a.p.q_label = q_labels_dev;
-    a.p.n_qlab = q_labels_dev ? n_per_query : 0;
+    fill_scan_inputs(a.p, ix, queries, q_dtype, q_labels_dev, n_per_query);
     a.p.beta = beta;
     a.p.out_max = out_max;
     a.p.out_log_rel = out_log_rel;
     a.out_mean = out_mean;
-    // queries per slice: a multiple of 128 (or 64) up to 1024 that keeps the group accumulators under VODHIP_POSTERIOR_TEMP_BYTES
-    const size_t per_query = std::max<size_t>(1, (size_t)posterior_mean_groups(a.p.ntotal)) * (size_t)ix->dim_pad * sizeof(float);
-    int64_t slice = (int64_t)((size_t)VODHIP_POSTERIOR_TEMP_BYTES / per_query) / 128 * 128;
-    slice = std::min<int64_t>(1024, std::max<int64_t>(64, slice));
-    const int64_t nq_pad = log_partition_nq_pad(std::min(nq, slice));
-    const size_t stage_bytes = (size_t)nq_pad * (size_t)ix->dim_pad * 2;
-    const size_t part_bytes = std::max<size_t>(8, (size_t)log_partition_tiles(a.p.ntotal) * (size_t)nq_pad * 8);
-    const size_t acc_bytes = per_query * (size_t)nq_pad;
-    void* tmp[3] = {nullptr, nullptr, nullptr};
-    const size_t bytes[3] = {stage_bytes, part_bytes, acc_bytes};
-    for (int i = 0; i < 3; ++i) {
-        if (hipError_t e = hipMallocAsync(&tmp[i], bytes[i], stream); e != hipSuccess) {
-            (void)hipGetLastError();
-            for (int j = 0; j < i; ++j) (void)hipFreeAsync(tmp[j], stream);
-            return fail("hipMallocAsync of a %zu-byte temporary failed: %s", bytes[i], hipGetErrorString(e));
-        }
-    }
-    a.p.q_stage = tmp[0];
-    a.p.part = tmp[1];
-    a.acc = (float*)tmp[2];
+    const size_t per_query = std::max<size_t>(1, (size_t)posterior_mean_groups(a.p.ntotal)) * (size_t)ix->dim_pad * sizeof(float);  // the group accumulators
+    const int64_t slice = scan_slice_queries(per_query);
+    const int64_t nq_pad = scan_nq_pad(std::min(nq, slice));
+    ScanTemps tmp;
+    tmp.stream = stream;
+    if (tmp.alloc({(size_t)nq_pad * (size_t)ix->dim_pad * 2, std::max<size_t>(8, (size_t)scan_tiles(a.p.ntotal) * (size_t)nq_pad * 8), per_query * (size_t)nq_pad}))
+        return -1;
+    a.p.q_stage = tmp.p[0];
+    a.p.part = tmp.p[1];
+    a.acc = (float*)tmp.p[2];
     hipError_t le = hipSuccess;
     for (int64_t q0 = 0; q0 < nq && le == hipSuccess; q0 += slice) le = launch_posterior_mean(a, q0, std::min(slice, nq - q0), stream);
     if (le != hipSuccess) (void)hipGetLastError();
-    hipError_t fe = hipSuccess;
-    for (int i = 0; i < 3; ++i)
-        if (hipError_t e = hipFreeAsync(tmp[i], stream); e != hipSuccess) fe = e;
+    const hipError_t fe = tmp.release();
     if (le != hipSuccess) return fail("posterior-mean launch failed: %s", hipGetErrorString(le));
     HIP_OK(fe);
     return 0;
@@ -1428,32 +1432,18 @@ int vodhip_index_sample_posterior(vodhip_index_t* ix, const void* queries, int q
                                   float* out_log_rel, int64_t* out_ids, float* out_scores, float* out_log_p, float* out_log_weight,
                                   float* out_keys, void* stream_) {
     if (!ix) return fail("index is NULL");
-    if (const char* msg = log_partition_args_error(queries, q_dtype, nq, beta, q_labels_dev, n_per_query, out_max, out_log_rel)) {
-        if (!strcmp(msg, "invalid q_dtype")) return fail("invalid q_dtype %d", q_dtype);
-        if (!strncmp(msg, "beta", 4)) return fail("beta=%g: %s", (double)beta, msg);
-        return fail("%s", msg);
-    }
+    if (const char* msg = log_partition_args_error(queries, q_dtype, nq, beta, q_labels_dev, n_per_query, out_max, out_log_rel))
+        return partition_args_fail(msg, q_dtype, beta);
     if (const char* msg = sample_posterior_args_error(nq, k, query_offset, id_base, out_ids, out_scores, out_log_p, out_log_weight, out_keys)) {
         if (msg[0] == 'k') return fail("k=%d: %s", k, msg);
         return fail("%s", msg);
     }
-    if (ix->l2) return fail("sample_posterior is not supported on an L2 index (VODHIP_L2): its scores are distances, not similarities");
-    if (ix->exact) return fail("sample_posterior is not supported on a VODHIP_EXACT_F32 store: the scan scores the rounded rows, that store's contract is the float32 rows");
-    if (q_labels_dev && !ix->row_label) return fail("set the row labels first (vodhip_index_set_row_labels)");
+    if (scan_refusal(ix, "sample_posterior", q_labels_dev)) return -1;
     if (nq == 0) return 0;
     HIP_OK(hipSetDevice(ix->device));
     hipStream_t stream = (hipStream_t)stream_;
     PosteriorSampleArgs a;
-    a.p.store = ix->data;
-    a.p.dim = ix->dim;
-    a.p.dim_pad = ix->dim_pad;
-    a.p.ntotal = ix->ntotal;
-    a.p.store_dtype = ix->dtype;
-    a.p.q_src = queries;
-    a.p.q_dtype = q_dtype;
-    a.p.row_label = ix->row_label;
-    a.p.q_label = q_labels_dev;
-    a.p.n_qlab = q_labels_dev ? n_per_query : 0;
+    fill_scan_inputs(a.p, ix, queries, q_dtype, q_labels_dev, n_per_query);
     a.p.beta = beta;
     a.p.out_max = out_max;
     a.p.out_log_rel = out_log_rel;
@@ -1467,12 +1457,9 @@ int vodhip_index_sample_posterior(vodhip_index_t* ix, const void* queries, int q
     a.out_log_p = out_log_p;
     a.out_log_weight = out_log_weight;
     a.out_keys = out_keys;
-    // queries per slice: a multiple of 128 (or 64) up to 1024 that keeps the candidate lists and the tile words under VODHIP_POSTERIOR_TEMP_BYTES
-    const size_t n_tiles = std::max<size_t>(1, (size_t)log_partition_tiles(a.p.ntotal));
-    const size_t per_query = (size_t)a.stride * 12 + n_tiles * 12;
-    int64_t slice = (int64_t)((size_t)VODHIP_POSTERIOR_TEMP_BYTES / per_query) / 128 * 128;
-    slice = std::min<int64_t>(1024, std::max<int64_t>(64, slice));
-    const int64_t nq_pad = log_partition_nq_pad(std::min(nq, slice));
+    const size_t n_tiles = std::max<size_t>(1, (size_t)scan_tiles(a.p.ntotal));
+    const int64_t slice = scan_slice_queries((size_t)a.stride * 12 + n_tiles * 12);  // the candidate lists and the tile words
+    const int64_t nq_pad = scan_nq_pad(std::min(nq, slice));
     constexpr int NT = 7;
     const size_t bytes[NT] = {(size_t)nq_pad * (size_t)ix->dim_pad * 2, n_tiles * (size_t)nq_pad * 8, n_tiles * (size_t)nq_pad * 4,
                               (size_t)nq_pad * (size_t)a.stride * 8, (size_t)nq_pad * (size_t)a.stride * 4,
@@ -1513,7 +1500,7 @@ int vodhip_index_sample_posterior(vodhip_index_t* ix, const void* queries, int q
         const int64_t n = std::min(slice, nq - q0);
         if (profile) le = hipEventRecord(ev[0], stream);
         if (le == hipSuccess) le = launch_sample_posterior(a, q0, n, stream);
-        emit_groups += log_partition_tiles(a.p.ntotal) * (log_partition_nq_pad(n) / (n <= 64 ? 64 : 128));
+        emit_groups += scan_tiles(a.p.ntotal) * (scan_nq_pad(n) / (n <= 64 ? 64 : 128));
         if (profile && le == hipSuccess) {  // (one slice at a time: the events are reused)
             le = hipEventSynchronize(ev[5]);
             for (int i = 0; i < 5 && le == hipSuccess; ++i) {

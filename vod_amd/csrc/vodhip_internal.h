@@ -233,8 +233,8 @@ hipError_t launch_l2_stage_queries(const void* q_src, int q_dtype, int64_t nq, i
 // sim [nq, k] similarity-form scores (pads -inf) -> dist [nq, k] = max(0, qn - 2 sim), pads +inf
 hipError_t launch_l2_finish(const float* sim, const float* qn, int64_t nq, int k, float* dist, hipStream_t stream);
 
-// ---- launchers (kernels_partition.hip): log sum exp(beta * score) over the whole store -----------
-struct PartitionArgs {
+// ---- the whole-store scans (store_scan.h): what log_partition, posterior_mean, sample_posterior and the rank calls share ----------
+struct ScanInputs {
     const void* store = nullptr;      // [>= round_up(ntotal, 256) rows][dim_pad] fp16 / bf16 rows
     int64_t dim = 0, dim_pad = 0, ntotal = 0;
     int store_dtype = 0;              // 0 = f16, 1 = bf16
@@ -243,33 +243,32 @@ struct PartitionArgs {
     const int* row_label = nullptr;   // the store's subset labels; read only with q_label
     const int* q_label = nullptr;     // [.., n_qlab] rows of the caller's batch, or NULL = unrestricted
     int n_qlab = 0;
+    void* q_stage = nullptr;          // temporary: scan_nq_pad(queries of a launch) * dim_pad 16-bit words
+};
+int64_t scan_nq_pad(int64_t nq);      // the staged queries of a launch: 64, or a multiple of 128
+int64_t scan_tiles(int64_t ntotal);   // 256-row tiles
+// queries [q_first, q_first + nq) of the caller's batch -> s.q_stage, rounded to the store dtype and zero padded to [nq_pad][dim_pad]
+hipError_t launch_scan_stage(const ScanInputs& s, int64_t q_first, int64_t nq, int64_t nq_pad, hipStream_t stream);
+// the subset filter of the slice that starts at query q_first (no q_label: unrestricted)
+FilterExtra scan_filter_extra(const ScanInputs& s, int64_t q_first);
+
+// ---- launchers (kernels_partition.hip): log sum exp(beta * score) over the whole store -----------
+struct PartitionArgs : ScanInputs {
     float beta = 1.f;
-    void* q_stage = nullptr;          // temporary: log_partition_nq_pad(nq) * dim_pad 16-bit words
-    void* part = nullptr;             // temporary: log_partition_tiles(ntotal) * log_partition_nq_pad(nq) float2
+    void* part = nullptr;             // temporary: scan_tiles(ntotal) * scan_nq_pad(nq) float2
     float* out_max = nullptr;         // [rows of the caller's batch]
     float* out_log_rel = nullptr;
 };
-int64_t log_partition_nq_pad(int64_t nq);
-int64_t log_partition_tiles(int64_t ntotal);
 // queries [q_first, q_first + nq) of the caller's batch -> out_max / out_log_rel [q_first ..); a query's bits do not depend on the split
 hipError_t launch_log_partition(const PartitionArgs& a, int64_t q_first, int64_t nq, hipStream_t stream);
 
 // ---- launchers (kernels_rank.hip): exact ranks of listed rows / counts above thresholds over the whole store ----
-struct RankArgs {
-    const void* store = nullptr;      // [>= round_up(ntotal, 256) rows][dim_pad] fp16 / bf16 rows
-    int64_t dim = 0, dim_pad = 0, ntotal = 0;
-    int store_dtype = 0;              // 0 = f16, 1 = bf16
-    const void* q_src = nullptr;      // the caller's queries [.., dim] of q_dtype
-    int q_dtype = 0;
-    const int* row_label = nullptr;   // the store's subset labels; read only with q_label
-    const int* q_label = nullptr;     // [.., n_qlab] rows of the caller's batch, or NULL = unrestricted
-    int n_qlab = 0;
+struct RankArgs : ScanInputs {
     int64_t m = 0, id_base = 0;       // slots per query (1 .. VODHIP_RANK_MAX_LISTED), global id of row 0
     const int64_t* ids = nullptr;     // PICK / RANK: [.., m] listed ids
     const float* thresholds = nullptr;  // THRESHOLDS: [.., m]
     const int64_t* tie_ids = nullptr;   // THRESHOLDS: [.., m], or NULL = strict counts
-    // temporaries, sized for P = rank_nq_pad(queries of a launch)
-    void* q_stage = nullptr;          // P * dim_pad 16-bit words
+    // temporaries, sized for P = scan_nq_pad(queries of a launch)
     void* mini = nullptr;             // PICK / RANK: rank_mini_rows(P, m) * dim_pad 16-bit words
     int* slot_row = nullptr;          // PICK / RANK: P * m words
     unsigned int* table = nullptr;    // RANK / THRESHOLDS: 3 * P * m words (keys, tie rows, counts)
@@ -278,7 +277,6 @@ struct RankArgs {
     int64_t* out_count = nullptr;     // RANK / THRESHOLDS: the same shape
 };
 enum : int { RANK_MODE_PICK = 0, RANK_MODE_RANK = 1, RANK_MODE_THRESHOLDS = 2 };
-int64_t rank_nq_pad(int64_t nq);
 int64_t rank_mini_rows(int64_t nq_pad, int64_t m);
 // queries [q_first, q_first + nq) of the caller's batch; a query's results do not depend on the split
 hipError_t launch_rank(const RankArgs& a, int mode, int64_t q_first, int64_t nq, hipStream_t stream);
@@ -286,7 +284,7 @@ hipError_t launch_rank(const RankArgs& a, int mode, int64_t q_first, int64_t nq,
 // ---- launchers (kernels_posterior.hip): the posterior mean of the rows, sum_z p(z | q) x_z, behind the log-partition launches ----
 struct PosteriorArgs {
     PartitionArgs p;                  // the log-partition call of the same batch: its launches run first, unchanged
-    float* acc = nullptr;             // temporary: posterior_mean_groups(ntotal) * log_partition_nq_pad(nq) * dim_pad floats
+    float* acc = nullptr;             // temporary: posterior_mean_groups(ntotal) * scan_nq_pad(nq) * dim_pad floats
     float* out_mean = nullptr;        // [rows of the caller's batch][dim]
 };
 int64_t posterior_mean_groups(int64_t ntotal);
@@ -302,8 +300,8 @@ struct PosteriorSampleArgs {
     int64_t query_offset = 0;         // stream index of query 0 of the caller's batch
     int64_t id_base = 0;              // global id of row 0
     int64_t stride = 0;               // candidate slots per query: sample_posterior_stride(ntotal, k)
-    // temporaries, sized for P = log_partition_nq_pad(queries of a launch)
-    float* keymax = nullptr;          // P * log_partition_tiles(ntotal) floats
+    // temporaries, sized for P = scan_nq_pad(queries of a launch)
+    float* keymax = nullptr;          // P * scan_tiles(ntotal) floats
     void* cand_key = nullptr;         // P * stride 64-bit keys
     float* cand_score = nullptr;      // P * stride floats
     unsigned int* ctl = nullptr;      // sample_posterior_ctl_words(P) words: counters, hit tiles, thresholds (cleared by every launch)
