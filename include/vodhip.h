@@ -211,6 +211,29 @@ int vodhip_index_log_partition(vodhip_index_t* index, const void* queries, int q
                                const int32_t* q_labels_dev /* NULL = unrestricted */, int n_per_query,
                                float* out_max /* DEVICE [nq] */, float* out_log_rel /* DEVICE [nq] */, void* stream);
 
+/* H2t. The moments of the score under that softmax (kernels_stats.hip): with p(z | q) = exp(beta s_z - log Z_beta(q)), s_z = <q~, x~_z>,
+ *     out_mean_rel[q] = E_p[s] - out_max[q] <= 0,    out_var[q] = Var_p[s] >= 0,
+ *     d log Z_beta / d beta = out_max + out_mean_rel,   d^2 log Z_beta / d beta^2 = out_var,
+ *     entropy H(p(. | q)) = out_log_rel - beta * out_mean_rel   (two non-negative terms: no beta * max cancellation).
+ * out_max / out_log_rel are the bits vodhip_index_log_partition returns for the same query; eligibility, queries, labels, stream and
+ * concurrency rules are H2p's.  ONE scan: H2p's with two more accumulators per (query, 256-row tile) - with d = s - m <= 0 (m the
+ * tile's maximum) and e = exp(beta d), the very value H2p sums, a = sum e d and b = sum e d^2 in float32, same-sign sums in H2p's
+ * order; a row whose e is 0 (underflow, a -inf score) adds +0.  The finish re-centres the tiles on the maximum in double,
+ * A = sum_t c_t (a_t + D_t l_t), B = sum_t c_t (b_t + 2 D_t a_t + D_t^2 l_t), L' = sum_t c_t l_t with D_t = m_t - max and
+ * c_t = exp(beta D_t), in increasing tile order: mean_rel = A / L', var = max(0, B / L' - (A / L')^2), each rounded to float32 once.
+ * ONE order per query, fixed by ntotal and the padded width alone: the four words are the same bits whatever the batch around the
+ * query, and on every repeat; there are no atomics.
+ * No eligible row (or scores that are all -inf): (-inf, -inf, NaN, NaN).  A +inf score: (+inf, +inf, NaN, NaN).  Eligible rows that all
+ * score the same: mean_rel == 0 and var == 0 exactly.
+ * All four outputs: DEVICE float32 [nq], complete on `stream`.  Temporaries are hipMallocAsync on `stream`: the staged queries and 16
+ * bytes per (query, tile); batches run in slices of 64 .. 1024 queries chosen so that the partials stay at or below
+ * VODHIP_POSTERIOR_TEMP_BYTES unless a 64-query slice alone needs more.  The call only enqueues work.
+ * nq == 0 returns 0 and writes nothing; a refused call writes nothing.  REFUSED as H2p, and a NULL out_mean_rel / out_var. */
+int vodhip_index_posterior_stats(vodhip_index_t* index, const void* queries, int q_dtype, int64_t nq, float beta,
+                                 const int32_t* q_labels_dev /* NULL = unrestricted */, int n_per_query,
+                                 float* out_max, float* out_log_rel, float* out_mean_rel, float* out_var /* DEVICE [nq] each */,
+                                 void* stream);
+
 /* H2m. The posterior mean of the stored rows under that softmax (kernels_posterior.hip) = the gradient of log Z with respect to q:
  *     out_mean[q, :] = sum_{z < ntotal, eligible} p(z | q) x~_z,   p(z | q) = exp(beta <q~, x~_z> - log Z_beta(q)),
  *     d log Z_beta / d q = beta * out_mean[q, :].
@@ -475,6 +498,13 @@ int vodhip_node_index_sum_ids(vodhip_node_index_t* index, const int64_t* ids, co
 int vodhip_node_index_log_partition(vodhip_node_index_t* index, const void* queries, int q_dtype, int64_t nq, float beta,
                                     const int32_t* q_labels /* HOST or NULL */, int n_per_query,
                                     float* out_max, float* out_log_rel /* HOST [nq] */);
+/* H2t behind the one handle: HOST buffers, as above.  Every shard runs vodhip_index_posterior_stats; the 4 * nq floats per shard are
+ * folded on the host in increasing shard order, in double (stats_fold.h): the pair as above; with w_g = exp(beta (max_g - max) +
+ * log_rel_g - log_rel) and u_g = mean_rel_g + max_g - max, mean_rel = sum_g w_g u_g and var = max(0, sum_g w_g (var_g + u_g^2) -
+ * mean_rel^2).  A shard with no eligible row carries weight 0; a folded maximum that is not finite gives NaN statistics. */
+int vodhip_node_index_posterior_stats(vodhip_node_index_t* index, const void* queries, int q_dtype, int64_t nq, float beta,
+                                      const int32_t* q_labels /* HOST or NULL */, int n_per_query,
+                                      float* out_max, float* out_log_rel, float* out_mean_rel, float* out_var /* HOST [nq] each */);
 /* H2r behind the one handle: queries, ids / thresholds / tie ids, `q_labels` (may be NULL) and the outputs are HOST buffers; ids are
  * GLOBAL row ids.  rank_ids: every shard picks the scan scores of the ids it owns (vodhip_index_scan_score_ids with id_base = its
  * first global row), the host combines them by ownership - no values are compared -, every shard counts its rows against the combined

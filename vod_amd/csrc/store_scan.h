@@ -1,6 +1,7 @@
-// The core of the whole-store scans: log_partition (kernels_partition.hip), posterior_mean (kernels_posterior.hip), sample_posterior
-// (kernels_sample_posterior.hip) and rank_ids / count_above (kernels_rank.hip).  Each of them scores a tile of 256 stored rows against
-// 64 | 128 staged queries with the ONE K loop below and differs from the others in its epilogue alone.
+// The core of the whole-store scans: log_partition (kernels_partition.hip), posterior_stats (kernels_stats.hip), posterior_mean
+// (kernels_posterior.hip), sample_posterior (kernels_sample_posterior.hip) and rank_ids / count_above (kernels_rank.hip).  Each of
+// them scores a tile of 256 stored rows against 64 | 128 staged queries with the ONE K loop below and differs from the others in its
+// epilogue alone.
 //
 // THE CONTRACT.  A (query, row) pair has one score, the same bits in every scan and the bits a search returns:
 //   score     scan_k_loop is the K loop of mips_filter_kernel (kernels_mips.hip): LDS-DMA with the source-side XOR swizzle, a 3-slot

@@ -21,6 +21,7 @@
 #include "partition_fold.h"
 #include "sample_fold.h"
 #include "rank_fold.h"
+#include "stats_fold.h"
 #include "search_plan.h"
 #include "vodhip_internal.h"
 
@@ -1214,7 +1215,7 @@ int vodhip_index_sum_ids(vodhip_index_t* ix, const int64_t* ids_dev, const float
     return 0;
 }
 
-// ---- the whole-store scans (store_scan.h): log_partition, the rank calls, posterior_mean, sample_posterior ---------------------------
+// ---- the whole-store scans (store_scan.h): log_partition, posterior_stats, the rank calls, posterior_mean, sample_posterior ----------
 // Like the listed calls they read the store (and the row labels) only.  What the four flat calls share:
 
 // a message of log_partition_args_error, as the flat calls report it
@@ -1315,6 +1316,41 @@ int vodhip_index_log_partition(vodhip_index_t* ix, const void* queries, int q_dt
     if (le != hipSuccess) return fail("log-partition launch failed: %s", hipGetErrorString(le));
     HIP_OK(f1);
     HIP_OK(f2);
+    return 0;
+}
+
+// ---- posterior statistics (kernels_stats.hip): the log-partition scan with two more accumulators; 16-byte partials, so the batch runs
+// in slices that keep them under VODHIP_POSTERIOR_TEMP_BYTES ------------------------------------------------------------------------
+int vodhip_index_posterior_stats(vodhip_index_t* ix, const void* queries, int q_dtype, int64_t nq, float beta, const int32_t* q_labels_dev,
+                                 int n_per_query, float* out_max, float* out_log_rel, float* out_mean_rel, float* out_var, void* stream_) {
+    if (!ix) return fail("index is NULL");
+    if (const char* msg = posterior_stats_args_error(queries, q_dtype, nq, beta, q_labels_dev, n_per_query, out_max, out_log_rel, out_mean_rel, out_var))
+        return partition_args_fail(msg, q_dtype, beta);
+    if (scan_refusal(ix, "posterior_stats", q_labels_dev)) return -1;
+    if (nq == 0) return 0;
+    HIP_OK(hipSetDevice(ix->device));
+    hipStream_t stream = (hipStream_t)stream_;
+    StatsArgs a;
+    fill_scan_inputs(a, ix, queries, q_dtype, q_labels_dev, n_per_query);
+    a.beta = beta;
+    a.out_max = out_max;
+    a.out_log_rel = out_log_rel;
+    a.out_mean_rel = out_mean_rel;
+    a.out_var = out_var;
+    const size_t per_query = std::max<size_t>(1, (size_t)scan_tiles(a.ntotal)) * 16;  // the partials
+    const int64_t slice = scan_slice_queries(per_query);
+    const int64_t nq_pad = scan_nq_pad(std::min(nq, slice));
+    ScanTemps tmp;
+    tmp.stream = stream;
+    if (tmp.alloc({(size_t)nq_pad * (size_t)ix->dim_pad * 2, per_query * (size_t)nq_pad})) return -1;
+    a.q_stage = tmp.p[0];
+    a.part = tmp.p[1];
+    hipError_t le = hipSuccess;
+    for (int64_t q0 = 0; q0 < nq && le == hipSuccess; q0 += slice) le = launch_posterior_stats(a, q0, std::min(slice, nq - q0), stream);
+    if (le != hipSuccess) (void)hipGetLastError();
+    const hipError_t fe = tmp.release();
+    if (le != hipSuccess) return fail("posterior-stats launch failed: %s", hipGetErrorString(le));
+    HIP_OK(fe);
     return 0;
 }
 

@@ -262,6 +262,18 @@ struct PartitionArgs : ScanInputs {
 // queries [q_first, q_first + nq) of the caller's batch -> out_max / out_log_rel [q_first ..); a query's bits do not depend on the split
 hipError_t launch_log_partition(const PartitionArgs& a, int64_t q_first, int64_t nq, hipStream_t stream);
 
+// ---- launchers (kernels_stats.hip): the log-partition pair plus the posterior mean and variance of the score ----
+struct StatsArgs : ScanInputs {
+    float beta = 1.f;
+    void* part = nullptr;             // temporary: scan_tiles(ntotal) * scan_nq_pad(nq) float4
+    float* out_max = nullptr;         // [rows of the caller's batch]: the bits of launch_log_partition
+    float* out_log_rel = nullptr;
+    float* out_mean_rel = nullptr;    // E_p[s] - max
+    float* out_var = nullptr;         // Var_p[s]
+};
+// queries [q_first, q_first + nq) of the caller's batch -> the four outputs [q_first ..); a query's bits do not depend on the split
+hipError_t launch_posterior_stats(const StatsArgs& a, int64_t q_first, int64_t nq, hipStream_t stream);
+
 // ---- launchers (kernels_rank.hip): exact ranks of listed rows / counts above thresholds over the whole store ----
 struct RankArgs : ScanInputs {
     int64_t m = 0, id_base = 0;       // slots per query (1 .. VODHIP_RANK_MAX_LISTED), global id of row 0

@@ -20,6 +20,7 @@
 #include "partition_fold.h"
 #include "sample_fold.h"
 #include "rank_fold.h"
+#include "stats_fold.h"
 #include "vodhip_internal.h"
 
 namespace {
@@ -976,6 +977,69 @@ int vodhip_node_index_log_partition(vodhip_node_index_t* nx, const void* queries
     (void)hipSetDevice(nx->device[0]);
     if (rc) return nfail("%s", err.c_str());
     vodhip::fold_log_partition(parts.data(), parts.data() + nq, G, 2 * nq, nq, beta, out_max, out_log_rel);
+    return 0;
+}
+
+// The posterior statistics behind the one handle (include/vodhip.h, H2t): the shape of the log-partition call above with 4 * nq floats
+// per shard, folded on the host in increasing shard order, in double (stats_fold.h).
+int vodhip_node_index_posterior_stats(vodhip_node_index_t* nx, const void* queries, int q_dtype, int64_t nq, float beta, const int32_t* q_labels,
+                                      int n_per_query, float* out_max, float* out_log_rel, float* out_mean_rel, float* out_var) {
+    if (!nx) return nfail("index is NULL");
+    if (const char* msg = vodhip::posterior_stats_args_error(queries, q_dtype, nq, beta, q_labels, n_per_query, out_max, out_log_rel, out_mean_rel, out_var)) {
+        if (!strcmp(msg, "invalid q_dtype")) return nfail("invalid q_dtype %d", q_dtype);
+        if (!strncmp(msg, "beta", 4)) return nfail("beta=%g: %s", (double)beta, msg);
+        return nfail("%s", msg);
+    }
+    if (nx->dtype & VODHIP_L2) return nfail("posterior_stats is not supported on an L2 index (VODHIP_L2): its scores are distances, not similarities");
+    if (nx->dtype & VODHIP_EXACT_F32) return nfail("posterior_stats is not supported on a VODHIP_EXACT_F32 store: the scan scores the rounded rows, that store's contract is the float32 rows");
+    std::lock_guard<std::mutex> guard(nx->mu);
+    if (q_labels && !nx->has_row_labels) return nfail("set the row labels first (vodhip_node_index_set_row_labels)");
+    if (nq == 0) return 0;
+    const int G = nx->n;
+    const size_t n = (size_t)nq;
+    const size_t q_bytes = n * (size_t)nx->dim * elem_bytes(q_dtype);
+    const size_t lab_bytes = q_labels ? n * (size_t)n_per_query * sizeof(int32_t) : 0;
+    std::vector<float> parts((size_t)G * 4 * n);  // shard g: [max | log_rel | mean_rel | var] at g * 4 nq
+    struct Tmp { void* q = nullptr; int32_t* lab = nullptr; float* out = nullptr; };
+    std::vector<Tmp> tmp((size_t)G);
+    int rc = 0;
+    std::string err;
+    auto hip_step = [&](hipError_t e, const char* what) {
+        if (e != hipSuccess && !rc) {
+            (void)hipGetLastError();
+            err = std::string(what) + " failed: " + hipGetErrorString(e);
+            rc = -1;
+        }
+        return e == hipSuccess;
+    };
+    for (int g = 0; g < G && !rc; ++g) {  // (the devices run side by side: nothing is waited for until every shard is enqueued)
+        hipStream_t st = nx->stream[g];
+        Tmp& t = tmp[(size_t)g];
+        if (!hip_step(hipSetDevice(nx->device[g]), "hipSetDevice")) break;
+        if (!hip_step(hipMallocAsync(&t.q, q_bytes, st), "hipMallocAsync")) break;
+        if (!hip_step(hipMallocAsync((void**)&t.out, 4 * n * sizeof(float), st), "hipMallocAsync")) break;
+        if (q_labels && !hip_step(hipMallocAsync((void**)&t.lab, lab_bytes, st), "hipMallocAsync")) break;
+        if (!hip_step(hipMemcpyAsync(t.q, queries, q_bytes, hipMemcpyHostToDevice, st), "hipMemcpyAsync")) break;
+        if (q_labels && !hip_step(hipMemcpyAsync(t.lab, q_labels, lab_bytes, hipMemcpyHostToDevice, st), "hipMemcpyAsync")) break;
+        if (vodhip_index_posterior_stats(nx->shard[g], t.q, q_dtype, nq, beta, t.lab, n_per_query, t.out, t.out + n, t.out + 2 * n, t.out + 3 * n, st)) {
+            err = std::string("shard ") + std::to_string(g) + ": " + vodhip_last_error();
+            rc = -1;
+            break;
+        }
+        hip_step(hipMemcpyAsync(parts.data() + (size_t)g * 4 * n, t.out, 4 * n * sizeof(float), hipMemcpyDeviceToHost, st), "hipMemcpyAsync");
+    }
+    for (int g = 0; g < G; ++g) {  // (also after a failure: what was enqueued reads the caller's host buffers)
+        Tmp& t = tmp[(size_t)g];
+        if (hipSetDevice(nx->device[g]) != hipSuccess) continue;
+        if (t.q) (void)hipFreeAsync(t.q, nx->stream[g]);
+        if (t.lab) (void)hipFreeAsync(t.lab, nx->stream[g]);
+        if (t.out) (void)hipFreeAsync(t.out, nx->stream[g]);
+        hip_step(hipStreamSynchronize(nx->stream[g]), "hipStreamSynchronize");
+    }
+    (void)hipSetDevice(nx->device[0]);
+    if (rc) return nfail("%s", err.c_str());
+    vodhip::fold_posterior_stats(parts.data(), parts.data() + n, parts.data() + 2 * n, parts.data() + 3 * n, G, 4 * nq, nq, beta, out_max, out_log_rel,
+                                 out_mean_rel, out_var);
     return 0;
 }
 

@@ -508,6 +508,36 @@ class HipFlatIndex:
                 t.record_stream(torch.cuda.current_stream(self.device))
         return LogPartition(max_score * beta + log_rel, max_score, log_rel)  # (-inf + -inf and +inf + +inf: never NaN)
 
+    def posterior_stats(self, queries, temperature: float = 1.0, subset=None, out=None) -> "PosteriorStats":
+        """The entropy and the score moments of the posterior over the WHOLE store, `p(z | q) = exp(<q~, x~_z> / temperature - log Z(q))`,
+        from ONE scan (the `log_partition` scan with two more accumulators; no `[nq, N]` matrix):
+        `PosteriorStats(entropy, mean_score, var_score, mean_rel, log_partition)`, float32 device tensors `[nq]`.
+        `mean_score = E_p[s] = d log Z / d beta` (`beta = 1 / temperature`), `var_score = Var_p[s] = d^2 log Z / d beta^2`,
+        `mean_rel = mean_score - max_score <= 0` (what the library returns: it keeps the digits that adding `max_score` rounds away),
+        `entropy = log_rel - beta * mean_rel` in nats, two non-negative terms; `log_partition` is the `LogPartition` that
+        `log_partition` returns for the same call, bit for bit.  A query's words are the same bits whatever the batch around it.
+        No eligible row, or a +inf score: `log_partition` as `log_partition` gives it, the statistics NaN.
+
+        Arguments, stream behaviour and refusals as `log_partition`; `out`: a (max_score, log_rel, mean_rel, var_score) 4-tuple to
+        write into."""
+        q = self._prep_queries(queries)
+        nq = q.shape[0]
+        beta = 1.0 / float(temperature) if temperature else float("nan")
+        sub, n_sub = self._subset_labels(subset, nq)
+        if out is None:
+            max_score, log_rel, mean_rel, var = (torch.empty((nq,), dtype=torch.float32, device=self.device) for _ in range(4))
+        else:
+            max_score, log_rel, mean_rel, var = out
+        with torch.cuda.device(self.device):
+            _native.check(self._lib.vodhip_index_posterior_stats(
+                self._h, q.data_ptr(), _native.torch_dtype_code(q.dtype), nq, beta, None if sub is None else sub.data_ptr(), n_sub,
+                max_score.data_ptr(), log_rel.data_ptr(), mean_rel.data_ptr(), var.data_ptr(), _native.current_stream_ptr(self.device)))
+        for t, given in ((q, queries), (sub, subset)):
+            if t is not None and t is not given:
+                t.record_stream(torch.cuda.current_stream(self.device))
+        return PosteriorStats(log_rel - beta * mean_rel, max_score + mean_rel, var, mean_rel,
+                              LogPartition(max_score * beta + log_rel, max_score, log_rel))
+
     def posterior_mean(self, queries, temperature: float = 1.0, subset=None, out=None) -> "PosteriorMean":
         """The posterior mean of the stored rows under the softmax over the WHOLE store, `mean[q] = sum_z p(z | q) x~_z` with
         `p(z | q) = exp(<q~, x~_z> / temperature - log Z(q))`: `PosteriorMean(mean, log_partition)`, `mean` a float32 device tensor
@@ -594,11 +624,18 @@ class HipFlatIndex:
         log_tau = torch.where(torch.isnan(log_tau), torch.full_like(log_tau, float("-inf")), log_tau)
         return PosteriorSample(ids, scores, log_p, log_weight, log_tau, keys, LogPartition(max_score * beta + log_rel, max_score, log_rel))
 
-    def log_z(self, queries: torch.Tensor, temperature: float = 1.0, subset=None) -> torch.Tensor:
+    def log_z(self, queries: torch.Tensor, temperature=1.0, subset=None) -> torch.Tensor:
         """`log Z(q)` over the whole store as a float32 `[nq]` tensor that is differentiable with respect to `queries`: forward is
         `posterior_mean`, backward `grad_q = grad_out[:, None] * mean / temperature`, cast to the dtype of `queries` (straight through
         the rounding of the queries to the store dtype).  No gradient flows to the store; rows of `grad_q` whose `log_z` is not finite
-        are zero.  The exact retrieval NLL of a positive row: `-(<q, x_pos> / T - index.log_z(q, T))`."""
+        are zero.  The exact retrieval NLL of a positive row: `-(<q, x_pos> / T - index.log_z(q, T))`.
+
+        `temperature` may be a one-element tensor (a learnable scale): reading its value is ONE host synchronisation.  If it requires
+        grad, `grad_T = -sum_q grad_out[q] * mean_score[q] / T^2` with `mean_score` of `posterior_stats` (queries whose `log_z` is not
+        finite contribute 0).  With a tensor temperature `posterior_mean` runs only when `queries` requires grad: temperature-only
+        calibration costs about one `log_partition`.  With a float temperature nothing changes."""
+        if isinstance(temperature, torch.Tensor):
+            return _LogZ.apply(queries, self, temperature, subset)
         return _LogZ.apply(queries, self, float(temperature), subset)
 
 
@@ -624,6 +661,17 @@ class PosteriorMean(NamedTuple):
     log_partition: LogPartition
 
 
+class PosteriorStats(NamedTuple):
+    """`posterior_stats`: `entropy = log_rel - mean_rel / temperature`, `mean_score = max_score + mean_rel = E_p[s]`,
+    `var_score = Var_p[s]`, `mean_rel = E_p[s] - max_score <= 0`, each `[nq]`, with the `LogPartition` of the same call."""
+
+    entropy: Any
+    mean_score: Any
+    var_score: Any
+    mean_rel: Any
+    log_partition: LogPartition
+
+
 class PosteriorSample(NamedTuple):
     """`k` rows without replacement from `p(z | q)` over the whole store (`sample_posterior`): `ids`, `scores`, `log_p`, `log_weight`
     `[nq, k]`, `log_tau` `[nq]`, `keys` `[nq, k + 1]`, with the `LogPartition` of the same call."""
@@ -644,23 +692,57 @@ def log_z_backward(grad_out: torch.Tensor, mean: torch.Tensor, log_z: torch.Tens
     return g.to(dtype)
 
 
+def log_z_temperature_backward(grad_out: torch.Tensor, mean_score: torch.Tensor, log_z: torch.Tensor, temperature: float) -> torch.Tensor:
+    """The backward of `log_z` with respect to the temperature: `-sum_q grad_out[q] * mean_score[q] / T^2` (`d log Z / d beta =
+    E_p[s]`, `beta = 1 / T`), summed in float64 over the queries whose `log_z` is finite; a 0-d float64 tensor."""
+    g = grad_out.to(torch.float64) * mean_score.to(torch.float64)
+    g = torch.where(torch.isfinite(log_z), g, torch.zeros_like(g))
+    return -g.sum() / (float(temperature) ** 2)
+
+
 class _LogZ(torch.autograd.Function):
-    """`index.log_z`: `index` is anything with `posterior_mean(queries, temperature, subset)`."""
+    """`index.log_z`: `index` is anything with `posterior_mean(queries, temperature, subset)` and - for a tensor temperature -
+    `posterior_stats(queries, temperature, subset)`."""
 
     @staticmethod
     def forward(ctx, queries, index, temperature, subset):
-        pm = index.posterior_mean(queries.detach(), temperature, subset)
-        log_z = torch.as_tensor(pm.log_partition.log_z)
-        ctx.save_for_backward(torch.as_tensor(pm.mean), log_z)
-        ctx.beta = 1.0 / temperature
+        ctx.t_tensor = isinstance(temperature, torch.Tensor)
         ctx.q_dtype, ctx.q_device = queries.dtype, queries.device
+        if not ctx.t_tensor:
+            pm = index.posterior_mean(queries.detach(), temperature, subset)
+            log_z = torch.as_tensor(pm.log_partition.log_z)
+            ctx.save_for_backward(torch.as_tensor(pm.mean), log_z)
+            ctx.beta = 1.0 / temperature
+            return log_z.clone()
+        if temperature.numel() != 1:
+            raise ValueError(f"expected a one-element temperature tensor, got shape {tuple(temperature.shape)}")
+        ctx.t_shape, ctx.t_dtype, ctx.t_device = temperature.shape, temperature.dtype, temperature.device
+        t = float(temperature.detach().reshape(()).item())  # (the one host synchronisation)
+        ctx.temperature = t
+        ctx.beta = 1.0 / t if t else float("nan")
+        st = index.posterior_stats(queries.detach(), t, subset)
+        log_z = torch.as_tensor(st.log_partition.log_z)
+        mean = None
+        if ctx.needs_input_grad[0]:
+            pm = index.posterior_mean(queries.detach(), t, subset)
+            mean, log_z = torch.as_tensor(pm.mean), torch.as_tensor(pm.log_partition.log_z)  # (the bits of the float path)
+        ctx.save_for_backward(mean, log_z, torch.as_tensor(st.mean_score))
         return log_z.clone()
 
     @staticmethod
     def backward(ctx, grad_out):
-        mean, log_z = ctx.saved_tensors
-        g = log_z_backward(grad_out.to(mean.device), mean, log_z, ctx.beta, ctx.q_dtype)
-        return g.to(ctx.q_device), None, None, None
+        if not ctx.t_tensor:
+            mean, log_z = ctx.saved_tensors
+            g = log_z_backward(grad_out.to(mean.device), mean, log_z, ctx.beta, ctx.q_dtype)
+            return g.to(ctx.q_device), None, None, None
+        mean, log_z, mean_score = ctx.saved_tensors
+        g_q = g_t = None
+        if ctx.needs_input_grad[0]:
+            g_q = log_z_backward(grad_out.to(mean.device), mean, log_z, ctx.beta, ctx.q_dtype).to(ctx.q_device)
+        if ctx.needs_input_grad[2]:
+            g_t = log_z_temperature_backward(grad_out.to(log_z.device), mean_score, log_z, ctx.temperature)
+            g_t = g_t.to(device=ctx.t_device, dtype=ctx.t_dtype).reshape(ctx.t_shape)
+        return g_q, None, g_t, None
 
 
 def listed_scores_backward(index, ids, grad_out: torch.Tensor, dtype: torch.dtype, device: torch.device, **kw) -> torch.Tensor:
@@ -981,6 +1063,25 @@ class HipNodeIndex:
         with np.errstate(invalid="ignore"):
             log_z = (max_score * np.float32(beta) + log_rel).astype(np.float32)
         return LogPartition(log_z, max_score, log_rel)
+
+    def posterior_stats(self, queries, temperature: float = 1.0, subset: np.ndarray | None = None) -> "PosteriorStats":
+        """`HipFlatIndex.posterior_stats` over every shard: each shard runs the flat call on its own device, the four words per shard
+        are folded on the host in shard order, in double (a mixture of the shards' posteriors).  Host queries -> `PosteriorStats` of
+        float32 NumPy arrays `[nq]`; `max_score` equals one index holding all the rows bit for bit."""
+        q = self._host_queries(queries)
+        nq = int(q.shape[0])
+        beta = 1.0 / float(temperature) if temperature else float("nan")
+        sub, n_sub = self._host_subset(subset, nq)
+        max_score, log_rel, mean_rel, var = (np.empty((nq,), dtype=np.float32) for _ in range(4))
+        with torch.cuda.device(self.device):
+            _native.check(self._lib.vodhip_node_index_posterior_stats(
+                self._h, q.ctypes.data, 2 if q.dtype == np.float32 else 0, nq, beta, None if sub is None else sub.ctypes.data, n_sub,
+                max_score.ctypes.data, log_rel.ctypes.data, mean_rel.ctypes.data, var.ctypes.data))
+        with np.errstate(invalid="ignore"):
+            log_z = (max_score * np.float32(beta) + log_rel).astype(np.float32)
+            entropy = (log_rel - np.float32(beta) * mean_rel).astype(np.float32)
+            mean_score = (max_score + mean_rel).astype(np.float32)
+        return PosteriorStats(entropy, mean_score, var, mean_rel, LogPartition(log_z, max_score, log_rel))
 
     def _host_queries(self, queries) -> np.ndarray:
         if isinstance(queries, torch.Tensor):
