@@ -234,6 +234,35 @@ int vodhip_index_posterior_stats(vodhip_index_t* index, const void* queries, int
                                  float* out_max, float* out_log_rel, float* out_mean_rel, float* out_var /* DEVICE [nq] each */,
                                  void* stream);
 
+/* H2d. TWO posteriors over the same rows (kernels_divergence.hip): pair i is (queries_a[i], queries_b[i]) with beta_a and beta_b,
+ *     p = softmax(beta_a s_a),  r = softmax(beta_b s_b),  s_a = <a~, x~_z>,  s_b = <b~, x~_z>  (the scan's scores, H2p)
+ * over the rows eligible for the PAIR: z < ntotal, neither score NaN, allowed by the pair's labels (one label row per pair).  Eight words:
+ *     out_max_a, out_log_rel_a, out_mean_rel_a = E_p[s_a] - max_a <= 0,  out_cross_rel_ab = E_p[s_b] - max_b <= 0,
+ *     out_max_b, out_log_rel_b, out_mean_rel_b = E_r[s_b] - max_b <= 0,  out_cross_rel_ba = E_r[s_a] - max_a <= 0,
+ *     H(p) = log_rel_a - beta_a mean_rel_a,   H(p, r) = log_rel_b - beta_b cross_rel_ab,
+ *     KL(p || r) = (log_rel_b - log_rel_a) + (beta_a mean_rel_a - beta_b cross_rel_ab)   (and the mirror): no beta * max cancellation.
+ * ONE scan, H2t's over 2 nq staged queries: pair p of a launch stages a at column p % 32 and b at column 32 + p % 32 of the 64-column
+ * block p / 32, so that a lane holds both scores of a row in the same registers.  Two 16-byte partials per (pair, 256-row tile),
+ * (m, l, a, c) per side: m, l, a as H2t forms them, c_ab = sum e_a (s_b - m_b) with m_b the tile's maximum of side b - same-sign, in
+ * H2t's order, a row whose e_a is 0 adds +0.  The finish re-centres in double, in increasing tile order:
+ * C_ab = sum_t c^a_t (c_ab_t + (m_b_t - max_b) l_a_t), cross_rel_ab = C_ab / L'_a, rounded to float32 once.
+ * When no row scores NaN against exactly one side, (max, log_rel, mean_rel) of each side are the bits H2t returns for that side alone.
+ * A pair's eight words are the same bits whatever the batch around it, at any position, and on every repeat; there are no atomics.  A
+ * pair whose two queries and betas are identical has cross_rel_ab == mean_rel_a bit for bit.
+ * A row with p_z > 0 that side b scores -inf: cross_rel_ab = -inf (H(p, r) = KL = +inf).  A row side a scores -inf adds nothing to
+ * side a.  A side with no eligible row (or scores all -inf): (-inf, -inf, NaN); with a +inf score: (+inf, +inf, NaN); BOTH cross words
+ * are NaN then and the other side's own three words are unaffected.
+ * All eight outputs: DEVICE float32 [nq], complete on `stream`.  nq <= 2^19.  Temporaries are hipMallocAsync on `stream`: the staged
+ * queries and 32 bytes per (pair, tile); batches run in slices of 64 .. 1024 pairs chosen as H2t's.  The call only enqueues work.
+ * nq == 0 returns 0 and writes nothing; a refused call writes nothing.  REFUSED as H2t (each beta finite and > 0), and any NULL
+ * query / output pointer. */
+int vodhip_index_posterior_divergence(vodhip_index_t* index, const void* queries_a, const void* queries_b /* DEVICE [nq, dim] */, int q_dtype,
+                                      int64_t nq, float beta_a, float beta_b,
+                                      const int32_t* q_labels_dev /* NULL = unrestricted */, int n_per_query,
+                                      float* out_max_a, float* out_log_rel_a, float* out_mean_rel_a, float* out_cross_rel_ab,
+                                      float* out_max_b, float* out_log_rel_b, float* out_mean_rel_b, float* out_cross_rel_ba /* DEVICE [nq] each */,
+                                      void* stream);
+
 /* H2m. The posterior mean of the stored rows under that softmax (kernels_posterior.hip) = the gradient of log Z with respect to q:
  *     out_mean[q, :] = sum_{z < ntotal, eligible} p(z | q) x~_z,   p(z | q) = exp(beta <q~, x~_z> - log Z_beta(q)),
  *     d log Z_beta / d q = beta * out_mean[q, :].
@@ -505,6 +534,14 @@ int vodhip_node_index_log_partition(vodhip_node_index_t* index, const void* quer
 int vodhip_node_index_posterior_stats(vodhip_node_index_t* index, const void* queries, int q_dtype, int64_t nq, float beta,
                                       const int32_t* q_labels /* HOST or NULL */, int n_per_query,
                                       float* out_max, float* out_log_rel, float* out_mean_rel, float* out_var /* HOST [nq] each */);
+/* H2d behind the one handle: HOST buffers, as above.  Every shard runs vodhip_index_posterior_divergence; the 8 * nq floats per shard
+ * are folded on the host in increasing shard order, in double (divergence_fold.h): each side's pair and mean_rel as H2t's fold, and
+ * cross_rel_ab = sum_g w^a_g (cross_rel_ab_g + max_b_g - max_b) with side a's weights.  A shard in which side a has mass and side b
+ * no finite score gives -inf; a side whose folded maximum is not finite gives NaN for its mean_rel and for both cross words. */
+int vodhip_node_index_posterior_divergence(vodhip_node_index_t* index, const void* queries_a, const void* queries_b, int q_dtype, int64_t nq,
+                                           float beta_a, float beta_b, const int32_t* q_labels /* HOST or NULL */, int n_per_query,
+                                           float* out_max_a, float* out_log_rel_a, float* out_mean_rel_a, float* out_cross_rel_ab,
+                                           float* out_max_b, float* out_log_rel_b, float* out_mean_rel_b, float* out_cross_rel_ba /* HOST [nq] each */);
 /* H2r behind the one handle: queries, ids / thresholds / tie ids, `q_labels` (may be NULL) and the outputs are HOST buffers; ids are
  * GLOBAL row ids.  rank_ids: every shard picks the scan scores of the ids it owns (vodhip_index_scan_score_ids with id_base = its
  * first global row), the host combines them by ownership - no values are compared -, every shard counts its rows against the combined

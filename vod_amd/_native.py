@@ -68,6 +68,7 @@ SIGNATURES: dict[str, tuple] = {
     "vodhip_index_sum_ids": (_i32, [_vp, _vp, _vp, _i64, _i64, _i64, _vp, _i32, _vp, _vp]),
     "vodhip_index_log_partition": (_i32, [_vp, _vp, _i32, _i64, _c.c_float, _vp, _i32, _vp, _vp, _vp]),
     "vodhip_index_posterior_stats": (_i32, [_vp, _vp, _i32, _i64, _c.c_float, _vp, _i32, _vp, _vp, _vp, _vp, _vp]),
+    "vodhip_index_posterior_divergence": (_i32, [_vp, _vp, _vp, _i32, _i64, _c.c_float, _c.c_float, _vp, _i32] + [_vp] * 8 + [_vp]),
     "vodhip_index_posterior_mean": (_i32, [_vp, _vp, _i32, _i64, _c.c_float, _vp, _i32, _vp, _vp, _vp, _vp]),
     "vodhip_index_count_above": (_i32, [_vp, _vp, _i32, _i64, _vp, _vp, _i64, _i64, _vp, _i32, _vp, _vp]),
     "vodhip_index_rank_ids": (_i32, [_vp, _vp, _i32, _i64, _vp, _i64, _i64, _vp, _i32, _vp, _vp, _vp]),
@@ -102,6 +103,7 @@ SIGNATURES: dict[str, tuple] = {
     "vodhip_node_index_sum_ids": (_i32, [_vp, _vp, _vp, _i64, _i64, _vp, _i32, _i32, _vp, _vp]),
     "vodhip_node_index_log_partition": (_i32, [_vp, _vp, _i32, _i64, _c.c_float, _vp, _i32, _vp, _vp]),
     "vodhip_node_index_posterior_stats": (_i32, [_vp, _vp, _i32, _i64, _c.c_float, _vp, _i32, _vp, _vp, _vp, _vp]),
+    "vodhip_node_index_posterior_divergence": (_i32, [_vp, _vp, _vp, _i32, _i64, _c.c_float, _c.c_float, _vp, _i32] + [_vp] * 8),
     "vodhip_node_index_posterior_mean": (_i32, [_vp, _vp, _i32, _i64, _c.c_float, _vp, _i32, _vp, _vp, _vp]),
     "vodhip_node_index_rank_ids": (_i32, [_vp, _vp, _i32, _i64, _vp, _i64, _vp, _i32, _vp, _vp]),
     "vodhip_node_index_count_above": (_i32, [_vp, _vp, _i32, _i64, _vp, _vp, _i64, _vp, _i32, _vp]),

@@ -1,7 +1,8 @@
-// The core of the whole-store scans: log_partition (kernels_partition.hip), posterior_stats (kernels_stats.hip), posterior_mean
-// (kernels_posterior.hip), sample_posterior (kernels_sample_posterior.hip) and rank_ids / count_above (kernels_rank.hip).  Each of
-// them scores a tile of 256 stored rows against 64 | 128 staged queries with the ONE K loop below and differs from the others in its
-// epilogue alone.
+// The core of the whole-store scans: log_partition (kernels_partition.hip), posterior_stats (kernels_stats.hip), posterior_divergence
+// (kernels_divergence.hip), posterior_mean (kernels_posterior.hip), sample_posterior (kernels_sample_posterior.hip) and rank_ids /
+// count_above (kernels_rank.hip).  Each of them scores a tile of 256 stored rows against 64 | 128 staged queries with the ONE K loop
+// below and differs from the others in its epilogue alone (posterior_divergence also in the row map of its staging: the two queries of
+// a pair sit 32 columns apart, in the two accumulator columns of one lane).
 //
 // THE CONTRACT.  A (query, row) pair has one score, the same bits in every scan and the bits a search returns:
 //   score     scan_k_loop is the K loop of mips_filter_kernel (kernels_mips.hip): LDS-DMA with the source-side XOR swizzle, a 3-slot

@@ -22,6 +22,7 @@
 #include "sample_fold.h"
 #include "rank_fold.h"
 #include "stats_fold.h"
+#include "divergence_fold.h"
 #include "search_plan.h"
 #include "vodhip_internal.h"
 
@@ -1215,7 +1216,7 @@ int vodhip_index_sum_ids(vodhip_index_t* ix, const int64_t* ids_dev, const float
     return 0;
 }
 
-// ---- the whole-store scans (store_scan.h): log_partition, posterior_stats, the rank calls, posterior_mean, sample_posterior ----------
+// ---- the whole-store scans (store_scan.h): log_partition, posterior_stats, posterior_divergence, the rank calls, posterior_mean, sample_posterior ----------
 // Like the listed calls they read the store (and the row labels) only.  What the four flat calls share:
 
 // a message of log_partition_args_error, as the flat calls report it
@@ -1350,6 +1351,47 @@ int vodhip_index_posterior_stats(vodhip_index_t* ix, const void* queries, int q_
     if (le != hipSuccess) (void)hipGetLastError();
     const hipError_t fe = tmp.release();
     if (le != hipSuccess) return fail("posterior-stats launch failed: %s", hipGetErrorString(le));
+    HIP_OK(fe);
+    return 0;
+}
+
+// ---- posterior divergence (kernels_divergence.hip): the posterior-stats scan over the two staged queries of every pair; 32 bytes of
+// partials per (pair, tile), sliced as above ------------------------------------------------------------------------------------------
+int vodhip_index_posterior_divergence(vodhip_index_t* ix, const void* queries_a, const void* queries_b, int q_dtype, int64_t nq, float beta_a,
+                                      float beta_b, const int32_t* q_labels_dev, int n_per_query, float* out_max_a, float* out_log_rel_a,
+                                      float* out_mean_rel_a, float* out_cross_rel_ab, float* out_max_b, float* out_log_rel_b,
+                                      float* out_mean_rel_b, float* out_cross_rel_ba, void* stream_) {
+    if (!ix) return fail("index is NULL");
+    float* const outs[8] = {out_max_a, out_log_rel_a, out_mean_rel_a, out_cross_rel_ab, out_max_b, out_log_rel_b, out_mean_rel_b, out_cross_rel_ba};
+    if (const char* msg = posterior_divergence_args_error(queries_a, queries_b, q_dtype, nq, beta_a, beta_b, q_labels_dev, n_per_query, (const void* const*)outs)) {
+        if (!strcmp(msg, "invalid q_dtype")) return fail("invalid q_dtype %d", q_dtype);
+        if (!strncmp(msg, "beta_a", 6)) return fail("beta_a=%g: %s", (double)beta_a, msg);
+        if (!strncmp(msg, "beta_b", 6)) return fail("beta_b=%g: %s", (double)beta_b, msg);
+        return fail("%s", msg);
+    }
+    if (scan_refusal(ix, "posterior_divergence", q_labels_dev)) return -1;
+    if (nq == 0) return 0;
+    HIP_OK(hipSetDevice(ix->device));
+    hipStream_t stream = (hipStream_t)stream_;
+    DivergenceArgs a;
+    fill_scan_inputs(a, ix, queries_a, q_dtype, q_labels_dev, n_per_query);
+    a.q_src_b = queries_b;
+    a.beta_a = beta_a;
+    a.beta_b = beta_b;
+    for (int k = 0; k < 8; ++k) a.out[k] = outs[k];
+    const size_t per_pair = std::max<size_t>(1, (size_t)scan_tiles(a.ntotal)) * 32;  // the partials
+    const int64_t slice = scan_slice_queries(per_pair);                             // pairs of a launch
+    const int64_t nq_pad = scan_nq_pad(2 * std::min(nq, slice));                     // staged queries of a launch
+    ScanTemps tmp;
+    tmp.stream = stream;
+    if (tmp.alloc({(size_t)nq_pad * (size_t)ix->dim_pad * 2, per_pair * (size_t)(nq_pad / 2)})) return -1;
+    a.q_stage = tmp.p[0];
+    a.part = tmp.p[1];
+    hipError_t le = hipSuccess;
+    for (int64_t q0 = 0; q0 < nq && le == hipSuccess; q0 += slice) le = launch_posterior_divergence(a, q0, std::min(slice, nq - q0), stream);
+    if (le != hipSuccess) (void)hipGetLastError();
+    const hipError_t fe = tmp.release();
+    if (le != hipSuccess) return fail("posterior-divergence launch failed: %s", hipGetErrorString(le));
     HIP_OK(fe);
     return 0;
 }

@@ -274,6 +274,17 @@ struct StatsArgs : ScanInputs {
 // queries [q_first, q_first + nq) of the caller's batch -> the four outputs [q_first ..); a query's bits do not depend on the split
 hipError_t launch_posterior_stats(const StatsArgs& a, int64_t q_first, int64_t nq, hipStream_t stream);
 
+// ---- launchers (kernels_divergence.hip): two posteriors over the same rows - each side's (max, log_rel, mean_rel) and the cross moments ----
+struct DivergenceArgs : ScanInputs {   // q_src: the queries of side a
+    const void* q_src_b = nullptr;    // the queries of side b [.., dim] of q_dtype; q_label: ONE row per pair
+    float beta_a = 1.f, beta_b = 1.f;
+    void* part = nullptr;             // temporary: scan_tiles(ntotal) * scan_nq_pad(2 nq) float4 (two per (pair, tile))
+    float* out[8] = {};               // [pairs of the caller's batch] each: max_a, log_rel_a, mean_rel_a, cross_rel_ab, then side b's
+    // q_stage: scan_nq_pad(2 * pairs of a launch) * dim_pad 16-bit words
+};
+// pairs [q_first, q_first + nq) of the caller's batch -> the eight outputs [q_first ..); a pair's bits do not depend on the split
+hipError_t launch_posterior_divergence(const DivergenceArgs& a, int64_t q_first, int64_t nq, hipStream_t stream);
+
 // ---- launchers (kernels_rank.hip): exact ranks of listed rows / counts above thresholds over the whole store ----
 struct RankArgs : ScanInputs {
     int64_t m = 0, id_base = 0;       // slots per query (1 .. VODHIP_RANK_MAX_LISTED), global id of row 0

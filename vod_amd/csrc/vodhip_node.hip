@@ -21,6 +21,7 @@
 #include "sample_fold.h"
 #include "rank_fold.h"
 #include "stats_fold.h"
+#include "divergence_fold.h"
 #include "vodhip_internal.h"
 
 namespace {
@@ -1040,6 +1041,76 @@ int vodhip_node_index_posterior_stats(vodhip_node_index_t* nx, const void* queri
     if (rc) return nfail("%s", err.c_str());
     vodhip::fold_posterior_stats(parts.data(), parts.data() + n, parts.data() + 2 * n, parts.data() + 3 * n, G, 4 * nq, nq, beta, out_max, out_log_rel,
                                  out_mean_rel, out_var);
+    return 0;
+}
+
+// The posterior divergence behind the one handle (include/vodhip.h, H2d): the shape of the posterior-stats call above with two query
+// sets and 8 * nq floats per shard, folded on the host in increasing shard order, in double (divergence_fold.h).
+int vodhip_node_index_posterior_divergence(vodhip_node_index_t* nx, const void* queries_a, const void* queries_b, int q_dtype, int64_t nq,
+                                           float beta_a, float beta_b, const int32_t* q_labels, int n_per_query, float* out_max_a,
+                                           float* out_log_rel_a, float* out_mean_rel_a, float* out_cross_rel_ab, float* out_max_b,
+                                           float* out_log_rel_b, float* out_mean_rel_b, float* out_cross_rel_ba) {
+    if (!nx) return nfail("index is NULL");
+    float* const outs[8] = {out_max_a, out_log_rel_a, out_mean_rel_a, out_cross_rel_ab, out_max_b, out_log_rel_b, out_mean_rel_b, out_cross_rel_ba};
+    if (const char* msg = vodhip::posterior_divergence_args_error(queries_a, queries_b, q_dtype, nq, beta_a, beta_b, q_labels, n_per_query, (const void* const*)outs)) {
+        if (!strcmp(msg, "invalid q_dtype")) return nfail("invalid q_dtype %d", q_dtype);
+        if (!strncmp(msg, "beta_a", 6)) return nfail("beta_a=%g: %s", (double)beta_a, msg);
+        if (!strncmp(msg, "beta_b", 6)) return nfail("beta_b=%g: %s", (double)beta_b, msg);
+        return nfail("%s", msg);
+    }
+    if (nx->dtype & VODHIP_L2) return nfail("posterior_divergence is not supported on an L2 index (VODHIP_L2): its scores are distances, not similarities");
+    if (nx->dtype & VODHIP_EXACT_F32) return nfail("posterior_divergence is not supported on a VODHIP_EXACT_F32 store: the scan scores the rounded rows, that store's contract is the float32 rows");
+    std::lock_guard<std::mutex> guard(nx->mu);
+    if (q_labels && !nx->has_row_labels) return nfail("set the row labels first (vodhip_node_index_set_row_labels)");
+    if (nq == 0) return 0;
+    const int G = nx->n;
+    const size_t n = (size_t)nq;
+    const size_t q_bytes = n * (size_t)nx->dim * elem_bytes(q_dtype);
+    const size_t lab_bytes = q_labels ? n * (size_t)n_per_query * sizeof(int32_t) : 0;
+    std::vector<float> parts((size_t)G * 8 * n);  // shard g: the eight words, [nq] each, at g * 8 nq
+    struct Tmp { void* qa = nullptr; void* qb = nullptr; int32_t* lab = nullptr; float* out = nullptr; };
+    std::vector<Tmp> tmp((size_t)G);
+    int rc = 0;
+    std::string err;
+    auto hip_step = [&](hipError_t e, const char* what) {
+        if (e != hipSuccess && !rc) {
+            (void)hipGetLastError();
+            err = std::string(what) + " failed: " + hipGetErrorString(e);
+            rc = -1;
+        }
+        return e == hipSuccess;
+    };
+    for (int g = 0; g < G && !rc; ++g) {  // (the devices run side by side: nothing is waited for until every shard is enqueued)
+        hipStream_t st = nx->stream[g];
+        Tmp& t = tmp[(size_t)g];
+        if (!hip_step(hipSetDevice(nx->device[g]), "hipSetDevice")) break;
+        if (!hip_step(hipMallocAsync(&t.qa, q_bytes, st), "hipMallocAsync")) break;
+        if (!hip_step(hipMallocAsync(&t.qb, q_bytes, st), "hipMallocAsync")) break;
+        if (!hip_step(hipMallocAsync((void**)&t.out, 8 * n * sizeof(float), st), "hipMallocAsync")) break;
+        if (q_labels && !hip_step(hipMallocAsync((void**)&t.lab, lab_bytes, st), "hipMallocAsync")) break;
+        if (!hip_step(hipMemcpyAsync(t.qa, queries_a, q_bytes, hipMemcpyHostToDevice, st), "hipMemcpyAsync")) break;
+        if (!hip_step(hipMemcpyAsync(t.qb, queries_b, q_bytes, hipMemcpyHostToDevice, st), "hipMemcpyAsync")) break;
+        if (q_labels && !hip_step(hipMemcpyAsync(t.lab, q_labels, lab_bytes, hipMemcpyHostToDevice, st), "hipMemcpyAsync")) break;
+        if (vodhip_index_posterior_divergence(nx->shard[g], t.qa, t.qb, q_dtype, nq, beta_a, beta_b, t.lab, n_per_query, t.out, t.out + n, t.out + 2 * n,
+                                              t.out + 3 * n, t.out + 4 * n, t.out + 5 * n, t.out + 6 * n, t.out + 7 * n, st)) {
+            err = std::string("shard ") + std::to_string(g) + ": " + vodhip_last_error();
+            rc = -1;
+            break;
+        }
+        hip_step(hipMemcpyAsync(parts.data() + (size_t)g * 8 * n, t.out, 8 * n * sizeof(float), hipMemcpyDeviceToHost, st), "hipMemcpyAsync");
+    }
+    for (int g = 0; g < G; ++g) {  // (also after a failure: what was enqueued reads the caller's host buffers)
+        Tmp& t = tmp[(size_t)g];
+        if (hipSetDevice(nx->device[g]) != hipSuccess) continue;
+        if (t.qa) (void)hipFreeAsync(t.qa, nx->stream[g]);
+        if (t.qb) (void)hipFreeAsync(t.qb, nx->stream[g]);
+        if (t.lab) (void)hipFreeAsync(t.lab, nx->stream[g]);
+        if (t.out) (void)hipFreeAsync(t.out, nx->stream[g]);
+        hip_step(hipStreamSynchronize(nx->stream[g]), "hipStreamSynchronize");
+    }
+    (void)hipSetDevice(nx->device[0]);
+    if (rc) return nfail("%s", err.c_str());
+    vodhip::fold_posterior_divergence(parts.data(), G, nq, beta_a, beta_b, outs);
     return 0;
 }
 

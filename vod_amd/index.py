@@ -538,6 +538,55 @@ class HipFlatIndex:
         return PosteriorStats(log_rel - beta * mean_rel, max_score + mean_rel, var, mean_rel,
                               LogPartition(max_score * beta + log_rel, max_score, log_rel))
 
+    def posterior_divergence(self, queries_a, queries_b, temperature_a: float = 1.0, temperature_b: float | None = None, subset=None,
+                             out=None) -> "PosteriorDivergence":
+        """The exact divergences between TWO posteriors over the WHOLE store from ONE scan: pair `i` is `(queries_a[i], queries_b[i])`,
+        `p = softmax(<a~, x~_z> / temperature_a)` and `r = softmax(<b~, x~_z> / temperature_b)` over the rows eligible for the pair
+        (`temperature_b=None`: as a) - a teacher against a student, the last period's retriever against the current one, one query at two
+        temperatures.  `PosteriorDivergence(kl_ab, kl_ba, cross_entropy_ab, cross_entropy_ba, entropy_a, entropy_b, cross_rel_ab,
+        cross_rel_ba, stats_a, stats_b)`, float32 device tensors `[nq]`: `kl_ab = KL(p || r)`, `cross_entropy_ab = H(p, r)`,
+        `cross_rel_ab = E_p[s_b] - max_b <= 0` (what the library returns), `stats_a` / `stats_b` the `DivergenceSide(max_score, log_rel,
+        mean_rel, log_partition)` of each side - the bits `posterior_stats` returns for that side alone unless a row scores NaN
+        against exactly one side.  The derived words are formed in float64 from the eight float32 words and rounded once; an identical
+        pair returns `kl == 0.0` exactly.  A pair's words are the same bits whatever the batch around it.
+        A row with `p > 0` that side b scores -inf: `cross_entropy_ab = kl_ab = +inf`.  A side with no eligible row or a +inf score:
+        its `mean_rel` and both cross words (hence every divergence) are NaN.
+
+        Arguments, stream behaviour and refusals as `posterior_stats`; one `subset` row per pair; `out`: the eight library words
+        (max_a, log_rel_a, mean_rel_a, cross_rel_ab, max_b, log_rel_b, mean_rel_b, cross_rel_ba) to write into."""
+        qa = self._prep_queries(queries_a)
+        qb = self._prep_queries(queries_b)
+        if qb.dtype != qa.dtype:  # (one q_dtype per call: float32 holds every input dtype)
+            qa, qb = qa.float(), qb.float()
+        nq = qa.shape[0]
+        if qb.shape[0] != nq:
+            raise ValueError(f"expected {nq} queries on each side, got {qb.shape[0]} for b")
+        beta_a = 1.0 / float(temperature_a) if temperature_a else float("nan")
+        beta_b = beta_a if temperature_b is None else (1.0 / float(temperature_b) if temperature_b else float("nan"))
+        sub, n_sub = self._subset_labels(subset, nq)
+        words = tuple(torch.empty((nq,), dtype=torch.float32, device=self.device) for _ in range(8)) if out is None else tuple(out)
+        if len(words) != 8:
+            raise ValueError(f"expected an 8-tuple of outputs, got {len(words)}")
+        with torch.cuda.device(self.device):
+            _native.check(self._lib.vodhip_index_posterior_divergence(
+                self._h, qa.data_ptr(), qb.data_ptr(), _native.torch_dtype_code(qa.dtype), nq, beta_a, beta_b,
+                None if sub is None else sub.data_ptr(), n_sub, *[w.data_ptr() for w in words], _native.current_stream_ptr(self.device)))
+        for t, given in ((qa, queries_a), (qb, queries_b), (sub, subset)):
+            if t is not None and t is not given:
+                t.record_stream(torch.cuda.current_stream(self.device))
+        return posterior_divergence_words(words, beta_a, beta_b)
+
+    def kl_to(self, teacher_queries, student_queries: torch.Tensor, temperature: float = 1.0, temperature_teacher: float | None = None,
+              subset=None) -> torch.Tensor:
+        """`KL(p_teacher || p_student)` over the whole store as a float32 `[nq]` tensor that is differentiable with respect to
+        `student_queries` only (the teacher is a constant): forward is `posterior_divergence(teacher, student).kl_ab`, backward
+        `grad_student = grad_out[:, None] * (posterior_mean(student) - posterior_mean(teacher)) / temperature`, cast to the student's
+        dtype; rows whose KL is not finite get zero.  `temperature` is the student's, `temperature_teacher=None` means the same.  The
+        two `posterior_mean` calls run in forward, and only when the student requires grad."""
+        t_teacher = float(temperature) if temperature_teacher is None else float(temperature_teacher)
+        teacher = teacher_queries.detach() if isinstance(teacher_queries, torch.Tensor) else teacher_queries
+        return _KlTo.apply(student_queries, self, teacher, float(temperature), t_teacher, subset)
+
     def posterior_mean(self, queries, temperature: float = 1.0, subset=None, out=None) -> "PosteriorMean":
         """The posterior mean of the stored rows under the softmax over the WHOLE store, `mean[q] = sum_z p(z | q) x~_z` with
         `p(z | q) = exp(<q~, x~_z> / temperature - log Z(q))`: `PosteriorMean(mean, log_partition)`, `mean` a float32 device tensor
@@ -670,6 +719,99 @@ class PosteriorStats(NamedTuple):
     var_score: Any
     mean_rel: Any
     log_partition: LogPartition
+
+
+class DivergenceSide(NamedTuple):
+    """One side of `posterior_divergence`: `max_score`, `log_rel`, `mean_rel = E[s] - max_score <= 0` under the side's own posterior,
+    each `[nq]`, with the side's `LogPartition`."""
+
+    max_score: Any
+    log_rel: Any
+    mean_rel: Any
+    log_partition: LogPartition
+
+
+class PosteriorDivergence(NamedTuple):
+    """`posterior_divergence` of `p = softmax(s_a / T_a)` and `r = softmax(s_b / T_b)`: `kl_ab = KL(p || r)`, `cross_entropy_ab =
+    H(p, r)`, `entropy_a = H(p)`, `cross_rel_ab = E_p[s_b] - max_b <= 0` and the mirrors, each `[nq]`, with each side's words."""
+
+    kl_ab: Any
+    kl_ba: Any
+    cross_entropy_ab: Any
+    cross_entropy_ba: Any
+    entropy_a: Any
+    entropy_b: Any
+    cross_rel_ab: Any
+    cross_rel_ba: Any
+    stats_a: DivergenceSide
+    stats_b: DivergenceSide
+
+
+def posterior_divergence_words(words, beta_a: float, beta_b: float) -> PosteriorDivergence:
+    """The eight library words (max_a, log_rel_a, mean_rel_a, cross_rel_ab, max_b, log_rel_b, mean_rel_b, cross_rel_ba; torch tensors
+    or NumPy arrays) -> `PosteriorDivergence`.  Every derived word is formed in float64 from the float32 words and rounded to float32
+    once, in a grouping that pairs each word with its own side's counterpart,
+        entropy_a = log_rel_a - beta_a mean_rel_a,   cross_entropy_ab = log_rel_b - beta_b cross_rel_ab,
+        kl_ab = max(0, (log_rel_b - log_rel_a) + (beta_a mean_rel_a - beta_b cross_rel_ab)),
+    so that identical pairs give exactly 0; the betas are the float32 values the library received."""
+    ma, ra, aa, cab, mb, rb, ab, cba = words
+    is_torch = isinstance(ma, torch.Tensor)
+    ba, bb = float(np.float32(beta_a)), float(np.float32(beta_b))
+
+    def f64(t):
+        return t.double() if is_torch else np.asarray(t, dtype=np.float64)
+
+    def f32(t):
+        return t.float() if is_torch else t.astype(np.float32)
+
+    def clamp0(t):  # (NaN stays NaN)
+        return torch.clamp(t, min=0.0) if is_torch else np.where(t < 0.0, 0.0, t)
+
+    Ra, Aa, Cab, Rb, Ab, Cba = (f64(t) for t in (ra, aa, cab, rb, ab, cba))
+    with np.errstate(invalid="ignore"):
+        ent_a, ent_b = f32(Ra - ba * Aa), f32(Rb - bb * Ab)
+        ce_ab, ce_ba = f32(Rb - bb * Cab), f32(Ra - ba * Cba)
+        kl_ab = f32(clamp0((Rb - Ra) + (ba * Aa - bb * Cab)))
+        kl_ba = f32(clamp0((Ra - Rb) + (bb * Ab - ba * Cba)))
+        if is_torch:
+            lz_a, lz_b = ma * ba + ra, mb * bb + rb  # (-inf + -inf and +inf + +inf: never NaN)
+        else:
+            lz_a, lz_b = (ma * np.float32(ba) + ra).astype(np.float32), (mb * np.float32(bb) + rb).astype(np.float32)
+    return PosteriorDivergence(kl_ab, kl_ba, ce_ab, ce_ba, ent_a, ent_b, cab, cba,
+                               DivergenceSide(ma, ra, aa, LogPartition(lz_a, ma, ra)), DivergenceSide(mb, rb, ab, LogPartition(lz_b, mb, rb)))
+
+
+def kl_to_backward(grad_out: torch.Tensor, mean_student: torch.Tensor, mean_teacher: torch.Tensor, kl: torch.Tensor, beta: float,
+                   dtype: torch.dtype) -> torch.Tensor:
+    """The backward of `kl_to` in the student's queries: `d KL(p_teacher || p_student) / d b = beta (E_student[x] - E_teacher[x])`
+    (`beta = 1 / temperature` of the student), so `grad = grad_out[:, None] * beta * (mean_student - mean_teacher)`, zero where `kl` is
+    not finite, cast to `dtype`."""
+    g = grad_out.to(torch.float32)[:, None] * (beta * (mean_student.to(torch.float32) - mean_teacher.to(torch.float32)))
+    g = torch.where(torch.isfinite(kl)[:, None], g, torch.zeros_like(g))
+    return g.to(dtype)
+
+
+class _KlTo(torch.autograd.Function):
+    """`index.kl_to`: `index` is anything with `posterior_divergence(a, b, T_a, T_b, subset)` and `posterior_mean(q, T, subset)`."""
+
+    @staticmethod
+    def forward(ctx, student, index, teacher, temperature, temperature_teacher, subset):
+        teacher = teacher.detach() if isinstance(teacher, torch.Tensor) else teacher
+        div = index.posterior_divergence(teacher, student.detach(), temperature_teacher, temperature, subset)
+        kl = torch.as_tensor(div.kl_ab)
+        ctx.q_dtype, ctx.q_device = student.dtype, student.device
+        ctx.beta = 1.0 / temperature
+        if ctx.needs_input_grad[0]:
+            mean_s = torch.as_tensor(index.posterior_mean(student.detach(), temperature, subset).mean)
+            mean_t = torch.as_tensor(index.posterior_mean(teacher, temperature_teacher, subset).mean)
+            ctx.save_for_backward(mean_s, mean_t, kl)
+        return kl.clone()
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        mean_s, mean_t, kl = ctx.saved_tensors
+        g = kl_to_backward(grad_out.to(mean_s.device), mean_s, mean_t, kl, ctx.beta, ctx.q_dtype)
+        return g.to(ctx.q_device), None, None, None, None, None
 
 
 class PosteriorSample(NamedTuple):
@@ -1082,6 +1224,38 @@ class HipNodeIndex:
             entropy = (log_rel - np.float32(beta) * mean_rel).astype(np.float32)
             mean_score = (max_score + mean_rel).astype(np.float32)
         return PosteriorStats(entropy, mean_score, var, mean_rel, LogPartition(log_z, max_score, log_rel))
+
+    def posterior_divergence(self, queries_a, queries_b, temperature_a: float = 1.0, temperature_b: float | None = None,
+                             subset: np.ndarray | None = None, out=None) -> "PosteriorDivergence":
+        """`HipFlatIndex.posterior_divergence` over every shard: each shard runs the flat call on its own device, the eight words per
+        shard are folded on the host in shard order, in double (a mixture of the shards' posteriors on each side).  Host queries ->
+        `PosteriorDivergence` of float32 NumPy arrays `[nq]`; `max_score` of each side equals one index holding all the rows bit for
+        bit.  `out`: eight float32 NumPy arrays `[nq]` to write the library words into."""
+        qa = self._host_queries(queries_a)
+        qb = self._host_queries(queries_b)
+        if qb.dtype != qa.dtype:
+            qa, qb = qa.astype(np.float32), qb.astype(np.float32)
+        nq = int(qa.shape[0])
+        if qb.shape[0] != nq:
+            raise ValueError(f"expected {nq} queries on each side, got {qb.shape[0]} for b")
+        beta_a = 1.0 / float(temperature_a) if temperature_a else float("nan")
+        beta_b = beta_a if temperature_b is None else (1.0 / float(temperature_b) if temperature_b else float("nan"))
+        sub, n_sub = self._host_subset(subset, nq)
+        words = tuple(np.empty((nq,), dtype=np.float32) for _ in range(8)) if out is None else tuple(out)
+        if len(words) != 8 or any(w.dtype != np.float32 or w.shape != (nq,) or not w.flags.c_contiguous for w in words):
+            raise ValueError("expected eight contiguous float32 [nq] arrays as out")
+        with torch.cuda.device(self.device):
+            _native.check(self._lib.vodhip_node_index_posterior_divergence(
+                self._h, qa.ctypes.data, qb.ctypes.data, 2 if qa.dtype == np.float32 else 0, nq, beta_a, beta_b,
+                None if sub is None else sub.ctypes.data, n_sub, *[w.ctypes.data for w in words]))
+        return posterior_divergence_words(words, beta_a, beta_b)
+
+    def kl_to(self, teacher_queries, student_queries: torch.Tensor, temperature: float = 1.0, temperature_teacher: float | None = None,
+              subset=None) -> torch.Tensor:
+        """`HipFlatIndex.kl_to` over every shard: a float32 host tensor `[nq]`, differentiable in `student_queries`."""
+        t_teacher = float(temperature) if temperature_teacher is None else float(temperature_teacher)
+        teacher = teacher_queries.detach() if isinstance(teacher_queries, torch.Tensor) else teacher_queries
+        return _KlTo.apply(student_queries, self, teacher, float(temperature), t_teacher, subset)
 
     def _host_queries(self, queries) -> np.ndarray:
         if isinstance(queries, torch.Tensor):
