@@ -278,3 +278,62 @@ def test_two_searches_in_flight_return_what_the_synchronous_search_returns(locat
                 nx.finish()
         s, i = nx.search(as_in(qs[3]), ks[3])  # the synchronous call still works afterwards
         np.testing.assert_array_equal(as_out(i), want[3][1])
+
+
+def _arrays(result):
+    """Every array of a (nested) result tuple, in order."""
+    if isinstance(result, tuple):
+        return [a for part in result for a in _arrays(part)]
+    return [np.asarray(result)]
+
+
+def _assert_same_bits(got, want):
+    got, want = _arrays(got), _arrays(want)
+    assert len(got) == len(want)
+    for a, b in zip(got, want):
+        assert a.dtype == b.dtype and a.dtype in (np.float32, np.int64)
+        view = np.uint32 if a.dtype == np.float32 else np.int64
+        np.testing.assert_array_equal(a.view(view), b.view(view))
+
+
+def test_a_shard_that_refuses_mid_fan_out_leaves_the_handle_usable():
+    """Every operation that replicates host inputs to the shards, when shard 1's flat call refuses (its row labels were cleared behind
+    the node index's back) after shard 0 was enqueued: the error names the shard, what shard 0 had in flight is freed and waited for,
+    and once the labels are back every operation returns the bits it returned before."""
+    from vod_amd import _native
+    from vod_amd.index import HipNodeIndex
+
+    rng = np.random.default_rng(21)
+    n, d, nq = 600, 65, 3
+    x = rng.standard_normal((n, d)).astype(np.float16)
+    q = rng.standard_normal((nq, d)).astype(np.float16)
+    qb = rng.standard_normal((nq, d)).astype(np.float16)
+    labels = (np.arange(n) % 2).astype(np.int32)
+    subset = np.array([[r % 2] for r in range(nq)], dtype=np.int32)
+    ids = np.array([[r, 199, 200 + 7 * r, 401, 599 - r] for r in range(nq)], dtype=np.int64)  # all three shards, both labels
+    weights = rng.standard_normal(ids.shape).astype(np.float32)
+    thresholds = rng.standard_normal(ids.shape).astype(np.float32)
+    with HipNodeIndex(d, n, [0, 0, 0]) as nx:
+        nx.add(x)
+        nx.set_row_labels(labels)
+        ops = {
+            "score_ids": lambda: nx.score_ids(q, ids, subset=subset),
+            "score_ids_k2": lambda: nx.score_ids(q, ids, 2, subset=subset),
+            "sum_ids": lambda: nx.sum_ids(ids, weights, subset=subset),
+            "log_partition": lambda: nx.log_partition(q, subset=subset),
+            "posterior_stats": lambda: nx.posterior_stats(q, subset=subset),
+            "posterior_divergence": lambda: nx.posterior_divergence(q, qb, subset=subset),
+            "posterior_mean": lambda: nx.posterior_mean(q, subset=subset),
+            "sample_posterior": lambda: nx.sample_posterior(q, 4, seed=7, subset=subset),
+            "rank_ids": lambda: nx.rank_ids(q, ids, subset=subset),
+            "count_above": lambda: nx.count_above(q, thresholds, tie_ids=ids, subset=subset),
+        }
+        before = {name: op() for name, op in ops.items()}
+        lib = _native.load_library()
+        _native.check(lib.vodhip_index_set_row_labels(ctypes.c_void_p(nx.shard(1)[0]), None, 0, 0, None))
+        for name, op in ops.items():
+            with pytest.raises(_native.NativeLibraryError, match=r"shard 1: set the row labels first \(vodhip_index_set_row_labels\)"):
+                op()
+        nx.set_row_labels(labels)
+        for name, op in ops.items():
+            _assert_same_bits(op(), before[name])

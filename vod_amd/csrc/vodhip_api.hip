@@ -1217,7 +1217,7 @@ int vodhip_index_sum_ids(vodhip_index_t* ix, const int64_t* ids_dev, const float
 }
 
 // ---- the whole-store scans (store_scan.h): log_partition, posterior_stats, posterior_divergence, the rank calls, posterior_mean, sample_posterior ----------
-// Like the listed calls they read the store (and the row labels) only.  What the four flat calls share:
+// Like the listed calls they read the store (and the row labels) only.  What the flat calls share:
 
 // a message of log_partition_args_error, as the flat calls report it
 static int partition_args_fail(const char* msg, int q_dtype, float beta) {
@@ -1228,8 +1228,8 @@ static int partition_args_fail(const char* msg, int q_dtype, float beta) {
 
 // the indexes no scan accepts; `what` names the operation in the message
 static int scan_refusal(const vodhip_index_t* ix, const char* what, const void* q_labels_dev) {
-    if (ix->l2) return fail("%s is not supported on an L2 index (VODHIP_L2): its scores are distances, not similarities", what);
-    if (ix->exact) return fail("%s is not supported on a VODHIP_EXACT_F32 store: the scan scores the rounded rows, that store's contract is the float32 rows", what);
+    if (ix->l2) return fail(SCAN_REFUSES_L2, what);
+    if (ix->exact) return fail(SCAN_REFUSES_EXACT_F32, what);
     if (q_labels_dev && !ix->row_label) return fail("set the row labels first (vodhip_index_set_row_labels)");
     return 0;
 }
@@ -1302,21 +1302,17 @@ int vodhip_index_log_partition(vodhip_index_t* ix, const void* queries, int q_dt
     a.out_max = out_max;
     a.out_log_rel = out_log_rel;
     const int64_t nq_pad = scan_nq_pad(std::min(nq, Q_CHUNK));
-    const size_t stage_bytes = (size_t)nq_pad * (size_t)ix->dim_pad * 2;
-    const size_t part_bytes = std::max<size_t>(8, (size_t)scan_tiles(a.ntotal) * (size_t)nq_pad * 8);
-    HIP_OK(hipMallocAsync(&a.q_stage, stage_bytes, stream));
-    if (hipError_t e = hipMallocAsync(&a.part, part_bytes, stream); e != hipSuccess) {
-        (void)hipGetLastError();
-        (void)hipFreeAsync(a.q_stage, stream);
-        return fail("hipMallocAsync of the %zu-byte partials failed: %s", part_bytes, hipGetErrorString(e));
-    }
+    ScanTemps tmp;
+    tmp.stream = stream;
+    if (tmp.alloc({(size_t)nq_pad * (size_t)ix->dim_pad * 2, std::max<size_t>(8, (size_t)scan_tiles(a.ntotal) * (size_t)nq_pad * 8)})) return -1;
+    a.q_stage = tmp.p[0];
+    a.part = tmp.p[1];
     hipError_t le = hipSuccess;
     for (int64_t q0 = 0; q0 < nq && le == hipSuccess; q0 += Q_CHUNK) le = launch_log_partition(a, q0, std::min(Q_CHUNK, nq - q0), stream);
     if (le != hipSuccess) (void)hipGetLastError();
-    const hipError_t f1 = hipFreeAsync(a.q_stage, stream), f2 = hipFreeAsync(a.part, stream);
+    const hipError_t fe = tmp.release();
     if (le != hipSuccess) return fail("log-partition launch failed: %s", hipGetErrorString(le));
-    HIP_OK(f1);
-    HIP_OK(f2);
+    HIP_OK(fe);
     return 0;
 }
 

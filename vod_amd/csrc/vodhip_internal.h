@@ -33,6 +33,11 @@ namespace vodhip {
 
 void set_last_error(const char* msg);  // the calling thread's vodhip_last_error() text (vodhip_node.hip composes public entry points)
 
+// the index kinds no whole-store scan accepts, as the flat and the node entry points refuse them; %s = the operation's name
+constexpr const char* SCAN_REFUSES_L2 = "%s is not supported on an L2 index (VODHIP_L2): its scores are distances, not similarities";
+constexpr const char* SCAN_REFUSES_EXACT_F32 =
+    "%s is not supported on a VODHIP_EXACT_F32 store: the scan scores the rounded rows, that store's contract is the float32 rows";
+
 // which: 0 = merge_hybrid_kernel, 1 = priority_sample_kernel, 2 = flatten_inbatch_kernel; out: 256 words = 64 (cycles, 10 ns ticks) phase pairs + 64 (begin, end) workgroup pairs
 hipError_t read_probe_hybrid(long long* out);
 hipError_t read_probe_sample(int which, long long* out);

@@ -9,6 +9,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <cassert>
 #include <cstdarg>
 #include <cstdio>
 #include <cstring>
@@ -131,6 +132,94 @@ int ensure(void** p, size_t* have, size_t want, size_t elem) {
     *have = n;
     return 0;
 }
+
+// ---- what the host-synchronous calls (every operation but `search`) share ----------------------------------------------------------
+
+// a message of log_partition_args_error (or of a check built on it), as the node calls report it: partition_args_fail of vodhip_api.hip
+int node_partition_args_fail(const char* msg, int q_dtype, float beta) {
+    if (!strcmp(msg, "invalid q_dtype")) return nfail("invalid q_dtype %d", q_dtype);
+    if (!strncmp(msg, "beta", 4)) return nfail("beta=%g: %s", (double)beta, msg);
+    return nfail("%s", msg);
+}
+
+// the index kinds no whole-store scan accepts; `what` names the operation in the message (scan_refusal of vodhip_api.hip)
+int node_scan_refusal(const vodhip_node_index* nx, const char* what) {
+    if (nx->dtype & VODHIP_L2) return nfail(vodhip::SCAN_REFUSES_L2, what);
+    if (nx->dtype & VODHIP_EXACT_F32) return nfail(vodhip::SCAN_REFUSES_EXACT_F32, what);
+    return 0;
+}
+
+// subset labels without row labels; the caller holds nx->mu
+int node_labels_refusal(const vodhip_node_index* nx, const void* q_labels) {
+    if (!q_labels || nx->has_row_labels) return 0;
+    return nfail("set the row labels first (vodhip_node_index_set_row_labels)");
+}
+
+inline size_t query_bytes(const vodhip_node_index* nx, int64_t nq, int q_dtype) { return (size_t)nq * (size_t)nx->dim * elem_bytes(q_dtype); }
+inline size_t label_bytes(const void* q_labels, int64_t nq, int n_per_query) { return q_labels ? (size_t)nq * (size_t)n_per_query * sizeof(int32_t) : 0; }
+
+// The route of those calls: host inputs are replicated to every shard, every shard runs the flat call on its own device and stream,
+// the per-shard outputs return through host memory (the caller folds them).  A SLOT is one stream-ordered device block per shard:
+// an input is uploaded before the flat call, an output downloaded after it returned 0 - shard g's bytes land at base + g * bytes.
+// A slot of no bytes (a NULL host pointer) allocates nothing and stays NULL.  The caller holds nx->mu.
+struct ShardFanout {
+    static constexpr int MAX_SLOTS = 7;  // (the rank pass)
+    struct Slot { const void* up; char* down; size_t bytes; };
+    vodhip_node_index* nx;
+    Slot slot[MAX_SLOTS];
+    int n_slots = 0;
+    explicit ShardFanout(vodhip_node_index* nx_) : nx(nx_) {}
+    int input(const void* host, size_t bytes) { return add({host, nullptr, host ? bytes : 0}); }
+    int output(void* host_base, size_t bytes_per_shard) { return add({nullptr, (char*)host_base, host_base ? bytes_per_shard : 0}); }
+    int add(Slot s) {
+        assert(n_slots < MAX_SLOTS);
+        slot[n_slots] = s;
+        return n_slots++;
+    }
+    // call(g, p, stream): the flat call of shard g, p[i] = slot i on its device; 0, or -1 with vodhip_last_error() set.  Nothing is
+    // waited for until every shard is enqueued (unless the flat call itself waits); the first error wins and ends the enqueueing
+    template <class Call>
+    int run(Call&& call) {
+        const int G = nx->n;
+        std::vector<void*> dev((size_t)G * MAX_SLOTS, nullptr);
+        bool failed = false;
+        std::string err;
+        auto hip_step = [&](hipError_t e, const char* what) {
+            if (e != hipSuccess && !failed) {
+                (void)hipGetLastError();
+                err = std::string(what) + " failed: " + hipGetErrorString(e);
+                failed = true;
+            }
+            return e == hipSuccess;
+        };
+        auto enqueue = [&](int g) {
+            hipStream_t st = nx->stream[g];
+            void** p = &dev[(size_t)g * MAX_SLOTS];
+            if (!hip_step(hipSetDevice(nx->device[g]), "hipSetDevice")) return;
+            for (int i = 0; i < n_slots; ++i)
+                if (slot[i].bytes && !hip_step(hipMallocAsync(&p[i], slot[i].bytes, st), "hipMallocAsync")) return;
+            for (int i = 0; i < n_slots; ++i)
+                if (slot[i].bytes && slot[i].up && !hip_step(hipMemcpyAsync(p[i], slot[i].up, slot[i].bytes, hipMemcpyHostToDevice, st), "hipMemcpyAsync")) return;
+            if (call(g, (void* const*)p, st)) {
+                err = std::string("shard ") + std::to_string(g) + ": " + vodhip_last_error();
+                failed = true;
+                return;
+            }
+            for (int i = 0; i < n_slots; ++i)
+                if (slot[i].bytes && slot[i].down)
+                    hip_step(hipMemcpyAsync(slot[i].down + (size_t)g * slot[i].bytes, p[i], slot[i].bytes, hipMemcpyDeviceToHost, st), "hipMemcpyAsync");
+        };
+        for (int g = 0; g < G && !failed; ++g) enqueue(g);
+        for (int g = 0; g < G; ++g) {  // (also after a failure: what was enqueued reads and writes the caller's host memory)
+            if (hipSetDevice(nx->device[g]) != hipSuccess) continue;
+            for (int i = 0; i < MAX_SLOTS; ++i)
+                if (void* p = dev[(size_t)g * MAX_SLOTS + i]) (void)hipFreeAsync(p, nx->stream[g]);
+            hip_step(hipStreamSynchronize(nx->stream[g]), "hipStreamSynchronize");
+        }
+        (void)hipSetDevice(nx->device[0]);
+        return failed ? nfail("%s", err.c_str()) : 0;
+    }
+};
 
 }  // namespace
 
@@ -368,7 +457,7 @@ int vodhip_node_index_set_row_labels(vodhip_node_index_t* nx, const int32_t* lab
 int vodhip_node_index_set_query_labels(vodhip_node_index_t* nx, const int32_t* q_labels, int n_per_query, int location) {
     if (!nx) return nfail("index is NULL");
     if (q_labels && (n_per_query < 1 || n_per_query > 64)) return nfail("n_per_query must be in [1, 64]");
-    if (q_labels && !nx->has_row_labels) return nfail("set the row labels first (vodhip_node_index_set_row_labels)");
+    if (node_labels_refusal(nx, q_labels)) return -1;
     if (location != VODHIP_HOST && location != VODHIP_DEVICE) return nfail("invalid location %d", location);
     std::lock_guard<std::mutex> guard(nx->mu);
     nx->q_labels = q_labels;
@@ -686,12 +775,11 @@ static int node_listed(vodhip_node_index* nx, const void* queries, int q_dtype, 
     if (location != VODHIP_HOST && location != VODHIP_DEVICE) return nfail("invalid location %d", location);
     if (q_labels && (n_per_query < 1 || n_per_query > 64)) return nfail("n_per_query must be in [1, 64]");
     std::lock_guard<std::mutex> guard(nx->mu);
-    if (q_labels && !nx->has_row_labels) return nfail("set the row labels first (vodhip_node_index_set_row_labels)");
+    if (node_labels_refusal(nx, q_labels)) return -1;
     if (nq == 0) return 0;
     const int G = nx->n, dev0 = nx->device[0];
     hipStream_t user = location == VODHIP_DEVICE ? (hipStream_t)stream_ : nx->merge_stream;
-    const size_t q_bytes = (size_t)nq * (size_t)nx->dim * elem_bytes(q_dtype), n = (size_t)nq * (size_t)m;
-    const size_t lab_bytes = q_labels ? (size_t)nq * (size_t)n_per_query * sizeof(int32_t) : 0;
+    const size_t q_bytes = query_bytes(nx, nq, q_dtype), n = (size_t)nq * (size_t)m, lab_bytes = label_bytes(q_labels, nq, n_per_query);
     // 1. the batch in host memory
     std::vector<char> hq, hl;
     std::vector<int64_t> hi;
@@ -713,47 +801,14 @@ static int node_listed(vodhip_node_index* nx, const void* queries, int q_dtype, 
     }
     // 2. every shard scores the whole list (the devices run side by side: nothing is waited for until every shard is enqueued)
     std::vector<float> parts((size_t)G * n);
-    struct Tmp { void* q = nullptr; int64_t* ids = nullptr; int32_t* lab = nullptr; float* out = nullptr; };
-    std::vector<Tmp> tmp((size_t)G);
-    int rc = 0;
-    std::string err;
-    auto hip_step = [&](hipError_t e, const char* what) {
-        if (e != hipSuccess && !rc) {
-            (void)hipGetLastError();
-            err = std::string(what) + " failed: " + hipGetErrorString(e);
-            rc = -1;
-        }
-        return e == hipSuccess;
-    };
-    for (int g = 0; g < G && !rc; ++g) {
-        hipStream_t st = nx->stream[g];
-        Tmp& t = tmp[(size_t)g];
-        if (!hip_step(hipSetDevice(nx->device[g]), "hipSetDevice")) break;
-        if (!hip_step(hipMallocAsync(&t.q, q_bytes, st), "hipMallocAsync")) break;
-        if (!hip_step(hipMallocAsync((void**)&t.ids, n * sizeof(int64_t), st), "hipMallocAsync")) break;
-        if (!hip_step(hipMallocAsync((void**)&t.out, n * sizeof(float), st), "hipMallocAsync")) break;
-        if (lab_host && !hip_step(hipMallocAsync((void**)&t.lab, lab_bytes, st), "hipMallocAsync")) break;
-        if (!hip_step(hipMemcpyAsync(t.q, q_host, q_bytes, hipMemcpyHostToDevice, st), "hipMemcpyAsync")) break;
-        if (!hip_step(hipMemcpyAsync(t.ids, ids_host, n * sizeof(int64_t), hipMemcpyHostToDevice, st), "hipMemcpyAsync")) break;
-        if (lab_host && !hip_step(hipMemcpyAsync(t.lab, lab_host, lab_bytes, hipMemcpyHostToDevice, st), "hipMemcpyAsync")) break;
-        if (vodhip_index_score_ids(nx->shard[g], t.q, q_dtype, nq, t.ids, m, g * nx->rows_per_shard, t.lab, n_per_query, t.out, st)) {
-            err = std::string("shard ") + std::to_string(g) + ": " + vodhip_last_error();
-            rc = -1;
-            break;
-        }
-        hip_step(hipMemcpyAsync(parts.data() + (size_t)g * n, t.out, n * sizeof(float), hipMemcpyDeviceToHost, st), "hipMemcpyAsync");
-    }
-    for (int g = 0; g < G; ++g) {  // (also after a failure: what was enqueued reads the host vectors of this frame)
-        Tmp& t = tmp[(size_t)g];
-        if (hipSetDevice(nx->device[g]) != hipSuccess) continue;
-        if (t.q) (void)hipFreeAsync(t.q, nx->stream[g]);
-        if (t.ids) (void)hipFreeAsync(t.ids, nx->stream[g]);
-        if (t.lab) (void)hipFreeAsync(t.lab, nx->stream[g]);
-        if (t.out) (void)hipFreeAsync(t.out, nx->stream[g]);
-        hip_step(hipStreamSynchronize(nx->stream[g]), "hipStreamSynchronize");
-    }
-    (void)hipSetDevice(dev0);
-    if (rc) return nfail("%s", err.c_str());
+    ShardFanout f(nx);
+    const int iq = f.input(q_host, q_bytes), ii = f.input(ids_host, n * sizeof(int64_t)), il = f.input(lab_host, lab_bytes);
+    const int io = f.output(parts.data(), n * sizeof(float));
+    if (f.run([&](int g, void* const* p, hipStream_t st) {
+            return vodhip_index_score_ids(nx->shard[g], p[iq], q_dtype, nq, (const int64_t*)p[ii], m, g * nx->rows_per_shard, (const int32_t*)p[il], n_per_query,
+                                          (float*)p[io], st);
+        }))
+        return -1;
     // 3. on devices[0]: combine by ownership, select once
     float *d_parts = nullptr, *d_aligned = nullptr, *d_s = nullptr;
     int64_t *d_ids = nullptr, *d_i = nullptr;
@@ -792,7 +847,7 @@ static int node_listed(vodhip_node_index* nx, const void* queries, int q_dtype, 
         }
         return 0;
     };
-    rc = steps();
+    const int rc = steps();
     const std::string keep = rc ? vodhip_last_error() : "";
     for (void* p : {(void*)d_parts, (void*)d_aligned, (void*)d_s, (void*)d_ids, (void*)d_i})
         if (p) (void)hipFreeAsync(p, user);
@@ -826,12 +881,12 @@ int vodhip_node_index_sum_ids(vodhip_node_index_t* nx, const int64_t* ids, const
     if (location != VODHIP_HOST && location != VODHIP_DEVICE) return nfail("invalid location %d", location);
     if (q_labels && (n_per_query < 1 || n_per_query > 64)) return nfail("n_per_query must be in [1, 64]");
     std::lock_guard<std::mutex> guard(nx->mu);
-    if (q_labels && !nx->has_row_labels) return nfail("set the row labels first (vodhip_node_index_set_row_labels)");
+    if (node_labels_refusal(nx, q_labels)) return -1;
     if (nq == 0) return 0;
     const int G = nx->n, dev0 = nx->device[0];
     hipStream_t user = location == VODHIP_DEVICE ? (hipStream_t)stream_ : nx->merge_stream;
     const size_t n = (size_t)nq * (size_t)m, n_out = (size_t)nq * (size_t)nx->dim;
-    const size_t lab_bytes = q_labels ? (size_t)nq * (size_t)n_per_query * sizeof(int32_t) : 0;
+    const size_t lab_bytes = label_bytes(q_labels, nq, n_per_query);
     // 1. the batch in host memory
     std::vector<int64_t> hi;
     std::vector<float> hw;
@@ -854,47 +909,14 @@ int vodhip_node_index_sum_ids(vodhip_node_index_t* nx, const int64_t* ids, const
     }
     // 2. every shard sums its own rows (the devices run side by side: nothing is waited for until every shard is enqueued)
     std::vector<float> parts((size_t)G * n_out);
-    struct Tmp { int64_t* ids = nullptr; float* w = nullptr; int32_t* lab = nullptr; float* out = nullptr; };
-    std::vector<Tmp> tmp((size_t)G);
-    int rc = 0;
-    std::string err;
-    auto hip_step = [&](hipError_t e, const char* what) {
-        if (e != hipSuccess && !rc) {
-            (void)hipGetLastError();
-            err = std::string(what) + " failed: " + hipGetErrorString(e);
-            rc = -1;
-        }
-        return e == hipSuccess;
-    };
-    for (int g = 0; g < G && !rc; ++g) {
-        hipStream_t st = nx->stream[g];
-        Tmp& t = tmp[(size_t)g];
-        if (!hip_step(hipSetDevice(nx->device[g]), "hipSetDevice")) break;
-        if (!hip_step(hipMallocAsync((void**)&t.ids, n * sizeof(int64_t), st), "hipMallocAsync")) break;
-        if (!hip_step(hipMallocAsync((void**)&t.w, n * sizeof(float), st), "hipMallocAsync")) break;
-        if (!hip_step(hipMallocAsync((void**)&t.out, n_out * sizeof(float), st), "hipMallocAsync")) break;
-        if (lab_host && !hip_step(hipMallocAsync((void**)&t.lab, lab_bytes, st), "hipMallocAsync")) break;
-        if (!hip_step(hipMemcpyAsync(t.ids, ids_host, n * sizeof(int64_t), hipMemcpyHostToDevice, st), "hipMemcpyAsync")) break;
-        if (!hip_step(hipMemcpyAsync(t.w, w_host, n * sizeof(float), hipMemcpyHostToDevice, st), "hipMemcpyAsync")) break;
-        if (lab_host && !hip_step(hipMemcpyAsync(t.lab, lab_host, lab_bytes, hipMemcpyHostToDevice, st), "hipMemcpyAsync")) break;
-        if (vodhip_index_sum_ids(nx->shard[g], t.ids, t.w, nq, m, g * nx->rows_per_shard, t.lab, n_per_query, t.out, st)) {
-            err = std::string("shard ") + std::to_string(g) + ": " + vodhip_last_error();
-            rc = -1;
-            break;
-        }
-        hip_step(hipMemcpyAsync(parts.data() + (size_t)g * n_out, t.out, n_out * sizeof(float), hipMemcpyDeviceToHost, st), "hipMemcpyAsync");
-    }
-    for (int g = 0; g < G; ++g) {  // (also after a failure: what was enqueued reads the host vectors of this frame)
-        Tmp& t = tmp[(size_t)g];
-        if (hipSetDevice(nx->device[g]) != hipSuccess) continue;
-        if (t.ids) (void)hipFreeAsync(t.ids, nx->stream[g]);
-        if (t.w) (void)hipFreeAsync(t.w, nx->stream[g]);
-        if (t.lab) (void)hipFreeAsync(t.lab, nx->stream[g]);
-        if (t.out) (void)hipFreeAsync(t.out, nx->stream[g]);
-        hip_step(hipStreamSynchronize(nx->stream[g]), "hipStreamSynchronize");
-    }
-    (void)hipSetDevice(dev0);
-    if (rc) return nfail("%s", err.c_str());
+    ShardFanout f(nx);
+    const int ii = f.input(ids_host, n * sizeof(int64_t)), iw = f.input(w_host, n * sizeof(float)), il = f.input(lab_host, lab_bytes);
+    const int io = f.output(parts.data(), n_out * sizeof(float));
+    if (f.run([&](int g, void* const* p, hipStream_t st) {
+            return vodhip_index_sum_ids(nx->shard[g], (const int64_t*)p[ii], (const float*)p[iw], nq, m, g * nx->rows_per_shard, (const int32_t*)p[il],
+                                        n_per_query, (float*)p[io], st);
+        }))
+        return -1;
     // 3. on devices[0]: the shards' sums added in increasing shard order
     float *d_parts = nullptr, *d_out = nullptr;
     auto steps = [&]() -> int {
@@ -909,7 +931,7 @@ int vodhip_node_index_sum_ids(vodhip_node_index_t* nx, const int64_t* ids, const
         if (location == VODHIP_HOST) NODE_HIP_OK(hipMemcpyAsync(out, sum, n_out * sizeof(float), hipMemcpyDeviceToHost, user));
         return 0;
     };
-    rc = steps();
+    const int rc = steps();
     const std::string keep = rc ? vodhip_last_error() : "";
     for (void* p : {(void*)d_parts, (void*)d_out})
         if (p) (void)hipFreeAsync(p, user);
@@ -919,64 +941,27 @@ int vodhip_node_index_sum_ids(vodhip_node_index_t* nx, const int64_t* ids, const
     return 0;
 }
 
-// The log-partition scan behind the one handle (include/vodhip.h, H2p): host queries and labels are replicated to every shard, every
-// shard runs the flat call on its own device and stream, the 2 * nq floats per shard return through host memory and are folded there in
-// increasing shard order (partition_fold.h).  No peer copies, no streams beyond the shards' own.
+// The log-partition scan behind the one handle (include/vodhip.h, H2p): one ShardFanout of the flat call, the 2 * nq floats per shard
+// folded on the host in increasing shard order (partition_fold.h).  No peer copies, no streams beyond the shards' own.
 int vodhip_node_index_log_partition(vodhip_node_index_t* nx, const void* queries, int q_dtype, int64_t nq, float beta, const int32_t* q_labels,
                                     int n_per_query, float* out_max, float* out_log_rel) {
     if (!nx) return nfail("index is NULL");
-    if (const char* msg = vodhip::log_partition_args_error(queries, q_dtype, nq, beta, q_labels, n_per_query, out_max, out_log_rel)) {
-        if (!strcmp(msg, "invalid q_dtype")) return nfail("invalid q_dtype %d", q_dtype);
-        if (!strncmp(msg, "beta", 4)) return nfail("beta=%g: %s", (double)beta, msg);
-        return nfail("%s", msg);
-    }
-    if (nx->dtype & VODHIP_L2) return nfail("log_partition is not supported on an L2 index (VODHIP_L2): its scores are distances, not similarities");
-    if (nx->dtype & VODHIP_EXACT_F32) return nfail("log_partition is not supported on a VODHIP_EXACT_F32 store: the scan scores the rounded rows, that store's contract is the float32 rows");
+    if (const char* msg = vodhip::log_partition_args_error(queries, q_dtype, nq, beta, q_labels, n_per_query, out_max, out_log_rel))
+        return node_partition_args_fail(msg, q_dtype, beta);
+    if (node_scan_refusal(nx, "log_partition")) return -1;
     std::lock_guard<std::mutex> guard(nx->mu);
-    if (q_labels && !nx->has_row_labels) return nfail("set the row labels first (vodhip_node_index_set_row_labels)");
+    if (node_labels_refusal(nx, q_labels)) return -1;
     if (nq == 0) return 0;
     const int G = nx->n;
-    const size_t q_bytes = (size_t)nq * (size_t)nx->dim * elem_bytes(q_dtype);
-    const size_t lab_bytes = q_labels ? (size_t)nq * (size_t)n_per_query * sizeof(int32_t) : 0;
     std::vector<float> parts((size_t)G * 2 * (size_t)nq);  // shard g: [max | log_rel] at g * 2 nq
-    struct Tmp { void* q = nullptr; int32_t* lab = nullptr; float* out = nullptr; };
-    std::vector<Tmp> tmp((size_t)G);
-    int rc = 0;
-    std::string err;
-    auto hip_step = [&](hipError_t e, const char* what) {
-        if (e != hipSuccess && !rc) {
-            (void)hipGetLastError();
-            err = std::string(what) + " failed: " + hipGetErrorString(e);
-            rc = -1;
-        }
-        return e == hipSuccess;
-    };
-    for (int g = 0; g < G && !rc; ++g) {  // (the devices run side by side: nothing is waited for until every shard is enqueued)
-        hipStream_t st = nx->stream[g];
-        Tmp& t = tmp[(size_t)g];
-        if (!hip_step(hipSetDevice(nx->device[g]), "hipSetDevice")) break;
-        if (!hip_step(hipMallocAsync(&t.q, q_bytes, st), "hipMallocAsync")) break;
-        if (!hip_step(hipMallocAsync((void**)&t.out, 2 * (size_t)nq * sizeof(float), st), "hipMallocAsync")) break;
-        if (q_labels && !hip_step(hipMallocAsync((void**)&t.lab, lab_bytes, st), "hipMallocAsync")) break;
-        if (!hip_step(hipMemcpyAsync(t.q, queries, q_bytes, hipMemcpyHostToDevice, st), "hipMemcpyAsync")) break;
-        if (q_labels && !hip_step(hipMemcpyAsync(t.lab, q_labels, lab_bytes, hipMemcpyHostToDevice, st), "hipMemcpyAsync")) break;
-        if (vodhip_index_log_partition(nx->shard[g], t.q, q_dtype, nq, beta, t.lab, n_per_query, t.out, t.out + nq, st)) {
-            err = std::string("shard ") + std::to_string(g) + ": " + vodhip_last_error();
-            rc = -1;
-            break;
-        }
-        hip_step(hipMemcpyAsync(parts.data() + (size_t)g * 2 * (size_t)nq, t.out, 2 * (size_t)nq * sizeof(float), hipMemcpyDeviceToHost, st), "hipMemcpyAsync");
-    }
-    for (int g = 0; g < G; ++g) {  // (also after a failure: what was enqueued reads the caller's host buffers)
-        Tmp& t = tmp[(size_t)g];
-        if (hipSetDevice(nx->device[g]) != hipSuccess) continue;
-        if (t.q) (void)hipFreeAsync(t.q, nx->stream[g]);
-        if (t.lab) (void)hipFreeAsync(t.lab, nx->stream[g]);
-        if (t.out) (void)hipFreeAsync(t.out, nx->stream[g]);
-        hip_step(hipStreamSynchronize(nx->stream[g]), "hipStreamSynchronize");
-    }
-    (void)hipSetDevice(nx->device[0]);
-    if (rc) return nfail("%s", err.c_str());
+    ShardFanout f(nx);
+    const int iq = f.input(queries, query_bytes(nx, nq, q_dtype)), il = f.input(q_labels, label_bytes(q_labels, nq, n_per_query));
+    const int io = f.output(parts.data(), 2 * (size_t)nq * sizeof(float));
+    if (f.run([&](int g, void* const* p, hipStream_t st) {
+            float* out = (float*)p[io];
+            return vodhip_index_log_partition(nx->shard[g], p[iq], q_dtype, nq, beta, (const int32_t*)p[il], n_per_query, out, out + nq, st);
+        }))
+        return -1;
     vodhip::fold_log_partition(parts.data(), parts.data() + nq, G, 2 * nq, nq, beta, out_max, out_log_rel);
     return 0;
 }
@@ -986,59 +971,23 @@ int vodhip_node_index_log_partition(vodhip_node_index_t* nx, const void* queries
 int vodhip_node_index_posterior_stats(vodhip_node_index_t* nx, const void* queries, int q_dtype, int64_t nq, float beta, const int32_t* q_labels,
                                       int n_per_query, float* out_max, float* out_log_rel, float* out_mean_rel, float* out_var) {
     if (!nx) return nfail("index is NULL");
-    if (const char* msg = vodhip::posterior_stats_args_error(queries, q_dtype, nq, beta, q_labels, n_per_query, out_max, out_log_rel, out_mean_rel, out_var)) {
-        if (!strcmp(msg, "invalid q_dtype")) return nfail("invalid q_dtype %d", q_dtype);
-        if (!strncmp(msg, "beta", 4)) return nfail("beta=%g: %s", (double)beta, msg);
-        return nfail("%s", msg);
-    }
-    if (nx->dtype & VODHIP_L2) return nfail("posterior_stats is not supported on an L2 index (VODHIP_L2): its scores are distances, not similarities");
-    if (nx->dtype & VODHIP_EXACT_F32) return nfail("posterior_stats is not supported on a VODHIP_EXACT_F32 store: the scan scores the rounded rows, that store's contract is the float32 rows");
+    if (const char* msg = vodhip::posterior_stats_args_error(queries, q_dtype, nq, beta, q_labels, n_per_query, out_max, out_log_rel, out_mean_rel, out_var))
+        return node_partition_args_fail(msg, q_dtype, beta);
+    if (node_scan_refusal(nx, "posterior_stats")) return -1;
     std::lock_guard<std::mutex> guard(nx->mu);
-    if (q_labels && !nx->has_row_labels) return nfail("set the row labels first (vodhip_node_index_set_row_labels)");
+    if (node_labels_refusal(nx, q_labels)) return -1;
     if (nq == 0) return 0;
     const int G = nx->n;
     const size_t n = (size_t)nq;
-    const size_t q_bytes = n * (size_t)nx->dim * elem_bytes(q_dtype);
-    const size_t lab_bytes = q_labels ? n * (size_t)n_per_query * sizeof(int32_t) : 0;
     std::vector<float> parts((size_t)G * 4 * n);  // shard g: [max | log_rel | mean_rel | var] at g * 4 nq
-    struct Tmp { void* q = nullptr; int32_t* lab = nullptr; float* out = nullptr; };
-    std::vector<Tmp> tmp((size_t)G);
-    int rc = 0;
-    std::string err;
-    auto hip_step = [&](hipError_t e, const char* what) {
-        if (e != hipSuccess && !rc) {
-            (void)hipGetLastError();
-            err = std::string(what) + " failed: " + hipGetErrorString(e);
-            rc = -1;
-        }
-        return e == hipSuccess;
-    };
-    for (int g = 0; g < G && !rc; ++g) {  // (the devices run side by side: nothing is waited for until every shard is enqueued)
-        hipStream_t st = nx->stream[g];
-        Tmp& t = tmp[(size_t)g];
-        if (!hip_step(hipSetDevice(nx->device[g]), "hipSetDevice")) break;
-        if (!hip_step(hipMallocAsync(&t.q, q_bytes, st), "hipMallocAsync")) break;
-        if (!hip_step(hipMallocAsync((void**)&t.out, 4 * n * sizeof(float), st), "hipMallocAsync")) break;
-        if (q_labels && !hip_step(hipMallocAsync((void**)&t.lab, lab_bytes, st), "hipMallocAsync")) break;
-        if (!hip_step(hipMemcpyAsync(t.q, queries, q_bytes, hipMemcpyHostToDevice, st), "hipMemcpyAsync")) break;
-        if (q_labels && !hip_step(hipMemcpyAsync(t.lab, q_labels, lab_bytes, hipMemcpyHostToDevice, st), "hipMemcpyAsync")) break;
-        if (vodhip_index_posterior_stats(nx->shard[g], t.q, q_dtype, nq, beta, t.lab, n_per_query, t.out, t.out + n, t.out + 2 * n, t.out + 3 * n, st)) {
-            err = std::string("shard ") + std::to_string(g) + ": " + vodhip_last_error();
-            rc = -1;
-            break;
-        }
-        hip_step(hipMemcpyAsync(parts.data() + (size_t)g * 4 * n, t.out, 4 * n * sizeof(float), hipMemcpyDeviceToHost, st), "hipMemcpyAsync");
-    }
-    for (int g = 0; g < G; ++g) {  // (also after a failure: what was enqueued reads the caller's host buffers)
-        Tmp& t = tmp[(size_t)g];
-        if (hipSetDevice(nx->device[g]) != hipSuccess) continue;
-        if (t.q) (void)hipFreeAsync(t.q, nx->stream[g]);
-        if (t.lab) (void)hipFreeAsync(t.lab, nx->stream[g]);
-        if (t.out) (void)hipFreeAsync(t.out, nx->stream[g]);
-        hip_step(hipStreamSynchronize(nx->stream[g]), "hipStreamSynchronize");
-    }
-    (void)hipSetDevice(nx->device[0]);
-    if (rc) return nfail("%s", err.c_str());
+    ShardFanout f(nx);
+    const int iq = f.input(queries, query_bytes(nx, nq, q_dtype)), il = f.input(q_labels, label_bytes(q_labels, nq, n_per_query));
+    const int io = f.output(parts.data(), 4 * n * sizeof(float));
+    if (f.run([&](int g, void* const* p, hipStream_t st) {
+            float* out = (float*)p[io];
+            return vodhip_index_posterior_stats(nx->shard[g], p[iq], q_dtype, nq, beta, (const int32_t*)p[il], n_per_query, out, out + n, out + 2 * n, out + 3 * n, st);
+        }))
+        return -1;
     vodhip::fold_posterior_stats(parts.data(), parts.data() + n, parts.data() + 2 * n, parts.data() + 3 * n, G, 4 * nq, nq, beta, out_max, out_log_rel,
                                  out_mean_rel, out_var);
     return 0;
@@ -1058,133 +1007,47 @@ int vodhip_node_index_posterior_divergence(vodhip_node_index_t* nx, const void* 
         if (!strncmp(msg, "beta_b", 6)) return nfail("beta_b=%g: %s", (double)beta_b, msg);
         return nfail("%s", msg);
     }
-    if (nx->dtype & VODHIP_L2) return nfail("posterior_divergence is not supported on an L2 index (VODHIP_L2): its scores are distances, not similarities");
-    if (nx->dtype & VODHIP_EXACT_F32) return nfail("posterior_divergence is not supported on a VODHIP_EXACT_F32 store: the scan scores the rounded rows, that store's contract is the float32 rows");
+    if (node_scan_refusal(nx, "posterior_divergence")) return -1;
     std::lock_guard<std::mutex> guard(nx->mu);
-    if (q_labels && !nx->has_row_labels) return nfail("set the row labels first (vodhip_node_index_set_row_labels)");
+    if (node_labels_refusal(nx, q_labels)) return -1;
     if (nq == 0) return 0;
     const int G = nx->n;
     const size_t n = (size_t)nq;
-    const size_t q_bytes = n * (size_t)nx->dim * elem_bytes(q_dtype);
-    const size_t lab_bytes = q_labels ? n * (size_t)n_per_query * sizeof(int32_t) : 0;
     std::vector<float> parts((size_t)G * 8 * n);  // shard g: the eight words, [nq] each, at g * 8 nq
-    struct Tmp { void* qa = nullptr; void* qb = nullptr; int32_t* lab = nullptr; float* out = nullptr; };
-    std::vector<Tmp> tmp((size_t)G);
-    int rc = 0;
-    std::string err;
-    auto hip_step = [&](hipError_t e, const char* what) {
-        if (e != hipSuccess && !rc) {
-            (void)hipGetLastError();
-            err = std::string(what) + " failed: " + hipGetErrorString(e);
-            rc = -1;
-        }
-        return e == hipSuccess;
-    };
-    for (int g = 0; g < G && !rc; ++g) {  // (the devices run side by side: nothing is waited for until every shard is enqueued)
-        hipStream_t st = nx->stream[g];
-        Tmp& t = tmp[(size_t)g];
-        if (!hip_step(hipSetDevice(nx->device[g]), "hipSetDevice")) break;
-        if (!hip_step(hipMallocAsync(&t.qa, q_bytes, st), "hipMallocAsync")) break;
-        if (!hip_step(hipMallocAsync(&t.qb, q_bytes, st), "hipMallocAsync")) break;
-        if (!hip_step(hipMallocAsync((void**)&t.out, 8 * n * sizeof(float), st), "hipMallocAsync")) break;
-        if (q_labels && !hip_step(hipMallocAsync((void**)&t.lab, lab_bytes, st), "hipMallocAsync")) break;
-        if (!hip_step(hipMemcpyAsync(t.qa, queries_a, q_bytes, hipMemcpyHostToDevice, st), "hipMemcpyAsync")) break;
-        if (!hip_step(hipMemcpyAsync(t.qb, queries_b, q_bytes, hipMemcpyHostToDevice, st), "hipMemcpyAsync")) break;
-        if (q_labels && !hip_step(hipMemcpyAsync(t.lab, q_labels, lab_bytes, hipMemcpyHostToDevice, st), "hipMemcpyAsync")) break;
-        if (vodhip_index_posterior_divergence(nx->shard[g], t.qa, t.qb, q_dtype, nq, beta_a, beta_b, t.lab, n_per_query, t.out, t.out + n, t.out + 2 * n,
-                                              t.out + 3 * n, t.out + 4 * n, t.out + 5 * n, t.out + 6 * n, t.out + 7 * n, st)) {
-            err = std::string("shard ") + std::to_string(g) + ": " + vodhip_last_error();
-            rc = -1;
-            break;
-        }
-        hip_step(hipMemcpyAsync(parts.data() + (size_t)g * 8 * n, t.out, 8 * n * sizeof(float), hipMemcpyDeviceToHost, st), "hipMemcpyAsync");
-    }
-    for (int g = 0; g < G; ++g) {  // (also after a failure: what was enqueued reads the caller's host buffers)
-        Tmp& t = tmp[(size_t)g];
-        if (hipSetDevice(nx->device[g]) != hipSuccess) continue;
-        if (t.qa) (void)hipFreeAsync(t.qa, nx->stream[g]);
-        if (t.qb) (void)hipFreeAsync(t.qb, nx->stream[g]);
-        if (t.lab) (void)hipFreeAsync(t.lab, nx->stream[g]);
-        if (t.out) (void)hipFreeAsync(t.out, nx->stream[g]);
-        hip_step(hipStreamSynchronize(nx->stream[g]), "hipStreamSynchronize");
-    }
-    (void)hipSetDevice(nx->device[0]);
-    if (rc) return nfail("%s", err.c_str());
+    ShardFanout f(nx);
+    const int ia = f.input(queries_a, query_bytes(nx, nq, q_dtype)), ib = f.input(queries_b, query_bytes(nx, nq, q_dtype));
+    const int il = f.input(q_labels, label_bytes(q_labels, nq, n_per_query));
+    const int io = f.output(parts.data(), 8 * n * sizeof(float));
+    if (f.run([&](int g, void* const* p, hipStream_t st) {
+            float* out = (float*)p[io];
+            return vodhip_index_posterior_divergence(nx->shard[g], p[ia], p[ib], q_dtype, nq, beta_a, beta_b, (const int32_t*)p[il], n_per_query, out, out + n,
+                                                     out + 2 * n, out + 3 * n, out + 4 * n, out + 5 * n, out + 6 * n, out + 7 * n, st);
+        }))
+        return -1;
     vodhip::fold_posterior_divergence(parts.data(), G, nq, beta_a, beta_b, outs);
     return 0;
 }
 
-// The rank calls behind the one handle (include/vodhip.h, H2r).  One PASS = the same flat call on every shard, on its own device and
-// stream, with id_base = the shard's first global row: host inputs are replicated, the per-shard outputs return through host memory.
+// The rank calls behind the one handle (include/vodhip.h, H2r).  One PASS = one ShardFanout of the same flat call, with id_base = the
+// shard's first global row.
 //   thresholds == NULL  vodhip_index_scan_score_ids of `ids`     -> score_g / row_g  [G][n]
 //   else                vodhip_index_count_above (`ids` = the tie ids, may be NULL)  -> count_g [G][n]
 // The caller holds nx->mu.
 static int node_rank_pass(vodhip_node_index_t* nx, const void* queries, int q_dtype, int64_t nq, int64_t m, const int64_t* ids, const float* thresholds,
                           const int32_t* q_labels, int n_per_query, float* score_g, int32_t* row_g, int64_t* count_g) {
-    const int G = nx->n;
     const size_t n = (size_t)nq * (size_t)m;
-    const size_t q_bytes = (size_t)nq * (size_t)nx->dim * elem_bytes(q_dtype);
-    const size_t lab_bytes = q_labels ? (size_t)nq * (size_t)n_per_query * sizeof(int32_t) : 0;
-    struct Tmp { void* q = nullptr; int64_t* ids = nullptr; float* thr = nullptr; int32_t* lab = nullptr; float* score = nullptr; int32_t* row = nullptr; int64_t* cnt = nullptr; };
-    std::vector<Tmp> tmp((size_t)G);
-    int rc = 0;
-    std::string err;
-    auto hip_step = [&](hipError_t e, const char* what) {
-        if (e != hipSuccess && !rc) {
-            (void)hipGetLastError();
-            err = std::string(what) + " failed: " + hipGetErrorString(e);
-            rc = -1;
-        }
-        return e == hipSuccess;
-    };
-    for (int g = 0; g < G && !rc; ++g) {  // (the devices run side by side: nothing is waited for until every shard is enqueued)
-        hipStream_t st = nx->stream[g];
-        Tmp& t = tmp[(size_t)g];
-        if (!hip_step(hipSetDevice(nx->device[g]), "hipSetDevice")) break;
-        if (!hip_step(hipMallocAsync(&t.q, q_bytes, st), "hipMallocAsync")) break;
-        if (!hip_step(hipMemcpyAsync(t.q, queries, q_bytes, hipMemcpyHostToDevice, st), "hipMemcpyAsync")) break;
-        if (ids) {
-            if (!hip_step(hipMallocAsync((void**)&t.ids, n * sizeof(int64_t), st), "hipMallocAsync")) break;
-            if (!hip_step(hipMemcpyAsync(t.ids, ids, n * sizeof(int64_t), hipMemcpyHostToDevice, st), "hipMemcpyAsync")) break;
-        }
-        if (q_labels) {
-            if (!hip_step(hipMallocAsync((void**)&t.lab, lab_bytes, st), "hipMallocAsync")) break;
-            if (!hip_step(hipMemcpyAsync(t.lab, q_labels, lab_bytes, hipMemcpyHostToDevice, st), "hipMemcpyAsync")) break;
-        }
+    ShardFanout f(nx);
+    const int iq = f.input(queries, query_bytes(nx, nq, q_dtype)), ii = f.input(ids, n * sizeof(int64_t));
+    const int il = f.input(q_labels, label_bytes(q_labels, nq, n_per_query)), it = f.input(thresholds, n * sizeof(float));
+    const int is = f.output(score_g, n * sizeof(float)), ir = f.output(row_g, n * sizeof(int32_t)), ic = f.output(count_g, n * sizeof(int64_t));
+    return f.run([&](int g, void* const* p, hipStream_t st) {
         const int64_t base = (int64_t)g * nx->rows_per_shard;
-        int call;
-        if (!thresholds) {
-            if (!hip_step(hipMallocAsync((void**)&t.score, n * sizeof(float), st), "hipMallocAsync")) break;
-            if (!hip_step(hipMallocAsync((void**)&t.row, n * sizeof(int32_t), st), "hipMallocAsync")) break;
-            call = vodhip_index_scan_score_ids(nx->shard[g], t.q, q_dtype, nq, t.ids, m, base, t.lab, n_per_query, t.score, t.row, st);
-        } else {
-            if (!hip_step(hipMallocAsync((void**)&t.thr, n * sizeof(float), st), "hipMallocAsync")) break;
-            if (!hip_step(hipMemcpyAsync(t.thr, thresholds, n * sizeof(float), hipMemcpyHostToDevice, st), "hipMemcpyAsync")) break;
-            if (!hip_step(hipMallocAsync((void**)&t.cnt, n * sizeof(int64_t), st), "hipMallocAsync")) break;
-            call = vodhip_index_count_above(nx->shard[g], t.q, q_dtype, nq, t.thr, t.ids, m, base, t.lab, n_per_query, t.cnt, st);
-        }
-        if (call) {
-            err = std::string("shard ") + std::to_string(g) + ": " + vodhip_last_error();
-            rc = -1;
-            break;
-        }
-        if (!thresholds) {
-            hip_step(hipMemcpyAsync(score_g + (size_t)g * n, t.score, n * sizeof(float), hipMemcpyDeviceToHost, st), "hipMemcpyAsync");
-            hip_step(hipMemcpyAsync(row_g + (size_t)g * n, t.row, n * sizeof(int32_t), hipMemcpyDeviceToHost, st), "hipMemcpyAsync");
-        } else {
-            hip_step(hipMemcpyAsync(count_g + (size_t)g * n, t.cnt, n * sizeof(int64_t), hipMemcpyDeviceToHost, st), "hipMemcpyAsync");
-        }
-    }
-    for (int g = 0; g < G; ++g) {  // (also after a failure: what was enqueued reads the caller's host buffers)
-        Tmp& t = tmp[(size_t)g];
-        if (hipSetDevice(nx->device[g]) != hipSuccess) continue;
-        for (void* p : {t.q, (void*)t.ids, (void*)t.thr, (void*)t.lab, (void*)t.score, (void*)t.row, (void*)t.cnt})
-            if (p) (void)hipFreeAsync(p, nx->stream[g]);
-        hip_step(hipStreamSynchronize(nx->stream[g]), "hipStreamSynchronize");
-    }
-    (void)hipSetDevice(nx->device[0]);
-    if (rc) return nfail("%s", err.c_str());
-    return 0;
+        if (!thresholds)
+            return vodhip_index_scan_score_ids(nx->shard[g], p[iq], q_dtype, nq, (const int64_t*)p[ii], m, base, (const int32_t*)p[il], n_per_query,
+                                               (float*)p[is], (int32_t*)p[ir], st);
+        return vodhip_index_count_above(nx->shard[g], p[iq], q_dtype, nq, (const float*)p[it], (const int64_t*)p[ii], m, base, (const int32_t*)p[il],
+                                        n_per_query, (int64_t*)p[ic], st);
+    });
 }
 
 static int node_rank_check(vodhip_node_index_t* nx, const char* what, const void* queries, int q_dtype, int64_t nq, int64_t m, const void* q_labels,
@@ -1195,9 +1058,7 @@ static int node_rank_check(vodhip_node_index_t* nx, const char* what, const void
         if (msg[0] == 'm') return nfail("m=%lld: %s", (long long)m, msg + 2);
         return nfail("%s", msg);
     }
-    if (nx->dtype & VODHIP_L2) return nfail("%s is not supported on an L2 index (VODHIP_L2): its scores are distances, not similarities", what);
-    if (nx->dtype & VODHIP_EXACT_F32) return nfail("%s is not supported on a VODHIP_EXACT_F32 store: the scan scores the rounded rows, that store's contract is the float32 rows", what);
-    return 0;
+    return node_scan_refusal(nx, what);
 }
 
 int vodhip_node_index_count_above(vodhip_node_index_t* nx, const void* queries, int q_dtype, int64_t nq, const float* thresholds, const int64_t* tie_ids,
@@ -1206,7 +1067,7 @@ int vodhip_node_index_count_above(vodhip_node_index_t* nx, const void* queries, 
     if (nq > 0 && !thresholds) return nfail("thresholds is NULL");
     if (nq > 0 && !out_counts) return nfail("out_counts is NULL");
     std::lock_guard<std::mutex> guard(nx->mu);
-    if (q_labels && !nx->has_row_labels) return nfail("set the row labels first (vodhip_node_index_set_row_labels)");
+    if (node_labels_refusal(nx, q_labels)) return -1;
     if (nq == 0) return 0;
     const size_t n = (size_t)nq * (size_t)m;
     std::vector<int64_t> count_g((size_t)nx->n * n);
@@ -1222,7 +1083,7 @@ int vodhip_node_index_rank_ids(vodhip_node_index_t* nx, const void* queries, int
     if (nq > 0 && !out_ranks) return nfail("out_ranks is NULL");
     if (nq > 0 && !out_scores) return nfail("out_scores is NULL");
     std::lock_guard<std::mutex> guard(nx->mu);
-    if (q_labels && !nx->has_row_labels) return nfail("set the row labels first (vodhip_node_index_set_row_labels)");
+    if (node_labels_refusal(nx, q_labels)) return -1;
     if (nq == 0) return 0;
     const int G = nx->n;
     const size_t n = (size_t)nq * (size_t)m;
@@ -1242,61 +1103,25 @@ int vodhip_node_index_rank_ids(vodhip_node_index_t* nx, const void* queries, int
 int vodhip_node_index_posterior_mean(vodhip_node_index_t* nx, const void* queries, int q_dtype, int64_t nq, float beta, const int32_t* q_labels,
                                      int n_per_query, float* out_max, float* out_log_rel, float* out_mean) {
     if (!nx) return nfail("index is NULL");
-    if (const char* msg = vodhip::log_partition_args_error(queries, q_dtype, nq, beta, q_labels, n_per_query, out_max, out_log_rel)) {
-        if (!strcmp(msg, "invalid q_dtype")) return nfail("invalid q_dtype %d", q_dtype);
-        if (!strncmp(msg, "beta", 4)) return nfail("beta=%g: %s", (double)beta, msg);
-        return nfail("%s", msg);
-    }
+    if (const char* msg = vodhip::log_partition_args_error(queries, q_dtype, nq, beta, q_labels, n_per_query, out_max, out_log_rel))
+        return node_partition_args_fail(msg, q_dtype, beta);
     if (nq > 0 && !out_mean) return nfail("invalid query / output pointers");
-    if (nx->dtype & VODHIP_L2) return nfail("log_partition is not supported on an L2 index (VODHIP_L2): its scores are distances, not similarities");
-    if (nx->dtype & VODHIP_EXACT_F32) return nfail("log_partition is not supported on a VODHIP_EXACT_F32 store: the scan scores the rounded rows, that store's contract is the float32 rows");
+    if (node_scan_refusal(nx, "log_partition")) return -1;  // (the name these two refusals have always carried here, as in the flat call)
     std::lock_guard<std::mutex> guard(nx->mu);
-    if (q_labels && !nx->has_row_labels) return nfail("set the row labels first (vodhip_node_index_set_row_labels)");
+    if (node_labels_refusal(nx, q_labels)) return -1;
     if (nq == 0) return 0;
     const int G = nx->n;
     const size_t dim = (size_t)nx->dim;
-    const size_t q_bytes = (size_t)nq * dim * elem_bytes(q_dtype);
-    const size_t lab_bytes = q_labels ? (size_t)nq * (size_t)n_per_query * sizeof(int32_t) : 0;
     const size_t per_shard = (size_t)nq * (2 + dim);  // shard g: [max | log_rel | mean rows] at g * per_shard
     std::vector<float> parts((size_t)G * per_shard);
-    struct Tmp { void* q = nullptr; int32_t* lab = nullptr; float* out = nullptr; };
-    std::vector<Tmp> tmp((size_t)G);
-    int rc = 0;
-    std::string err;
-    auto hip_step = [&](hipError_t e, const char* what) {
-        if (e != hipSuccess && !rc) {
-            (void)hipGetLastError();
-            err = std::string(what) + " failed: " + hipGetErrorString(e);
-            rc = -1;
-        }
-        return e == hipSuccess;
-    };
-    for (int g = 0; g < G && !rc; ++g) {  // (the devices run side by side: nothing is waited for until every shard is enqueued)
-        hipStream_t st = nx->stream[g];
-        Tmp& t = tmp[(size_t)g];
-        if (!hip_step(hipSetDevice(nx->device[g]), "hipSetDevice")) break;
-        if (!hip_step(hipMallocAsync(&t.q, q_bytes, st), "hipMallocAsync")) break;
-        if (!hip_step(hipMallocAsync((void**)&t.out, per_shard * sizeof(float), st), "hipMallocAsync")) break;
-        if (q_labels && !hip_step(hipMallocAsync((void**)&t.lab, lab_bytes, st), "hipMallocAsync")) break;
-        if (!hip_step(hipMemcpyAsync(t.q, queries, q_bytes, hipMemcpyHostToDevice, st), "hipMemcpyAsync")) break;
-        if (q_labels && !hip_step(hipMemcpyAsync(t.lab, q_labels, lab_bytes, hipMemcpyHostToDevice, st), "hipMemcpyAsync")) break;
-        if (vodhip_index_posterior_mean(nx->shard[g], t.q, q_dtype, nq, beta, t.lab, n_per_query, t.out, t.out + nq, t.out + 2 * nq, st)) {
-            err = std::string("shard ") + std::to_string(g) + ": " + vodhip_last_error();
-            rc = -1;
-            break;
-        }
-        hip_step(hipMemcpyAsync(parts.data() + (size_t)g * per_shard, t.out, per_shard * sizeof(float), hipMemcpyDeviceToHost, st), "hipMemcpyAsync");
-    }
-    for (int g = 0; g < G; ++g) {  // (also after a failure: what was enqueued reads the caller's host buffers)
-        Tmp& t = tmp[(size_t)g];
-        if (hipSetDevice(nx->device[g]) != hipSuccess) continue;
-        if (t.q) (void)hipFreeAsync(t.q, nx->stream[g]);
-        if (t.lab) (void)hipFreeAsync(t.lab, nx->stream[g]);
-        if (t.out) (void)hipFreeAsync(t.out, nx->stream[g]);
-        hip_step(hipStreamSynchronize(nx->stream[g]), "hipStreamSynchronize");
-    }
-    (void)hipSetDevice(nx->device[0]);
-    if (rc) return nfail("%s", err.c_str());
+    ShardFanout f(nx);
+    const int iq = f.input(queries, query_bytes(nx, nq, q_dtype)), il = f.input(q_labels, label_bytes(q_labels, nq, n_per_query));
+    const int io = f.output(parts.data(), per_shard * sizeof(float));
+    if (f.run([&](int g, void* const* p, hipStream_t st) {
+            float* out = (float*)p[io];
+            return vodhip_index_posterior_mean(nx->shard[g], p[iq], q_dtype, nq, beta, (const int32_t*)p[il], n_per_query, out, out + nq, out + 2 * nq, st);
+        }))
+        return -1;
     vodhip::fold_log_partition(parts.data(), parts.data() + nq, G, (int64_t)per_shard, nq, beta, out_max, out_log_rel);
     vodhip::fold_posterior_mean(parts.data(), parts.data() + nq, parts.data() + 2 * nq, G, (int64_t)per_shard, (int64_t)per_shard, nq, (int64_t)dim, beta,
                                 out_max, out_log_rel, out_mean);
@@ -1309,71 +1134,32 @@ int vodhip_node_index_sample_posterior(vodhip_node_index_t* nx, const void* quer
                                        int64_t query_offset, const int32_t* q_labels, int n_per_query, float* out_max, float* out_log_rel,
                                        int64_t* out_ids, float* out_scores, float* out_log_p, float* out_log_weight, float* out_keys) {
     if (!nx) return nfail("index is NULL");
-    if (const char* msg = vodhip::log_partition_args_error(queries, q_dtype, nq, beta, q_labels, n_per_query, out_max, out_log_rel)) {
-        if (!strcmp(msg, "invalid q_dtype")) return nfail("invalid q_dtype %d", q_dtype);
-        if (!strncmp(msg, "beta", 4)) return nfail("beta=%g: %s", (double)beta, msg);
-        return nfail("%s", msg);
-    }
+    if (const char* msg = vodhip::log_partition_args_error(queries, q_dtype, nq, beta, q_labels, n_per_query, out_max, out_log_rel))
+        return node_partition_args_fail(msg, q_dtype, beta);
     if (const char* msg = vodhip::sample_posterior_args_error(nq, k, query_offset, 0, out_ids, out_scores, out_log_p, out_log_weight, out_keys)) {
         if (msg[0] == 'k') return nfail("k=%d: %s", k, msg);
         return nfail("%s", msg);
     }
-    if (nx->dtype & VODHIP_L2) return nfail("sample_posterior is not supported on an L2 index (VODHIP_L2): its scores are distances, not similarities");
-    if (nx->dtype & VODHIP_EXACT_F32) return nfail("sample_posterior is not supported on a VODHIP_EXACT_F32 store: the scan scores the rounded rows, that store's contract is the float32 rows");
+    if (node_scan_refusal(nx, "sample_posterior")) return -1;
     std::lock_guard<std::mutex> guard(nx->mu);
-    if (q_labels && !nx->has_row_labels) return nfail("set the row labels first (vodhip_node_index_set_row_labels)");
+    if (node_labels_refusal(nx, q_labels)) return -1;
     if (nq == 0) return 0;
     const int G = nx->n;
-    const size_t q_bytes = (size_t)nq * (size_t)nx->dim * elem_bytes(q_dtype);
-    const size_t lab_bytes = q_labels ? (size_t)nq * (size_t)n_per_query * sizeof(int32_t) : 0;
     // shard g, floats: [max | log_rel | scores nq k | log_p | log_weight | keys nq (k + 1)] at g * per_f; ids at g * nq k
     const size_t rows = (size_t)nq * (size_t)k;
     const size_t per_f = 2 * (size_t)nq + 3 * rows + (size_t)nq * (size_t)(k + 1);
     std::vector<float> parts((size_t)G * per_f);
     std::vector<int64_t> ids((size_t)G * rows);
-    struct Tmp { void* q = nullptr; int32_t* lab = nullptr; float* out = nullptr; int64_t* ids = nullptr; };
-    std::vector<Tmp> tmp((size_t)G);
-    int rc = 0;
-    std::string err;
-    auto hip_step = [&](hipError_t e, const char* what) {
-        if (e != hipSuccess && !rc) {
-            (void)hipGetLastError();
-            err = std::string(what) + " failed: " + hipGetErrorString(e);
-            rc = -1;
-        }
-        return e == hipSuccess;
-    };
-    for (int g = 0; g < G && !rc; ++g) {  // (the flat call waits for its stream: the shards run one after the other)
-        hipStream_t st = nx->stream[g];
-        Tmp& t = tmp[(size_t)g];
-        if (!hip_step(hipSetDevice(nx->device[g]), "hipSetDevice")) break;
-        if (!hip_step(hipMallocAsync(&t.q, q_bytes, st), "hipMallocAsync")) break;
-        if (!hip_step(hipMallocAsync((void**)&t.out, per_f * sizeof(float), st), "hipMallocAsync")) break;
-        if (!hip_step(hipMallocAsync((void**)&t.ids, rows * sizeof(int64_t), st), "hipMallocAsync")) break;
-        if (q_labels && !hip_step(hipMallocAsync((void**)&t.lab, lab_bytes, st), "hipMallocAsync")) break;
-        if (!hip_step(hipMemcpyAsync(t.q, queries, q_bytes, hipMemcpyHostToDevice, st), "hipMemcpyAsync")) break;
-        if (q_labels && !hip_step(hipMemcpyAsync(t.lab, q_labels, lab_bytes, hipMemcpyHostToDevice, st), "hipMemcpyAsync")) break;
-        float* f = t.out;
-        if (vodhip_index_sample_posterior(nx->shard[g], t.q, q_dtype, nq, k, beta, seed, query_offset, g * nx->rows_per_shard, t.lab, n_per_query, f,
-                                          f + nq, t.ids, f + 2 * nq, f + 2 * nq + rows, f + 2 * nq + 2 * rows, f + 2 * nq + 3 * rows, st)) {
-            err = std::string("shard ") + std::to_string(g) + ": " + vodhip_last_error();
-            rc = -1;
-            break;
-        }
-        hip_step(hipMemcpyAsync(parts.data() + (size_t)g * per_f, t.out, per_f * sizeof(float), hipMemcpyDeviceToHost, st), "hipMemcpyAsync");
-        hip_step(hipMemcpyAsync(ids.data() + (size_t)g * rows, t.ids, rows * sizeof(int64_t), hipMemcpyDeviceToHost, st), "hipMemcpyAsync");
-    }
-    for (int g = 0; g < G; ++g) {  // (also after a failure: what was enqueued reads the caller's host buffers)
-        Tmp& t = tmp[(size_t)g];
-        if (hipSetDevice(nx->device[g]) != hipSuccess) continue;
-        if (t.q) (void)hipFreeAsync(t.q, nx->stream[g]);
-        if (t.lab) (void)hipFreeAsync(t.lab, nx->stream[g]);
-        if (t.out) (void)hipFreeAsync(t.out, nx->stream[g]);
-        if (t.ids) (void)hipFreeAsync(t.ids, nx->stream[g]);
-        hip_step(hipStreamSynchronize(nx->stream[g]), "hipStreamSynchronize");
-    }
-    (void)hipSetDevice(nx->device[0]);
-    if (rc) return nfail("%s", err.c_str());
+    ShardFanout f(nx);
+    const int iq = f.input(queries, query_bytes(nx, nq, q_dtype)), il = f.input(q_labels, label_bytes(q_labels, nq, n_per_query));
+    const int io = f.output(parts.data(), per_f * sizeof(float)), ii = f.output(ids.data(), rows * sizeof(int64_t));
+    if (f.run([&](int g, void* const* p, hipStream_t st) {  // (the flat call waits for its stream: the shards run one after the other)
+            float* o = (float*)p[io];
+            return vodhip_index_sample_posterior(nx->shard[g], p[iq], q_dtype, nq, k, beta, seed, query_offset, g * nx->rows_per_shard, (const int32_t*)p[il],
+                                                 n_per_query, o, o + nq, (int64_t*)p[ii], o + 2 * nq, o + 2 * nq + rows, o + 2 * nq + 2 * rows,
+                                                 o + 2 * nq + 3 * rows, st);
+        }))
+        return -1;
     vodhip::fold_log_partition(parts.data(), parts.data() + nq, G, (int64_t)per_f, nq, beta, out_max, out_log_rel);
     vodhip::fold_sample_posterior(parts.data() + 2 * nq + 3 * rows, ids.data(), parts.data() + 2 * nq, G, (int64_t)per_f, (int64_t)rows, (int64_t)per_f, nq, k, beta,
                                   out_max, out_log_rel, out_ids, out_scores, out_log_p, out_log_weight, out_keys);
