@@ -362,6 +362,37 @@ int vodhip_index_scan_score_ids(vodhip_index_t* index, const void* queries, int 
                                 int64_t id_base, const int32_t* q_labels_dev /* NULL = unrestricted */, int n_per_query,
                                 float* out_scores /* DEVICE [nq][m] */, int32_t* out_rows /* DEVICE [nq][m], or NULL */, void* stream);
 
+/* H2g. RANGE SEARCH over the whole store (kernels_range.hip): WHICH rows score above a per-query threshold - the rows H2r counts.
+ * Replaces: faiss's range_search (lims, D, I) of the flat index this library stands in for; the reference never calls it.
+ * Eligibility, order and the predicate are H2r's.  For thresholds[q] = t and tie_ids[q] = r (tie_ids_dev NULL: the strict test) the
+ * result of query q is
+ *     R(q) = { eligible rows z : s(q, z) > t  or  (s(q, z) == t and id_base + z < r) },
+ * exactly the set vodhip_index_count_above counts with m = 1.  A NaN threshold gives an empty list; r past every row makes the test
+ * inclusive.  The result is CSR: lims_dev int64 [nq + 1] (lims[0] = 0), and at positions lims[q] .. lims[q + 1] of out_scores_dev /
+ * out_ids_dev the scan's scores (the bits vodhip_index_search returns) and the ids id_base + z, ids ASCENDING within a query.  It is
+ * a function of the store and the query alone: the same bytes in any batch, any slice and on every repeat (positions come from
+ * prefix sums of integer counts, not from atomics).
+ *   out_scores_dev == NULL (and out_ids_dev == NULL): the SIZING call - one scan, lims alone; it only enqueues work and never
+ *     synchronises with the host.
+ *   with outputs of `capacity` elements each: a second scan emits the rows; a workgroup whose tile holds no hit of its queries leaves
+ *     before its K loop.  When lims[nq] > capacity the call writes the complete lims, writes only the positions below `capacity`, sets
+ *     the stat "last_range_overflow" (positions not written) and returns an error whose message names both numbers.  To report that, this
+ *     form reads lims[nq] and its status words back and so waits for `stream`.  Stats of the last such call: "last_range_selfcheck"
+ *     ((query, tile) pairs whose emitted count differed from the counted one; never above 0), "last_range_emit_skipped" /
+ *     "last_range_emit_groups" (emit workgroups that left early / in all).
+ * Temporaries are hipMallocAsync on `stream`: the staged queries, 12 bytes per query and 4 bytes per (query, tile); batches run in
+ * slices of 64 .. 1024 queries so that the table stays at or below VODHIP_POSTERIOR_TEMP_BYTES unless a 64-query slice alone needs
+ * more.  The call uses neither the search workspace nor the index's query labels: it may run beside searches in flight; it must not
+ * overlap add / reset / set_row_labels.  nq == 0 writes lims[0] = 0.
+ * REFUSED, each with its own vodhip_last_error: NULL index / queries / thresholds with nq > 0, NULL lims, one of the two outputs
+ * without the other, capacity < 0, q_dtype outside 0..2, n_per_query outside [1, 64], labels without row labels, VODHIP_L2 and
+ * VODHIP_EXACT_F32 stores (H2p's reasons). */
+int vodhip_index_range_search(vodhip_index_t* index, const void* queries, int q_dtype, int64_t nq, const float* thresholds_dev /* DEVICE [nq] */,
+                              const int64_t* tie_ids_dev /* DEVICE [nq], NULL = strict */, int64_t id_base,
+                              const int32_t* q_labels_dev /* NULL = unrestricted */, int n_per_query, int64_t* lims_dev /* DEVICE [nq + 1] */,
+                              float* out_scores_dev /* DEVICE [capacity], or NULL */, int64_t* out_ids_dev /* DEVICE [capacity], or NULL */,
+                              int64_t capacity, void* stream);
+
 /* Optional subset filter.  The reference's SearchClient.search carries `subset_ids`; its Elasticsearch and
  * Qdrant engines restrict hits to sections whose subset id is listed (src/vod_search/es_search/client.py:185-191,
  * qdrant_search/client.py:124-136) while its faiss client ignores it (faiss_search/client.py:67-72).  Here every stored
@@ -554,6 +585,16 @@ int vodhip_node_index_rank_ids(vodhip_node_index_t* index, const void* queries, 
 int vodhip_node_index_count_above(vodhip_node_index_t* index, const void* queries, int q_dtype, int64_t nq, const float* thresholds,
                                   const int64_t* tie_ids /* HOST or NULL = strict */, int64_t m,
                                   const int32_t* q_labels /* HOST or NULL */, int n_per_query, int64_t* out_counts /* HOST [nq][m] */);
+/* H2g behind the one handle: queries, thresholds, tie ids (GLOBAL row ids), `q_labels` (may be NULL), lims and the outputs are HOST
+ * buffers.  Every shard runs vodhip_index_range_search with id_base = its first global row - the sizing call first, then, with outputs,
+ * the full call - and the host concatenates a query's per-shard lists in shard order (range_fold.h): ascending ids, since shards own
+ * ascending id ranges.  lims, scores and ids equal one index holding all the rows bit for bit.  lims[nq] > capacity: lims is complete,
+ * positions below `capacity` are written, and the call returns an error that names both numbers.  Host-synchronous; serialised with the
+ * other calls on the handle; refusals as for the flat call. */
+int vodhip_node_index_range_search(vodhip_node_index_t* index, const void* queries, int q_dtype, int64_t nq, const float* thresholds /* HOST [nq] */,
+                                   const int64_t* tie_ids /* HOST [nq] or NULL = strict */, const int32_t* q_labels /* HOST or NULL */,
+                                   int n_per_query, int64_t* lims /* HOST [nq + 1] */, float* out_scores /* HOST [capacity], or NULL */,
+                                   int64_t* out_ids /* HOST [capacity], or NULL */, int64_t capacity);
 /* H2m behind the one handle: HOST buffers, as above.  Every shard runs vodhip_index_posterior_mean; the shards are folded on the host
  * in increasing shard order, in double: the pair as above, mean = sum_g w_g mean_g with w_g = exp(beta (max_g - max) + log_rel_g -
  * log_rel); a shard with no eligible row carries weight 0 (its row is not read).  No eligible row anywhere, or a +inf score: zeros. */

@@ -73,6 +73,7 @@ SIGNATURES: dict[str, tuple] = {
     "vodhip_index_count_above": (_i32, [_vp, _vp, _i32, _i64, _vp, _vp, _i64, _i64, _vp, _i32, _vp, _vp]),
     "vodhip_index_rank_ids": (_i32, [_vp, _vp, _i32, _i64, _vp, _i64, _i64, _vp, _i32, _vp, _vp, _vp]),
     "vodhip_index_scan_score_ids": (_i32, [_vp, _vp, _i32, _i64, _vp, _i64, _i64, _vp, _i32, _vp, _vp, _vp]),
+    "vodhip_index_range_search": (_i32, [_vp, _vp, _i32, _i64, _vp, _vp, _i64, _vp, _i32, _vp, _vp, _vp, _i64, _vp]),
     "vodhip_index_sample_posterior": (
         _i32, [_vp, _vp, _i32, _i64, _i32, _c.c_float, _c.c_uint64, _i64, _i64, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "vodhip_index_set_row_labels": (_i32, [_vp, _vp, _i64, _i32, _vp]),
@@ -107,6 +108,7 @@ SIGNATURES: dict[str, tuple] = {
     "vodhip_node_index_posterior_mean": (_i32, [_vp, _vp, _i32, _i64, _c.c_float, _vp, _i32, _vp, _vp, _vp]),
     "vodhip_node_index_rank_ids": (_i32, [_vp, _vp, _i32, _i64, _vp, _i64, _vp, _i32, _vp, _vp]),
     "vodhip_node_index_count_above": (_i32, [_vp, _vp, _i32, _i64, _vp, _vp, _i64, _vp, _i32, _vp]),
+    "vodhip_node_index_range_search": (_i32, [_vp, _vp, _i32, _i64, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _i64]),
     "vodhip_node_index_sample_posterior": (
         _i32, [_vp, _vp, _i32, _i64, _i32, _c.c_float, _c.c_uint64, _i64, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "vodhip_merge_topk": (_i32, [_vp, _vp, _i32, _i64, _i32, _i32, _vp, _vp, _vp]),

@@ -21,6 +21,7 @@
 #include "partition_fold.h"
 #include "sample_fold.h"
 #include "rank_fold.h"
+#include "range_fold.h"
 #include "stats_fold.h"
 #include "divergence_fold.h"
 #include "search_plan.h"
@@ -161,6 +162,7 @@ struct vodhip_index {
     // the last vodhip_index_sample_posterior: its status words, the emit launches' workgroups, with "profile" the ns per launch
     std::atomic<int64_t> last_sample[6] = {};      // overflow, selfcheck, max candidates, emit skipped, candidates, emit groups
     std::atomic<int64_t> last_sample_ns[5] = {};   // partition, keymax, threshold, emit, select
+    std::atomic<int64_t> last_range[4] = {};       // the last vodhip_index_range_search: overflow, selfcheck, emit skipped, emit groups
     // its temporaries: one grow-only block, kept between calls (the call waits for its stream at its end, and a stream-ordered pool
     // hands its memory back at every such wait: allocating per call cost 1.1 ms of a 3.8 ms call at 256 queries); held by
     // sample_mu for the length of a call, so two calls on one index run one after the other
@@ -1464,6 +1466,75 @@ int vodhip_index_scan_score_ids(vodhip_index_t* ix, const void* queries, int q_d
                      nullptr, out_scores, out_rows, (hipStream_t)stream_);
 }
 
+// ---- range scan (kernels_range.hip): count pass, prefix, lims and - with outputs - the emit pass, slice by slice ------------------
+int vodhip_index_range_search(vodhip_index_t* ix, const void* queries, int q_dtype, int64_t nq, const float* thresholds_dev,
+                              const int64_t* tie_ids_dev, int64_t id_base, const int32_t* q_labels_dev, int n_per_query, int64_t* lims_dev,
+                              float* out_scores_dev, int64_t* out_ids_dev, int64_t capacity, void* stream_) {
+    if (!ix) return fail("index is NULL");
+    if (const char* msg = range_args_error(queries, q_dtype, nq, thresholds_dev, q_labels_dev, n_per_query, lims_dev, out_scores_dev, out_ids_dev, capacity)) {
+        if (!strcmp(msg, "invalid q_dtype")) return fail("invalid q_dtype %d", q_dtype);
+        if (!strncmp(msg, "capacity", 8)) return fail("capacity=%lld: %s", (long long)capacity, msg);
+        return fail("%s", msg);
+    }
+    if (scan_refusal(ix, "range_search", q_labels_dev)) return -1;
+    HIP_OK(hipSetDevice(ix->device));
+    hipStream_t stream = (hipStream_t)stream_;
+    const bool emit = out_scores_dev != nullptr;
+    for (auto& w : ix->last_range) w = 0;
+    if (nq == 0) {
+        HIP_OK(hipMemsetAsync(lims_dev, 0, sizeof(int64_t), stream));
+        return 0;
+    }
+    RangeArgs a;
+    fill_scan_inputs(a, ix, queries, q_dtype, q_labels_dev, n_per_query);
+    a.id_base = id_base;
+    a.thresholds = thresholds_dev;
+    a.tie_ids = tie_ids_dev;
+    a.lims = lims_dev;
+    a.out_scores = out_scores_dev;
+    a.out_ids = out_ids_dev;
+    a.capacity = capacity;
+    const size_t row_bytes = (size_t)ix->dim_pad * 2;
+    const size_t n_tiles = (size_t)scan_tiles(a.ntotal);
+    const int64_t slice = scan_slice_queries(std::max<size_t>(1, n_tiles) * 4 + row_bytes + 12);  // the count table, the staged query, the words
+    const int64_t nq_pad = scan_nq_pad(std::min(nq, slice));
+    ScanTemps tmp;
+    tmp.stream = stream;
+    if (tmp.alloc({(size_t)nq_pad * row_bytes, n_tiles * (size_t)nq_pad * 4, (size_t)nq_pad * 12, emit ? RGS_WORDS * sizeof(unsigned int) : 0})) return -1;
+    a.q_stage = tmp.p[0];
+    a.table = (int*)tmp.p[1];
+    a.words = (unsigned int*)tmp.p[2];
+    a.status = (unsigned int*)tmp.p[3];
+    hipError_t le = emit ? hipMemsetAsync(a.status, 0, RGS_WORDS * sizeof(unsigned int), stream) : hipSuccess;
+    int64_t emit_groups = 0;
+    for (int64_t q0 = 0; q0 < nq && le == hipSuccess; q0 += slice) {
+        const int64_t n = std::min(slice, nq - q0);
+        le = launch_range(a, q0, n, stream);
+        emit_groups += (int64_t)n_tiles * (scan_nq_pad(n) / (n <= 64 ? 64 : 128));
+    }
+    // With outputs the call reports an overflow itself: the status words and lims[nq] come back, which waits for the stream
+    unsigned int st[RGS_WORDS] = {};
+    int64_t total = 0;
+    if (emit && le == hipSuccess) le = hipMemcpyAsync(st, a.status, sizeof(st), hipMemcpyDeviceToHost, stream);
+    if (emit && le == hipSuccess) le = hipMemcpyAsync(&total, lims_dev + nq, sizeof(total), hipMemcpyDeviceToHost, stream);
+    if (le != hipSuccess) (void)hipGetLastError();
+    const hipError_t fe = tmp.release();
+    const hipError_t se = emit ? hipStreamSynchronize(stream) : hipSuccess;
+    if (le != hipSuccess) return fail("range_search launch failed: %s", hipGetErrorString(le));
+    HIP_OK(fe);
+    HIP_OK(se);
+    if (emit) {
+        ix->last_range[0] = total > capacity ? total - capacity : 0;
+        ix->last_range[1] = st[RGS_SELFCHECK];
+        ix->last_range[2] = st[RGS_SKIPPED];
+        ix->last_range[3] = emit_groups;
+        if (total > capacity)
+            return fail("range_search: the result holds %lld rows, the outputs %lld (capacity); lims is complete, rows at positions below the capacity are written",
+                        (long long)total, (long long)capacity);
+    }
+    return 0;
+}
+
 // ---- posterior mean (kernels_posterior.hip): the log-partition launches, then the second scan and its finish -------------------
 int vodhip_index_posterior_mean(vodhip_index_t* ix, const void* queries, int q_dtype, int64_t nq, float beta, const int32_t* q_labels_dev,
                                 int n_per_query, float* out_max, float* out_log_rel, float* out_mean, void* stream_) {
@@ -1717,6 +1788,14 @@ int vodhip_index_get_stat(const vodhip_index_t* ix, const char* key, int64_t* ou
         *out = ix->last_sample[4];
     else if (!strcmp(key, "last_sample_emit_groups"))
         *out = ix->last_sample[5];
+    else if (!strcmp(key, "last_range_overflow"))
+        *out = ix->last_range[0];
+    else if (!strcmp(key, "last_range_selfcheck"))
+        *out = ix->last_range[1];
+    else if (!strcmp(key, "last_range_emit_skipped"))
+        *out = ix->last_range[2];
+    else if (!strcmp(key, "last_range_emit_groups"))
+        *out = ix->last_range[3];
     else if (!strcmp(key, "last_sample_ns_partition"))
         *out = ix->last_sample_ns[0];
     else if (!strcmp(key, "last_sample_ns_keymax"))

@@ -309,6 +309,26 @@ int64_t rank_mini_rows(int64_t nq_pad, int64_t m);
 // queries [q_first, q_first + nq) of the caller's batch; a query's results do not depend on the split
 hipError_t launch_rank(const RankArgs& a, int mode, int64_t q_first, int64_t nq, hipStream_t stream);
 
+// ---- launchers (kernels_range.hip): every row above a per-query threshold over the whole store, as a CSR list ----
+struct RangeArgs : ScanInputs {
+    int64_t id_base = 0;              // global id of row 0
+    const float* thresholds = nullptr;  // [rows of the caller's batch]
+    const int64_t* tie_ids = nullptr;   // the same shape, or NULL = strict
+    // temporaries, sized for P = scan_nq_pad(queries of a launch)
+    int* table = nullptr;             // P * scan_tiles(ntotal) words: hits per (query, tile), then their offsets
+    unsigned int* words = nullptr;    // 3 * P words: keys, tie rows, hits per query
+    unsigned int* status = nullptr;   // RGS_WORDS words, cleared by the caller once per call; NULL without outputs
+    int64_t* lims = nullptr;          // [rows of the caller's batch + 1]
+    float* out_scores = nullptr;      // [capacity], or NULL: counts and lims only
+    int64_t* out_ids = nullptr;
+    int64_t capacity = 0;
+};
+// status words: (query, tile) pairs whose emit count differs from the stored count; emit workgroups that skipped their K loop
+enum : int { RGS_SELFCHECK = 0, RGS_SKIPPED = 1, RGS_WORDS = 8 };
+// queries [q_first, q_first + nq) of the caller's batch, nq <= 1024; slices run in query order on one stream (lims carries over); a
+// query's list does not depend on the split
+hipError_t launch_range(const RangeArgs& a, int64_t q_first, int64_t nq, hipStream_t stream);
+
 // ---- launchers (kernels_posterior.hip): the posterior mean of the rows, sum_z p(z | q) x_z, behind the log-partition launches ----
 struct PosteriorArgs {
     PartitionArgs p;                  // the log-partition call of the same batch: its launches run first, unchanged

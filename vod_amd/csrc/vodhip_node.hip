@@ -21,6 +21,7 @@
 #include "partition_fold.h"
 #include "sample_fold.h"
 #include "rank_fold.h"
+#include "range_fold.h"
 #include "stats_fold.h"
 #include "divergence_fold.h"
 #include "vodhip_internal.h"
@@ -1096,6 +1097,54 @@ int vodhip_node_index_rank_ids(vodhip_node_index_t* nx, const void* queries, int
     vodhip::rank_thresholds(out_scores, present.data(), (int64_t)n, thr.data());
     if (node_rank_pass(nx, queries, q_dtype, nq, m, ids, thr.data(), q_labels, n_per_query, nullptr, nullptr, count_g.data())) return -1;
     vodhip::sum_counts(count_g.data(), (int64_t)n, G, out_ranks);
+    return 0;
+}
+
+// range_search behind the one handle (H2g).  Pass 1: every shard's sizing call (id_base = its first global row; the flat call maps the
+// GLOBAL tie ids to its local rows) -> its own lims; the host adds the list lengths.  Pass 2, with outputs: every shard's full call into
+// a block of the longest shard list, then the host concatenates a query's lists in shard order (range_fold.h) - ascending ids.
+static int node_range_pass(vodhip_node_index_t* nx, const void* queries, int q_dtype, int64_t nq, const float* thresholds, const int64_t* tie_ids,
+                           const int32_t* q_labels, int n_per_query, int64_t* lims_g, float* scores_g, int64_t* ids_g, int64_t stride) {
+    ShardFanout f(nx);
+    const int iq = f.input(queries, query_bytes(nx, nq, q_dtype)), it = f.input(thresholds, (size_t)nq * sizeof(float));
+    const int ii = f.input(tie_ids, (size_t)nq * sizeof(int64_t)), il = f.input(q_labels, label_bytes(q_labels, nq, n_per_query));
+    const int im = f.output(lims_g, (size_t)(nq + 1) * sizeof(int64_t));
+    const int is = f.output(scores_g, (size_t)stride * sizeof(float)), io = f.output(ids_g, (size_t)stride * sizeof(int64_t));
+    return f.run([&](int g, void* const* p, hipStream_t st) {
+        return vodhip_index_range_search(nx->shard[g], p[iq], q_dtype, nq, (const float*)p[it], (const int64_t*)p[ii], (int64_t)g * nx->rows_per_shard,
+                                         (const int32_t*)p[il], n_per_query, (int64_t*)p[im], (float*)p[is], (int64_t*)p[io], stride, st);
+    });
+}
+
+int vodhip_node_index_range_search(vodhip_node_index_t* nx, const void* queries, int q_dtype, int64_t nq, const float* thresholds, const int64_t* tie_ids,
+                                   const int32_t* q_labels, int n_per_query, int64_t* lims, float* out_scores, int64_t* out_ids, int64_t capacity) {
+    if (!nx) return nfail("index is NULL");
+    if (const char* msg = vodhip::range_args_error(queries, q_dtype, nq, thresholds, q_labels, n_per_query, lims, out_scores, out_ids, capacity)) {
+        if (!strcmp(msg, "invalid q_dtype")) return nfail("invalid q_dtype %d", q_dtype);
+        if (!strncmp(msg, "capacity", 8)) return nfail("capacity=%lld: %s", (long long)capacity, msg);
+        return nfail("%s", msg);
+    }
+    if (node_scan_refusal(nx, "range_search")) return -1;
+    std::lock_guard<std::mutex> guard(nx->mu);
+    if (node_labels_refusal(nx, q_labels)) return -1;
+    lims[0] = 0;
+    if (nq == 0) return 0;
+    const int G = nx->n;
+    std::vector<int64_t> lims_g((size_t)G * (size_t)(nq + 1));
+    if (node_range_pass(nx, queries, q_dtype, nq, thresholds, tie_ids, q_labels, n_per_query, lims_g.data(), nullptr, nullptr, 0)) return -1;
+    const int64_t total = vodhip::fold_range_lims(lims_g.data(), G, nq, lims);
+    if (!out_scores) return 0;
+    int64_t stride = 0;  // the longest shard list
+    for (int g = 0; g < G; ++g) stride = std::max(stride, lims_g[(size_t)g * (size_t)(nq + 1) + (size_t)nq]);
+    if (stride > 0 && capacity > 0) {
+        std::vector<float> scores_g((size_t)G * (size_t)stride);
+        std::vector<int64_t> ids_g((size_t)G * (size_t)stride);
+        if (node_range_pass(nx, queries, q_dtype, nq, thresholds, tie_ids, q_labels, n_per_query, lims_g.data(), scores_g.data(), ids_g.data(), stride)) return -1;
+        vodhip::fold_range_lists(lims_g.data(), scores_g.data(), ids_g.data(), stride, G, nq, lims, out_scores, out_ids, capacity);
+    }
+    if (total > capacity)
+        return nfail("range_search: the result holds %lld rows, the outputs %lld (capacity); lims is complete, rows at positions below the capacity are written",
+                     (long long)total, (long long)capacity);
     return 0;
 }
 

@@ -10,6 +10,7 @@ from __future__ import annotations
 
 import collections
 import ctypes
+import math
 from typing import Any, NamedTuple
 
 import numpy as np
@@ -475,6 +476,92 @@ class HipFlatIndex:
                 t.record_stream(torch.cuda.current_stream(self.device))
         return out
 
+    def range_search(self, queries, thresholds, *, tie_ids=None, inclusive: bool = False, subset=None, id_base: int = 0,
+                     max_results: int | None = None, order: str = "id") -> "RangeResult":
+        """WHICH eligible rows of the WHOLE store score above a per-query threshold - the rows `count_above` counts - as CSR:
+        `RangeResult(lims, scores, ids)`, device tensors int64 `[nq + 1]`, float32 `[total]` (the scan's bits, which are the bits
+        `search` returns) and int64 `[total]`; query `q` owns positions `lims[q] .. lims[q + 1]`.  Row `z` is in the list of `q` when
+        `score(q, z) > thresholds[q]`, or - with `tie_ids` - the score is equal (`-0.0 == +0.0`) and `id_base + z < tie_ids[q]`: with a
+        hit `(s, i)` of `search` as threshold and tie id, exactly the hits a search returns ahead of it.  `inclusive=True` (without
+        `tie_ids`) also takes the rows that equal the threshold.  A NaN threshold gives an empty list, `-inf` every eligible row above
+        `-inf`.  Within a query ids ascend (`order="id"`), or `order="score"` re-sorts every list by (score descending, id ascending)
+        on the device.  The result depends on the store and the query alone: the same bytes in any batch and on every repeat.
+
+        `thresholds`: float32 `[nq]`; `tie_ids`: int64 `[nq]`.  With `max_results` the outputs are allocated up front and ONE native
+        call runs (count scan + emit scan); more hits than that raise, with the needed size in the message.  Without it a sizing call
+        (one scan) runs first, `lims[-1]` is read back, and the full call follows.  Eligibility, queries, `subset`, and refusals as
+        `rank_ids`; the call that emits waits for the current stream (it reports overflow), the sizing call does not."""
+        q = self._prep_queries(queries)
+        nq = q.shape[0]
+        thr = thresholds if isinstance(thresholds, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(thresholds, dtype=np.float32))
+        thr = thr.to(self.device, torch.float32).contiguous()
+        tie = None
+        if tie_ids is not None:
+            tie = tie_ids if isinstance(tie_ids, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(tie_ids, dtype=np.int64))
+            tie = tie.to(self.device, torch.int64).contiguous()
+        check_range_args(nq, tuple(thr.shape), None if tie is None else tuple(tie.shape), inclusive, max_results, order)
+        if inclusive:  # a tie row past every row
+            tie = torch.full((nq,), torch.iinfo(torch.int64).max, dtype=torch.int64, device=self.device)
+        sub, n_sub = self._subset_labels(subset, nq)
+        lims = torch.empty((nq + 1,), dtype=torch.int64, device=self.device)
+
+        def call(scores, ids, capacity):
+            with torch.cuda.device(self.device):
+                _native.check(self._lib.vodhip_index_range_search(
+                    self._h, q.data_ptr(), _native.torch_dtype_code(q.dtype), nq, thr.data_ptr(), None if tie is None else tie.data_ptr(),
+                    int(id_base), None if sub is None else sub.data_ptr(), n_sub, lims.data_ptr(), None if scores is None else scores.data_ptr(),
+                    None if ids is None else ids.data_ptr(), int(capacity), _native.current_stream_ptr(self.device)))
+
+        if max_results is None:
+            call(None, None, 0)
+            capacity = int(lims[-1])
+        else:
+            capacity = int(max_results)
+        scores = torch.empty((max(capacity, 1),), dtype=torch.float32, device=self.device)  # (never a NULL pointer: that is the sizing call)
+        ids = torch.empty((max(capacity, 1),), dtype=torch.int64, device=self.device)
+        try:
+            call(scores, ids, capacity)
+        except _native.NativeLibraryError as exc:
+            if self.get_stat("last_range_overflow") > 0:
+                raise _native.NativeLibraryError(f"{exc}: call range_search with max_results >= {int(lims[-1])}") from None
+            raise
+        finally:
+            for t, given in ((q, queries), (thr, thresholds), (tie, tie_ids), (sub, subset)):
+                if t is not None and t is not given:
+                    t.record_stream(torch.cuda.current_stream(self.device))
+        total = capacity if max_results is None else int(lims[-1])
+        res = RangeResult(lims, scores[:total], ids[:total])
+        return sort_range_by_score(res) if order == "score" else res
+
+    def outranking(self, queries, ids, *, subset=None, id_base: int = 0, order: str = "score") -> "RangeResult":
+        """Per query, the rows a search returns AHEAD of row `ids[q]` (int64 `[nq]`, one id per query), however deep it sits: `rank_ids`
+        gives the target's scan score, `range_search` with `(score, id)` as threshold and tie id the rows - as many as the target's
+        rank, in search order (`order="score"`) or by ascending id.  A target that is absent (out of range, outside `subset`) or scores
+        NaN gives an empty list."""
+        tgt = ids if isinstance(ids, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(ids, dtype=np.int64))
+        tgt = tgt.to(self.device, torch.int64).reshape(-1).contiguous()
+        ranks = self.rank_ids(queries, tgt[:, None], subset=subset, id_base=id_base)
+        thr = torch.where(ranks.rank[:, 0] >= 0, ranks.score[:, 0], torch.full_like(ranks.score[:, 0], float("nan")))
+        return self.range_search(queries, thr, tie_ids=tgt, subset=subset, id_base=id_base, order=order)
+
+    def posterior_support(self, queries, min_prob: float, temperature: float = 1.0, subset=None) -> "PosteriorSupport":
+        """The exact support of the posterior above a probability floor: every eligible row with `p(z | q) > min_prob`, an adaptive K in
+        place of a fixed top-K.  One `log_partition`, then `range_search(q, thr)` with
+        `thr = float32(temperature * (log_z + log(min_prob)))`, computed in double from the returned `max_score` and `log_rel`.
+        MEMBERSHIP IS DEFINED BY THAT ROUNDED THRESHOLD: a row is returned when its scan score is above `thr` as a float32, which can
+        differ from the real-valued test `p > min_prob` for a row within a rounding of the boundary.  Returns `PosteriorSupport(lims,
+        scores, ids, log_p, log_partition)`, `log_p = score / temperature - log_z` per hit (float32, computed in double)."""
+        if not 0.0 < float(min_prob) <= 1.0:
+            raise ValueError(f"min_prob must be in (0, 1], got {min_prob}")
+        t = float(temperature)
+        lp = self.log_partition(queries, temperature=t, subset=subset)
+        log_z = lp.max_score.double() / t + lp.log_rel.double()
+        thr = (t * (log_z + math.log(float(min_prob)))).float()
+        res = self.range_search(queries, thr, subset=subset)
+        seg = torch.repeat_interleave(torch.arange(thr.shape[0], device=self.device), res.lims[1:] - res.lims[:-1])
+        log_p = (res.scores.double() / t - log_z[seg]).float()
+        return PosteriorSupport(res.lims, res.scores, res.ids, log_p, lp)
+
     def log_partition(self, queries, temperature: float = 1.0, subset=None, out=None) -> LogPartition:
         """The exact softmax normaliser over the WHOLE store, `log Z(q) = log sum_z exp(<q~, x~_z> / temperature)`, from one scan on
         the MFMA path (no `[nq, N]` score matrix): `LogPartition(log_z, max_score, log_rel)`, float32 device tensors `[nq]` with
@@ -701,6 +788,55 @@ class ListedRanks(NamedTuple):
 
     rank: Any
     score: Any
+
+
+class RangeResult(NamedTuple):
+    """The CSR result of `range_search`: `lims` int64 `[nq + 1]`, and at positions `lims[q] .. lims[q + 1]` of `scores` (float32, the
+    scan's bits) and `ids` (int64) the hits of query `q`."""
+
+    lims: Any
+    scores: Any
+    ids: Any
+
+
+class PosteriorSupport(NamedTuple):
+    """`posterior_support`: the `RangeResult` fields, `log_p = score / temperature - log_z` per hit and the `LogPartition` of the call."""
+
+    lims: Any
+    scores: Any
+    ids: Any
+    log_p: Any
+    log_partition: LogPartition
+
+
+def check_range_args(nq: int, thr_shape: tuple, tie_shape: tuple | None, inclusive: bool, max_results: int | None, order: str) -> None:
+    """The refusals of `range_search` that need no index: one threshold (and tie id) per query, `order`, `max_results`."""
+    if thr_shape != (nq,):
+        raise ValueError(f"expected thresholds of shape ({nq},), got {thr_shape}")
+    if tie_shape is not None and tie_shape != (nq,):
+        raise ValueError(f"expected tie_ids of shape ({nq},), got {tie_shape}")
+    if inclusive and tie_shape is not None:
+        raise ValueError("inclusive=True is a tie id past every row: it cannot be combined with tie_ids")
+    if order not in ("id", "score"):
+        raise ValueError(f"order must be 'id' or 'score', got {order!r}")
+    if max_results is not None and int(max_results) < 0:
+        raise ValueError(f"max_results must be >= 0, got {max_results}")
+
+
+def sort_range_by_score(result: RangeResult) -> RangeResult:
+    """Every list of a `RangeResult` re-sorted by (score descending, id ascending) - the order of `search` - with plain torch ops on
+    the device of the result (NumPy arrays: on the host, NumPy arrays back).  Scores compare as the search's keys do: `-0.0` equals
+    `+0.0`, so two zeros of either sign are ordered by id.  The score bits are kept."""
+    as_numpy = isinstance(result.scores, np.ndarray)
+    lims, scores, ids = (torch.as_tensor(t) for t in result)
+    seg = torch.repeat_interleave(torch.arange(lims.numel() - 1, device=lims.device), lims[1:] - lims[:-1])
+    by_id = torch.argsort(ids, stable=True)
+    by_score = by_id[torch.argsort(-(scores[by_id] + 0.0), stable=True)]  # (x + 0.0: -0.0 -> +0.0; stable: ties keep ascending ids)
+    perm = by_score[torch.argsort(seg[by_score], stable=True)]
+    scores, ids = scores[perm], ids[perm]
+    if as_numpy:
+        return RangeResult(result.lims, scores.numpy(), ids.numpy())
+    return RangeResult(result.lims, scores, ids)
 
 
 class PosteriorMean(NamedTuple):
@@ -1322,6 +1458,74 @@ class HipNodeIndex:
                 self._h, q.ctypes.data, 2 if q.dtype == np.float32 else 0, nq, thr.ctypes.data, None if tie is None else tie.ctypes.data, m,
                 None if sub is None else sub.ctypes.data, n_sub, out.ctypes.data))
         return out
+
+    def range_search(self, queries, thresholds, *, tie_ids=None, inclusive: bool = False, subset=None, max_results: int | None = None,
+                     order: str = "id") -> "RangeResult":
+        """`HipFlatIndex.range_search` over every shard (`tie_ids` GLOBAL row ids): each shard runs the flat call with its own id base,
+        the host concatenates a query's per-shard lists in shard order, which is ascending ids.  Host inputs -> `RangeResult` of NumPy
+        arrays that equals one index holding all the rows byte for byte.  With `max_results` the outputs are sized up front and more
+        hits raise with the needed size; without it a sizing call runs first."""
+        q = self._host_queries(queries)
+        nq = int(q.shape[0])
+        if isinstance(thresholds, torch.Tensor):
+            thresholds = thresholds.detach().cpu().numpy()
+        thr = np.ascontiguousarray(thresholds, dtype=np.float32)
+        tie = None
+        if tie_ids is not None:
+            if isinstance(tie_ids, torch.Tensor):
+                tie_ids = tie_ids.detach().cpu().numpy()
+            tie = np.ascontiguousarray(tie_ids, dtype=np.int64)
+        check_range_args(nq, tuple(thr.shape), None if tie is None else tuple(tie.shape), inclusive, max_results, order)
+        if inclusive:  # a tie row past every row
+            tie = np.full((nq,), np.iinfo(np.int64).max, dtype=np.int64)
+        sub, n_sub = self._host_subset(subset, nq)
+        lims = np.zeros((nq + 1,), dtype=np.int64)
+
+        def call(scores, ids, capacity):
+            with torch.cuda.device(self.device):
+                return self._lib.vodhip_node_index_range_search(
+                    self._h, q.ctypes.data, 2 if q.dtype == np.float32 else 0, nq, thr.ctypes.data, None if tie is None else tie.ctypes.data,
+                    None if sub is None else sub.ctypes.data, n_sub, lims.ctypes.data, None if scores is None else scores.ctypes.data,
+                    None if ids is None else ids.ctypes.data, int(capacity))
+
+        if max_results is None:
+            _native.check(call(None, None, 0))
+            capacity = int(lims[-1])
+        else:
+            capacity = int(max_results)
+        scores = np.empty((max(capacity, 1),), dtype=np.float32)  # (never a NULL pointer: NULL outputs mean the sizing call)
+        ids = np.empty((max(capacity, 1),), dtype=np.int64)
+        status = call(scores, ids, capacity)
+        if status != 0 and int(lims[-1]) > capacity:
+            msg = self._lib.vodhip_last_error().decode("utf-8", "replace")
+            raise _native.NativeLibraryError(f"{msg}: call range_search with max_results >= {int(lims[-1])}")
+        _native.check(status)
+        total = int(lims[-1])
+        res = RangeResult(lims, scores[:total], ids[:total])
+        return sort_range_by_score(res) if order == "score" else res
+
+    def outranking(self, queries, ids, *, subset=None, order: str = "score") -> "RangeResult":
+        """`HipFlatIndex.outranking` over every shard (`ids` GLOBAL row ids, int64 `[nq]`): NumPy arrays."""
+        if isinstance(ids, torch.Tensor):
+            ids = ids.detach().cpu().numpy()
+        tgt = np.ascontiguousarray(ids, dtype=np.int64).reshape(-1)
+        ranks = self.rank_ids(queries, tgt[:, None], subset=subset)
+        thr = np.where(ranks.rank[:, 0] >= 0, ranks.score[:, 0], np.float32(np.nan)).astype(np.float32)
+        return self.range_search(queries, thr, tie_ids=tgt, subset=subset, order=order)
+
+    def posterior_support(self, queries, min_prob: float, temperature: float = 1.0, subset=None) -> "PosteriorSupport":
+        """`HipFlatIndex.posterior_support` over every shard: the folded `log_partition`, the same rounded threshold (membership is
+        defined by it), `range_search`; NumPy arrays."""
+        if not 0.0 < float(min_prob) <= 1.0:
+            raise ValueError(f"min_prob must be in (0, 1], got {min_prob}")
+        t = float(temperature)
+        lp = self.log_partition(queries, temperature=t, subset=subset)
+        log_z = np.asarray(lp.max_score, dtype=np.float64) / t + np.asarray(lp.log_rel, dtype=np.float64)
+        thr = (t * (log_z + math.log(float(min_prob)))).astype(np.float32)
+        res = self.range_search(queries, thr, subset=subset)
+        seg = np.repeat(np.arange(thr.shape[0]), np.diff(res.lims))
+        log_p = (res.scores.astype(np.float64) / t - log_z[seg]).astype(np.float32)
+        return PosteriorSupport(res.lims, res.scores, res.ids, log_p, lp)
 
     def posterior_mean(self, queries, temperature: float = 1.0, subset: np.ndarray | None = None) -> "PosteriorMean":
         """`HipFlatIndex.posterior_mean` over every shard: each shard runs the flat call on its own device, the shards are folded on the
