@@ -289,6 +289,48 @@ int vodhip_index_posterior_mean(vodhip_index_t* index, const void* queries, int 
                                 float* out_max /* DEVICE [nq] */, float* out_log_rel /* DEVICE [nq] */,
                                 float* out_mean /* DEVICE [nq][dim] */, void* stream);
 
+/* H2e. The posterior EXPECTATION of a per-row value table under that softmax (kernels_readout.hip): exact attention with the store as
+ * keys and the table as values - the mass per class (a one-hot table), a soft k-NN read-out, a posterior mean in another space:
+ *     out_values[q, c] = sum_{z < ntotal, eligible} p(z | q) v~[z, c],   p(z | q) = exp(beta <q~, x~_z> - log Z_beta(q)).
+ * THE TABLE.  vodhip_index_set_row_values: `values` [n_rows][n_cols] of src_dtype (0 = f16, 1 = bf16, 2 = f32), HOST or DEVICE
+ * (`location`); n_rows must equal ntotal, 1 <= n_cols <= 256 (wider tables are refused); values == NULL clears the table.  The index
+ * keeps a copy on its device in the STORE dtype, rounded as the rows are (saturating), laid out [tiles * 256][c_pad] with c_pad =
+ * 64 * ceil(n_cols / 64); pad columns and the rows from n_rows to the end of the last 256-row tile are written as zero.  The call waits
+ * for `stream`; like set_row_labels it refuses while searches are in flight and must not overlap a read-out.  vodhip_index_reset drops
+ * the table.  Rows added after the table was set leave it short: the read-out is then refused with a message that names both row
+ * counts.  Saving and reloading an index (HipFlatIndex.save / HipFlatIndex.load write and read the rows) does NOT carry the table:
+ * set it again after a load.
+ * vodhip_index_row_values_info: the table's (n_rows, n_cols), (0, 0) when there is none; either pointer may be NULL.
+ * THE CALL.  out_max / out_log_rel are the bits vodhip_index_log_partition returns for the same query; eligibility, queries, labels,
+ * stream and concurrency rules are H2p's.  ONE scan of the store (H2m runs two): per group of VODHIP_READOUT_GROUP_ROWS consecutive
+ * rows and per 256-row tile in increasing order, H2p's epilogue gives the tile maximum m_t, the exponentials e = expf(beta (s - m_t))
+ * and their sum (the partial that H2p's finish folds); a running maximum M per query either rescales the group's accumulator by
+ * expf(beta (M - m_t)) (m_t > M, then M = m_t) or shrinks the tile's weights by gamma = expf(beta (m_t - M)); the weights e * gamma are
+ * rounded ONCE to the store dtype - one expf per (row, query) - and contracted with the tile's table rows on the MFMA (float32
+ * accumulate).  fp16 stores keep a weight as a normal fp16 number down to 2^-29 of the running maximum's weight; smaller ones may be
+ * flushed to zero (an absolute error below rows-per-group * 2^-29 * max |v| of the column).  The groups are folded in increasing order
+ * with the weights expf(beta (M_g - max) - log_rel).
+ * ONE order per (query, column), fixed by ntotal, the padded width of the store and c_pad alone: a row of the result is the same bits
+ * whatever the batch around it and on every repeat; there are no atomics.
+ * No eligible row, or a +inf score: the two words as in H2p, the value row all zeros.
+ * NON-FINITE TABLE VALUES (H2m's contract): an excluded row has weight 0, and 0 * NaN is NaN on the MFMA.  A NaN or an infinity in
+ * column c of the table - in an excluded row included - makes column c of every query NaN; the other columns and the two scalar words
+ * are unaffected.  There is no sanitising pass.
+ * out_values: DEVICE float32 [nq, n_cols].  Temporaries are hipMallocAsync on `stream`: the staged queries and partials of H2p, and the
+ * group accumulators, groups * slice * c_pad * 4 bytes; batches run in slices of 64 .. 1024 queries chosen so that partials and
+ * accumulators stay at or below VODHIP_POSTERIOR_TEMP_BYTES unless a 64-query slice alone needs more.  The call only enqueues work.
+ * nq == 0 returns 0 and writes nothing; a refused call writes nothing.  REFUSED as H2p (L2 and VODHIP_EXACT_F32 stores, bad arguments,
+ * labels without row labels), and: no table, a table whose n_rows is not ntotal, a NULL out_values. */
+#define VODHIP_READOUT_GROUP_ROWS 4096
+#define VODHIP_READOUT_MAX_COLS 256
+int vodhip_index_set_row_values(vodhip_index_t* index, const void* values, int64_t n_rows, int64_t n_cols, int src_dtype, int location,
+                                void* stream);
+int vodhip_index_row_values_info(const vodhip_index_t* index, int64_t* n_rows, int64_t* n_cols);
+int vodhip_index_posterior_expectation(vodhip_index_t* index, const void* queries, int q_dtype, int64_t nq, float beta,
+                                       const int32_t* q_labels_dev /* NULL = unrestricted */, int n_per_query,
+                                       float* out_max /* DEVICE [nq] */, float* out_log_rel /* DEVICE [nq] */,
+                                       float* out_values /* DEVICE [nq][n_cols] */, void* stream);
+
 /* H2s. k rows drawn WITHOUT replacement from that softmax over the whole store, with priority-sampling weights
  * (kernels_sample_posterior.hip).  Gumbel-top-k: the k eligible rows with the largest keys
  *     key(q, z) = fl(fl(beta * s(q, z)) - logf(E)),   E = -log1pf(-v),   by (key desc, id asc),
@@ -601,6 +643,20 @@ int vodhip_node_index_range_search(vodhip_node_index_t* index, const void* queri
 int vodhip_node_index_posterior_mean(vodhip_node_index_t* index, const void* queries, int q_dtype, int64_t nq, float beta,
                                      const int32_t* q_labels /* HOST or NULL */, int n_per_query,
                                      float* out_max, float* out_log_rel /* HOST [nq] */, float* out_mean /* HOST [nq][dim] */);
+/* H2e behind the one handle.  set_row_values: a HOST table [n_rows][n_cols] of src_dtype for the global rows (n_rows must equal ntotal;
+ * NULL clears), split by shard row ranges - shard g keeps rows [g R, (g + 1) R) of it, a shard that holds no row a table of no rows;
+ * reset drops it; rows added afterwards leave it short and the read-out is refused.  posterior_expectation: HOST buffers, as above.
+ * Every shard runs vodhip_index_posterior_expectation; the shards are folded on the host in increasing shard order, in double
+ * (readout_fold.h): the pair as H2p's fold, values = sum_g w_g values_g with w_g = exp(beta (max_g - max) + log_rel_g - log_rel); a
+ * shard with no eligible row carries weight 0 (its rows are not read).  No eligible row anywhere, or a +inf score: zeros.  out_max
+ * equals one index holding all the rows bit for bit.  Host-synchronous; serialised with the other calls on the handle; refusals as for
+ * the flat calls. */
+int vodhip_node_index_set_row_values(vodhip_node_index_t* index, const void* values /* HOST or NULL */, int64_t n_rows, int64_t n_cols,
+                                     int src_dtype);
+int vodhip_node_index_row_values_info(const vodhip_node_index_t* index, int64_t* n_rows, int64_t* n_cols);
+int vodhip_node_index_posterior_expectation(vodhip_node_index_t* index, const void* queries, int q_dtype, int64_t nq, float beta,
+                                            const int32_t* q_labels /* HOST or NULL */, int n_per_query,
+                                            float* out_max, float* out_log_rel /* HOST [nq] */, float* out_values /* HOST [nq][n_cols] */);
 /* H2s behind the one handle: HOST buffers, host-synchronous.  Every shard runs vodhip_index_sample_posterior with id_base = its first
  * global row; keys are unnormalised and the noise is a function of the global row, so the k + 1 best of the union of the shards'
  * lists ARE the k + 1 best of the whole store: ids, scores and keys equal one index holding all the rows bit for bit.  The pairs are

@@ -216,8 +216,13 @@ hipError_t launch_log_partition(const PartitionArgs& a, int64_t q_first, int64_t
         });
         if (e != hipSuccess) return e;
     }
-    hipLaunchKernelGGL(partition_finish_kernel, dim3((unsigned)nq), dim3(FIN_T), 0, stream, (const float2*)a.part, n_tiles, a.beta, a.out_max + q_first,
-                       a.out_log_rel + q_first);
+    return launch_partition_finish(a, q_first, nq, stream);
+}
+
+hipError_t launch_partition_finish(const PartitionArgs& a, int64_t q_first, int64_t nq, hipStream_t stream) {
+    if (nq <= 0) return hipSuccess;
+    hipLaunchKernelGGL(partition_finish_kernel, dim3((unsigned)nq), dim3(FIN_T), 0, stream, (const float2*)a.part, scan_tiles(a.ntotal), a.beta,
+                       a.out_max + q_first, a.out_log_rel + q_first);
     return hipGetLastError();
 }
 

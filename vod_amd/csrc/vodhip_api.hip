@@ -24,6 +24,7 @@
 #include "range_fold.h"
 #include "stats_fold.h"
 #include "divergence_fold.h"
+#include "readout_fold.h"
 #include "search_plan.h"
 #include "vodhip_internal.h"
 
@@ -98,6 +99,9 @@ struct vodhip_index {
     int dtype = VODHIP_F16;
     uint16_t* data = nullptr;
     int* row_label = nullptr;        // [capacity_pad] subset label per row (optional)
+    // the value table of the posterior read-out (kernels_readout.hip): [round_up(value_rows, 256)][value_c_pad] of the store dtype, zero padded
+    uint16_t* row_value = nullptr;
+    int64_t value_rows = 0, value_cols = 0, value_c_pad = 0;
     const int* q_label = nullptr;    // caller-owned device [nq, n_qlab] for the next searches (optional)
     int n_qlab = 0;
     // host ingest pipeline: two slots of (pinned host staging, device staging of the raw dtype, completion event), one stream
@@ -626,6 +630,7 @@ int vodhip_index_destroy(vodhip_index_t* ix) {
         (void)hipFree(ix->l2_sim[i]);
     }
     (void)hipFree(ix->row_label);
+    (void)hipFree(ix->row_value);
     (void)hipFree(ix->sample_ws);
     (void)hipFree(ix->ovf_q);
     (void)hipFree(ix->q_map);
@@ -734,6 +739,13 @@ int vodhip_index_reset(vodhip_index_t* ix) {
         HIP_OK(hipMemset(ix->l2_sat, 0, sizeof(unsigned int)));
         HIP_OK(hipStreamSynchronize(nullptr));
     }
+    if (ix->row_value) {  // the value table describes the rows that leave
+        HIP_OK(hipSetDevice(ix->device));
+        HIP_OK(hipDeviceSynchronize());  // a read-out of the old rows may still run on some stream
+        (void)hipFree(ix->row_value);
+        ix->row_value = nullptr;
+        ix->value_rows = ix->value_cols = ix->value_c_pad = 0;
+    }
     ix->ntotal = 0;
     return 0;
 }
@@ -824,6 +836,69 @@ int vodhip_index_set_row_labels(vodhip_index_t* ix, const int32_t* labels, int64
     HIP_OK(hipMemcpyAsync(ix->row_label, labels, (size_t)n_rows * sizeof(int),
                           location == VODHIP_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, stream));
     HIP_OK(hipStreamSynchronize(stream));
+    return 0;
+}
+
+// the value table of vodhip_index_posterior_expectation: converted to the store dtype on the device, pad columns and pad rows zero
+int vodhip_index_set_row_values(vodhip_index_t* ix, const void* values, int64_t n_rows, int64_t n_cols, int src_dtype, int location, void* stream_) {
+    if (!ix) return fail("index is NULL");
+    std::lock_guard<std::mutex> guard(ix->mu);
+    if (!ix->inflight.empty() || ix->unfinished) return fail("%d searches are in flight: finish them before changing the row values", (int)ix->inflight.size() + ix->unfinished);
+    if (values) {
+        if (const char* msg = row_values_args_error(n_rows, n_cols, src_dtype, location, ix->ntotal)) {
+            if (!strcmp(msg, "invalid src_dtype")) return fail("invalid src_dtype %d", src_dtype);
+            if (!strcmp(msg, "invalid location")) return fail("invalid location %d", location);
+            if (msg[2] == 'c') return fail("n_cols=%lld: %s (wider tables are not supported)", (long long)n_cols, msg);
+            return fail("n_rows=%lld, ntotal=%lld: %s", (long long)n_rows, (long long)ix->ntotal, msg);
+        }
+    }
+    HIP_OK(hipSetDevice(ix->device));
+    hipStream_t stream = (hipStream_t)stream_;
+    HIP_OK(hipDeviceSynchronize());  // a read-out of the old table may still run on some stream (as in vodhip_index_reset)
+    (void)hipFree(ix->row_value);
+    ix->row_value = nullptr;
+    ix->value_rows = ix->value_cols = ix->value_c_pad = 0;
+    if (!values) return 0;
+    const int64_t c_pad = readout_c_pad(n_cols);
+    const int64_t rows_pad = std::max<int64_t>(1, scan_tiles(n_rows)) * 256;
+    uint16_t* table = nullptr;
+    HIP_OK(hipMalloc((void**)&table, (size_t)rows_pad * (size_t)c_pad * 2));
+    auto fill = [&]() -> hipError_t {
+        if (n_rows < rows_pad)
+            if (hipError_t e = hipMemsetAsync(table + (size_t)n_rows * c_pad, 0, (size_t)(rows_pad - n_rows) * (size_t)c_pad * 2, stream); e != hipSuccess) return e;
+        if (n_rows == 0) return hipSuccess;
+        const void* src = values;
+        void* staged = nullptr;
+        if (location == VODHIP_HOST) {
+            const size_t bytes = (size_t)n_rows * (size_t)n_cols * (size_t)elem_size(src_dtype);
+            if (hipError_t e = hipMalloc(&staged, bytes); e != hipSuccess) return e;
+            if (hipError_t e = hipMemcpyAsync(staged, values, bytes, hipMemcpyHostToDevice, stream); e != hipSuccess) {
+                (void)hipFree(staged);
+                return e;
+            }
+            src = staged;
+        }
+        hipError_t e = launch_convert_rows(src, src_dtype, n_rows, n_cols, table, ix->dtype, c_pad, stream);
+        const hipError_t se = hipStreamSynchronize(stream);
+        if (staged) (void)hipFree(staged);
+        return e != hipSuccess ? e : se;
+    };
+    if (hipError_t e = fill(); e != hipSuccess) {
+        (void)hipGetLastError();
+        (void)hipFree(table);
+        return fail("building the row-value table failed: %s", hipGetErrorString(e));
+    }
+    ix->row_value = table;
+    ix->value_rows = n_rows;
+    ix->value_cols = n_cols;
+    ix->value_c_pad = c_pad;
+    return 0;
+}
+
+int vodhip_index_row_values_info(const vodhip_index_t* ix, int64_t* n_rows, int64_t* n_cols) {
+    if (!ix) return fail("index is NULL");
+    if (n_rows) *n_rows = ix->row_value ? ix->value_rows : 0;
+    if (n_cols) *n_cols = ix->row_value ? ix->value_cols : 0;
     return 0;
 }
 
@@ -1567,6 +1642,48 @@ int vodhip_index_posterior_mean(vodhip_index_t* ix, const void* queries, int q_d
     if (le != hipSuccess) (void)hipGetLastError();
     const hipError_t fe = tmp.release();
     if (le != hipSuccess) return fail("posterior-mean launch failed: %s", hipGetErrorString(le));
+    HIP_OK(fe);
+    return 0;
+}
+
+// ---- posterior read-out (kernels_readout.hip): ONE scan - partition partials, running-maximum value accumulators - and two finishes ----
+int vodhip_index_posterior_expectation(vodhip_index_t* ix, const void* queries, int q_dtype, int64_t nq, float beta, const int32_t* q_labels_dev,
+                                       int n_per_query, float* out_max, float* out_log_rel, float* out_values, void* stream_) {
+    if (!ix) return fail("index is NULL");
+    if (const char* msg = posterior_expectation_args_error(queries, q_dtype, nq, beta, q_labels_dev, n_per_query, out_max, out_log_rel, out_values))
+        return partition_args_fail(msg, q_dtype, beta);
+    if (scan_refusal(ix, "posterior_expectation", q_labels_dev)) return -1;
+    if (!ix->row_value) return fail("posterior_expectation: the index has no value table (vodhip_index_set_row_values)");
+    if (ix->value_rows != ix->ntotal)
+        return fail("posterior_expectation: the value table holds %lld rows, the index %lld: set the table again after adding rows", (long long)ix->value_rows,
+                    (long long)ix->ntotal);
+    if (nq == 0) return 0;
+    HIP_OK(hipSetDevice(ix->device));
+    hipStream_t stream = (hipStream_t)stream_;
+    ReadoutArgs a;
+    fill_scan_inputs(a.p, ix, queries, q_dtype, q_labels_dev, n_per_query);
+    a.p.beta = beta;
+    a.p.out_max = out_max;
+    a.p.out_log_rel = out_log_rel;
+    a.values = ix->row_value;
+    a.n_cols = (int)ix->value_cols;
+    a.c_pad = (int)ix->value_c_pad;
+    a.out_values = out_values;
+    const size_t acc_per_query = std::max<size_t>(1, (size_t)readout_groups(a.p.ntotal)) * (size_t)a.c_pad * sizeof(float);  // the group accumulators
+    const size_t part_per_query = std::max<size_t>(1, (size_t)scan_tiles(a.p.ntotal)) * 8;                                 // the partition partials
+    const int64_t slice = scan_slice_queries(acc_per_query + part_per_query);
+    const int64_t nq_pad = scan_nq_pad(std::min(nq, slice));
+    ScanTemps tmp;
+    tmp.stream = stream;
+    if (tmp.alloc({(size_t)nq_pad * (size_t)ix->dim_pad * 2, part_per_query * (size_t)nq_pad, acc_per_query * (size_t)nq_pad})) return -1;
+    a.p.q_stage = tmp.p[0];
+    a.p.part = tmp.p[1];
+    a.acc = (float*)tmp.p[2];
+    hipError_t le = hipSuccess;
+    for (int64_t q0 = 0; q0 < nq && le == hipSuccess; q0 += slice) le = launch_posterior_expectation(a, q0, std::min(slice, nq - q0), stream);
+    if (le != hipSuccess) (void)hipGetLastError();
+    const hipError_t fe = tmp.release();
+    if (le != hipSuccess) return fail("posterior-expectation launch failed: %s", hipGetErrorString(le));
     HIP_OK(fe);
     return 0;
 }

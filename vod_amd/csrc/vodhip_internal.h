@@ -266,6 +266,8 @@ struct PartitionArgs : ScanInputs {
 };
 // queries [q_first, q_first + nq) of the caller's batch -> out_max / out_log_rel [q_first ..); a query's bits do not depend on the split
 hipError_t launch_log_partition(const PartitionArgs& a, int64_t q_first, int64_t nq, hipStream_t stream);
+// its last launch alone: a.part (written by any scan that restates the partition epilogue) -> out_max / out_log_rel [q_first ..)
+hipError_t launch_partition_finish(const PartitionArgs& a, int64_t q_first, int64_t nq, hipStream_t stream);
 
 // ---- launchers (kernels_stats.hip): the log-partition pair plus the posterior mean and variance of the score ----
 struct StatsArgs : ScanInputs {
@@ -339,6 +341,19 @@ int64_t posterior_mean_groups(int64_t ntotal);
 // queries [q_first, q_first + nq) of the caller's batch -> out_max / out_log_rel (the bits of launch_log_partition) and out_mean rows
 // [q_first ..); a query's bits do not depend on the split
 hipError_t launch_posterior_mean(const PosteriorArgs& a, int64_t q_first, int64_t nq, hipStream_t stream);
+
+// ---- launchers (kernels_readout.hip): the posterior expectation of a per-row value table, sum_z p(z | q) v_z, in ONE scan ----------
+struct ReadoutArgs {
+    PartitionArgs p;                  // what the log-partition call of the same batch takes: `part` is written by the read-out scan itself
+    const void* values = nullptr;     // the table [>= round_up(ntotal, 256) rows][c_pad] of the store dtype, zero padded
+    int n_cols = 0, c_pad = 0;        // 1 <= n_cols <= c_pad = 64 * ceil(n_cols / 64) <= 256
+    float* acc = nullptr;             // temporary: readout_groups(ntotal) * scan_nq_pad(nq) * c_pad floats
+    float* out_values = nullptr;      // [rows of the caller's batch][n_cols]
+};
+int64_t readout_groups(int64_t ntotal);
+// queries [q_first, q_first + nq) of the caller's batch -> out_max / out_log_rel (the bits of launch_log_partition) and out_values rows
+// [q_first ..); a query's bits do not depend on the split
+hipError_t launch_posterior_expectation(const ReadoutArgs& a, int64_t q_first, int64_t nq, hipStream_t stream);
 
 // ---- launchers (kernels_sample_posterior.hip): k rows without replacement from p(z | q) over the whole store --------------------
 struct PosteriorSampleArgs {

@@ -24,6 +24,7 @@
 #include "range_fold.h"
 #include "stats_fold.h"
 #include "divergence_fold.h"
+#include "readout_fold.h"
 #include "vodhip_internal.h"
 
 namespace {
@@ -107,6 +108,7 @@ struct vodhip_node_index {
     const int32_t* q_labels = nullptr;  // the caller's per-query labels for the next searches (host, or devices[0])
     int q_labels_per_query = 0, q_labels_location = VODHIP_HOST;
     bool has_row_labels = false;
+    int64_t value_rows = 0, value_cols = 0;  // the value table of the posterior read-out as it was set (0, 0: none); the shards hold its rows
     // topology (read once at create): can devices[0] and shard g's device copy into each other's memory directly?  A shard without
     // peer access - or every shard but the first with `host_staging` set (bring-up, tests on a 1-GPU box) - exchanges its queries and
     // its top-k list with devices[0] through pinned host memory instead (two DMA hops over PCIe, no xGMI)
@@ -418,6 +420,7 @@ int vodhip_node_index_reset(vodhip_node_index_t* nx) {
     for (int g = 0; g < nx->n; ++g)
         if (vodhip_index_reset(nx->shard[g])) return -1;
     nx->ntotal = 0;
+    nx->value_rows = nx->value_cols = 0;  // (every shard dropped its part of the value table)
     return 0;
 }
 
@@ -452,6 +455,44 @@ int vodhip_node_index_set_row_labels(vodhip_node_index_t* nx, const int32_t* lab
     }
     nx->has_row_labels = labels != nullptr;
     if (!labels) nx->q_labels = nullptr;
+    return 0;
+}
+
+// The value table of the posterior read-out behind the one handle: a HOST table for the global rows, split by shard row ranges
+// (readout_fold.h).
+int vodhip_node_index_set_row_values(vodhip_node_index_t* nx, const void* values, int64_t n_rows, int64_t n_cols, int src_dtype) {
+    if (!nx) return nfail("index is NULL");
+    std::lock_guard<std::mutex> guard(nx->mu);
+    if (nx->n_pending) return nfail("%d searches are in flight: finish them before changing the row values", nx->n_pending);
+    if (values) {
+        if (const char* msg = vodhip::row_values_args_error(n_rows, n_cols, src_dtype, VODHIP_HOST, nx->ntotal)) {
+            if (!strcmp(msg, "invalid src_dtype")) return nfail("invalid src_dtype %d", src_dtype);
+            if (msg[2] == 'c') return nfail("n_cols=%lld: %s (wider tables are not supported)", (long long)n_cols, msg);
+            return nfail("n_rows=%lld, ntotal=%lld: %s", (long long)n_rows, (long long)nx->ntotal, msg);
+        }
+    }
+    nx->value_rows = nx->value_cols = 0;
+    for (int g = 0; g < nx->n; ++g) {
+        int64_t lo = 0, hi = 0;
+        if (values) vodhip::readout_shard_rows(n_rows, nx->rows_per_shard, g, &lo, &hi);
+        if (!values) {
+            if (vodhip_index_set_row_values(nx->shard[g], nullptr, 0, 0, 0, VODHIP_HOST, nx->stream[g])) return -1;
+        } else {  // (a shard past the table's end holds no row: it gets a table of no rows and reads out the zero row)
+            const char* src = (const char*)values + (size_t)lo * (size_t)n_cols * elem_bytes(src_dtype);
+            if (vodhip_index_set_row_values(nx->shard[g], src, hi - lo, n_cols, src_dtype, VODHIP_HOST, nx->stream[g])) return -1;
+        }
+    }
+    if (values) {
+        nx->value_rows = n_rows;
+        nx->value_cols = n_cols;
+    }
+    return 0;
+}
+
+int vodhip_node_index_row_values_info(const vodhip_node_index_t* nx, int64_t* n_rows, int64_t* n_cols) {
+    if (!nx) return nfail("index is NULL");
+    if (n_rows) *n_rows = nx->value_cols ? nx->value_rows : 0;
+    if (n_cols) *n_cols = nx->value_cols;
     return 0;
 }
 
@@ -1174,6 +1215,37 @@ int vodhip_node_index_posterior_mean(vodhip_node_index_t* nx, const void* querie
     vodhip::fold_log_partition(parts.data(), parts.data() + nq, G, (int64_t)per_shard, nq, beta, out_max, out_log_rel);
     vodhip::fold_posterior_mean(parts.data(), parts.data() + nq, parts.data() + 2 * nq, G, (int64_t)per_shard, (int64_t)per_shard, nq, (int64_t)dim, beta,
                                 out_max, out_log_rel, out_mean);
+    return 0;
+}
+
+// The posterior read-out behind the one handle (H2e): as the posterior mean, with n_cols value columns in place of the dim row columns.
+// A shard that holds no row returns (-inf, -inf, zeros), the weight-0 part of the fold.
+int vodhip_node_index_posterior_expectation(vodhip_node_index_t* nx, const void* queries, int q_dtype, int64_t nq, float beta, const int32_t* q_labels,
+                                            int n_per_query, float* out_max, float* out_log_rel, float* out_values) {
+    if (!nx) return nfail("index is NULL");
+    if (const char* msg = vodhip::posterior_expectation_args_error(queries, q_dtype, nq, beta, q_labels, n_per_query, out_max, out_log_rel, out_values))
+        return node_partition_args_fail(msg, q_dtype, beta);
+    if (node_scan_refusal(nx, "posterior_expectation")) return -1;
+    std::lock_guard<std::mutex> guard(nx->mu);
+    if (node_labels_refusal(nx, q_labels)) return -1;
+    if (!nx->value_cols) return nfail("posterior_expectation: the index has no value table (vodhip_node_index_set_row_values)");
+    if (nx->value_rows != nx->ntotal)
+        return nfail("posterior_expectation: the value table holds %lld rows, the index %lld: set the table again after adding rows",
+                     (long long)nx->value_rows, (long long)nx->ntotal);
+    if (nq == 0) return 0;
+    const int G = nx->n;
+    const size_t n_cols = (size_t)nx->value_cols;
+    const size_t per_shard = (size_t)nq * (2 + n_cols);  // shard g: [max | log_rel | value rows] at g * per_shard
+    std::vector<float> parts((size_t)G * per_shard);
+    ShardFanout f(nx);
+    const int iq = f.input(queries, query_bytes(nx, nq, q_dtype)), il = f.input(q_labels, label_bytes(q_labels, nq, n_per_query));
+    const int io = f.output(parts.data(), per_shard * sizeof(float));
+    if (f.run([&](int g, void* const* p, hipStream_t st) {
+            float* out = (float*)p[io];
+            return vodhip_index_posterior_expectation(nx->shard[g], p[iq], q_dtype, nq, beta, (const int32_t*)p[il], n_per_query, out, out + nq, out + 2 * nq, st);
+        }))
+        return -1;
+    vodhip::fold_posterior_expectation(parts.data(), G, nq, (int64_t)n_cols, beta, out_max, out_log_rel, out_values);
     return 0;
 }
 

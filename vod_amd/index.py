@@ -188,6 +188,45 @@ class HipFlatIndex:
             _native.check(self._lib.vodhip_index_set_row_labels(self._h, lab.ctypes.data, lab.size, _native.HOST,
                                                                 _native.current_stream_ptr(self.device)))
 
+    # -- value table of the posterior read-out ---------------------------------------------------------
+    def set_row_values(self, values: np.ndarray | torch.Tensor | None) -> None:
+        """Attach a value row `[n_cols]` (1 <= n_cols <= 256) to every stored row: `values` is `[ntotal, n_cols]` (a vector is one
+        column), NumPy or torch, host or device, fp16 / bf16 / fp32 (anything else is cast to fp32); None clears.  The index keeps a copy
+        in the store dtype, rounded as the rows are.  `reset` drops the table, `save` / `load` do not carry it, and rows added afterwards
+        leave it short (`posterior_expectation` then refuses).  Needed before `posterior_expectation`."""
+        with torch.cuda.device(self.device):
+            stream = _native.current_stream_ptr(self.device)
+            if values is None:
+                _native.check(self._lib.vodhip_index_set_row_values(self._h, None, 0, 0, 0, _native.HOST, stream))
+                return
+            if isinstance(values, torch.Tensor):
+                v = values.detach()
+                v = v.reshape(-1, 1) if v.ndim == 1 else v
+                if v.ndim != 2:
+                    raise ValueError(f"expected [ntotal, n_cols] values, got {tuple(values.shape)}")
+                if v.dtype not in (torch.float16, torch.bfloat16, torch.float32):
+                    v = v.float()
+                v = v.to(self.device).contiguous() if v.is_cuda else v.contiguous()
+                src = v if v.numel() else v.new_zeros(1)  # (a table of no rows is still a table: NULL would clear it)
+                _native.check(self._lib.vodhip_index_set_row_values(self._h, src.data_ptr(), v.shape[0], v.shape[1], _native.torch_dtype_code(v.dtype),
+                                                                    _native.DEVICE if v.is_cuda else _native.HOST, stream))
+                return
+            v = np.asarray(values)
+            v = v.reshape(-1, 1) if v.ndim == 1 else v
+            if v.ndim != 2:
+                raise ValueError(f"expected [ntotal, n_cols] values, got {tuple(v.shape)}")
+            if v.dtype not in (np.float32, np.float16):
+                v = v.astype(np.float32)
+            v = np.ascontiguousarray(v)
+            src = v if v.size else np.zeros(1, dtype=v.dtype)  # (a table of no rows is still a table: NULL would clear it)
+            _native.check(self._lib.vodhip_index_set_row_values(self._h, src.ctypes.data, v.shape[0], v.shape[1],
+                                                                2 if v.dtype == np.float32 else 0, _native.HOST, stream))
+
+    @property
+    def row_values_shape(self) -> tuple[int, int] | None:
+        """`(n_rows, n_cols)` of the value table, or None when there is none."""
+        return _row_values_shape(self._lib.vodhip_index_row_values_info, self._h)
+
     # -- persistence (SURVEY 8f-1: the store itself is the on-disk format, no faiss file round trip) -----------
     def save(self, path, chunk: int = 1 << 20) -> None:
         """Write the stored rows (as stored: fp16, or bf16 widened to fp32; the float32 rows of an `exact_f32` store - what
@@ -708,6 +747,45 @@ class HipFlatIndex:
                 t.record_stream(torch.cuda.current_stream(self.device))
         return PosteriorMean(mean, LogPartition(max_score * beta + log_rel, max_score, log_rel))
 
+    def posterior_expectation(self, queries, temperature: float = 1.0, subset=None, out=None) -> "PosteriorExpectation":
+        """The posterior expectation of the value table (`set_row_values`) under the softmax over the WHOLE store, `values[q] =
+        sum_z p(z | q) v~_z` with `p(z | q) = exp(<q~, x~_z> / temperature - log Z(q))`: `PosteriorExpectation(values, log_partition)`,
+        `values` a float32 device tensor `[nq, n_cols]`, `log_partition` the `LogPartition` that `log_partition` returns for the same
+        call, bit for bit.  Exact attention with the store as keys and the table as values: a one-hot table gives the posterior mass per
+        class, a score table the expected score, a projected copy of the rows a posterior mean in that space.  ONE scan on the MFMA path
+        (running maximum with rescaling), no `[nq, N]` matrix; a `values` row is the same bits whatever the batch around it.  A query with
+        no eligible row (or a +inf score) gets the zero row.  A NaN / infinity in column c of the table makes column c of every query NaN
+        (the library's contract, `vodhip.h` H2e).  Not differentiable: the gradient in the query needs the cross moments `E_p[v x]`.
+
+        Arguments as `log_partition`; `out`: a (max_score, log_rel, values) triple to write into."""
+        q = self._prep_queries(queries)
+        nq = q.shape[0]
+        beta = 1.0 / float(temperature) if temperature else float("nan")
+        sub, n_sub = None, 0
+        if subset is not None:
+            sub = subset if isinstance(subset, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(subset))
+            sub = sub.to(self.device, torch.int32).contiguous()
+            if sub.ndim != 2 or sub.shape[0] != nq:
+                raise ValueError(f"expected subset labels of shape [{nq}, S], got {tuple(sub.shape)}")
+            n_sub = int(sub.shape[1])
+        shape = self.row_values_shape
+        n_cols = shape[1] if shape else 0
+        if out is None:
+            max_score = torch.empty((nq,), dtype=torch.float32, device=self.device)
+            log_rel = torch.empty((nq,), dtype=torch.float32, device=self.device)
+            values = torch.empty((nq, n_cols), dtype=torch.float32, device=self.device)
+        else:
+            max_score, log_rel, values = out
+        with torch.cuda.device(self.device):
+            _native.check(self._lib.vodhip_index_posterior_expectation(
+                self._h, q.data_ptr(), _native.torch_dtype_code(q.dtype), nq, beta, None if sub is None else sub.data_ptr(), n_sub,
+                max_score.data_ptr(), log_rel.data_ptr(), (values if values.numel() else max_score.new_empty(1)).data_ptr(),
+                _native.current_stream_ptr(self.device)))  # (no table: a non-NULL pointer, so that the library's own refusal names it)
+        for t, given in ((q, queries), (sub, subset)):
+            if t is not None and t is not given:
+                t.record_stream(torch.cuda.current_stream(self.device))
+        return PosteriorExpectation(values, LogPartition(max_score * beta + log_rel, max_score, log_rel))
+
     def sample_posterior(self, queries, k: int, temperature: float = 1.0, *, seed: int, query_offset: int = 0, subset=None,
                          id_base: int = 0, out=None) -> "PosteriorSample":
         """`k` rows drawn WITHOUT replacement from the softmax over the WHOLE store, `p(z | q) = exp(<q~, x~_z> / temperature - log Z(q))`,
@@ -844,6 +922,19 @@ class PosteriorMean(NamedTuple):
 
     mean: Any
     log_partition: LogPartition
+
+
+class PosteriorExpectation(NamedTuple):
+    """`values[q] = sum_z p(z | q) v_z` (`[nq, n_cols]`) of `posterior_expectation`, with the `LogPartition` of the same call."""
+
+    values: Any
+    log_partition: LogPartition
+
+
+def _row_values_shape(info, handle) -> "tuple[int, int] | None":
+    n_rows, n_cols = ctypes.c_int64(0), ctypes.c_int64(0)
+    _native.check(info(handle, ctypes.byref(n_rows), ctypes.byref(n_cols)))
+    return (int(n_rows.value), int(n_cols.value)) if n_cols.value else None
 
 
 class PosteriorStats(NamedTuple):
@@ -1233,6 +1324,31 @@ class HipNodeIndex:
         lab = np.ascontiguousarray(labels, dtype=np.int32)
         _native.check(self._lib.vodhip_node_index_set_row_labels(self._h, lab.ctypes.data, lab.size))
 
+    def set_row_values(self, values: np.ndarray | None) -> None:
+        """One value row per stored row (global row order, `[ntotal, n_cols]`, 1 <= n_cols <= 256; None clears), split by shard row
+        ranges: see `HipFlatIndex.set_row_values`."""
+        if values is None:
+            _native.check(self._lib.vodhip_node_index_set_row_values(self._h, None, 0, 0, 0))
+            return
+        if isinstance(values, torch.Tensor):
+            values = values.detach().float().cpu().numpy()
+        v = np.asarray(values)
+        v = v.reshape(-1, 1) if v.ndim == 1 else v
+        if v.ndim != 2:
+            raise ValueError(f"expected [ntotal, n_cols] values, got {tuple(v.shape)}")
+        if v.dtype not in (np.float32, np.float16):
+            v = v.astype(np.float32)
+        v = np.ascontiguousarray(v)
+        src = v if v.size else np.zeros(1, dtype=v.dtype)  # (a table of no rows is still a table: NULL would clear it)
+        with torch.cuda.device(self.device):
+            _native.check(self._lib.vodhip_node_index_set_row_values(self._h, src.ctypes.data, v.shape[0], v.shape[1],
+                                                                     2 if v.dtype == np.float32 else 0))
+
+    @property
+    def row_values_shape(self) -> tuple[int, int] | None:
+        """`(n_rows, n_cols)` of the value table, or None when there is none."""
+        return _row_values_shape(self._lib.vodhip_node_index_row_values_info, self._h)
+
     def _set_subset(self, subset: np.ndarray | None, nq: int):
         if subset is None:
             _native.check(self._lib.vodhip_node_index_set_query_labels(self._h, None, 0, 0))
@@ -1556,6 +1672,38 @@ class HipNodeIndex:
         with np.errstate(invalid="ignore"):
             log_z = (max_score * np.float32(beta) + log_rel).astype(np.float32)
         return PosteriorMean(mean, LogPartition(log_z, max_score, log_rel))
+
+    def posterior_expectation(self, queries, temperature: float = 1.0, subset: np.ndarray | None = None) -> "PosteriorExpectation":
+        """`HipFlatIndex.posterior_expectation` over every shard: each shard reads out its rows of the value table on its own device, the
+        shards are folded on the host in shard order, in double (`values = sum_g w_g values_g`).  Host queries ->
+        `PosteriorExpectation` of float32 NumPy arrays; `max_score` equals one index holding all the rows bit for bit."""
+        if isinstance(queries, torch.Tensor):
+            queries = queries.detach().float().cpu().numpy()
+        q = np.ascontiguousarray(queries)
+        if q.dtype not in (np.float32, np.float16):
+            q = q.astype(np.float32)
+        if q.ndim != 2 or q.shape[1] != self.dim:
+            raise ValueError(f"expected [nq, {self.dim}] queries, got {tuple(q.shape)}")
+        nq = int(q.shape[0])
+        beta = 1.0 / float(temperature) if temperature else float("nan")
+        sub, n_sub = None, 0
+        if subset is not None:
+            sub = np.ascontiguousarray(subset.cpu().numpy() if isinstance(subset, torch.Tensor) else subset, dtype=np.int32)
+            if sub.ndim != 2 or sub.shape[0] != nq:
+                raise ValueError(f"subset must be int32 [nq, n_per_query], got {tuple(sub.shape)}")
+            n_sub = int(sub.shape[1])
+        shape = self.row_values_shape
+        n_cols = shape[1] if shape else 0
+        max_score = np.empty((nq,), dtype=np.float32)
+        log_rel = np.empty((nq,), dtype=np.float32)
+        values = np.empty((nq, max(n_cols, 1)), dtype=np.float32)[:, :n_cols]
+        with torch.cuda.device(self.device):
+            _native.check(self._lib.vodhip_node_index_posterior_expectation(
+                self._h, q.ctypes.data, 2 if q.dtype == np.float32 else 0, nq, beta, None if sub is None else sub.ctypes.data, n_sub,
+                max_score.ctypes.data, log_rel.ctypes.data, values.ctypes.data))
+        with np.errstate(invalid="ignore"):
+            log_z = (max_score * np.float32(beta) + log_rel).astype(np.float32)
+        return PosteriorExpectation(values, LogPartition(log_z, max_score, log_rel))
 
     def sample_posterior(self, queries, k: int, temperature: float = 1.0, *, seed: int, query_offset: int = 0,
                          subset: np.ndarray | None = None) -> "PosteriorSample":
