@@ -331,6 +331,44 @@ int vodhip_index_posterior_expectation(vodhip_index_t* index, const void* querie
                                        float* out_max /* DEVICE [nq] */, float* out_log_rel /* DEVICE [nq] */,
                                        float* out_values /* DEVICE [nq][n_cols] */, void* stream);
 
+/* H2b. The gradient of H2e's read-out in the QUERY (kernels_readout_grad.hip): with y = out_values of H2e, g = grad_values = dL / dy,
+ *     out_grad_queries[q, :] = beta * sum_{z < ntotal, eligible} p(z | q) (u_z - ubar_q) x~_z,
+ *     u_z = sum_c g[q, c] v~[z, c],   ubar_q = sum_c g[q, c] y[q, c]:
+ * a posterior mean with signed, centred per-(row, query) weights (the centring is inside the weight: a table column of ones cancels
+ * exactly, not catastrophically).  INPUTS: the queries, beta and labels of the forward call and its three outputs - max_score, log_rel
+ * (DEVICE [nq]) and values (DEVICE float32 [nq][n_cols]) - so no partition scan runs in front: ONE scan of the store.  Eligibility,
+ * queries, labels, stream and concurrency rules are H2p's; the table is the one H2e reads.
+ * g is staged per query: k_q = the exponent of max_c |g[q, c]|, g^ = g * 2^-k_q (exact; the largest entry in [1, 2), so a loss gradient
+ * of 1e-6 does not flush in fp16) rounded ONCE to the store dtype; ubar_q = float32 of sum_c g^ y summed in double in increasing c over
+ * the columns with g^ != 0; R_q = the power of two above (sum_c |g^[q, c]| vmax_c + |ubar_q|) (1 + 2^-10), vmax_c the largest finite
+ * |v~[., c]|, so that no weight exceeds 1.  vmax is computed by the first call after the table was set (one reduction; that call waits
+ * for `stream` once) and kept beside the table; setting, clearing or resetting the table drops it.
+ * The scan has H2e's geometry - groups of VODHIP_READOUT_GROUP_ROWS rows, 64 queries, the running maximum with rescaling - split over
+ * chunks of 192 store columns; per 256-row tile the scores and u come from the shared K loop (u with the table as rows and g^ as
+ * queries), the weights round16(e * gamma * ((u - ubar_q) / R_q)) are contracted with the tile's rows on the MFMA (float32 accumulate);
+ * the groups are folded in increasing order with expf(beta (M_g - max_score) - log_rel), M_g the group's own maximum, and the row is
+ * multiplied by beta and by 2^k_q R_q.  fp16 stores keep a weight as a normal fp16 number down to 2^-29 of the running maximum's.
+ * ONE order per (query, column), fixed by ntotal, the padded width of the store and c_pad alone: a row of the result is the same bits
+ * whatever the batch around it and on every repeat; there are no atomics.  Scaling g[q, :] by a power of two scales the row by exactly
+ * that power (unless it leaves float32's range).
+ * ZERO ROWS, exact bits: a query without a finite max_score (no eligible row, a +inf score), an all-zero g[q, :].
+ * NON-FINITE INPUT.  A NaN or an infinity in g[q, :] makes row q all NaN and leaves the other rows untouched; so does one in a y[q, c]
+ * whose g^[q, c] is not zero - H2e returns such a column for a non-finite table entry.  A NaN or an infinity in the table in a row that
+ * is ELIGIBLE for query q makes u of that row, and row q, NaN; in a row that is not eligible it does nothing through u (the weight is
+ * selected as +0 after the product).  A stored NaN or infinity in column d of any scanned tile makes column d of every scanned query
+ * NaN (H2m's contract: 0 * NaN on the MFMA).  There is no sanitising pass.
+ * out_grad_queries: DEVICE float32 [nq][dim].  Temporaries are hipMallocAsync on `stream`: the staged queries and g^, the group
+ * accumulators, groups * slice * dim_pad * 4 bytes, and the group maxima; batches run in slices of 64 .. 1024 queries chosen so that
+ * they stay at or below VODHIP_POSTERIOR_TEMP_BYTES unless a 64-query slice alone needs more.  The call only enqueues work (but see
+ * vmax).  nq == 0 returns 0 and writes nothing; a refused call writes nothing.  REFUSED as H2e, and: a NULL max_score, log_rel, values,
+ * grad_values or out_grad_queries.
+ * NOT BUILT: the gradient in beta, the gradient in the table, tables wider than VODHIP_READOUT_MAX_COLS, second derivatives. */
+int vodhip_index_posterior_expectation_backward(vodhip_index_t* index, const void* queries, int q_dtype, int64_t nq, float beta,
+                                                const int32_t* q_labels_dev /* NULL = unrestricted */, int n_per_query,
+                                                const float* max_score /* DEVICE [nq] */, const float* log_rel /* DEVICE [nq] */,
+                                                const float* values /* DEVICE [nq][n_cols] */, const float* grad_values /* DEVICE [nq][n_cols] */,
+                                                float* out_grad_queries /* DEVICE [nq][dim] */, void* stream);
+
 /* H2s. k rows drawn WITHOUT replacement from that softmax over the whole store, with priority-sampling weights
  * (kernels_sample_posterior.hip).  Gumbel-top-k: the k eligible rows with the largest keys
  *     key(q, z) = fl(fl(beta * s(q, z)) - logf(E)),   E = -log1pf(-v),   by (key desc, id asc),
@@ -657,6 +695,14 @@ int vodhip_node_index_row_values_info(const vodhip_node_index_t* index, int64_t*
 int vodhip_node_index_posterior_expectation(vodhip_node_index_t* index, const void* queries, int q_dtype, int64_t nq, float beta,
                                             const int32_t* q_labels /* HOST or NULL */, int n_per_query,
                                             float* out_max, float* out_log_rel /* HOST [nq] */, float* out_values /* HOST [nq][n_cols] */);
+/* H2b behind the one handle: HOST buffers, host-synchronous.  Every shard runs vodhip_index_posterior_expectation_backward on its own
+ * rows with the GLOBAL (max_score, log_rel, values) of vodhip_node_index_posterior_expectation, so the shard results simply add: they
+ * are folded on the host in increasing shard order, in double, and rounded once (readout_grad_fold.h).  Refusals as for the flat call. */
+int vodhip_node_index_posterior_expectation_backward(vodhip_node_index_t* index, const void* queries, int q_dtype, int64_t nq, float beta,
+                                                     const int32_t* q_labels /* HOST or NULL */, int n_per_query,
+                                                     const float* max_score, const float* log_rel /* HOST [nq] */,
+                                                     const float* values, const float* grad_values /* HOST [nq][n_cols] */,
+                                                     float* out_grad_queries /* HOST [nq][dim] */);
 /* H2s behind the one handle: HOST buffers, host-synchronous.  Every shard runs vodhip_index_sample_posterior with id_base = its first
  * global row; keys are unnormalised and the noise is a function of the global row, so the k + 1 best of the union of the shards'
  * lists ARE the k + 1 best of the whole store: ids, scores and keys equal one index holding all the rows bit for bit.  The pairs are

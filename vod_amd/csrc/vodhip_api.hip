@@ -25,6 +25,7 @@
 #include "stats_fold.h"
 #include "divergence_fold.h"
 #include "readout_fold.h"
+#include "readout_grad_fold.h"
 #include "search_plan.h"
 #include "vodhip_internal.h"
 
@@ -102,6 +103,10 @@ struct vodhip_index {
     // the value table of the posterior read-out (kernels_readout.hip): [round_up(value_rows, 256)][value_c_pad] of the store dtype, zero padded
     uint16_t* row_value = nullptr;
     int64_t value_rows = 0, value_cols = 0, value_c_pad = 0;
+    // beside it: the per-column maxima of the finite |v~| (kernels_readout_grad.hip), computed by the first backward call after the
+    // table was set (under `mu`) and dropped with the table
+    float* value_vmax = nullptr;     // [value_c_pad]
+    bool value_vmax_ready = false;
     const int* q_label = nullptr;    // caller-owned device [nq, n_qlab] for the next searches (optional)
     int n_qlab = 0;
     // host ingest pipeline: two slots of (pinned host staging, device staging of the raw dtype, completion event), one stream
@@ -631,6 +636,7 @@ int vodhip_index_destroy(vodhip_index_t* ix) {
     }
     (void)hipFree(ix->row_label);
     (void)hipFree(ix->row_value);
+    (void)hipFree(ix->value_vmax);
     (void)hipFree(ix->sample_ws);
     (void)hipFree(ix->ovf_q);
     (void)hipFree(ix->q_map);
@@ -743,7 +749,10 @@ int vodhip_index_reset(vodhip_index_t* ix) {
         HIP_OK(hipSetDevice(ix->device));
         HIP_OK(hipDeviceSynchronize());  // a read-out of the old rows may still run on some stream
         (void)hipFree(ix->row_value);
+        (void)hipFree(ix->value_vmax);
         ix->row_value = nullptr;
+        ix->value_vmax = nullptr;
+        ix->value_vmax_ready = false;
         ix->value_rows = ix->value_cols = ix->value_c_pad = 0;
     }
     ix->ntotal = 0;
@@ -856,7 +865,10 @@ int vodhip_index_set_row_values(vodhip_index_t* ix, const void* values, int64_t 
     hipStream_t stream = (hipStream_t)stream_;
     HIP_OK(hipDeviceSynchronize());  // a read-out of the old table may still run on some stream (as in vodhip_index_reset)
     (void)hipFree(ix->row_value);
+    (void)hipFree(ix->value_vmax);
     ix->row_value = nullptr;
+    ix->value_vmax = nullptr;
+    ix->value_vmax_ready = false;
     ix->value_rows = ix->value_cols = ix->value_c_pad = 0;
     if (!values) return 0;
     const int64_t c_pad = readout_c_pad(n_cols);
@@ -1685,6 +1697,76 @@ int vodhip_index_posterior_expectation(vodhip_index_t* ix, const void* queries, 
     const hipError_t fe = tmp.release();
     if (le != hipSuccess) return fail("posterior-expectation launch failed: %s", hipGetErrorString(le));
     HIP_OK(fe);
+    return 0;
+}
+
+// ---- the read-out's gradient in the query (kernels_readout_grad.hip): g staged, ONE scan behind the forward's words, one finish ----
+int vodhip_index_posterior_expectation_backward(vodhip_index_t* ix, const void* queries, int q_dtype, int64_t nq, float beta, const int32_t* q_labels_dev,
+                                                int n_per_query, const float* max_score, const float* log_rel, const float* values, const float* grad_values,
+                                                float* out_grad_queries, void* stream_) {
+    if (!ix) return fail("index is NULL");
+    if (const char* msg = posterior_expectation_backward_args_error(queries, q_dtype, nq, beta, q_labels_dev, n_per_query, max_score, log_rel, values, grad_values,
+                                                                    out_grad_queries))
+        return partition_args_fail(msg, q_dtype, beta);
+    if (scan_refusal(ix, "posterior_expectation_backward", q_labels_dev)) return -1;
+    if (!ix->row_value) return fail("posterior_expectation_backward: the index has no value table (vodhip_index_set_row_values)");
+    if (ix->value_rows != ix->ntotal)
+        return fail("posterior_expectation_backward: the value table holds %lld rows, the index %lld: set the table again after adding rows",
+                    (long long)ix->value_rows, (long long)ix->ntotal);
+    if (nq == 0) return 0;
+    HIP_OK(hipSetDevice(ix->device));
+    hipStream_t stream = (hipStream_t)stream_;
+    {  // the column maxima of the table: once per table; the first call waits for them, so that a later call on any stream may read them
+        std::lock_guard<std::mutex> guard(ix->mu);
+        if (!ix->value_vmax_ready) {
+            if (!ix->value_vmax) HIP_OK(hipMalloc((void**)&ix->value_vmax, (size_t)ix->value_c_pad * sizeof(float)));
+            const hipError_t e = launch_readout_grad_vmax(ix->row_value, ix->value_rows, (int)ix->value_c_pad, ix->dtype, ix->value_vmax, stream);
+            if (e != hipSuccess) {
+                (void)hipGetLastError();
+                return fail("posterior-expectation-backward launch failed: %s", hipGetErrorString(e));
+            }
+            HIP_OK(hipStreamSynchronize(stream));
+            ix->value_vmax_ready = true;
+        }
+    }
+    ReadoutGradArgs a;
+    fill_scan_inputs(a.p, ix, queries, q_dtype, q_labels_dev, n_per_query);
+    a.p.beta = beta;
+    a.p.out_max = const_cast<float*>(max_score);  // (read only: ReadoutGradArgs)
+    a.p.out_log_rel = const_cast<float*>(log_rel);
+    a.values = ix->row_value;
+    a.n_cols = (int)ix->value_cols;
+    a.c_pad = (int)ix->value_c_pad;
+    a.vmax = ix->value_vmax;
+    a.y = values;
+    a.g = grad_values;
+    a.out_grad = out_grad_queries;
+    const size_t groups = std::max<size_t>(1, (size_t)readout_groups(a.p.ntotal));
+    const size_t acc_per_query = groups * (size_t)ix->dim_pad * sizeof(float);  // the group accumulators
+    const size_t mg_per_query = groups * sizeof(float);                          // the group maxima
+    const size_t small_per_query = (size_t)a.c_pad * 2 + readout_grad_aux_bytes();
+    const int64_t slice = scan_slice_queries(acc_per_query + mg_per_query + small_per_query);
+    const int64_t nq_pad = scan_nq_pad(std::min(nq, slice));
+    ScanTemps tmp, tmp2;
+    tmp.stream = tmp2.stream = stream;
+    if (tmp.alloc({(size_t)nq_pad * (size_t)ix->dim_pad * 2, acc_per_query * (size_t)nq_pad, mg_per_query * (size_t)nq_pad, (size_t)nq_pad * (size_t)a.c_pad * 2})) return -1;
+    if (tmp2.alloc({(size_t)nq_pad * readout_grad_aux_bytes()})) {
+        (void)tmp.release();
+        return -1;
+    }
+    a.p.q_stage = tmp.p[0];
+    a.acc = (float*)tmp.p[1];
+    a.mg = (float*)tmp.p[2];
+    a.g_stage = tmp.p[3];
+    a.aux = tmp2.p[0];
+    hipError_t le = hipSuccess;
+    for (int64_t q0 = 0; q0 < nq && le == hipSuccess; q0 += slice) le = launch_posterior_expectation_backward(a, q0, std::min(slice, nq - q0), stream);
+    if (le != hipSuccess) (void)hipGetLastError();
+    const hipError_t fe = tmp.release();
+    const hipError_t fe2 = tmp2.release();
+    if (le != hipSuccess) return fail("posterior-expectation-backward launch failed: %s", hipGetErrorString(le));
+    HIP_OK(fe);
+    HIP_OK(fe2);
     return 0;
 }
 

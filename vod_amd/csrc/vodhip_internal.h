@@ -355,6 +355,27 @@ int64_t readout_groups(int64_t ntotal);
 // [q_first ..); a query's bits do not depend on the split
 hipError_t launch_posterior_expectation(const ReadoutArgs& a, int64_t q_first, int64_t nq, hipStream_t stream);
 
+// ---- launchers (kernels_readout_grad.hip): the gradient of that read-out in the query, ONE scan behind the forward's words ---------
+struct ReadoutGradArgs {
+    PartitionArgs p;                  // the forward's call; out_max / out_log_rel are INPUTS here (the forward's words), `part` is unused
+    const void* values = nullptr;     // the table, as ReadoutArgs
+    int n_cols = 0, c_pad = 0;
+    const float* vmax = nullptr;      // [c_pad] the largest finite |v~| per column (launch_readout_grad_vmax)
+    const float* y = nullptr;         // [rows of the caller's batch][n_cols]: the forward's values
+    const float* g = nullptr;         // the same shape: dL / dy
+    // temporaries, sized for P = scan_nq_pad(queries of a launch)
+    void* g_stage = nullptr;          // P * c_pad 16-bit words
+    void* aux = nullptr;              // P * readout_grad_aux_bytes()
+    float* acc = nullptr;             // readout_groups(ntotal) * P * dim_pad floats
+    float* mg = nullptr;              // readout_groups(ntotal) * P floats
+    float* out_grad = nullptr;        // [rows of the caller's batch][dim]
+};
+size_t readout_grad_aux_bytes();
+// vmax [c_pad] <- the per-column maxima of the finite |v~| over n_rows rows of the table
+hipError_t launch_readout_grad_vmax(const void* values, int64_t n_rows, int c_pad, int store_dtype, float* vmax, hipStream_t stream);
+// queries [q_first, q_first + nq) of the caller's batch -> out_grad rows [q_first ..); a query's bits do not depend on the split
+hipError_t launch_posterior_expectation_backward(const ReadoutGradArgs& a, int64_t q_first, int64_t nq, hipStream_t stream);
+
 // ---- launchers (kernels_sample_posterior.hip): k rows without replacement from p(z | q) over the whole store --------------------
 struct PosteriorSampleArgs {
     PartitionArgs p;                  // the log-partition call of the same batch: its launches run first, unchanged

@@ -25,6 +25,7 @@
 #include "stats_fold.h"
 #include "divergence_fold.h"
 #include "readout_fold.h"
+#include "readout_grad_fold.h"
 #include "vodhip_internal.h"
 
 namespace {
@@ -1246,6 +1247,41 @@ int vodhip_node_index_posterior_expectation(vodhip_node_index_t* nx, const void*
         }))
         return -1;
     vodhip::fold_posterior_expectation(parts.data(), G, nq, (int64_t)n_cols, beta, out_max, out_log_rel, out_values);
+    return 0;
+}
+
+// The read-out's gradient behind the one handle (H2b): every shard runs the flat call on its own rows with the GLOBAL forward words, so
+// the shard results add (readout_grad_fold.h).  A shard that holds no row returns zeros.
+int vodhip_node_index_posterior_expectation_backward(vodhip_node_index_t* nx, const void* queries, int q_dtype, int64_t nq, float beta, const int32_t* q_labels,
+                                                     int n_per_query, const float* max_score, const float* log_rel, const float* values, const float* grad_values,
+                                                     float* out_grad_queries) {
+    if (!nx) return nfail("index is NULL");
+    if (const char* msg = vodhip::posterior_expectation_backward_args_error(queries, q_dtype, nq, beta, q_labels, n_per_query, max_score, log_rel, values,
+                                                                            grad_values, out_grad_queries))
+        return node_partition_args_fail(msg, q_dtype, beta);
+    if (node_scan_refusal(nx, "posterior_expectation_backward")) return -1;
+    std::lock_guard<std::mutex> guard(nx->mu);
+    if (node_labels_refusal(nx, q_labels)) return -1;
+    if (!nx->value_cols) return nfail("posterior_expectation_backward: the index has no value table (vodhip_node_index_set_row_values)");
+    if (nx->value_rows != nx->ntotal)
+        return nfail("posterior_expectation_backward: the value table holds %lld rows, the index %lld: set the table again after adding rows",
+                     (long long)nx->value_rows, (long long)nx->ntotal);
+    if (nq == 0) return 0;
+    const int G = nx->n;
+    const size_t n_cols = (size_t)nx->value_cols, dim = (size_t)nx->dim;
+    const size_t per_shard = (size_t)nq * dim;
+    std::vector<float> parts((size_t)G * per_shard);
+    ShardFanout f(nx);
+    const int iq = f.input(queries, query_bytes(nx, nq, q_dtype)), il = f.input(q_labels, label_bytes(q_labels, nq, n_per_query));
+    const int im = f.input(max_score, (size_t)nq * sizeof(float)), ir = f.input(log_rel, (size_t)nq * sizeof(float));
+    const int iy = f.input(values, (size_t)nq * n_cols * sizeof(float)), ig = f.input(grad_values, (size_t)nq * n_cols * sizeof(float));
+    const int io = f.output(parts.data(), per_shard * sizeof(float));
+    if (f.run([&](int g, void* const* p, hipStream_t st) {
+            return vodhip_index_posterior_expectation_backward(nx->shard[g], p[iq], q_dtype, nq, beta, (const int32_t*)p[il], n_per_query, (const float*)p[im],
+                                                               (const float*)p[ir], (const float*)p[iy], (const float*)p[ig], (float*)p[io], st);
+        }))
+        return -1;
+    vodhip::fold_posterior_expectation_backward(parts.data(), G, nq, (int64_t)dim, out_grad_queries);
     return 0;
 }
 

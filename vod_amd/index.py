@@ -755,7 +755,7 @@ class HipFlatIndex:
         class, a score table the expected score, a projected copy of the rows a posterior mean in that space.  ONE scan on the MFMA path
         (running maximum with rescaling), no `[nq, N]` matrix; a `values` row is the same bits whatever the batch around it.  A query with
         no eligible row (or a +inf score) gets the zero row.  A NaN / infinity in column c of the table makes column c of every query NaN
-        (the library's contract, `vodhip.h` H2e).  Not differentiable: the gradient in the query needs the cross moments `E_p[v x]`.
+        (the library's contract, `vodhip.h` H2e).  Forward only: `expected_values` is the same read-out with its gradient in the query.
 
         Arguments as `log_partition`; `out`: a (max_score, log_rel, values) triple to write into."""
         q = self._prep_queries(queries)
@@ -785,6 +785,61 @@ class HipFlatIndex:
             if t is not None and t is not given:
                 t.record_stream(torch.cuda.current_stream(self.device))
         return PosteriorExpectation(values, LogPartition(max_score * beta + log_rel, max_score, log_rel))
+
+    def posterior_expectation_backward(self, queries, grad_values, expectation: "PosteriorExpectation", temperature: float = 1.0,
+                                       subset=None, out=None) -> torch.Tensor:
+        """The gradient of `posterior_expectation` in the queries: with `y = expectation.values` and `g = grad_values = dL / dy`,
+        `grad[q] = sum_z p(z | q) (u_z - ubar_q) x~_z / temperature`, `u_z = <g[q], v~_z>`, `ubar_q = <g[q], y[q]>` - a float32 device
+        tensor `[nq, dim]`.  `expectation` is what `posterior_expectation` returned for the same queries, temperature and subset: its
+        `values`, `max_score` and `log_rel` are inputs, so ONE scan of the store runs and no partition scan in front.  Exact over every
+        stored row, no `[nq, N]` matrix; a row is the same bits whatever the batch around it; scaling a row of `g` by a power of two
+        scales the result by exactly that power (each row is normalised before it is rounded to the store dtype, so small loss gradients
+        do not flush in fp16).  A query with no eligible row (or a +inf score) and an all-zero `g` row give the zero row; a NaN or an
+        infinity in `g[q]` makes row `q` NaN (the library's contract, `vodhip.h` H2b).  The first call after `set_row_values` computes
+        the table's column maxima and waits for the stream once.
+
+        Other arguments as `posterior_expectation`; `out`: a float32 `[nq, dim]` device tensor to write into."""
+        q = self._prep_queries(queries)
+        nq = q.shape[0]
+        beta = 1.0 / float(temperature) if temperature else float("nan")
+        sub, n_sub = None, 0
+        if subset is not None:
+            sub = subset if isinstance(subset, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(subset))
+            sub = sub.to(self.device, torch.int32).contiguous()
+            if sub.ndim != 2 or sub.shape[0] != nq:
+                raise ValueError(f"expected subset labels of shape [{nq}, S], got {tuple(sub.shape)}")
+            n_sub = int(sub.shape[1])
+        y = torch.as_tensor(expectation.values).to(self.device, torch.float32).contiguous()
+        g = torch.as_tensor(grad_values).to(self.device, torch.float32).contiguous()
+        if y.ndim != 2 or y.shape[0] != nq or g.shape != y.shape:
+            raise ValueError(f"expected values and grad_values of one shape [{nq}, n_cols], got {tuple(y.shape)} and {tuple(g.shape)}")
+        shape = self.row_values_shape
+        if shape is not None and y.shape[1] != shape[1]:
+            raise ValueError(f"expected grad_values of shape [{nq}, {shape[1]}] (the table's columns), got {tuple(g.shape)}")
+        max_score = torch.as_tensor(expectation.log_partition.max_score).to(self.device, torch.float32).contiguous()
+        log_rel = torch.as_tensor(expectation.log_partition.log_rel).to(self.device, torch.float32).contiguous()
+        if max_score.shape != (nq,) or log_rel.shape != (nq,):
+            raise ValueError(f"expected max_score and log_rel of shape ({nq},)")
+        grad = torch.empty((nq, self.dim), dtype=torch.float32, device=self.device) if out is None else out
+        spare = max_score.new_empty(1)  # (no table: non-NULL pointers, so that the library's own refusal names it)
+        with torch.cuda.device(self.device):
+            _native.check(self._lib.vodhip_index_posterior_expectation_backward(
+                self._h, q.data_ptr(), _native.torch_dtype_code(q.dtype), nq, beta, None if sub is None else sub.data_ptr(), n_sub,
+                max_score.data_ptr(), log_rel.data_ptr(), (y if y.numel() else spare).data_ptr(), (g if g.numel() else spare).data_ptr(),
+                grad.data_ptr(), _native.current_stream_ptr(self.device)))
+        for t, given in ((q, queries), (sub, subset), (y, expectation.values), (g, grad_values), (max_score, expectation.log_partition.max_score),
+                         (log_rel, expectation.log_partition.log_rel)):
+            if t is not None and t is not given:
+                t.record_stream(torch.cuda.current_stream(self.device))
+        return grad
+
+    def expected_values(self, queries: torch.Tensor, temperature: float = 1.0, subset=None) -> torch.Tensor:
+        """`posterior_expectation(queries).values` as a float32 `[nq, n_cols]` tensor that is differentiable with respect to `queries`:
+        forward is the unchanged `posterior_expectation`, backward `posterior_expectation_backward` - one more scan of the store - cast
+        to the dtype of `queries` (straight through the rounding of the queries to the store dtype).  No gradient flows to the table,
+        the store or the temperature; not twice differentiable.  A cross-entropy on class masses: with a one-hot class table,
+        `-torch.log(index.expected_values(q, T)[torch.arange(nq), labels]).mean()`."""
+        return _ExpectedValues.apply(queries, self, float(temperature), subset)
 
     def sample_posterior(self, queries, k: int, temperature: float = 1.0, *, seed: int, query_offset: int = 0, subset=None,
                          id_base: int = 0, out=None) -> "PosteriorSample":
@@ -1137,6 +1192,29 @@ class _ListedScores(torch.autograd.Function):
     @torch.autograd.function.once_differentiable
     def backward(ctx, grad_out):
         return listed_scores_backward(ctx.index, ctx.ids, grad_out, ctx.q_dtype, ctx.q_device, **ctx.kw), None, None, None
+
+
+class _ExpectedValues(torch.autograd.Function):
+    """`index.expected_values`: `index` is anything with `posterior_expectation(queries, temperature, subset)` and
+    `posterior_expectation_backward(queries, grad_values, expectation, temperature, subset)`."""
+
+    @staticmethod
+    def forward(ctx, queries, index, temperature, subset):
+        pe = index.posterior_expectation(queries.detach(), temperature, subset)
+        values = torch.as_tensor(pe.values)
+        ctx.index, ctx.temperature, ctx.subset = index, temperature, subset
+        ctx.q_dtype, ctx.q_device = queries.dtype, queries.device
+        ctx.save_for_backward(queries.detach(), values, torch.as_tensor(pe.log_partition.max_score), torch.as_tensor(pe.log_partition.log_rel))
+        return values.to(queries.device).clone()
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_out):
+        queries, values, max_score, log_rel = ctx.saved_tensors
+        beta = 1.0 / ctx.temperature if ctx.temperature else float("nan")
+        pe = PosteriorExpectation(values, LogPartition(max_score * beta + log_rel, max_score, log_rel))
+        g = torch.as_tensor(ctx.index.posterior_expectation_backward(queries, grad_out, pe, ctx.temperature, ctx.subset))
+        return g.to(device=ctx.q_device, dtype=ctx.q_dtype), None, None, None
 
 
 def topk_log_coverage(scores: torch.Tensor, log_partition: LogPartition, temperature: float = 1.0) -> torch.Tensor:
@@ -1704,6 +1782,53 @@ class HipNodeIndex:
         with np.errstate(invalid="ignore"):
             log_z = (max_score * np.float32(beta) + log_rel).astype(np.float32)
         return PosteriorExpectation(values, LogPartition(log_z, max_score, log_rel))
+
+    def posterior_expectation_backward(self, queries, grad_values, expectation: "PosteriorExpectation", temperature: float = 1.0,
+                                       subset: np.ndarray | None = None) -> np.ndarray:
+        """`HipFlatIndex.posterior_expectation_backward` over every shard: each shard runs the flat call on its own rows with the GLOBAL
+        `expectation` (what this index's `posterior_expectation` returned), so the shard results add; they are folded on the host in
+        shard order, in double.  Host arrays -> a float32 NumPy array `[nq, dim]`."""
+        if isinstance(queries, torch.Tensor):
+            queries = queries.detach().float().cpu().numpy()
+        q = np.ascontiguousarray(queries)
+        if q.dtype not in (np.float32, np.float16):
+            q = q.astype(np.float32)
+        if q.ndim != 2 or q.shape[1] != self.dim:
+            raise ValueError(f"expected [nq, {self.dim}] queries, got {tuple(q.shape)}")
+        nq = int(q.shape[0])
+        beta = 1.0 / float(temperature) if temperature else float("nan")
+        sub, n_sub = None, 0
+        if subset is not None:
+            sub = np.ascontiguousarray(subset.cpu().numpy() if isinstance(subset, torch.Tensor) else subset, dtype=np.int32)
+            if sub.ndim != 2 or sub.shape[0] != nq:
+                raise ValueError(f"subset must be int32 [nq, n_per_query], got {tuple(sub.shape)}")
+            n_sub = int(sub.shape[1])
+
+        def host(a):
+            return np.ascontiguousarray(a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else a, dtype=np.float32)
+
+        y, g = host(expectation.values), host(grad_values)
+        if y.ndim != 2 or y.shape[0] != nq or g.shape != y.shape:
+            raise ValueError(f"expected values and grad_values of one shape [{nq}, n_cols], got {tuple(y.shape)} and {tuple(g.shape)}")
+        shape = self.row_values_shape
+        if shape is not None and y.shape[1] != shape[1]:
+            raise ValueError(f"expected grad_values of shape [{nq}, {shape[1]}] (the table's columns), got {tuple(g.shape)}")
+        max_score, log_rel = host(expectation.log_partition.max_score), host(expectation.log_partition.log_rel)
+        if max_score.shape != (nq,) or log_rel.shape != (nq,):
+            raise ValueError(f"expected max_score and log_rel of shape ({nq},)")
+        grad = np.empty((nq, self.dim), dtype=np.float32)
+        spare = np.zeros(1, dtype=np.float32)
+        with torch.cuda.device(self.device):
+            _native.check(self._lib.vodhip_node_index_posterior_expectation_backward(
+                self._h, q.ctypes.data, 2 if q.dtype == np.float32 else 0, nq, beta, None if sub is None else sub.ctypes.data, n_sub,
+                max_score.ctypes.data, log_rel.ctypes.data, (y if y.size else spare).ctypes.data, (g if g.size else spare).ctypes.data,
+                grad.ctypes.data))
+        return grad
+
+    def expected_values(self, queries: torch.Tensor, temperature: float = 1.0, subset=None) -> torch.Tensor:
+        """`HipFlatIndex.expected_values` over every shard: a float32 `[nq, n_cols]` tensor on the device of `queries`, differentiable
+        with respect to them (forward `posterior_expectation`, backward `posterior_expectation_backward`, both through the host)."""
+        return _ExpectedValues.apply(queries, self, float(temperature), subset)
 
     def sample_posterior(self, queries, k: int, temperature: float = 1.0, *, seed: int, query_offset: int = 0,
                          subset: np.ndarray | None = None) -> "PosteriorSample":
