@@ -281,7 +281,13 @@ int vodhip_index_posterior_divergence(vodhip_index_t* index, const void* queries
  * out_mean: DEVICE float32 [nq, dim].  Temporaries are hipMallocAsync on `stream`: the staged queries and partials of H2p, and the
  * group accumulators, groups * slice * dim_pad * 4 bytes; batches run in slices of 64 .. 1024 queries chosen so that the accumulators
  * stay at or below VODHIP_POSTERIOR_TEMP_BYTES (256 MiB) unless a 64-query slice alone needs more.
- * nq == 0 returns 0 and writes nothing; a refused call writes nothing.  REFUSED as H2p (same messages), and a NULL out_mean. */
+ * nq == 0 returns 0 and writes nothing; a refused call writes nothing.  REFUSED as H2p (same messages), and a NULL out_mean.
+ * VODHIP_POSTERIOR_TEMP_BYTES is the DEFAULT budget of every sliced scan (posterior_stats, posterior_divergence, rank_ids / count_above /
+ * scan_score_ids, range_search, posterior_mean, posterior_expectation and its backward, sample_posterior).  The index parameter
+ * "scan_temp_bytes" (vodhip_index_set_param; 0 = this default, >= 1 = that many bytes, negative refused) replaces it per index: a
+ * testing and memory-tuning knob.  It changes the slice - clamp(budget / per-query bytes / 128 * 128, 64, 1024) queries, or pairs for
+ * posterior_divergence - and nothing else: results are the same bits under any budget.  The stats "last_scan_slice" and
+ * "last_scan_per_query_bytes" report what the last sliced call of the index used; "scan_temp_bytes" reads the budget back. */
 #define VODHIP_POSTERIOR_GROUP_ROWS 16384
 #define VODHIP_POSTERIOR_TEMP_BYTES (256ll << 20)
 int vodhip_index_posterior_mean(vodhip_index_t* index, const void* queries, int q_dtype, int64_t nq, float beta,
@@ -507,7 +513,8 @@ int vodhip_index_set_query_labels(vodhip_index_t* index, const int32_t* q_labels
  *   needed ("exact_adapt" = 1, default; 0 = always the formula); speed only - results are exact for any value),
  *   "survivor_ring" (records per wave of the 8-phase filter kernel's survivor rings, in [0, 8192]; 0 = auto, sized by the planner for
  *   the search's largest stage, at most 1024 (8 x CUs x 1024 x 132 B = 277 MB of workspace per lane on 256 CUs); the rings are skipped
- *   when the device cannot hold them; a query block that does not fit takes the in-loop path; speed and workspace only - results are the same).
+ *   when the device cannot hold them; a query block that does not fit takes the in-loop path; speed and workspace only - results are the same),
+ *   "scan_temp_bytes" (the temporary budget of the sliced whole-store scans; 0 = VODHIP_POSTERIOR_TEMP_BYTES, the default: see there).
  * VODHIP_EXACT_F32 input range: finite float32 rows and queries of ANY magnitude whose squared norm is finite in float32 (|x| < 1.8e19)
  *   give the float32 brute-force result; values beyond the scan dtype's range (fp16: |v| > 65504) saturate in the scan copy only, and
  *   the up to 64 rows whose norm / rounding error exceeds the rest of the store's by 2x or more ("outliers") are scored exactly by

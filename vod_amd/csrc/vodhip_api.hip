@@ -26,6 +26,7 @@
 #include "divergence_fold.h"
 #include "readout_fold.h"
 #include "readout_grad_fold.h"
+#include "scan_slices.h"
 #include "search_plan.h"
 #include "vodhip_internal.h"
 
@@ -164,6 +165,7 @@ struct vodhip_index {
     int64_t force_safe = 0;
     int64_t kflags = 0;
     int64_t profile = 0;  // 1: bracket every filter launch with HIP events (bench / roofline accounting)
+    int64_t scan_temp_bytes = VODHIP_POSTERIOR_TEMP_BYTES;  // what the sliced whole-store scans keep their temporaries under (scan_slices.h)
     // stats
     int64_t last_overflow = 0, last_chunks = 0, last_survivor_ring = 0, last_ring_fallbacks = 0, last_safe_reruns = 0, last_recovered_queries = 0;
     int64_t last_filter_launches = 0, last_filter_ns = 0;
@@ -171,6 +173,7 @@ struct vodhip_index {
     // the last vodhip_index_sample_posterior: its status words, the emit launches' workgroups, with "profile" the ns per launch
     std::atomic<int64_t> last_sample[6] = {};      // overflow, selfcheck, max candidates, emit skipped, candidates, emit groups
     std::atomic<int64_t> last_sample_ns[5] = {};   // partition, keymax, threshold, emit, select
+    std::atomic<int64_t> last_scan[2] = {};        // the last sliced whole-store scan: queries (or pairs) per slice, temporary bytes per query
     std::atomic<int64_t> last_range[4] = {};       // the last vodhip_index_range_search: overflow, selfcheck, emit skipped, emit groups
     // its temporaries: one grow-only block, kept between calls (the call waits for its stream at its end, and a stream-ordered pool
     // hands its memory back at every such wait: allocating per call cost 1.1 ms of a 3.8 ms call at 256 queries); held by
@@ -1336,11 +1339,13 @@ static void fill_scan_inputs(ScanInputs& s, const vodhip_index_t* ix, const void
     s.n_qlab = q_labels_dev ? n_per_query : 0;
 }
 
-// queries per slice of a batch: a multiple of 128 (or 64) up to 1024 that keeps temporaries of per_query bytes each under
-// VODHIP_POSTERIOR_TEMP_BYTES unless a 64-query slice alone needs more
-static int64_t scan_slice_queries(size_t per_query) {
-    const int64_t slice = (int64_t)((size_t)VODHIP_POSTERIOR_TEMP_BYTES / per_query) / 128 * 128;
-    return std::min<int64_t>(1024, std::max<int64_t>(64, slice));
+// queries (or pairs) per slice of a batch under the index's budget (scan_slices.h), remembered for "last_scan_slice" /
+// "last_scan_per_query_bytes"
+static int64_t index_scan_slice(vodhip_index_t* ix, size_t per_query) {
+    const int64_t slice = scan_slice_queries(ix->scan_temp_bytes, per_query);
+    ix->last_scan[0] = slice;
+    ix->last_scan[1] = (int64_t)per_query;
+    return slice;
 }
 
 // the stream-ordered temporaries of a call: one block per byte count, none (NULL) for a count of 0
@@ -1424,7 +1429,7 @@ int vodhip_index_posterior_stats(vodhip_index_t* ix, const void* queries, int q_
     a.out_mean_rel = out_mean_rel;
     a.out_var = out_var;
     const size_t per_query = std::max<size_t>(1, (size_t)scan_tiles(a.ntotal)) * 16;  // the partials
-    const int64_t slice = scan_slice_queries(per_query);
+    const int64_t slice = index_scan_slice(ix, per_query);
     const int64_t nq_pad = scan_nq_pad(std::min(nq, slice));
     ScanTemps tmp;
     tmp.stream = stream;
@@ -1465,7 +1470,7 @@ int vodhip_index_posterior_divergence(vodhip_index_t* ix, const void* queries_a,
     a.beta_b = beta_b;
     for (int k = 0; k < 8; ++k) a.out[k] = outs[k];
     const size_t per_pair = std::max<size_t>(1, (size_t)scan_tiles(a.ntotal)) * 32;  // the partials
-    const int64_t slice = scan_slice_queries(per_pair);                             // pairs of a launch
+    const int64_t slice = index_scan_slice(ix, per_pair);                             // pairs of a launch
     const int64_t nq_pad = scan_nq_pad(2 * std::min(nq, slice));                     // staged queries of a launch
     ScanTemps tmp;
     tmp.stream = stream;
@@ -1513,7 +1518,7 @@ static int rank_call(vodhip_index_t* ix, int mode, const char* what, const void*
     const bool pick = mode != RANK_MODE_THRESHOLDS, count = mode != RANK_MODE_PICK;
     // a query's gathered rows are at most m + 3 rows of the mini-store
     const size_t row_bytes = (size_t)ix->dim_pad * 2;
-    const int64_t slice = scan_slice_queries(row_bytes * (size_t)(1 + (pick ? m + 3 : 0)) + (size_t)m * 16);
+    const int64_t slice = index_scan_slice(ix, row_bytes * (size_t)(1 + (pick ? m + 3 : 0)) + (size_t)m * 16);
     const int64_t nq_pad = scan_nq_pad(std::min(nq, slice));
     ScanTemps tmp;
     tmp.stream = stream;
@@ -1583,7 +1588,7 @@ int vodhip_index_range_search(vodhip_index_t* ix, const void* queries, int q_dty
     a.capacity = capacity;
     const size_t row_bytes = (size_t)ix->dim_pad * 2;
     const size_t n_tiles = (size_t)scan_tiles(a.ntotal);
-    const int64_t slice = scan_slice_queries(std::max<size_t>(1, n_tiles) * 4 + row_bytes + 12);  // the count table, the staged query, the words
+    const int64_t slice = index_scan_slice(ix, std::max<size_t>(1, n_tiles) * 4 + row_bytes + 12);  // the count table, the staged query, the words
     const int64_t nq_pad = scan_nq_pad(std::min(nq, slice));
     ScanTemps tmp;
     tmp.stream = stream;
@@ -1640,7 +1645,7 @@ int vodhip_index_posterior_mean(vodhip_index_t* ix, const void* queries, int q_d
     a.p.out_log_rel = out_log_rel;
     a.out_mean = out_mean;
     const size_t per_query = std::max<size_t>(1, (size_t)posterior_mean_groups(a.p.ntotal)) * (size_t)ix->dim_pad * sizeof(float);  // the group accumulators
-    const int64_t slice = scan_slice_queries(per_query);
+    const int64_t slice = index_scan_slice(ix, per_query);
     const int64_t nq_pad = scan_nq_pad(std::min(nq, slice));
     ScanTemps tmp;
     tmp.stream = stream;
@@ -1683,7 +1688,7 @@ int vodhip_index_posterior_expectation(vodhip_index_t* ix, const void* queries, 
     a.out_values = out_values;
     const size_t acc_per_query = std::max<size_t>(1, (size_t)readout_groups(a.p.ntotal)) * (size_t)a.c_pad * sizeof(float);  // the group accumulators
     const size_t part_per_query = std::max<size_t>(1, (size_t)scan_tiles(a.p.ntotal)) * 8;                                 // the partition partials
-    const int64_t slice = scan_slice_queries(acc_per_query + part_per_query);
+    const int64_t slice = index_scan_slice(ix, acc_per_query + part_per_query);
     const int64_t nq_pad = scan_nq_pad(std::min(nq, slice));
     ScanTemps tmp;
     tmp.stream = stream;
@@ -1745,7 +1750,7 @@ int vodhip_index_posterior_expectation_backward(vodhip_index_t* ix, const void* 
     const size_t acc_per_query = groups * (size_t)ix->dim_pad * sizeof(float);  // the group accumulators
     const size_t mg_per_query = groups * sizeof(float);                          // the group maxima
     const size_t small_per_query = (size_t)a.c_pad * 2 + readout_grad_aux_bytes();
-    const int64_t slice = scan_slice_queries(acc_per_query + mg_per_query + small_per_query);
+    const int64_t slice = index_scan_slice(ix, acc_per_query + mg_per_query + small_per_query);
     const int64_t nq_pad = scan_nq_pad(std::min(nq, slice));
     ScanTemps tmp, tmp2;
     tmp.stream = tmp2.stream = stream;
@@ -1802,7 +1807,7 @@ int vodhip_index_sample_posterior(vodhip_index_t* ix, const void* queries, int q
     a.out_log_weight = out_log_weight;
     a.out_keys = out_keys;
     const size_t n_tiles = std::max<size_t>(1, (size_t)scan_tiles(a.p.ntotal));
-    const int64_t slice = scan_slice_queries((size_t)a.stride * 12 + n_tiles * 12);  // the candidate lists and the tile words
+    const int64_t slice = index_scan_slice(ix, (size_t)a.stride * 12 + n_tiles * 12);  // the candidate lists and the tile words
     const int64_t nq_pad = scan_nq_pad(std::min(nq, slice));
     constexpr int NT = 7;
     const size_t bytes[NT] = {(size_t)nq_pad * (size_t)ix->dim_pad * 2, n_tiles * (size_t)nq_pad * 8, n_tiles * (size_t)nq_pad * 4,
@@ -1941,6 +1946,9 @@ int vodhip_index_set_param(vodhip_index_t* ix, const char* key, int64_t value) {
     } else if (!strcmp(key, "exact_expand")) {
         if (value < 0 || value > 100000) return fail("exact_expand (x100) must be in [0, 100000]");
         ix->exact_expand_x100 = value;
+    } else if (!strcmp(key, "scan_temp_bytes")) {
+        if (value < 0) return fail("scan_temp_bytes must be 0 (the default, VODHIP_POSTERIOR_TEMP_BYTES) or >= 1");
+        ix->scan_temp_bytes = value == 0 ? VODHIP_POSTERIOR_TEMP_BYTES : value;
     } else if (!strcmp(key, "tile")) {
         PlanTunables t;
         t.tile = value;
@@ -1995,6 +2003,12 @@ int vodhip_index_get_stat(const vodhip_index_t* ix, const char* key, int64_t* ou
         *out = ix->last_range[2];
     else if (!strcmp(key, "last_range_emit_groups"))
         *out = ix->last_range[3];
+    else if (!strcmp(key, "last_scan_slice"))
+        *out = ix->last_scan[0];
+    else if (!strcmp(key, "last_scan_per_query_bytes"))
+        *out = ix->last_scan[1];
+    else if (!strcmp(key, "scan_temp_bytes"))
+        *out = ix->scan_temp_bytes;
     else if (!strcmp(key, "last_sample_ns_partition"))
         *out = ix->last_sample_ns[0];
     else if (!strcmp(key, "last_sample_ns_keymax"))
