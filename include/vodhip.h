@@ -1050,10 +1050,18 @@ int vodhip_gather_by_id(const int64_t* queries, int64_t n_queries, const int64_t
  * *out_n_unique = number of distinct ids, may be NULL), and every value array gathered onto that list (outs[v] float32
  * [n_rows, U], first occurrence wins, fill[v] where the row does not hold the id).  `labels` uint8 [n_rows, n_keys] (non-zero =
  * positive; may be NULL) is gathered the same way into out_labels uint8 [n_rows, U] with the reference's fill 0.
- * DEVICE pointers; `values` / `outs` HOST arrays of n_values (<= 8) device pointers; U <= 8192. */
+ * DEVICE pointers; `values` / `outs` HOST arrays of n_values (<= 8) device pointers.
+ * Admitted shapes: U <= 8192, n_keys <= 1024, and the kernel's LDS (two id buffers of the whole batch + the row's 8 value arrays
+ * and labels) within the 160 KiB of one workgroup.  Of the shapes inside the first two bounds the third excludes exactly
+ * n_rows = 8 with n_keys = 1013 ... 1024 (8 rows hold at most 1012 ids each; 7 rows hold 1024).  Anything else is refused before
+ * a launch: gather such a batch with vodhip_gather_by_id. */
 int vodhip_flatten_inbatch(const int64_t* ids, int64_t n_rows, int n_keys, int n_values, const float* const* values,
                            const float* fill, float* const* outs, const uint8_t* labels, uint8_t* out_labels,
                            int64_t* out_unique, int32_t* out_n_unique, void* stream);
+
+/* 1 when vodhip_flatten_inbatch (and the flattening step of vodhip_collate, n_rows = nq, n_keys = k_total) admits the shape, else 0:
+ * the rule above, for callers that choose between the one-launch flattening and vodhip_gather_by_id.  No device work. */
+int vodhip_flatten_inbatch_admits(int64_t n_rows, int n_keys);
 
 /* ---------------------------------------------------------------------------------------------
  * The collate-side chain in ONE call: hybrid merge -> labeled priority sampling (+ gathers, rank diagnostic) -> optional
@@ -1095,7 +1103,8 @@ typedef struct vodhip_collate_args {
     float* out_lse_pos;                               /* [nq] */
     float* out_lse_neg;                               /* [nq] */
     float* out_max_sampling_id;                       /* [nq] */
-    /* flattened batch (in_batch_negatives != 0): U = nq * k_total <= 8192 */
+    /* flattened batch (in_batch_negatives != 0): U = nq * k_total; the shape (nq, k_total) must be one vodhip_flatten_inbatch admits
+     * (U <= 8192, k_total <= 1024, not 8 x 1013 ... 1024) - refused before anything is launched otherwise */
     int64_t* flat_ids;                                /* [U] */
     float* flat_scores;                               /* [nq, U] */
     float* flat_log_weights;                          /* [nq, U] */

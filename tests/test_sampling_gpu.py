@@ -139,8 +139,10 @@ def test_sample_search_results_wrapper_contract():
 
 
 def test_flatten_samples_matches_reference_golden():
-    """`flatten_samples` (in_batch_negatives.py:10-52) through `vodhip_gather_by_id`, against the vectors produced by
-    the reference's own function (tests/golden/make_golden.py) - bit for bit, NaN positions included."""
+    """`flatten_samples` (in_batch_negatives.py:10-52) against the vectors produced by the reference's own function
+    (tests/golden/make_golden.py) - bit for bit, NaN positions included.  This batch, like every case of this file (at most
+    8192 ids, 2 raw-score arrays), takes the one-launch `vodhip_flatten_inbatch`; tests/test_collate_limits_gpu.py runs
+    the `vodhip_gather_by_id` path."""
     from vod_amd import types as vt
     from vod_amd.core.in_batch_negatives import flatten_samples
     from vod_amd.core.sample import PrioritySampledSections

@@ -151,6 +151,7 @@ SIGNATURES: dict[str, tuple] = {
     "vodhip_collate": (_i32, [_vp, _vp]),
     "vodhip_collate_proposal": (_i32, [_vp, _vp]),
     "vodhip_flatten_inbatch": (_i32, [_vp, _i64, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "vodhip_flatten_inbatch_admits": (_i32, [_i64, _i32]),
     "vodhip_retrieval_backward": (_i32, [_vp, _vp, _i32, _i32, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp]),
     # H5l marginal likelihood (kernels_marginal.hip)
     "vodhip_lm_token_logprob_forward": (_i32, [_vp, _i32, _i64, _i64, _i64, _vp, _vp, _i32, _vp, _vp, _vp]),

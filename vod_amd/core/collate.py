@@ -258,8 +258,9 @@ def collate_on_device(
     total = int(total)
     U = nq * total
     flat = bool(in_batch_negatives)
-    if flat and (U > 8192 or total > 1024):
-        raise ValueError(f"{U} sampled ids in the batch ({total} per row): the one-launch flattening holds at most 8192 (1024 per row)")
+    if flat and not lib.vodhip_flatten_inbatch_admits(nq, total):  # the rule of include/vodhip.h, vodhip_flatten_inbatch
+        raise ValueError(f"{U} sampled ids in the batch ({total} per row): the one-launch flattening holds at most 8192 (1024 per row; "
+                         "8 rows at most 1012 per row)")
     if noise is None:
         noise = torch.empty((nq, stride), dtype=torch.float32, device=dev).exponential_(generator=generator)
     elif noise.dtype is not torch.float32 or noise.stride(-1) != 1:

@@ -4,7 +4,8 @@ Mirror of `flatten_samples` (/root/reference/src/vod_dataloaders/core/in_batch_n
 section ids of the whole batch become ONE id list shared by every row (padded to B * n with the reference's constant
 `1`), and each row's score / label / log-weight / raw engine scores are gathered onto that list
 (`gather_values_by_indices`, numpy_ops.py:24-143: first occurrence, NaN - or 0 for labels - where the row does not
-hold the id).  The gather of all value arrays is one launch of `vodhip_gather_by_id`.
+hold the id).  A batch the one-launch flattening admits (`vodhip_flatten_inbatch`) takes that launch; any other takes
+`torch.unique` and one launch of `vodhip_gather_by_id` per 8 value arrays.
 """
 from __future__ import annotations
 
@@ -55,8 +56,10 @@ def flatten_samples(samples: PrioritySampledSections, padding: bool = True, devi
     if proposal and (samples.log_proposal is None or samples.log_mass is None or samples.joint_log_weights is None):
         raise ValueError("proposal=True needs sections sampled with proposal=True")
     dev = torch.device("cuda", device)
-    if (0 < samples.batch.indices.size <= 8192 and len(samples.raw_scores) <= (3 if proposal else 5) and samples.batch.indices.ndim == 2
-            and samples.batch.indices.shape[1] <= 1024):
+    # one launch for the shapes `vodhip_flatten_inbatch` admits (include/vodhip.h: at most 8192 ids, 1024 per row, not 8 x 1013 ... 1024)
+    # with at most 8 value arrays; everything else: the distinct ids from torch, the gathers from `vodhip_gather_by_id`
+    if (samples.batch.indices.ndim == 2 and samples.batch.indices.size > 0 and len(samples.raw_scores) <= (3 if proposal else 5)
+            and _native.load_library().vodhip_flatten_inbatch_admits(*samples.batch.indices.shape)):
         return _flatten_one_launch(samples, padding, dev, proposal)
     indices = torch.from_numpy(np.ascontiguousarray(samples.batch.indices)).to(dev)
     unique = torch.unique(indices)  # sorted, like np.unique

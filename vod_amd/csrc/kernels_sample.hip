@@ -15,6 +15,7 @@
 // results agree to ~1e-6, tolerance stated in the tests); ties between equal priority keys go to the smaller
 // column (numpy's introsort order among equal keys is unspecified).
 #include "vodhip_internal.h"
+#include "collate_plan.h"
 #include "wg_sort.h"
 
 namespace vodhip {
@@ -26,7 +27,7 @@ __device__ long long g_probe_flatten[256];
 #define SM_PROBE(i) VODHIP_PROBE(g_probe_sample, i)
 #define FL_PROBE(i) VODHIP_PROBE(g_probe_flatten, i)
 
-constexpr int SM_THREADS = 256;
+// SM_THREADS, FL_THREADS, FL_MAX_VALUES: collate_plan.h (the LDS footprints depend on them)
 typedef unsigned long long u64;
 
 __device__ __forceinline__ float sm_wave_max(float v) {
@@ -441,12 +442,10 @@ __global__ __launch_bounds__(SM_THREADS) void priority_sample_kernel(SampleArgs 
 static hipError_t launch_sample_args(SampleArgs& a, int64_t nq, int max_width, hipStream_t stream) {
     // more positives than samples cannot be drawn (the reference's numba loop would write past its [k_total] output row there)
     if (a.k_positive > a.k_total) a.k_positive = a.k_total;
-    int P = 256;
-    while (P < max_width) P <<= 1;
-    a.P_cap = P;
+    a.P_cap = sample_sort_capacity(max_width);
     const bool proposal = a.out_log_proposal || a.out_log_mass || a.out_joint_logw;
-    // (+ mass_s [2] and wall [k_total] behind red_i when the proposal is asked for)
-    const size_t lds = (size_t)P * 8 + (size_t)P * 4 + (size_t)a.k_total * 12 + (size_t)P * 4 + 16 + 64 + 16 + (proposal ? 8 + (size_t)a.k_total * 4 : 0);
+    // sort capacity and LDS footprint: collate_plan.h (+ mass_s [2] and wall [k_total] behind red_i when the proposal is asked for)
+    const size_t lds = sample_lds_bytes(a.P_cap, a.k_total, proposal);
     const void* fn = proposal ? (const void*)priority_sample_kernel<true> : (const void*)priority_sample_kernel<false>;
     if (lds > 64 * 1024) {
         hipError_t e = allow_dynamic_lds(fn, (int)lds);
@@ -585,8 +584,6 @@ hipError_t launch_gather_by_id(const int64_t* queries, int64_t n_queries, const 
 // reference's constant 1, then gather_values_by_indices of every value array onto that list.  Every
 // workgroup (one per row) sorts the U = B * n ids itself in LDS (a bitonic sort of <= 8192 int64: cheaper than a second launch
 // and a device-wide dependency), compacts the distinct values, and gathers ITS row; workgroup 0 also writes the id list.
-constexpr int FL_THREADS = 1024;  // 16 wavefronts: the sort network is a latency chain per stage, so wide and shallow (2 keys per thread at U = 2048)
-
 __global__ __launch_bounds__(FL_THREADS) void flatten_inbatch_kernel(const int64_t* __restrict__ ids, int n_keys, int U, int P, int n_values,
                                                                      GatherArgs args, const uint8_t* __restrict__ labels,
                                                                      uint8_t* __restrict__ out_labels, int64_t* __restrict__ out_unique,
@@ -595,7 +592,7 @@ __global__ __launch_bounds__(FL_THREADS) void flatten_inbatch_kernel(const int64
     int64_t* srt = (int64_t*)f_smem;          // [P] sort buffer, later the row's keys
     int64_t* uq = srt + P;                    // [U] distinct ids ascending, then the padding
     float* vals = (float*)(uq + U);           // [n_values][n_keys] the row's value arrays
-    uint8_t* lab = (uint8_t*)(vals + 8 * n_keys);  // [n_keys] the row's labels
+    uint8_t* lab = (uint8_t*)(vals + FL_MAX_VALUES * n_keys);  // [n_keys] the row's labels
     int* s_w = (int*)(lab + ((n_keys + 3) & ~3));  // [16] wave sums
     const int row = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     FL_PROBE(0);
@@ -664,10 +661,11 @@ hipError_t launch_flatten_inbatch(const int64_t* ids, int64_t n_rows, int n_keys
         args.outs[v] = outs[v];
         args.fill[v] = fill[v];
     }
-    const int U = (int)(n_rows * n_keys);
-    int P = 1024;
-    while (P < U) P <<= 1;
-    const size_t lds = (size_t)P * 8 + (size_t)U * 8 + (size_t)n_keys * 8 * 4 + (size_t)((n_keys + 3) & ~3) + 16 * 4 + 16;
+    // sort size and LDS footprint: collate_plan.h.  The entry points admit `flatten_admits` shapes only; nothing larger is launched
+    if (!flatten_admits(n_rows, n_keys)) return hipErrorInvalidValue;
+    const FlattenPlan plan = flatten_plan(n_rows, n_keys);
+    const int U = plan.U, P = plan.P;
+    const size_t lds = plan.lds;
     if (lds > 64 * 1024) {
         hipError_t e = allow_dynamic_lds((const void*)flatten_inbatch_kernel, (int)lds);
         if (e != hipSuccess) return e;

@@ -28,6 +28,7 @@
 #include "readout_grad_fold.h"
 #include "scan_slices.h"
 #include "search_plan.h"
+#include "collate_plan.h"
 #include "vodhip_internal.h"
 
 using namespace vodhip;
@@ -2511,13 +2512,26 @@ int vodhip_priority_sample_merged_proposal(const int64_t* ids, const float* scor
                                        stream);
 }
 
+// The one-launch flattening's admitted shapes (collate_plan.h, flatten_admits): 0 = admitted; otherwise the refusal is recorded
+static int flatten_refused(int64_t n_rows, int64_t n_keys) {
+    if (n_keys > 0 && n_rows > FL_MAX_IDS / n_keys)
+        return fail("%lld rows of %lld ids: the one-launch flattening holds at most %d ids in the batch", (long long)n_rows, (long long)n_keys, FL_MAX_IDS);
+    if (n_keys > FL_MAX_KEYS)
+        return fail("%lld ids per row: the one-launch flattening stages at most %d per row in LDS (use vodhip_gather_by_id)", (long long)n_keys, FL_MAX_KEYS);
+    if (!flatten_admits(n_rows, n_keys))
+        return fail("%lld rows of %lld ids: the one-launch flattening needs %zu bytes of LDS, one workgroup has %zu - 8 rows hold at most 1012 ids each (use vodhip_gather_by_id)",
+                    (long long)n_rows, (long long)n_keys, flatten_plan(n_rows, (int)n_keys).lds, CL_LDS_LIMIT);
+    return 0;
+}
+
+int vodhip_flatten_inbatch_admits(int64_t n_rows, int n_keys) { return flatten_admits(n_rows, n_keys) ? 1 : 0; }
+
 int vodhip_flatten_inbatch(const int64_t* ids, int64_t n_rows, int n_keys, int n_values, const float* const* values, const float* fill,
                            float* const* outs, const uint8_t* labels, uint8_t* out_labels, int64_t* out_unique, int32_t* out_n_unique,
                            void* stream) {
     if (n_rows < 0 || n_keys < 0 || n_values < 0 || n_values > 8) return fail("invalid sizes (n_values <= 8)");
     if ((labels == nullptr) != (out_labels == nullptr)) return fail("labels and out_labels go together");
-    if (n_rows * (int64_t)n_keys > 8192) return fail("%lld ids in the batch: the one-launch flattening holds at most 8192", (long long)(n_rows * n_keys));
-    if (n_keys > 1024) return fail("%d ids per row: the one-launch flattening stages at most 1024 per row in LDS (use vodhip_gather_by_id)", n_keys);
+    if (flatten_refused(n_rows, n_keys)) return -1;
     if (n_rows == 0 || n_keys == 0) return 0;
     if (!ids || !out_unique || (n_values && (!values || !fill || !outs))) return fail("NULL argument");
     for (int v = 0; v < n_values; ++v)
@@ -2551,6 +2565,7 @@ static int collate_impl(const vodhip_collate_args_t* c, const vodhip_collate_pro
     if (stride - 1 > 4096) return fail("total width %lld exceeds 4096", (long long)stride - 1);
     if (c->k_total > 4096) return fail("k_total=%d exceeds 4096", c->k_total);
     if (c->noise_stride < stride) return fail("noise rows (%lld) are shorter than the merged rows (%lld)", (long long)c->noise_stride, (long long)stride);
+    if (c->in_batch_negatives && flatten_refused(c->nq, c->k_total)) return -1;  // before anything is launched
     if (c->nq == 0) return 0;
     if ((c->k_lookup && !c->lookup_idx) || !c->noise || !c->merged_idx || !c->merged_lbl || !c->merged_scr || !c->row_cursor || !c->out_local ||
         !c->out_ids || !c->out_scores || !c->out_log_weights || !c->out_labels || !c->out_lse_pos || !c->out_lse_neg)
@@ -2616,8 +2631,6 @@ static int collate_impl(const vodhip_collate_args_t* c, const vodhip_collate_pro
     }
     HIP_OK(launch_priority_sample_merged(m, stream));
     if (!c->in_batch_negatives) return 0;
-    if (c->nq * (int64_t)c->k_total > 8192) return fail("%lld ids in the batch: the one-launch flattening holds at most 8192", (long long)(c->nq * c->k_total));
-    if (c->k_total > 1024) return fail("k_total=%d: the one-launch flattening stages at most 1024 ids per row", c->k_total);
     if (!c->flat_ids || !c->flat_scores || !c->flat_log_weights || !c->flat_labels) return fail("NULL flattened output");
     const float* values[8];
     float* outs[8];
