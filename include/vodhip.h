@@ -368,12 +368,44 @@ int vodhip_index_posterior_expectation(vodhip_index_t* index, const void* querie
  * they stay at or below VODHIP_POSTERIOR_TEMP_BYTES unless a 64-query slice alone needs more.  The call only enqueues work (but see
  * vmax).  nq == 0 returns 0 and writes nothing; a refused call writes nothing.  REFUSED as H2e, and: a NULL max_score, log_rel, values,
  * grad_values or out_grad_queries.
- * NOT BUILT: the gradient in beta, the gradient in the table, tables wider than VODHIP_READOUT_MAX_COLS, second derivatives. */
+ * NOT BUILT: the gradient in beta, tables wider than VODHIP_READOUT_MAX_COLS, second derivatives.  The gradient in the table is H2a. */
 int vodhip_index_posterior_expectation_backward(vodhip_index_t* index, const void* queries, int q_dtype, int64_t nq, float beta,
                                                 const int32_t* q_labels_dev /* NULL = unrestricted */, int n_per_query,
                                                 const float* max_score /* DEVICE [nq] */, const float* log_rel /* DEVICE [nq] */,
                                                 const float* values /* DEVICE [nq][n_cols] */, const float* grad_values /* DEVICE [nq][n_cols] */,
                                                 float* out_grad_queries /* DEVICE [nq][dim] */, void* stream);
+
+/* H2a. The ADJOINT of H2e's read-out, its gradient in the value table (kernels_readout_adjoint.hip): with W = weights,
+ *     out[z, c] = sum_{q < nq, z eligible for q} p(z | q) W[q, c]     (P^T W: DEVICE float32 [ntotal][n_cols]),
+ * a reduction over the QUERIES per stored row.  W = dL / dy gives dL / dv of H2e's y = P v; one column of ones the exact posterior mass
+ * every stored row receives from the batch.  The call reads no value table: n_cols (1 .. VODHIP_READOUT_MAX_COLS) is the weights' own
+ * width.  INPUTS: the queries, beta and labels of a forward call (H2p, H2m, H2e, ..) and its two words max_score, log_rel (DEVICE [nq]),
+ * so no partition scan runs in front: ONE scan of the store.  Eligibility, queries, labels, stream and concurrency rules are H2p's.
+ * W is staged per COLUMN: k_c = the exponent of max_q |W[q, c]| over the whole batch (0 for a column of zeros), W^ = W * 2^-k_c (exact;
+ * the largest entry in [1, 2), so a loss gradient of 1e-6 does not flush in fp16) rounded ONCE to the store dtype; the output column is
+ * multiplied by 2^k_c, which is exact (unless it leaves float32's range).  Scaling a column of W by a power of two scales that output
+ * column by exactly that power.
+ * One workgroup owns 64 consecutive stored rows and walks the batch in tiles of 256 queries, in query order: the scores come from the
+ * shared K loop with its operands exchanged (the same bits as every other scan), the weights round16(expf(min(0, beta (s - max_score)) -
+ * log_rel)) are contracted with the tile's W^ rows on the MFMA (float32 accumulate); fp16 stores scale the weight by 2^15 before the
+ * rounding, so it stays a normal fp16 number down to 2^-29.  Batches above 1024 queries run in slices of 1024: the first slice stores,
+ * later slices add to `out` in slice order.  ONE order per (row, column), fixed by the queries' positions in the batch alone: an element
+ * does not depend on ntotal, on the other rows or on the grid, and is the same bits on every repeat; there are no atomics, no partials
+ * and no fold.  accumulate != 0: the first slice adds to what `out` holds as well (accumulate on a zeroed buffer gives the plain call's
+ * bits).
+ * WEIGH +0, exact: a query without finite (max_score, log_rel) (no eligible row, a +inf score), a row >= ntotal, a NaN score (a stored
+ * row or a query with a NaN component), a row the query's labels do not allow.  Queries whose W row is zero change no bit of `out`.
+ * NON-FINITE INPUT.  A NaN or an infinity in column c of W makes column c of every output row NaN; the other columns are unaffected.
+ * Temporaries are hipMallocAsync on `stream`: the staged queries and weights of a slice and the column exponents.  The call only
+ * enqueues work.  nq == 0 zero-fills `out` unless accumulating; ntotal == 0 is a no-op; a refused call writes nothing.  REFUSED as H2p,
+ * and: n_cols outside [1, 256], a NULL weights (nq > 0) or out.
+ * NOT BUILT: the gradient in the stored rows (three adjoint calls of up to 256 columns over a dim-768 store would give it), L2 and
+ * exact_f32 stores, weights wider than VODHIP_READOUT_MAX_COLS. */
+int vodhip_index_posterior_adjoint(vodhip_index_t* index, const void* queries, int q_dtype, int64_t nq, float beta,
+                                   const int32_t* q_labels_dev /* NULL = unrestricted */, int n_per_query,
+                                   const float* max_score /* DEVICE [nq] */, const float* log_rel /* DEVICE [nq] */,
+                                   const float* weights /* DEVICE [nq][n_cols] */, int64_t n_cols /* 1 .. 256 */, int accumulate,
+                                   float* out /* DEVICE [ntotal][n_cols] */, void* stream);
 
 /* H2s. k rows drawn WITHOUT replacement from that softmax over the whole store, with priority-sampling weights
  * (kernels_sample_posterior.hip).  Gumbel-top-k: the k eligible rows with the largest keys
@@ -710,6 +742,15 @@ int vodhip_node_index_posterior_expectation_backward(vodhip_node_index_t* index,
                                                      const float* max_score, const float* log_rel /* HOST [nq] */,
                                                      const float* values, const float* grad_values /* HOST [nq][n_cols] */,
                                                      float* out_grad_queries /* HOST [nq][dim] */);
+/* H2a behind the one handle: HOST buffers, host-synchronous.  Every shard runs vodhip_index_posterior_adjoint on its own rows with the
+ * GLOBAL (max_score, log_rel) it is handed (those of any node forward call), so shard g's result IS rows [g R, (g + 1) R) of the global
+ * one: the slabs are concatenated (readout_adjoint_fold.h), nothing is folded.  Handed the words of one index holding all the rows, the
+ * result equals that index's bit for bit.  `out` is overwritten (no accumulate).  Refusals as for the flat call. */
+int vodhip_node_index_posterior_adjoint(vodhip_node_index_t* index, const void* queries, int q_dtype, int64_t nq, float beta,
+                                        const int32_t* q_labels /* HOST or NULL */, int n_per_query,
+                                        const float* max_score, const float* log_rel /* HOST [nq] */,
+                                        const float* weights /* HOST [nq][n_cols] */, int64_t n_cols,
+                                        float* out /* HOST [ntotal][n_cols] */);
 /* H2s behind the one handle: HOST buffers, host-synchronous.  Every shard runs vodhip_index_sample_posterior with id_base = its first
  * global row; keys are unnormalised and the noise is a function of the global row, so the k + 1 best of the union of the shards'
  * lists ARE the k + 1 best of the whole store: ids, scores and keys equal one index holding all the rows bit for bit.  The pairs are

@@ -25,6 +25,7 @@
 #include "stats_fold.h"
 #include "divergence_fold.h"
 #include "readout_fold.h"
+#include "readout_adjoint_fold.h"
 #include "readout_grad_fold.h"
 #include "scan_slices.h"
 #include "search_plan.h"
@@ -1773,6 +1774,48 @@ int vodhip_index_posterior_expectation_backward(vodhip_index_t* ix, const void* 
     if (le != hipSuccess) return fail("posterior-expectation-backward launch failed: %s", hipGetErrorString(le));
     HIP_OK(fe);
     HIP_OK(fe2);
+    return 0;
+}
+
+// ---- the read-out's adjoint, its gradient in the table (kernels_readout_adjoint.hip): the column exponents, then per slice of 1024 queries
+// the two stagings and ONE scan whose workgroups own their output rows ----
+int vodhip_index_posterior_adjoint(vodhip_index_t* ix, const void* queries, int q_dtype, int64_t nq, float beta, const int32_t* q_labels_dev, int n_per_query,
+                                   const float* max_score, const float* log_rel, const float* weights, int64_t n_cols, int accumulate, float* out, void* stream_) {
+    if (!ix) return fail("index is NULL");
+    if (const char* msg = posterior_adjoint_args_error(queries, q_dtype, nq, beta, q_labels_dev, n_per_query, max_score, log_rel, weights, n_cols, out))
+        return partition_args_fail(msg, q_dtype, beta);
+    if (scan_refusal(ix, "posterior_adjoint", q_labels_dev)) return -1;
+    if (ix->ntotal == 0) return 0;
+    HIP_OK(hipSetDevice(ix->device));
+    hipStream_t stream = (hipStream_t)stream_;
+    if (nq == 0) {
+        if (!accumulate) HIP_OK(hipMemsetAsync(out, 0, (size_t)ix->ntotal * (size_t)n_cols * sizeof(float), stream));
+        return 0;
+    }
+    ReadoutAdjointArgs a;
+    fill_scan_inputs(a.p, ix, queries, q_dtype, q_labels_dev, n_per_query);
+    a.p.beta = beta;
+    a.p.out_max = const_cast<float*>(max_score);  // (read only: ReadoutAdjointArgs)
+    a.p.out_log_rel = const_cast<float*>(log_rel);
+    a.w = weights;
+    a.n_cols = (int)n_cols;
+    a.c_pad = (int)readout_adjoint_c_pad(n_cols);
+    a.out = out;
+    const int64_t slice = READOUT_ADJOINT_SLICE;
+    const int64_t nq_pad = readout_adjoint_nq_pad(std::min(nq, slice));
+    ScanTemps tmp;
+    tmp.stream = stream;
+    if (tmp.alloc({(size_t)nq_pad * (size_t)ix->dim_pad * 2, (size_t)nq_pad * (size_t)a.c_pad * 2, (size_t)a.c_pad * sizeof(int)})) return -1;
+    a.p.q_stage = tmp.p[0];
+    a.w_stage = tmp.p[1];
+    a.col_k = tmp.p[2];
+    hipError_t le = launch_readout_adjoint_columns(a, nq, stream);
+    for (int64_t q0 = 0; q0 < nq && le == hipSuccess; q0 += slice)
+        le = launch_posterior_adjoint(a, q0, std::min(slice, nq - q0), (q0 > 0 || accumulate) ? 1 : 0, stream);
+    if (le != hipSuccess) (void)hipGetLastError();
+    const hipError_t fe = tmp.release();
+    if (le != hipSuccess) return fail("posterior-adjoint launch failed: %s", hipGetErrorString(le));
+    HIP_OK(fe);
     return 0;
 }
 

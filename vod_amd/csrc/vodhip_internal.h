@@ -376,6 +376,23 @@ hipError_t launch_readout_grad_vmax(const void* values, int64_t n_rows, int c_pa
 // queries [q_first, q_first + nq) of the caller's batch -> out_grad rows [q_first ..); a query's bits do not depend on the split
 hipError_t launch_posterior_expectation_backward(const ReadoutGradArgs& a, int64_t q_first, int64_t nq, hipStream_t stream);
 
+// ---- launchers (kernels_readout_adjoint.hip): the read-out's adjoint P^T W, its gradient in the value table; ONE scan, a row per owner ----
+struct ReadoutAdjointArgs {
+    PartitionArgs p;                  // the forward's call; out_max / out_log_rel are INPUTS here (the forward's words), `part` is unused;
+                                      // q_stage: readout_adjoint_nq_pad(queries of a launch) * dim_pad 16-bit words
+    const float* w = nullptr;         // [rows of the caller's batch][n_cols]: the weights
+    int n_cols = 0, c_pad = 0;        // 1 <= n_cols <= c_pad = 64 * ceil(n_cols / 64) <= 256
+    // temporaries
+    void* w_stage = nullptr;          // readout_adjoint_nq_pad(queries of a launch) * c_pad 16-bit words
+    void* col_k = nullptr;            // c_pad ints: the exponent per weight column (launch_readout_adjoint_columns)
+    float* out = nullptr;             // [ntotal][n_cols]
+};
+int64_t readout_adjoint_nq_pad(int64_t nq);  // the staged queries of a launch: a multiple of 256
+// col_k <- the per-column exponents over all nq rows of a.w: once per call, in front of its slices
+hipError_t launch_readout_adjoint_columns(const ReadoutAdjointArgs& a, int64_t nq, hipStream_t stream);
+// queries [q_first, q_first + nq) of the caller's batch, nq <= 1024 * 1024: out = (add ? out : 0) + their contribution
+hipError_t launch_posterior_adjoint(const ReadoutAdjointArgs& a, int64_t q_first, int64_t nq, int add, hipStream_t stream);
+
 // ---- launchers (kernels_sample_posterior.hip): k rows without replacement from p(z | q) over the whole store --------------------
 struct PosteriorSampleArgs {
     PartitionArgs p;                  // the log-partition call of the same batch: its launches run first, unchanged

@@ -25,6 +25,7 @@
 #include "stats_fold.h"
 #include "divergence_fold.h"
 #include "readout_fold.h"
+#include "readout_adjoint_fold.h"
 #include "readout_grad_fold.h"
 #include "vodhip_internal.h"
 
@@ -1282,6 +1283,39 @@ int vodhip_node_index_posterior_expectation_backward(vodhip_node_index_t* nx, co
         }))
         return -1;
     vodhip::fold_posterior_expectation_backward(parts.data(), G, nq, (int64_t)dim, out_grad_queries);
+    return 0;
+}
+
+// The read-out's adjoint behind the one handle (H2a): every shard runs the flat call on its own rows with the GLOBAL forward words; its
+// result is its slab of rows of the global one, so the slabs are concatenated (readout_adjoint_fold.h).  A shard that holds no row is a
+// no-op and owns no slab.
+int vodhip_node_index_posterior_adjoint(vodhip_node_index_t* nx, const void* queries, int q_dtype, int64_t nq, float beta, const int32_t* q_labels, int n_per_query,
+                                        const float* max_score, const float* log_rel, const float* weights, int64_t n_cols, float* out) {
+    if (!nx) return nfail("index is NULL");
+    if (const char* msg = vodhip::posterior_adjoint_args_error(queries, q_dtype, nq, beta, q_labels, n_per_query, max_score, log_rel, weights, n_cols, out))
+        return node_partition_args_fail(msg, q_dtype, beta);
+    if (node_scan_refusal(nx, "posterior_adjoint")) return -1;
+    std::lock_guard<std::mutex> guard(nx->mu);
+    if (node_labels_refusal(nx, q_labels)) return -1;
+    if (nx->ntotal == 0) return 0;
+    if (nq == 0) {
+        std::memset(out, 0, (size_t)nx->ntotal * (size_t)n_cols * sizeof(float));
+        return 0;
+    }
+    const int G = nx->n;
+    const size_t slab = (size_t)nx->rows_per_shard * (size_t)n_cols;  // shard g: its rows [lo, hi) at g * slab
+    std::vector<float> parts((size_t)G * slab);
+    ShardFanout f(nx);
+    const int iq = f.input(queries, query_bytes(nx, nq, q_dtype)), il = f.input(q_labels, label_bytes(q_labels, nq, n_per_query));
+    const int im = f.input(max_score, (size_t)nq * sizeof(float)), ir = f.input(log_rel, (size_t)nq * sizeof(float));
+    const int iw = f.input(weights, (size_t)nq * (size_t)n_cols * sizeof(float));
+    const int io = f.output(parts.data(), slab * sizeof(float));
+    if (f.run([&](int g, void* const* p, hipStream_t st) {
+            return vodhip_index_posterior_adjoint(nx->shard[g], p[iq], q_dtype, nq, beta, (const int32_t*)p[il], n_per_query, (const float*)p[im], (const float*)p[ir],
+                                                  (const float*)p[iw], n_cols, 0, (float*)p[io], st);
+        }))
+        return -1;
+    for (int g = 0; g < G; ++g) vodhip::place_posterior_adjoint_slab(parts.data(), (int64_t)slab, g, nx->ntotal, nx->rows_per_shard, n_cols, out);
     return 0;
 }
 

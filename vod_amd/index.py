@@ -841,6 +841,78 @@ class HipFlatIndex:
         `-torch.log(index.expected_values(q, T)[torch.arange(nq), labels]).mean()`."""
         return _ExpectedValues.apply(queries, self, float(temperature), subset)
 
+    def posterior_adjoint(self, queries, weights, log_partition: "LogPartition | None" = None, temperature: float = 1.0, subset=None,
+                          out=None, accumulate: bool = False) -> torch.Tensor:
+        """The adjoint of the read-out, its gradient in the value table: `out[z, c] = sum_q p(z | q) weights[q, c]` with
+        `p(z | q) = exp(<q~, x~_z> / temperature - log Z(q))` - `P^T W`, a float32 device tensor `[ntotal, n_cols]`; it reduces over the
+        QUERIES per stored row.  `weights` is `[nq, n_cols]` (a vector is one column), 1 <= n_cols <= 256: with `weights = dL / dy` the
+        result is `dL / dV` of `y = posterior_expectation(...)`.  The call reads no value table.  `log_partition` is the `LogPartition` of
+        any forward call with the same queries, temperature and subset (its `max_score` and `log_rel` are inputs: ONE scan of the store);
+        with None the method runs `log_partition` first, two scans in all.  Exact over every stored row, no `[nq, N]` matrix; every row
+        has one owning workgroup that adds the queries in batch order: no atomics, the same bits on every repeat.  Each column of
+        `weights` is normalised by its power of two before it is rounded to the store dtype (1e-6 loss gradients do not flush in fp16);
+        scaling a column by a power of two scales the output column by exactly that power.  A query with no eligible row (or a +inf
+        score) contributes nothing; a NaN or an infinity in column c of `weights` makes column c of every row NaN (`vodhip.h` H2a).
+
+        `out`: a float32 `[ntotal, n_cols]` device tensor to write into; `accumulate=True` adds to what it holds.  Other arguments as
+        `log_partition`.  L2 and `exact_f32` indexes refuse (the library's message)."""
+        q = self._prep_queries(queries)
+        nq = q.shape[0]
+        beta = 1.0 / float(temperature) if temperature else float("nan")
+        sub, n_sub = None, 0
+        if subset is not None:
+            sub = subset if isinstance(subset, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(subset))
+            sub = sub.to(self.device, torch.int32).contiguous()
+            if sub.ndim != 2 or sub.shape[0] != nq:
+                raise ValueError(f"expected subset labels of shape [{nq}, S], got {tuple(sub.shape)}")
+            n_sub = int(sub.shape[1])
+        w_given = torch.as_tensor(weights)
+        w = w_given.detach().to(self.device, torch.float32)
+        w = (w.reshape(-1, 1) if w.ndim == 1 else w).contiguous()
+        if w.ndim != 2 or w.shape[0] != nq:
+            raise ValueError(f"expected weights of shape [{nq}, n_cols], got {tuple(w_given.shape)}")
+        n_cols = int(w.shape[1])
+        if log_partition is None:
+            log_partition = self.log_partition(q, temperature, sub)
+        max_score = torch.as_tensor(log_partition.max_score).to(self.device, torch.float32).contiguous()
+        log_rel = torch.as_tensor(log_partition.log_rel).to(self.device, torch.float32).contiguous()
+        if max_score.shape != (nq,) or log_rel.shape != (nq,):
+            raise ValueError(f"expected max_score and log_rel of shape ({nq},)")
+        ntotal = self.ntotal
+        if out is None:
+            if accumulate:
+                raise ValueError("accumulate=True needs `out`")
+            out = torch.empty((ntotal, n_cols), dtype=torch.float32, device=self.device)
+        elif out.shape != (ntotal, n_cols) or out.dtype != torch.float32 or not out.is_contiguous() or out.device != self.device:
+            raise ValueError(f"expected `out` a contiguous float32 [{ntotal}, {n_cols}] tensor on {self.device}")
+        spare = max_score.new_empty(1)  # (nothing to read or write: non-NULL pointers, so that the library's own refusals are the ones reported)
+        with torch.cuda.device(self.device):
+            _native.check(self._lib.vodhip_index_posterior_adjoint(
+                self._h, q.data_ptr(), _native.torch_dtype_code(q.dtype), nq, beta, None if sub is None else sub.data_ptr(), n_sub,
+                max_score.data_ptr(), log_rel.data_ptr(), (w if w.numel() else spare).data_ptr(), n_cols, 1 if accumulate else 0,
+                (out if out.numel() else spare).data_ptr(), _native.current_stream_ptr(self.device)))
+        for t, given in ((q, queries), (sub, subset), (w, weights), (max_score, log_partition.max_score), (log_rel, log_partition.log_rel)):
+            if t is not None and t is not given:
+                t.record_stream(torch.cuda.current_stream(self.device))
+        return out
+
+    def row_mass(self, queries, temperature: float = 1.0, query_weights=None, subset=None, log_partition: "LogPartition | None" = None) -> torch.Tensor:
+        """The exact posterior mass every stored row receives from a query set, `mass[z] = sum_q query_weights[q] p(z | q)`
+        (`query_weights` ones by default): a float32 device tensor `[ntotal]`, `posterior_adjoint` of one column.  It sums to the number
+        (the weight) of the queries that have an eligible row; a truncated top-k cannot give it: which rows a training set ever looks at,
+        which are hubs, which are dead."""
+        q = self._prep_queries(queries)
+        w = torch.ones((q.shape[0],), dtype=torch.float32, device=self.device) if query_weights is None else torch.as_tensor(query_weights).reshape(-1)
+        return self.posterior_adjoint(q, w, log_partition, temperature, subset).reshape(-1)
+
+    def read_out(self, queries: torch.Tensor, values: torch.Tensor, temperature: float = 1.0, subset=None) -> torch.Tensor:
+        """`set_row_values(values)` followed by the read-out `y = P V~`, a float32 `[nq, n_cols]` tensor differentiable (once) in
+        `queries` AND in `values`: exact attention over the store with a trainable value table.  The gradient in the queries is
+        `posterior_expectation_backward` (cast to their dtype), the gradient in the values `posterior_adjoint(queries, grad_out, the
+        forward's words)` cast to the dtype and device of `values` - straight through the table's rounding to the store dtype.  Each
+        costs one more scan of the store and runs only when that input requires a gradient.  The index keeps the table afterwards."""
+        return _ReadOut.apply(queries, values, self, float(temperature), subset)
+
     def sample_posterior(self, queries, k: int, temperature: float = 1.0, *, seed: int, query_offset: int = 0, subset=None,
                          id_base: int = 0, out=None) -> "PosteriorSample":
         """`k` rows drawn WITHOUT replacement from the softmax over the WHOLE store, `p(z | q) = exp(<q~, x~_z> / temperature - log Z(q))`,
@@ -1215,6 +1287,37 @@ class _ExpectedValues(torch.autograd.Function):
         pe = PosteriorExpectation(values, LogPartition(max_score * beta + log_rel, max_score, log_rel))
         g = torch.as_tensor(ctx.index.posterior_expectation_backward(queries, grad_out, pe, ctx.temperature, ctx.subset))
         return g.to(device=ctx.q_device, dtype=ctx.q_dtype), None, None, None
+
+
+class _ReadOut(torch.autograd.Function):
+    """`index.read_out`: `index` is anything with `set_row_values`, `posterior_expectation`, `posterior_expectation_backward` and
+    `posterior_adjoint(queries, weights, log_partition, temperature, subset)`."""
+
+    @staticmethod
+    def forward(ctx, queries, values, index, temperature, subset):
+        index.set_row_values(values.detach())
+        pe = index.posterior_expectation(queries.detach(), temperature, subset)
+        y = torch.as_tensor(pe.values)
+        ctx.index, ctx.temperature, ctx.subset = index, temperature, subset
+        ctx.q_dtype, ctx.q_device = queries.dtype, queries.device
+        ctx.v_dtype, ctx.v_device, ctx.v_shape = values.dtype, values.device, values.shape
+        ctx.save_for_backward(queries.detach(), y, torch.as_tensor(pe.log_partition.max_score), torch.as_tensor(pe.log_partition.log_rel))
+        return y.to(queries.device).clone()
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_out):
+        queries, y, max_score, log_rel = ctx.saved_tensors
+        beta = 1.0 / ctx.temperature if ctx.temperature else float("nan")
+        lp = LogPartition(max_score * beta + log_rel, max_score, log_rel)
+        grad_q = grad_v = None
+        if ctx.needs_input_grad[0]:
+            g = torch.as_tensor(ctx.index.posterior_expectation_backward(queries, grad_out, PosteriorExpectation(y, lp), ctx.temperature, ctx.subset))
+            grad_q = g.to(device=ctx.q_device, dtype=ctx.q_dtype)
+        if ctx.needs_input_grad[1]:
+            g = torch.as_tensor(ctx.index.posterior_adjoint(queries, grad_out, lp, ctx.temperature, ctx.subset))
+            grad_v = g.to(device=ctx.v_device, dtype=ctx.v_dtype).reshape(ctx.v_shape)
+        return grad_q, grad_v, None, None, None
 
 
 def topk_log_coverage(scores: torch.Tensor, log_partition: LogPartition, temperature: float = 1.0) -> torch.Tensor:
@@ -1829,6 +1932,57 @@ class HipNodeIndex:
         """`HipFlatIndex.expected_values` over every shard: a float32 `[nq, n_cols]` tensor on the device of `queries`, differentiable
         with respect to them (forward `posterior_expectation`, backward `posterior_expectation_backward`, both through the host)."""
         return _ExpectedValues.apply(queries, self, float(temperature), subset)
+
+    def posterior_adjoint(self, queries, weights, log_partition: "LogPartition | None" = None, temperature: float = 1.0,
+                          subset: np.ndarray | None = None, out: np.ndarray | None = None, accumulate: bool = False) -> np.ndarray:
+        """`HipFlatIndex.posterior_adjoint` over every shard: each shard computes its own rows of `P^T W` on its own device from the
+        GLOBAL `log_partition` (this index's, from any forward call; None runs `log_partition` first), and the slabs are concatenated:
+        nothing is folded, and handed the words of one index holding all the rows the result equals that index's bit for bit.  Host
+        arrays -> a float32 NumPy array `[ntotal, n_cols]`; `accumulate=True` adds the result to `out` on the host."""
+        q = self._host_queries(queries)
+        nq = int(q.shape[0])
+        beta = 1.0 / float(temperature) if temperature else float("nan")
+        sub, n_sub = self._host_subset(subset, nq)
+
+        def host(a):
+            return np.ascontiguousarray(a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else a, dtype=np.float32)
+
+        w = host(weights)
+        w = np.ascontiguousarray(w.reshape(-1, 1) if w.ndim == 1 else w)
+        if w.ndim != 2 or w.shape[0] != nq:
+            raise ValueError(f"expected weights of shape [{nq}, n_cols], got {tuple(w.shape)}")
+        n_cols = int(w.shape[1])
+        if log_partition is None:
+            log_partition = self.log_partition(q, temperature, sub)
+        max_score, log_rel = host(log_partition.max_score), host(log_partition.log_rel)
+        if max_score.shape != (nq,) or log_rel.shape != (nq,):
+            raise ValueError(f"expected max_score and log_rel of shape ({nq},)")
+        ntotal = self.ntotal
+        if accumulate and out is None:
+            raise ValueError("accumulate=True needs `out`")
+        if out is not None and (out.shape != (ntotal, n_cols) or out.dtype != np.float32 or not out.flags.c_contiguous):
+            raise ValueError(f"expected `out` a contiguous float32 [{ntotal}, {n_cols}] array")
+        res = np.empty((ntotal, n_cols), dtype=np.float32) if out is None or accumulate else out
+        spare = np.zeros(1, dtype=np.float32)
+        with torch.cuda.device(self.device):
+            _native.check(self._lib.vodhip_node_index_posterior_adjoint(
+                self._h, q.ctypes.data, 2 if q.dtype == np.float32 else 0, nq, beta, None if sub is None else sub.ctypes.data, n_sub,
+                max_score.ctypes.data, log_rel.ctypes.data, (w if w.size else spare).ctypes.data, n_cols, (res if res.size else spare).ctypes.data))
+        if accumulate:
+            out += res
+            return out
+        return res
+
+    def row_mass(self, queries, temperature: float = 1.0, query_weights=None, subset=None, log_partition: "LogPartition | None" = None) -> np.ndarray:
+        """`HipFlatIndex.row_mass` over every shard: a float32 NumPy array `[ntotal]`."""
+        q = self._host_queries(queries)
+        w = np.ones((q.shape[0],), dtype=np.float32) if query_weights is None else query_weights
+        return self.posterior_adjoint(q, w, log_partition, temperature, subset).reshape(-1)
+
+    def read_out(self, queries: torch.Tensor, values: torch.Tensor, temperature: float = 1.0, subset=None) -> torch.Tensor:
+        """`HipFlatIndex.read_out` over every shard: a float32 `[nq, n_cols]` tensor on the device of `queries`, differentiable in them
+        and in `values` (every call through the host)."""
+        return _ReadOut.apply(queries, values, self, float(temperature), subset)
 
     def sample_posterior(self, queries, k: int, temperature: float = 1.0, *, seed: int, query_offset: int = 0,
                          subset: np.ndarray | None = None) -> "PosteriorSample":
