@@ -399,13 +399,59 @@ int vodhip_index_posterior_expectation_backward(vodhip_index_t* index, const voi
  * Temporaries are hipMallocAsync on `stream`: the staged queries and weights of a slice and the column exponents.  The call only
  * enqueues work.  nq == 0 zero-fills `out` unless accumulating; ntotal == 0 is a no-op; a refused call writes nothing.  REFUSED as H2p,
  * and: n_cols outside [1, 256], a NULL weights (nq > 0) or out.
- * NOT BUILT: the gradient in the stored rows (three adjoint calls of up to 256 columns over a dim-768 store would give it), L2 and
- * exact_f32 stores, weights wider than VODHIP_READOUT_MAX_COLS. */
+ * NOT BUILT: L2 and exact_f32 stores, weights wider than VODHIP_READOUT_MAX_COLS.  The gradient in the STORED ROWS is H2k: adjoint
+ * calls with W[q, :] = a_q q~_q, ceil(dim / 256) of them, give its log Z term only - the read-out term's weight p(z | q) (u_qz - ubar_q)
+ * depends on the row and is not of the form P^T W. */
 int vodhip_index_posterior_adjoint(vodhip_index_t* index, const void* queries, int q_dtype, int64_t nq, float beta,
                                    const int32_t* q_labels_dev /* NULL = unrestricted */, int n_per_query,
                                    const float* max_score /* DEVICE [nq] */, const float* log_rel /* DEVICE [nq] */,
                                    const float* weights /* DEVICE [nq][n_cols] */, int64_t n_cols /* 1 .. 256 */, int accumulate,
                                    float* out /* DEVICE [ntotal][n_cols] */, void* stream);
+
+/* H2k. The posterior's gradient in the STORED ROWS (kernels_key_grad.hip): with a = grad_log_z, G = grad_values, y = values,
+ *     out[z, d] = beta * sum_{q < nq, z eligible for q} p(z | q) c_qz q~[q, d]     (DEVICE float32 [ntotal][dim]),
+ *     c_qz = a_q + (u_qz - ubar_q),   u_qz = sum_c G[q, c] v~[z, c],   ubar_q = sum_c G[q, c] y[q, c]:
+ * up to rounding the gradient of sum_q a_q log Z_q + sum_qc G_qc y_qc (H2p's log Z, H2e's y = P v~ on the attached table) in the stored
+ * values x~ as stored - the rounding of the rows at ingest is passed straight through.  With H2b (queries) and H2a (table) the exact
+ * attention over the store is differentiable in all three operands.  grad_log_z (DEVICE [nq]) or NULL = zero; grad_values (DEVICE
+ * float32 [nq][n_cols]) or NULL = zero, given together with `values`, the forward's out_values; at least one of the two.  With
+ * grad_values NULL no table is read and none needs to be attached.  INPUTS besides: the queries, beta and labels of the forward call and
+ * its two words max_score, log_rel (DEVICE [nq]), so no partition scan runs in front.  Eligibility, queries, labels, stream and
+ * concurrency rules are H2p's; vmax is H2b's cached one (the first call that needs it waits for `stream` once).
+ * SCALES, batch-wide.  k = the exponent of the largest finite |G| of the batch (of the largest |a| without G or with G all zero);
+ * G^ = round16(G 2^-k), a' = a 2^-k in float32, ubar_q as H2b forms it from G^; B_q = |a'_q| + sum_c |G^_qc| vmax_c + |ubar_q|;
+ * R = the power of two above max_q B_q (1 + 2^-10).  The scales cannot be per query: the contraction runs over the queries inside the
+ * MFMA, and a per-query factor could not be undone behind it.  CONSEQUENCE: on an fp16 store a query whose gradient is far below the
+ * batch's largest loses relative precision (its weights sit low in fp16's range; scaled by 2^15 they stay normal down to 2^-29 R), not
+ * absolute precision.  Scaling a and G together by a power of two scales `out` by exactly that power (within float32's range).
+ * One workgroup owns 64 consecutive stored rows and one chunk of the store's padded columns - 256 columns without grad_values, 192
+ * with (the u accumulator is live beside the scores) - and walks the batch in tiles of 256 queries, in query order: the scores from the
+ * shared K loop with its operands exchanged (the same bits as every scan), u from the same loop on (G^ tile, the 64 table rows), the
+ * weight round16(e * ((a'_q + (u - ubar_q)) / R)), e = expf(min(0, beta (s - max_score)) - log_rel), centred BEFORE its one rounding
+ * (fp16: scaled by 2^15 first), contracted with the tile's staged queries on the MFMA (float32 accumulate); the row is multiplied by
+ * beta and 2^k R.  Batches above 1024 queries run in slices of 1024: the first slice stores, later slices add in slice order.  ONE
+ * order per (row, column), fixed by the queries' positions in the batch alone; no atomics in the scan, no partials, no fold: an element
+ * depends on its row, the queries, their words and the batch-wide (k, R) alone and is the same bits on every repeat.  accumulate != 0:
+ * the first slice adds to what `out` holds as well.
+ * WEIGH +0, exact: a query without finite (max_score, log_rel), a query with B_q = 0 (a zero a_q and G[q, :]), a row >= ntotal, a NaN
+ * score, a row the query's labels do not allow.  Such queries behind a batch change no bit of `out`.
+ * NON-FINITE INPUT.  A NaN or an infinity in a_q, in G[q, :] or in a y[q, c] whose G^[q, c] is not zero (or scales beyond float32)
+ * makes EVERY element of `out` NaN: the query weighs on every row, as it would in a dense softmax.  A non-finite table entry in a row
+ * eligible for a query with G^ != 0 makes that row's u, and the row of `out`, NaN.  There is no sanitising pass.
+ * Temporaries are hipMallocAsync on `stream`.  The call only enqueues work (but see vmax).  nq == 0 zero-fills `out` unless
+ * accumulating; ntotal == 0 is a no-op; a refused call writes nothing.  REFUSED as H2p (an L2 index and a VODHIP_EXACT_F32 store with
+ * their own messages), and: grad_log_z and grad_values both NULL, grad_values without values, grad_values without an attached table or
+ * with one of another row count, a NULL out.
+ * NOT BUILT: the form in which each wave owns a column range and the scores are computed once per tile (K-loop steps K + K per tile
+ * against this design's chunks * (K + slices), K = dim_pad / 64; it needs a weight exchange through the LDS and half-tiles to fit
+ * 160 KB); the gradient of the listed scores (H2i) in the rows, a sparse index_add; L2 and exact_f32 stores; an HTTP route; the
+ * process-group engine; the gradient in beta. */
+int vodhip_index_posterior_key_gradient(vodhip_index_t* index, const void* queries, int q_dtype, int64_t nq, float beta,
+                                        const int32_t* q_labels_dev /* NULL = unrestricted */, int n_per_query,
+                                        const float* max_score /* DEVICE [nq] */, const float* log_rel /* DEVICE [nq] */,
+                                        const float* grad_log_z /* DEVICE [nq], or NULL */, const float* values /* DEVICE [nq][n_cols], or NULL */,
+                                        const float* grad_values /* DEVICE [nq][n_cols], or NULL */, int accumulate,
+                                        float* out /* DEVICE [ntotal][dim] */, void* stream);
 
 /* H2s. k rows drawn WITHOUT replacement from that softmax over the whole store, with priority-sampling weights
  * (kernels_sample_posterior.hip).  Gumbel-top-k: the k eligible rows with the largest keys
@@ -751,6 +797,18 @@ int vodhip_node_index_posterior_adjoint(vodhip_node_index_t* index, const void* 
                                         const float* max_score, const float* log_rel /* HOST [nq] */,
                                         const float* weights /* HOST [nq][n_cols] */, int64_t n_cols,
                                         float* out /* HOST [ntotal][n_cols] */);
+/* H2k behind the one handle: HOST buffers, host-synchronous.  Every shard computes its own rows from the GLOBAL (max_score, log_rel,
+ * values) and gradients it is handed.  The batch-wide scales are functions of those and of the table's column maxima: the node call
+ * takes the largest of the shards' cached maxima - the maxima over all the rows - once and hands it to every shard, so each forms the
+ * scales one index holding all the rows would (key_grad_fold.h).  The slabs are concatenated; nothing is folded.  Handed the words of
+ * one index holding all the rows, the result equals that index's bit for bit.  `out` is overwritten (no accumulate).  Refusals as for
+ * the flat call. */
+int vodhip_node_index_posterior_key_gradient(vodhip_node_index_t* index, const void* queries, int q_dtype, int64_t nq, float beta,
+                                             const int32_t* q_labels /* HOST or NULL */, int n_per_query,
+                                             const float* max_score, const float* log_rel /* HOST [nq] */,
+                                             const float* grad_log_z /* HOST [nq], or NULL */,
+                                             const float* values, const float* grad_values /* HOST [nq][n_cols], or NULL */,
+                                             float* out /* HOST [ntotal][dim] */);
 /* H2s behind the one handle: HOST buffers, host-synchronous.  Every shard runs vodhip_index_sample_posterior with id_base = its first
  * global row; keys are unnormalised and the noise is a function of the global row, so the k + 1 best of the union of the shards'
  * lists ARE the k + 1 best of the whole store: ids, scores and keys equal one index holding all the rows bit for bit.  The pairs are

@@ -27,6 +27,7 @@
 #include "readout_fold.h"
 #include "readout_adjoint_fold.h"
 #include "readout_grad_fold.h"
+#include "key_grad_fold.h"
 #include "scan_slices.h"
 #include "search_plan.h"
 #include "collate_plan.h"
@@ -1707,6 +1708,21 @@ int vodhip_index_posterior_expectation(vodhip_index_t* ix, const void* queries, 
     return 0;
 }
 
+// the column maxima of the value table: once per table; the first call waits for them, so that a later call on any stream may read them
+static int ensure_value_vmax(vodhip_index_t* ix, const char* what, hipStream_t stream) {
+    std::lock_guard<std::mutex> guard(ix->mu);
+    if (ix->value_vmax_ready) return 0;
+    if (!ix->value_vmax) HIP_OK(hipMalloc((void**)&ix->value_vmax, (size_t)ix->value_c_pad * sizeof(float)));
+    const hipError_t e = launch_readout_grad_vmax(ix->row_value, ix->value_rows, (int)ix->value_c_pad, ix->dtype, ix->value_vmax, stream);
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        return fail("%s launch failed: %s", what, hipGetErrorString(e));
+    }
+    HIP_OK(hipStreamSynchronize(stream));
+    ix->value_vmax_ready = true;
+    return 0;
+}
+
 // ---- the read-out's gradient in the query (kernels_readout_grad.hip): g staged, ONE scan behind the forward's words, one finish ----
 int vodhip_index_posterior_expectation_backward(vodhip_index_t* ix, const void* queries, int q_dtype, int64_t nq, float beta, const int32_t* q_labels_dev,
                                                 int n_per_query, const float* max_score, const float* log_rel, const float* values, const float* grad_values,
@@ -1723,19 +1739,7 @@ int vodhip_index_posterior_expectation_backward(vodhip_index_t* ix, const void* 
     if (nq == 0) return 0;
     HIP_OK(hipSetDevice(ix->device));
     hipStream_t stream = (hipStream_t)stream_;
-    {  // the column maxima of the table: once per table; the first call waits for them, so that a later call on any stream may read them
-        std::lock_guard<std::mutex> guard(ix->mu);
-        if (!ix->value_vmax_ready) {
-            if (!ix->value_vmax) HIP_OK(hipMalloc((void**)&ix->value_vmax, (size_t)ix->value_c_pad * sizeof(float)));
-            const hipError_t e = launch_readout_grad_vmax(ix->row_value, ix->value_rows, (int)ix->value_c_pad, ix->dtype, ix->value_vmax, stream);
-            if (e != hipSuccess) {
-                (void)hipGetLastError();
-                return fail("posterior-expectation-backward launch failed: %s", hipGetErrorString(e));
-            }
-            HIP_OK(hipStreamSynchronize(stream));
-            ix->value_vmax_ready = true;
-        }
-    }
+    if (ensure_value_vmax(ix, "posterior-expectation-backward", stream)) return -1;
     ReadoutGradArgs a;
     fill_scan_inputs(a.p, ix, queries, q_dtype, q_labels_dev, n_per_query);
     a.p.beta = beta;
@@ -1817,6 +1821,72 @@ int vodhip_index_posterior_adjoint(vodhip_index_t* ix, const void* queries, int 
     if (le != hipSuccess) return fail("posterior-adjoint launch failed: %s", hipGetErrorString(le));
     HIP_OK(fe);
     return 0;
+}
+
+// ---- the posterior's gradient in the stored rows (kernels_key_grad.hip): the batch-wide scales, then per slice of 1024 queries the
+// stagings and ONE scan whose workgroups own their output rows.  vmax_dev: the column maxima the scales are formed from - NULL = the
+// index's own (the flat call); a node index hands every shard the maxima over all the rows (vodhip_node.hip) ----
+static int index_key_gradient(vodhip_index_t* ix, const void* queries, int q_dtype, int64_t nq, float beta, const int32_t* q_labels_dev, int n_per_query,
+                              const float* max_score, const float* log_rel, const float* grad_log_z, const float* values, const float* grad_values,
+                              const float* vmax_dev, int accumulate, float* out, hipStream_t stream) {
+    if (!ix) return fail("index is NULL");
+    if (const char* msg = posterior_key_gradient_args_error(queries, q_dtype, nq, beta, q_labels_dev, n_per_query, max_score, log_rel, grad_log_z, values,
+                                                            grad_values, out))
+        return partition_args_fail(msg, q_dtype, beta);
+    if (scan_refusal(ix, "posterior_key_gradient", q_labels_dev)) return -1;
+    if (grad_values) {
+        if (!ix->row_value) return fail("posterior_key_gradient: grad_values needs a value table (vodhip_index_set_row_values)");
+        if (ix->value_rows != ix->ntotal)
+            return fail("posterior_key_gradient: the value table holds %lld rows, the index %lld: set the table again after adding rows", (long long)ix->value_rows,
+                        (long long)ix->ntotal);
+    }
+    if (ix->ntotal == 0) return 0;
+    HIP_OK(hipSetDevice(ix->device));
+    if (nq == 0) {
+        if (!accumulate) HIP_OK(hipMemsetAsync(out, 0, (size_t)ix->ntotal * (size_t)ix->dim * sizeof(float), stream));
+        return 0;
+    }
+    if (nq > 0x7fffffffll) return fail("posterior_key_gradient: nq=%lld is beyond 2^31 - 1", (long long)nq);
+    if (grad_values && !vmax_dev && ensure_value_vmax(ix, "posterior-key-gradient", stream)) return -1;
+    KeyGradArgs a;
+    fill_scan_inputs(a.p, ix, queries, q_dtype, q_labels_dev, n_per_query);
+    a.p.beta = beta;
+    a.p.out_max = const_cast<float*>(max_score);  // (read only: KeyGradArgs)
+    a.p.out_log_rel = const_cast<float*>(log_rel);
+    a.a = grad_log_z;
+    a.g = grad_values;
+    if (grad_values) {
+        a.y = values;
+        a.values = ix->row_value;
+        a.n_cols = (int)ix->value_cols;
+        a.c_pad = (int)ix->value_c_pad;
+        a.vmax = vmax_dev ? vmax_dev : ix->value_vmax;
+    }
+    a.out = out;
+    const int64_t slice = KEY_GRAD_SLICE;
+    const int64_t nq_pad = key_grad_nq_pad(std::min(nq, slice));
+    ScanTemps tmp;
+    tmp.stream = stream;
+    if (tmp.alloc({(size_t)nq_pad * (size_t)ix->dim_pad * 2, (size_t)nq_pad * (size_t)a.c_pad * 2, (size_t)nq * key_grad_aux_bytes(), key_grad_scales_bytes()})) return -1;
+    a.p.q_stage = tmp.p[0];
+    a.g_stage = tmp.p[1];
+    a.aux = tmp.p[2];
+    a.scales = tmp.p[3];
+    hipError_t le = launch_key_grad_scales(a, nq, stream);
+    for (int64_t q0 = 0; q0 < nq && le == hipSuccess; q0 += slice)
+        le = launch_posterior_key_gradient(a, q0, std::min(slice, nq - q0), (q0 > 0 || accumulate) ? 1 : 0, stream);
+    if (le != hipSuccess) (void)hipGetLastError();
+    const hipError_t fe = tmp.release();
+    if (le != hipSuccess) return fail("posterior-key-gradient launch failed: %s", hipGetErrorString(le));
+    HIP_OK(fe);
+    return 0;
+}
+
+int vodhip_index_posterior_key_gradient(vodhip_index_t* ix, const void* queries, int q_dtype, int64_t nq, float beta, const int32_t* q_labels_dev, int n_per_query,
+                                        const float* max_score, const float* log_rel, const float* grad_log_z, const float* values, const float* grad_values,
+                                        int accumulate, float* out, void* stream_) {
+    return index_key_gradient(ix, queries, q_dtype, nq, beta, q_labels_dev, n_per_query, max_score, log_rel, grad_log_z, values, grad_values, nullptr, accumulate, out,
+                              (hipStream_t)stream_);
 }
 
 // ---- posterior sampling (kernels_sample_posterior.hip): the log-partition launches, key-max scan, threshold, emit scan, select ------
@@ -2727,3 +2797,22 @@ int vodhip_debug_read_probe(int which, int64_t* out, int n) {
 
 }  // extern "C"
 
+// ---- what the node form of the key gradient needs of a shard beyond the C-ABI (vodhip_internal.h) ----
+namespace vodhip {
+
+int index_value_vmax(vodhip_index* ix, float* vmax_host, int64_t c_pad, hipStream_t stream) {
+    if (!ix || !ix->row_value || ix->value_c_pad != c_pad) return fail("posterior_key_gradient: the shard holds no value table of that width");
+    HIP_OK(hipSetDevice(ix->device));
+    if (ensure_value_vmax(ix, "posterior-key-gradient", stream)) return -1;
+    HIP_OK(hipMemcpyAsync(vmax_host, ix->value_vmax, (size_t)c_pad * sizeof(float), hipMemcpyDeviceToHost, stream));
+    HIP_OK(hipStreamSynchronize(stream));
+    return 0;
+}
+
+int index_posterior_key_gradient(vodhip_index* ix, const void* queries, int q_dtype, int64_t nq, float beta, const int32_t* q_labels_dev, int n_per_query,
+                                 const float* max_score, const float* log_rel, const float* grad_log_z, const float* values, const float* grad_values,
+                                 const float* vmax_dev, float* out, hipStream_t stream) {
+    return index_key_gradient(ix, queries, q_dtype, nq, beta, q_labels_dev, n_per_query, max_score, log_rel, grad_log_z, values, grad_values, vmax_dev, 0, out, stream);
+}
+
+}  // namespace vodhip

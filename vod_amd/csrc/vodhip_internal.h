@@ -393,6 +393,41 @@ hipError_t launch_readout_adjoint_columns(const ReadoutAdjointArgs& a, int64_t n
 // queries [q_first, q_first + nq) of the caller's batch, nq <= 1024 * 1024: out = (add ? out : 0) + their contribution
 hipError_t launch_posterior_adjoint(const ReadoutAdjointArgs& a, int64_t q_first, int64_t nq, int add, hipStream_t stream);
 
+// ---- launchers (kernels_key_grad.hip): the posterior's gradient in the stored rows; ONE scan per slice, a row per owner ----
+struct KeyGradArgs {
+    PartitionArgs p;                  // the forward's call; out_max / out_log_rel are INPUTS here (the forward's words), `part` is unused;
+                                      // q_stage: key_grad_nq_pad(queries of a launch) * dim_pad 16-bit words
+    const float* a = nullptr;         // [rows of the caller's batch]: dL / d log Z, or NULL = zero
+    const float* g = nullptr;         // [rows of the caller's batch][n_cols]: dL / dy, or NULL = zero (no table term is compiled in)
+    const float* y = nullptr;         // with g: the forward's values, the same shape
+    const void* values = nullptr;     // with g: the table, as ReadoutArgs
+    const float* vmax = nullptr;      // with g: [c_pad] the largest finite |v~| per column (launch_readout_grad_vmax)
+    int n_cols = 0, c_pad = 0;        // with g: 1 <= n_cols <= c_pad = 64 * ceil(n_cols / 64) <= 256
+    // temporaries
+    void* g_stage = nullptr;          // with g: key_grad_nq_pad(queries of a launch) * c_pad 16-bit words
+    void* aux = nullptr;              // (queries of the CALL) * key_grad_aux_bytes()
+    void* scales = nullptr;           // key_grad_scales_bytes(): the batch-wide words (launch_key_grad_scales)
+    float* out = nullptr;             // [ntotal][dim]
+};
+size_t key_grad_aux_bytes();
+size_t key_grad_scales_bytes();
+int64_t key_grad_nq_pad(int64_t nq);  // the staged queries of a launch: a multiple of 256
+// aux, scales <- the per-query words and the batch-wide scales over all nq rows of a.a / a.g / a.y: once per call, in front of its slices
+hipError_t launch_key_grad_scales(const KeyGradArgs& a, int64_t nq, hipStream_t stream);
+// queries [q_first, q_first + nq) of the caller's batch, nq <= 1024 * 1024: out = (add ? out : 0) + their contribution
+hipError_t launch_posterior_key_gradient(const KeyGradArgs& a, int64_t q_first, int64_t nq, int add, hipStream_t stream);
+
+}  // namespace vodhip
+struct vodhip_index;
+namespace vodhip {
+// the key gradient of one shard of a node index (vodhip_api.hip).  index_value_vmax: the shard's cached column maxima of its part of
+// the value table [c_pad] to the host (computed on first use; waits for `stream`).  index_posterior_key_gradient: the flat call with
+// the column maxima the batch-wide scales are formed from handed in (DEVICE [c_pad]; NULL without grad_values), no accumulate
+int index_value_vmax(vodhip_index* ix, float* vmax_host, int64_t c_pad, hipStream_t stream);
+int index_posterior_key_gradient(vodhip_index* ix, const void* queries, int q_dtype, int64_t nq, float beta, const int32_t* q_labels_dev, int n_per_query,
+                                 const float* max_score, const float* log_rel, const float* grad_log_z, const float* values, const float* grad_values,
+                                 const float* vmax_dev, float* out, hipStream_t stream);
+
 // ---- launchers (kernels_sample_posterior.hip): k rows without replacement from p(z | q) over the whole store --------------------
 struct PosteriorSampleArgs {
     PartitionArgs p;                  // the log-partition call of the same batch: its launches run first, unchanged

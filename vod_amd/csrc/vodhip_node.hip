@@ -27,6 +27,7 @@
 #include "readout_fold.h"
 #include "readout_adjoint_fold.h"
 #include "readout_grad_fold.h"
+#include "key_grad_fold.h"
 #include "vodhip_internal.h"
 
 namespace {
@@ -168,7 +169,7 @@ inline size_t label_bytes(const void* q_labels, int64_t nq, int n_per_query) { r
 // an input is uploaded before the flat call, an output downloaded after it returned 0 - shard g's bytes land at base + g * bytes.
 // A slot of no bytes (a NULL host pointer) allocates nothing and stays NULL.  The caller holds nx->mu.
 struct ShardFanout {
-    static constexpr int MAX_SLOTS = 7;  // (the rank pass)
+    static constexpr int MAX_SLOTS = 9;  // (the key gradient)
     struct Slot { const void* up; char* down; size_t bytes; };
     vodhip_node_index* nx;
     Slot slot[MAX_SLOTS];
@@ -1316,6 +1317,65 @@ int vodhip_node_index_posterior_adjoint(vodhip_node_index_t* nx, const void* que
         }))
         return -1;
     for (int g = 0; g < G; ++g) vodhip::place_posterior_adjoint_slab(parts.data(), (int64_t)slab, g, nx->ntotal, nx->rows_per_shard, n_cols, out);
+    return 0;
+}
+
+// The key gradient behind the one handle (H2k): every shard computes its own rows from the GLOBAL (max_score, log_rel, values) and the
+// global gradients.  The batch-wide scales are functions of those and of the table's column maxima alone: the node takes the largest
+// of the shards' cached maxima - the maxima over all the rows - once and hands it to every shard, so each forms the scales of one index
+// holding all the rows (key_grad_fold.h).  The slabs are concatenated as the adjoint's are; nothing is folded.
+int vodhip_node_index_posterior_key_gradient(vodhip_node_index_t* nx, const void* queries, int q_dtype, int64_t nq, float beta, const int32_t* q_labels,
+                                             int n_per_query, const float* max_score, const float* log_rel, const float* grad_log_z, const float* values,
+                                             const float* grad_values, float* out) {
+    if (!nx) return nfail("index is NULL");
+    if (const char* msg = vodhip::posterior_key_gradient_args_error(queries, q_dtype, nq, beta, q_labels, n_per_query, max_score, log_rel, grad_log_z, values,
+                                                                    grad_values, out))
+        return node_partition_args_fail(msg, q_dtype, beta);
+    if (node_scan_refusal(nx, "posterior_key_gradient")) return -1;
+    std::lock_guard<std::mutex> guard(nx->mu);
+    if (node_labels_refusal(nx, q_labels)) return -1;
+    if (grad_values) {
+        if (!nx->value_cols) return nfail("posterior_key_gradient: grad_values needs a value table (vodhip_node_index_set_row_values)");
+        if (nx->value_rows != nx->ntotal)
+            return nfail("posterior_key_gradient: the value table holds %lld rows, the index %lld: set the table again after adding rows",
+                         (long long)nx->value_rows, (long long)nx->ntotal);
+    }
+    if (nx->ntotal == 0) return 0;
+    const size_t dim = (size_t)nx->dim;
+    if (nq == 0) {
+        std::memset(out, 0, (size_t)nx->ntotal * dim * sizeof(float));
+        return 0;
+    }
+    const int G = nx->n;
+    const size_t n_cols = grad_values ? (size_t)nx->value_cols : 0;
+    const int64_t c_pad = grad_values ? vodhip::readout_c_pad((int64_t)n_cols) : 0;
+    std::vector<float> vmax((size_t)c_pad);
+    if (grad_values) {
+        std::vector<float> vparts((size_t)G * (size_t)c_pad);
+        for (int g = 0; g < G; ++g)
+            if (vodhip::index_value_vmax(nx->shard[g], vparts.data() + (size_t)g * (size_t)c_pad, c_pad, nx->stream[g])) {
+                (void)hipSetDevice(nx->device[0]);
+                return nfail("shard %d: %s", g, vodhip_last_error());
+            }
+        (void)hipSetDevice(nx->device[0]);
+        vodhip::fold_key_grad_vmax(vparts.data(), G, c_pad, vmax.data());
+    }
+    const size_t slab = (size_t)nx->rows_per_shard * dim;  // shard g: its rows [lo, hi) at g * slab
+    std::vector<float> parts((size_t)G * slab);
+    ShardFanout f(nx);
+    const int iq = f.input(queries, query_bytes(nx, nq, q_dtype)), il = f.input(q_labels, label_bytes(q_labels, nq, n_per_query));
+    const int im = f.input(max_score, (size_t)nq * sizeof(float)), ir = f.input(log_rel, (size_t)nq * sizeof(float));
+    const int ia = f.input(grad_log_z, (size_t)nq * sizeof(float));
+    const int iy = f.input(grad_values ? values : nullptr, (size_t)nq * n_cols * sizeof(float)), ig = f.input(grad_values, (size_t)nq * n_cols * sizeof(float));
+    const int iv = f.input(grad_values ? vmax.data() : nullptr, (size_t)c_pad * sizeof(float));
+    const int io = f.output(parts.data(), slab * sizeof(float));
+    if (f.run([&](int g, void* const* p, hipStream_t st) {
+            return vodhip::index_posterior_key_gradient(nx->shard[g], p[iq], q_dtype, nq, beta, (const int32_t*)p[il], n_per_query, (const float*)p[im],
+                                                        (const float*)p[ir], (const float*)p[ia], (const float*)p[iy], (const float*)p[ig], (const float*)p[iv],
+                                                        (float*)p[io], st);
+        }))
+        return -1;
+    for (int g = 0; g < G; ++g) vodhip::place_posterior_adjoint_slab(parts.data(), (int64_t)slab, g, nx->ntotal, nx->rows_per_shard, (int64_t)dim, out);
     return 0;
 }
 

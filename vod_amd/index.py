@@ -905,13 +905,94 @@ class HipFlatIndex:
         w = torch.ones((q.shape[0],), dtype=torch.float32, device=self.device) if query_weights is None else torch.as_tensor(query_weights).reshape(-1)
         return self.posterior_adjoint(q, w, log_partition, temperature, subset).reshape(-1)
 
-    def read_out(self, queries: torch.Tensor, values: torch.Tensor, temperature: float = 1.0, subset=None) -> torch.Tensor:
+    def read_out(self, queries: torch.Tensor, values: torch.Tensor, temperature: float = 1.0, subset=None, keys=None) -> torch.Tensor:
         """`set_row_values(values)` followed by the read-out `y = P V~`, a float32 `[nq, n_cols]` tensor differentiable (once) in
         `queries` AND in `values`: exact attention over the store with a trainable value table.  The gradient in the queries is
         `posterior_expectation_backward` (cast to their dtype), the gradient in the values `posterior_adjoint(queries, grad_out, the
         forward's words)` cast to the dtype and device of `values` - straight through the table's rounding to the store dtype.  Each
-        costs one more scan of the store and runs only when that input requires a gradient.  The index keeps the table afterwards."""
-        return _ReadOut.apply(queries, values, self, float(temperature), subset)
+        costs one more scan of the store and runs only when that input requires a gradient.  The index keeps the table afterwards.
+
+        `keys`: a float tensor `[ntotal, dim]`, e.g. `index.stored_rows().float().requires_grad_()`, of which the caller states that it is
+        the store.  It is not read: its only role is to receive `key_gradient(queries, grad_values=grad_out, the forward's words)`,
+        cast to its dtype and device, when it requires a gradient - straight through the rounding of the rows at ingest.  Without
+        `keys` the call is exactly what it was."""
+        if keys is None:
+            return _ReadOut.apply(queries, values, self, float(temperature), subset)
+        return _ReadOutKeys.apply(queries, values, _checked_keys(self, keys), self, float(temperature), subset)
+
+    def key_gradient(self, queries, *, grad_log_z=None, grad_values=None, expectation: "PosteriorExpectation | None" = None,
+                     log_partition: "LogPartition | None" = None, temperature: float = 1.0, subset=None, out=None,
+                     accumulate: bool = False) -> torch.Tensor:
+        """The posterior's exact gradient in the STORED ROWS: `out[z, d] = sum_q p(z | q) c_qz q~[q, d] / temperature` with
+        `c_qz = a_q + (u_qz - ubar_q)`, `a = grad_log_z` (`[nq]`), `u_qz = <G[q], v~_z>`, `ubar_q = <G[q], y[q]>`, `G = grad_values`
+        (`[nq, n_cols]`, acting on the attached value table) - a float32 device tensor `[ntotal, dim]`, up to rounding the gradient of
+        `sum_q a_q log Z_q + sum_qc G_qc y_qc` in the rows as stored.  At least one of the two gradients; an absent one counts as zero
+        (and without `grad_values` no table is needed).  `expectation` (what `posterior_expectation` returned for the same queries,
+        temperature and subset; needed values with `grad_values`) or `log_partition` hand in the forward's words: ONE scan of the
+        store; with neither the forward runs first.  Every row has one owning workgroup that adds the queries in batch order: no
+        atomics, the same bits on every repeat.  The gradients are normalised by ONE power of two per batch (not per query: the
+        contraction runs over the queries), so on an fp16 store a query whose gradient is far below the batch's largest loses
+        relative, not absolute, precision.  A query with no eligible row contributes nothing; a NaN or an infinity in `a[q]` or
+        `G[q]` makes the whole result NaN (`vodhip.h` H2k).
+
+        `out`: a float32 `[ntotal, dim]` device tensor to write into; `accumulate=True` adds to what it holds.  Other arguments as
+        `log_partition`.  L2 and `exact_f32` indexes refuse (the library's message)."""
+        q = self._prep_queries(queries)
+        nq = q.shape[0]
+        beta = 1.0 / float(temperature) if temperature else float("nan")
+        sub, n_sub = None, 0
+        if subset is not None:
+            sub = subset if isinstance(subset, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(subset))
+            sub = sub.to(self.device, torch.int32).contiguous()
+            if sub.ndim != 2 or sub.shape[0] != nq:
+                raise ValueError(f"expected subset labels of shape [{nq}, S], got {tuple(sub.shape)}")
+            n_sub = int(sub.shape[1])
+        a = g = y = None
+        if grad_log_z is not None:
+            a = torch.as_tensor(grad_log_z).detach().to(self.device, torch.float32).reshape(-1).contiguous()
+            if a.shape != (nq,):
+                raise ValueError(f"expected grad_log_z of shape ({nq},), got {tuple(torch.as_tensor(grad_log_z).shape)}")
+        if grad_values is not None:
+            g = torch.as_tensor(grad_values).detach().to(self.device, torch.float32).contiguous()
+            if expectation is None and self.row_values_shape is not None:
+                expectation = self.posterior_expectation(q, temperature, sub)
+            if expectation is not None:
+                y = torch.as_tensor(expectation.values).to(self.device, torch.float32).contiguous()
+                if y.ndim != 2 or y.shape[0] != nq or g.shape != y.shape:
+                    raise ValueError(f"expected values and grad_values of one shape [{nq}, n_cols], got {tuple(y.shape)} and {tuple(g.shape)}")
+            shape = self.row_values_shape
+            if shape is not None and (g.ndim != 2 or g.shape[1] != shape[1]):
+                raise ValueError(f"expected grad_values of shape [{nq}, {shape[1]}] (the table's columns), got {tuple(g.shape)}")
+        if expectation is not None and log_partition is None:
+            log_partition = expectation.log_partition
+        if log_partition is None:
+            log_partition = self.log_partition(q, temperature, sub)
+        max_score = torch.as_tensor(log_partition.max_score).to(self.device, torch.float32).contiguous()
+        log_rel = torch.as_tensor(log_partition.log_rel).to(self.device, torch.float32).contiguous()
+        if max_score.shape != (nq,) or log_rel.shape != (nq,):
+            raise ValueError(f"expected max_score and log_rel of shape ({nq},)")
+        ntotal = self.ntotal
+        if out is None:
+            if accumulate:
+                raise ValueError("accumulate=True needs `out`")
+            out = torch.empty((ntotal, self.dim), dtype=torch.float32, device=self.device)
+        elif out.shape != (ntotal, self.dim) or out.dtype != torch.float32 or not out.is_contiguous() or out.device != self.device:
+            raise ValueError(f"expected `out` a contiguous float32 [{ntotal}, {self.dim}] tensor on {self.device}")
+        spare = max_score.new_empty(1)  # (nothing to read or write: non-NULL pointers, so that the library's own refusals are the ones reported)
+
+        def ptr(t):
+            return None if t is None else (t if t.numel() else spare).data_ptr()
+
+        with torch.cuda.device(self.device):
+            _native.check(self._lib.vodhip_index_posterior_key_gradient(
+                self._h, q.data_ptr(), _native.torch_dtype_code(q.dtype), nq, beta, None if sub is None else sub.data_ptr(), n_sub,
+                max_score.data_ptr(), log_rel.data_ptr(), ptr(a), ptr(g if y is None else y), ptr(g), 1 if accumulate else 0,
+                (out if out.numel() else spare).data_ptr(), _native.current_stream_ptr(self.device)))
+        for t, given in ((q, queries), (sub, subset), (a, grad_log_z), (g, grad_values), (y, None), (max_score, log_partition.max_score),
+                         (log_rel, log_partition.log_rel)):
+            if t is not None and t is not given:
+                t.record_stream(torch.cuda.current_stream(self.device))
+        return out
 
     def sample_posterior(self, queries, k: int, temperature: float = 1.0, *, seed: int, query_offset: int = 0, subset=None,
                          id_base: int = 0, out=None) -> "PosteriorSample":
@@ -965,7 +1046,7 @@ class HipFlatIndex:
         log_tau = torch.where(torch.isnan(log_tau), torch.full_like(log_tau, float("-inf")), log_tau)
         return PosteriorSample(ids, scores, log_p, log_weight, log_tau, keys, LogPartition(max_score * beta + log_rel, max_score, log_rel))
 
-    def log_z(self, queries: torch.Tensor, temperature=1.0, subset=None) -> torch.Tensor:
+    def log_z(self, queries: torch.Tensor, temperature=1.0, subset=None, keys=None) -> torch.Tensor:
         """`log Z(q)` over the whole store as a float32 `[nq]` tensor that is differentiable with respect to `queries`: forward is
         `posterior_mean`, backward `grad_q = grad_out[:, None] * mean / temperature`, cast to the dtype of `queries` (straight through
         the rounding of the queries to the store dtype).  No gradient flows to the store; rows of `grad_q` whose `log_z` is not finite
@@ -974,7 +1055,16 @@ class HipFlatIndex:
         `temperature` may be a one-element tensor (a learnable scale): reading its value is ONE host synchronisation.  If it requires
         grad, `grad_T = -sum_q grad_out[q] * mean_score[q] / T^2` with `mean_score` of `posterior_stats` (queries whose `log_z` is not
         finite contribute 0).  With a tensor temperature `posterior_mean` runs only when `queries` requires grad: temperature-only
-        calibration costs about one `log_partition`.  With a float temperature nothing changes."""
+        calibration costs about one `log_partition`.  With a float temperature nothing changes.
+
+        `keys`: a float tensor `[ntotal, dim]`, e.g. `index.stored_rows().float().requires_grad_()`, of which the caller states that it is
+        the store.  It is not read: its only role is to receive `key_gradient(queries, grad_log_z=grad_out, the forward's words)`,
+        cast to its dtype and device, when it requires a gradient.  Not together with a tensor temperature (ValueError).  Without
+        `keys` the call is exactly what it was."""
+        if keys is not None:
+            if isinstance(temperature, torch.Tensor):
+                raise ValueError("log_z: `keys` together with a tensor temperature is not supported; pass a float temperature")
+            return _LogZKeys.apply(queries, _checked_keys(self, keys), self, float(temperature), subset)
         if isinstance(temperature, torch.Tensor):
             return _LogZ.apply(queries, self, temperature, subset)
         return _LogZ.apply(queries, self, float(temperature), subset)
@@ -1318,6 +1408,83 @@ class _ReadOut(torch.autograd.Function):
             g = torch.as_tensor(ctx.index.posterior_adjoint(queries, grad_out, lp, ctx.temperature, ctx.subset))
             grad_v = g.to(device=ctx.v_device, dtype=ctx.v_dtype).reshape(ctx.v_shape)
         return grad_q, grad_v, None, None, None
+
+
+def _checked_keys(index, keys) -> torch.Tensor:
+    """`keys` of `log_z` / `read_out`: a floating tensor of the store's shape."""
+    if not isinstance(keys, torch.Tensor) or not keys.is_floating_point() or tuple(keys.shape) != (index.ntotal, index.dim):
+        got = tuple(keys.shape) if isinstance(keys, torch.Tensor) else type(keys).__name__
+        raise ValueError(f"expected `keys` a float tensor [{index.ntotal}, {index.dim}] (the store), got {got}")
+    return keys
+
+
+def _key_grad_to(g, keys_meta):
+    dtype, device = keys_meta
+    return torch.as_tensor(g).to(device=device, dtype=dtype)
+
+
+class _LogZKeys(torch.autograd.Function):
+    """`index.log_z(..., keys=K)` with a float temperature: `_LogZ`'s forward and query gradient, bit for bit, and
+    `index.key_gradient(queries, grad_log_z=grad_out, log_partition=the forward's)` for `K`."""
+
+    @staticmethod
+    def forward(ctx, queries, keys, index, temperature, subset):
+        ctx.q_dtype, ctx.q_device = queries.dtype, queries.device
+        ctx.k_meta = (keys.dtype, keys.device)
+        pm = index.posterior_mean(queries.detach(), temperature, subset)
+        lp = pm.log_partition
+        log_z = torch.as_tensor(lp.log_z)
+        ctx.index, ctx.temperature, ctx.subset = index, temperature, subset
+        ctx.beta = 1.0 / temperature
+        ctx.save_for_backward(queries.detach(), torch.as_tensor(pm.mean), log_z, torch.as_tensor(lp.max_score), torch.as_tensor(lp.log_rel))
+        return log_z.clone()
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_out):
+        queries, mean, log_z, max_score, log_rel = ctx.saved_tensors
+        g_q = g_k = None
+        if ctx.needs_input_grad[0]:
+            g_q = log_z_backward(grad_out.to(mean.device), mean, log_z, ctx.beta, ctx.q_dtype).to(ctx.q_device)
+        if ctx.needs_input_grad[1]:
+            lp = LogPartition(log_z, max_score, log_rel)
+            g_k = _key_grad_to(ctx.index.key_gradient(queries, grad_log_z=grad_out, log_partition=lp, temperature=ctx.temperature, subset=ctx.subset), ctx.k_meta)
+        return g_q, g_k, None, None, None
+
+
+class _ReadOutKeys(torch.autograd.Function):
+    """`index.read_out(..., keys=K)`: `_ReadOut`'s forward and its two gradients, bit for bit, and
+    `index.key_gradient(queries, grad_values=grad_out, expectation=the forward's)` for `K`."""
+
+    @staticmethod
+    def forward(ctx, queries, values, keys, index, temperature, subset):
+        ctx.k_meta = (keys.dtype, keys.device)
+        index.set_row_values(values.detach())
+        pe = index.posterior_expectation(queries.detach(), temperature, subset)
+        y = torch.as_tensor(pe.values)
+        ctx.index, ctx.temperature, ctx.subset = index, temperature, subset
+        ctx.q_dtype, ctx.q_device = queries.dtype, queries.device
+        ctx.v_dtype, ctx.v_device, ctx.v_shape = values.dtype, values.device, values.shape
+        ctx.save_for_backward(queries.detach(), y, torch.as_tensor(pe.log_partition.max_score), torch.as_tensor(pe.log_partition.log_rel))
+        return y.to(queries.device).clone()
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_out):
+        queries, y, max_score, log_rel = ctx.saved_tensors
+        beta = 1.0 / ctx.temperature if ctx.temperature else float("nan")
+        lp = LogPartition(max_score * beta + log_rel, max_score, log_rel)
+        pe = PosteriorExpectation(y, lp)
+        grad_q = grad_v = grad_k = None
+        if ctx.needs_input_grad[0]:
+            g = torch.as_tensor(ctx.index.posterior_expectation_backward(queries, grad_out, pe, ctx.temperature, ctx.subset))
+            grad_q = g.to(device=ctx.q_device, dtype=ctx.q_dtype)
+        if ctx.needs_input_grad[1]:
+            g = torch.as_tensor(ctx.index.posterior_adjoint(queries, grad_out, lp, ctx.temperature, ctx.subset))
+            grad_v = g.to(device=ctx.v_device, dtype=ctx.v_dtype).reshape(ctx.v_shape)
+        if ctx.needs_input_grad[2]:
+            grad_k = _key_grad_to(ctx.index.key_gradient(queries, grad_values=grad_out, expectation=pe, temperature=ctx.temperature, subset=ctx.subset), ctx.k_meta)
+        return grad_q, grad_v, grad_k, None, None, None
 
 
 def topk_log_coverage(scores: torch.Tensor, log_partition: LogPartition, temperature: float = 1.0) -> torch.Tensor:
@@ -1979,10 +2146,71 @@ class HipNodeIndex:
         w = np.ones((q.shape[0],), dtype=np.float32) if query_weights is None else query_weights
         return self.posterior_adjoint(q, w, log_partition, temperature, subset).reshape(-1)
 
-    def read_out(self, queries: torch.Tensor, values: torch.Tensor, temperature: float = 1.0, subset=None) -> torch.Tensor:
+    def read_out(self, queries: torch.Tensor, values: torch.Tensor, temperature: float = 1.0, subset=None, keys=None) -> torch.Tensor:
         """`HipFlatIndex.read_out` over every shard: a float32 `[nq, n_cols]` tensor on the device of `queries`, differentiable in them
-        and in `values` (every call through the host)."""
-        return _ReadOut.apply(queries, values, self, float(temperature), subset)
+        and in `values` (every call through the host); `keys` as there."""
+        if keys is None:
+            return _ReadOut.apply(queries, values, self, float(temperature), subset)
+        return _ReadOutKeys.apply(queries, values, _checked_keys(self, keys), self, float(temperature), subset)
+
+    def key_gradient(self, queries, *, grad_log_z=None, grad_values=None, expectation: "PosteriorExpectation | None" = None,
+                     log_partition: "LogPartition | None" = None, temperature: float = 1.0, subset: np.ndarray | None = None,
+                     out: np.ndarray | None = None, accumulate: bool = False) -> np.ndarray:
+        """`HipFlatIndex.key_gradient` over every shard: each shard computes its own rows on its own device from the GLOBAL forward
+        words (this index's; with none handed in the forward runs first) and the batch-wide scales the node call forms once - the
+        column maxima of the table are taken over all the shards - and the slabs are concatenated: nothing is folded, and handed the
+        words of one index holding all the rows the result equals that index's bit for bit.  Host arrays -> a float32 NumPy array
+        `[ntotal, dim]`; `accumulate=True` adds the result to `out` on the host."""
+        q = self._host_queries(queries)
+        nq = int(q.shape[0])
+        beta = 1.0 / float(temperature) if temperature else float("nan")
+        sub, n_sub = self._host_subset(subset, nq)
+
+        def host(a):
+            return np.ascontiguousarray(a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else a, dtype=np.float32)
+
+        a = g = y = None
+        if grad_log_z is not None:
+            a = host(grad_log_z).reshape(-1)
+            if a.shape != (nq,):
+                raise ValueError(f"expected grad_log_z of shape ({nq},), got {tuple(a.shape)}")
+        if grad_values is not None:
+            g = host(grad_values)
+            if expectation is None and self.row_values_shape is not None:
+                expectation = self.posterior_expectation(q, temperature, sub)
+            if expectation is not None:
+                y = host(expectation.values)
+                if y.ndim != 2 or y.shape[0] != nq or g.shape != y.shape:
+                    raise ValueError(f"expected values and grad_values of one shape [{nq}, n_cols], got {tuple(y.shape)} and {tuple(g.shape)}")
+            shape = self.row_values_shape
+            if shape is not None and (g.ndim != 2 or g.shape[1] != shape[1]):
+                raise ValueError(f"expected grad_values of shape [{nq}, {shape[1]}] (the table's columns), got {tuple(g.shape)}")
+        if expectation is not None and log_partition is None:
+            log_partition = expectation.log_partition
+        if log_partition is None:
+            log_partition = self.log_partition(q, temperature, sub)
+        max_score, log_rel = host(log_partition.max_score), host(log_partition.log_rel)
+        if max_score.shape != (nq,) or log_rel.shape != (nq,):
+            raise ValueError(f"expected max_score and log_rel of shape ({nq},)")
+        ntotal = self.ntotal
+        if accumulate and out is None:
+            raise ValueError("accumulate=True needs `out`")
+        if out is not None and (out.shape != (ntotal, self.dim) or out.dtype != np.float32 or not out.flags.c_contiguous):
+            raise ValueError(f"expected `out` a contiguous float32 [{ntotal}, {self.dim}] array")
+        res = np.empty((ntotal, self.dim), dtype=np.float32) if out is None or accumulate else out
+        spare = np.zeros(1, dtype=np.float32)
+
+        def ptr(t):
+            return None if t is None else (t if t.size else spare).ctypes.data
+
+        with torch.cuda.device(self.device):
+            _native.check(self._lib.vodhip_node_index_posterior_key_gradient(
+                self._h, q.ctypes.data, 2 if q.dtype == np.float32 else 0, nq, beta, None if sub is None else sub.ctypes.data, n_sub,
+                max_score.ctypes.data, log_rel.ctypes.data, ptr(a), ptr(g if y is None else y), ptr(g), (res if res.size else spare).ctypes.data))
+        if accumulate:
+            out += res
+            return out
+        return res
 
     def sample_posterior(self, queries, k: int, temperature: float = 1.0, *, seed: int, query_offset: int = 0,
                          subset: np.ndarray | None = None) -> "PosteriorSample":
