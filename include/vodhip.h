@@ -453,6 +453,39 @@ int vodhip_index_posterior_key_gradient(vodhip_index_t* index, const void* queri
                                         const float* grad_values /* DEVICE [nq][n_cols], or NULL */, int accumulate,
                                         float* out /* DEVICE [ntotal][dim] */, void* stream);
 
+/* H2u. Stored rows CHANGED IN PLACE (kernels_update.hip): where H2k's gradient goes, and a partial refresh of the store by id.
+ *     VODHIP_UPDATE_SET   x[row] = rows[j]
+ *     VODHIP_UPDATE_ADD   x[row] = x[row] + alpha * rows[j]     (float32: p = alpha * rows[j] rounded, then the sum rounded - no fma)
+ * LISTED form (ids != NULL): slot j targets row ids[j] - id_base.  DENSE form (ids == NULL): slot j targets row row_begin + j; id_base
+ * is not read.  `rows` is [n, dim] of src_dtype (F16 / BF16 / F32), at `location` as `ids` is.
+ * EVERY plane the store keeps is written in the same launch, with the bytes vodhip_index_add writes for the same final values: the
+ * 16-bit plane (rounded, saturating, pad columns zero), an L2 store's three bias columns (from the values as stored, in the ingest's
+ * order of summation), a VODHIP_EXACT_F32 store's float32 plane and its two per-row statistics.  After the call the store equals, byte
+ * for byte, one freshly built by vodhip_index_add from the final rows.  ADD's `old` is the float32 row of a VODHIP_EXACT_F32 store -
+ * the master copy - and the 16-bit row widened anywhere else: there the 16-bit row IS the master copy, and a step below half a unit of
+ * its last place is lost.  ntotal, the row labels and the value table (H2e) are NOT touched: a table attached before stays attached.
+ * SLOTS.  A slot whose id is negative, below id_base or not below id_base + ntotal is SKIPPED and counted (H2i's pad rule).  The same
+ * id in several slots: the LAST slot is applied, SET and ADD alike (NumPy's x[ids] = rows), the others write nothing and are counted
+ * as duplicates - for ADD unique ids are the contract, the count is how a caller learns it was broken.  Resolved without a sort and
+ * without a race by one int32 word per capacity row (allocated by the first listed call, all zero between calls); the result is the
+ * same bytes on every repeat.
+ * STATS (vodhip_index_get_stat; they wait for the device): "last_update_written", "last_update_skipped", "last_update_duplicates" of
+ * the last call.  "l2_saturated_rows" grows by every saturated bias an update writes: it counts saturation EVENTS since create /
+ * reset, not rows now saturated - a row updated out of saturation stays counted.
+ * VODHIP_EXACT_F32: the two maxima of the error bound are re-derived from the per-row statistics of the rows NOW stored before the
+ * next search (8 bytes per row); a maximum left behind by a row that was replaced never made a result wrong, but it placed the
+ * outlier cuts.
+ * DEVICE sources only enqueue work on `stream`; HOST sources go through the ingest's staging slots and return when the rows are
+ * written, as vodhip_index_add.  n == 0 is a no-op that succeeds; SET ignores alpha.  REFUSED (-1, nothing written): searches in
+ * flight (the rule of vodhip_index_add), a dense range outside [0, ntotal), n < 0 or n >= 2^31 - 1, NULL rows with n > 0, a bad
+ * src_dtype, location or mode, a non-finite alpha with ADD.
+ * NOT BUILT: removing rows, an HTTP route, the value table or the labels by id, stochastic rounding. */
+#define VODHIP_UPDATE_SET 0
+#define VODHIP_UPDATE_ADD 1
+int vodhip_index_update_rows(vodhip_index_t* index, const int64_t* ids /* [n], or NULL: rows row_begin .. row_begin + n */, int64_t row_begin,
+                             const void* rows /* [n, dim] */, int64_t n, int src_dtype, int location /* of ids AND rows */,
+                             int mode, float alpha, int64_t id_base, void* stream);
+
 /* H2s. k rows drawn WITHOUT replacement from that softmax over the whole store, with priority-sampling weights
  * (kernels_sample_posterior.hip).  Gumbel-top-k: the k eligible rows with the largest keys
  *     key(q, z) = fl(fl(beta * s(q, z)) - logf(E)),   E = -log1pf(-v),   by (key desc, id asc),
@@ -809,6 +842,14 @@ int vodhip_node_index_posterior_key_gradient(vodhip_node_index_t* index, const v
                                              const float* grad_log_z /* HOST [nq], or NULL */,
                                              const float* values, const float* grad_values /* HOST [nq][n_cols], or NULL */,
                                              float* out /* HOST [ntotal][dim] */);
+/* H2u behind the one handle: HOST ids (GLOBAL row ids, or NULL with the global row_begin) and HOST rows.  The call is ROUTED on the
+ * host, not replicated (update_fold.h): the slots are partitioned by owning shard, id / rows_per_shard, in slot order - so the last
+ * slot that lists a row is still the last its shard sees - and shard g receives its slots and their rows only, with id_base = its
+ * first global row; the dense form splits at the shard boundaries.  A slot whose id is negative or not below ntotal goes to no shard
+ * and is counted as skipped.  The shards are updated one after the other; the three stats of H2u are sums over the shards (+ those
+ * slots) on vodhip_node_index_get_stat.  Refusals as for the flat call. */
+int vodhip_node_index_update_rows(vodhip_node_index_t* index, const int64_t* ids /* HOST or NULL */, int64_t row_begin,
+                                  const void* rows /* HOST */, int64_t n, int src_dtype, int mode, float alpha);
 /* H2s behind the one handle: HOST buffers, host-synchronous.  Every shard runs vodhip_index_sample_posterior with id_base = its first
  * global row; keys are unnormalised and the noise is a function of the global row, so the k + 1 best of the union of the shards'
  * lists ARE the k + 1 best of the whole store: ids, scores and keys equal one index holding all the rows bit for bit.  The pairs are

@@ -27,6 +27,7 @@ HOST, DEVICE = 0, 1
 MAX_K = 2048
 MAX_LISTED = 8192  # VODHIP_MAX_LISTED: slots per query of the top-k form of `score_ids`
 MAX_ENGINES = 4
+UPDATE_SET, UPDATE_ADD = 0, 1  # VODHIP_UPDATE_SET / VODHIP_UPDATE_ADD: `mode` of vodhip_index_update_rows
 
 
 class NativeLibraryError(RuntimeError):
@@ -76,6 +77,7 @@ SIGNATURES: dict[str, tuple] = {
     "vodhip_index_posterior_expectation_backward": (_i32, [_vp, _vp, _i32, _i64, _c.c_float, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
     "vodhip_index_posterior_adjoint": (_i32, [_vp, _vp, _i32, _i64, _c.c_float, _vp, _i32, _vp, _vp, _vp, _i64, _i32, _vp, _vp]),
     "vodhip_index_posterior_key_gradient": (_i32, [_vp, _vp, _i32, _i64, _c.c_float, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _vp]),
+    "vodhip_index_update_rows": (_i32, [_vp, _vp, _i64, _vp, _i64, _i32, _i32, _i32, _c.c_float, _i64, _vp]),
     "vodhip_index_count_above": (_i32, [_vp, _vp, _i32, _i64, _vp, _vp, _i64, _i64, _vp, _i32, _vp, _vp]),
     "vodhip_index_rank_ids": (_i32, [_vp, _vp, _i32, _i64, _vp, _i64, _i64, _vp, _i32, _vp, _vp, _vp]),
     "vodhip_index_scan_score_ids": (_i32, [_vp, _vp, _i32, _i64, _vp, _i64, _i64, _vp, _i32, _vp, _vp, _vp]),
@@ -118,6 +120,7 @@ SIGNATURES: dict[str, tuple] = {
     "vodhip_node_index_posterior_expectation_backward": (_i32, [_vp, _vp, _i32, _i64, _c.c_float, _vp, _i32, _vp, _vp, _vp, _vp, _vp]),
     "vodhip_node_index_posterior_adjoint": (_i32, [_vp, _vp, _i32, _i64, _c.c_float, _vp, _i32, _vp, _vp, _vp, _i64, _vp]),
     "vodhip_node_index_posterior_key_gradient": (_i32, [_vp, _vp, _i32, _i64, _c.c_float, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "vodhip_node_index_update_rows": (_i32, [_vp, _vp, _i64, _vp, _i64, _i32, _i32, _c.c_float]),
     "vodhip_node_index_rank_ids": (_i32, [_vp, _vp, _i32, _i64, _vp, _i64, _vp, _i32, _vp, _vp]),
     "vodhip_node_index_count_above": (_i32, [_vp, _vp, _i32, _i64, _vp, _vp, _i64, _vp, _i32, _vp]),
     "vodhip_node_index_range_search": (_i32, [_vp, _vp, _i32, _i64, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _i64]),

@@ -28,6 +28,7 @@
 #include "readout_adjoint_fold.h"
 #include "readout_grad_fold.h"
 #include "key_grad_fold.h"
+#include "update_fold.h"
 #include "scan_slices.h"
 #include "search_plan.h"
 #include "collate_plan.h"
@@ -119,13 +120,23 @@ struct vodhip_index {
     hipEvent_t stage_done[2] = {nullptr, nullptr};
     int64_t ingest_threads = 0;  // CPU threads that fill the pinned staging slots (0 = auto: min(8, hardware threads))
     int64_t last_ingest_pinned_src = 0;
+    // vodhip_index_update_rows, listed form (kernels_update.hip): the owner word per capacity row (zero between calls), the call's
+    // (skipped, duplicates) words, the ids of a host call; allocated by the first listed call.  last_update_n / _listed: the slots of
+    // the last call and whether it had a list (a dense call writes them all and has nothing to read back)
+    int* upd_owner = nullptr;
+    unsigned int* upd_counts = nullptr;
+    int64_t* upd_ids = nullptr;
+    int64_t upd_ids_cap = 0;
+    int64_t last_update_n = 0;
+    bool last_update_listed = false;
     // VODHIP_EXACT_F32 (kernels_exact.hip): the float32 rows, the statistics of the error bound, per-slot lists of the scan
     bool exact = false;
     float* data32 = nullptr;                 // [capacity + 1][dim_pad]
     unsigned int* norm_stats = nullptr;      // device [EXS_WORDS]: max |x|^2, max |x - x~|^2 (atomics at ingest), the ordinary maxima, the outliers
     float* row_n2 = nullptr;                 // device [capacity + 1]: |x|^2 of every row (written at ingest)
     float* row_d2 = nullptr;                 // device [capacity + 1]: |x - x~|^2
-    bool stats_dirty = true;                 // rows were added / the store was reset since the statistics below were derived
+    bool stats_dirty = true;                 // rows were added / updated / the store was reset since the statistics below were derived
+    bool maxima_stale = false;               // rows were updated since the two maxima words were derived: they may belong to rows that left
     float ord_n2 = 0.f, ord_d2 = 0.f, cut_n2 = 0.f, cut_d2 = 0.f;  // host copies (refresh_exact_stats): the bound's maxima over the ordinary rows, the outlier cuts
     int n_out = 0;                           // outlier rows (scored by every query instead of bounded)
     int64_t exact_adapt = 1;                 // 1: the list length k' follows what the last searches needed (0: always the formula)
@@ -276,6 +287,10 @@ void exact_bound_args(const vodhip_index* ix, ExactArgs& xa) {
 // fetch them.  ONE host sync per batch of adds.
 int refresh_exact_stats(vodhip_index* ix, hipStream_t stream) {
     if (!ix->exact || !ix->stats_dirty) return 0;
+    // rows were updated in place: the maxima the ingest launches kept may belong to rows that left.  They do not make a result wrong,
+    // but they place the outlier cuts (level_of: M / 4^j) - re-derive them from the rows now stored (8 bytes per row)
+    if (ix->maxima_stale) HIP_OK(launch_update_maxima(ix->row_n2, ix->row_d2, ix->ntotal, ix->norm_stats, stream));
+    ix->maxima_stale = false;
     HIP_OK(launch_exact_stats(ix->row_n2, ix->row_d2, ix->ntotal, ix->norm_stats, stream));
     unsigned int w[8];
     HIP_OK(hipMemcpyAsync(w, ix->norm_stats, sizeof(w), hipMemcpyDeviceToHost, stream));
@@ -520,6 +535,62 @@ int enqueue_l2_finish(vodhip_index* ix, const PendingSearch& ps, hipStream_t str
     return 0;
 }
 
+// `consume(dev_src, n, r)` is enqueued on `stream` for every slice: rows [r, r + n) of the source, staged at dev_src.  Nothing is waited
+// for behind the last slice.  Shared by vodhip_index_add and the host form of vodhip_index_update_rows.
+template <class Consume>
+int pipeline_host_rows(vodhip_index* ix, const void* rows, int64_t n_rows, int64_t row_bytes, hipStream_t stream, int64_t* pinned_src,
+                       Consume&& consume) {
+    // Host rows -> HBM, pipelined (round 3; the index is rebuilt every training period, /root/reference/src/vod_exps/recipes/
+    // periodic_training.py:53-96, so ingest time is on the trainer's critical path):
+    //   pageable source (a NumPy array, an .npy memory map, decoded zarr chunks): CPU threads copy slice i + 1 into a pinned staging
+    //   slot while the DMA engine moves slice i and the convert kernel rounds it into the store - two slots, one stream;
+    //   pinned / registered source: the DMA reads it in place, no CPU copy at all.
+    // Round 2 pushed 64 MB slices of pageable memory through hipMemcpyAsync (staged by the runtime, synchronous) and waited after each.
+    hipPointerAttribute_t attr;
+    bool src_pinned = false;
+    if (hipPointerGetAttributes(&attr, rows) == hipSuccess) src_pinned = attr.type == hipMemoryTypeHost;
+    else (void)hipGetLastError();  // an ordinary host pointer is "invalid value" to the runtime: not an error here
+    *pinned_src = src_pinned;
+    const int64_t rows_per_stage = std::max<int64_t>(1, STAGE_BYTES / row_bytes);
+    for (int b = 0; b < 2; ++b) {
+        if (!ix->stage_dev[b]) HIP_OK(hipMalloc(&ix->stage_dev[b], STAGE_BYTES));
+        if (!src_pinned && !ix->stage_pin[b]) HIP_OK(hipHostMalloc(&ix->stage_pin[b], STAGE_BYTES, hipHostMallocDefault));
+        if (!ix->stage_done[b]) HIP_OK(hipEventCreateWithFlags(&ix->stage_done[b], hipEventDisableTiming));
+    }
+    int n_thr = (int)ix->ingest_threads;
+    if (n_thr <= 0) n_thr = (int)std::min<unsigned>(8u, std::max(1u, std::thread::hardware_concurrency()));
+    bool used[2] = {false, false};
+    int slot = 0;
+    for (int64_t r = 0; r < n_rows; r += rows_per_stage, slot ^= 1) {
+        const int64_t n = std::min(rows_per_stage, n_rows - r);
+        const size_t bytes = (size_t)n * row_bytes;
+        const char* src = (const char*)rows + (size_t)r * row_bytes;
+        if (used[slot]) HIP_OK(hipEventSynchronize(ix->stage_done[slot]));  // the slot's previous slice has left the staging buffers
+        const void* dma_src = src;
+        if (!src_pinned) {
+            char* dst = (char*)ix->stage_pin[slot];
+            const int t_use = (int)std::min<size_t>((size_t)n_thr, std::max<size_t>(1, bytes >> 20));  // >= 1 MB per thread
+            if (t_use <= 1) {
+                memcpy(dst, src, bytes);
+            } else {
+                std::vector<std::thread> pool;
+                const size_t per = ((bytes + t_use - 1) / t_use + 4095) & ~(size_t)4095;
+                for (int t = 0; t < t_use; ++t) {
+                    const size_t lo = std::min(bytes, (size_t)t * per), hi = std::min(bytes, lo + per);
+                    if (hi > lo) pool.emplace_back([=] { memcpy(dst + lo, src + lo, hi - lo); });
+                }
+                for (auto& th : pool) th.join();
+            }
+            dma_src = dst;
+        }
+        HIP_OK(hipMemcpyAsync(ix->stage_dev[slot], dma_src, bytes, hipMemcpyHostToDevice, stream));
+        HIP_OK(consume(ix->stage_dev[slot], n, r));
+        HIP_OK(hipEventRecord(ix->stage_done[slot], stream));
+        used[slot] = true;
+    }
+    return 0;
+}
+
 }  // namespace
 
 extern "C" {
@@ -632,6 +703,9 @@ int vodhip_index_destroy(vodhip_index_t* ix) {
         (void)hipFree(ix->x_list_i[i]);
     }
     (void)hipFree(ix->l2_sat);
+    (void)hipFree(ix->upd_owner);
+    (void)hipFree(ix->upd_counts);
+    (void)hipFree(ix->upd_ids);
     for (int i = 0; i < MAX_IN_FLIGHT; ++i)
         for (hipEvent_t e : ix->l2_ev[i])
             if (e) (void)hipEventDestroy(e);
@@ -680,57 +754,112 @@ int vodhip_index_add(vodhip_index_t* ix, const void* rows, int64_t n_rows, int s
         return 0;
     }
     if (src_location != VODHIP_HOST) return fail("invalid src_location %d", src_location);
-    // Host rows -> HBM, pipelined (round 3; the index is rebuilt every training period, /root/reference/src/vod_exps/recipes/
-    // periodic_training.py:53-96, so ingest time is on the trainer's critical path):
-    //   pageable source (a NumPy array, an .npy memory map, decoded zarr chunks): CPU threads copy slice i + 1 into a pinned staging
-    //   slot while the DMA engine moves slice i and the convert kernel rounds it into the store - two slots, one stream;
-    //   pinned / registered source: the DMA reads it in place, no CPU copy at all.
-    // Round 2 pushed 64 MB slices of pageable memory through hipMemcpyAsync (staged by the runtime, synchronous) and waited after each.
-    hipPointerAttribute_t attr;
-    bool src_pinned = false;
-    if (hipPointerGetAttributes(&attr, rows) == hipSuccess) src_pinned = attr.type == hipMemoryTypeHost;
-    else (void)hipGetLastError();  // an ordinary host pointer is "invalid value" to the runtime: not an error here
+    int64_t src_pinned = 0;
+    const int rc = pipeline_host_rows(ix, rows, n_rows, ix->dim * es, stream, &src_pinned,
+                                      [&](const void* dev_src, int64_t n, int64_t r) { return ingest(dev_src, n, ix->ntotal + r); });
     ix->last_ingest_pinned_src = src_pinned;
-    const int64_t row_bytes = ix->dim * es;
-    const int64_t rows_per_stage = std::max<int64_t>(1, STAGE_BYTES / row_bytes);
-    for (int b = 0; b < 2; ++b) {
-        if (!ix->stage_dev[b]) HIP_OK(hipMalloc(&ix->stage_dev[b], STAGE_BYTES));
-        if (!src_pinned && !ix->stage_pin[b]) HIP_OK(hipHostMalloc(&ix->stage_pin[b], STAGE_BYTES, hipHostMallocDefault));
-        if (!ix->stage_done[b]) HIP_OK(hipEventCreateWithFlags(&ix->stage_done[b], hipEventDisableTiming));
-    }
-    int n_thr = (int)ix->ingest_threads;
-    if (n_thr <= 0) n_thr = (int)std::min<unsigned>(8u, std::max(1u, std::thread::hardware_concurrency()));
-    bool used[2] = {false, false};
-    int slot = 0;
-    for (int64_t r = 0; r < n_rows; r += rows_per_stage, slot ^= 1) {
-        const int64_t n = std::min(rows_per_stage, n_rows - r);
-        const size_t bytes = (size_t)n * row_bytes;
-        const char* src = (const char*)rows + (size_t)r * row_bytes;
-        if (used[slot]) HIP_OK(hipEventSynchronize(ix->stage_done[slot]));  // the slot's previous slice has left the staging buffers
-        const void* dma_src = src;
-        if (!src_pinned) {
-            char* dst = (char*)ix->stage_pin[slot];
-            const int t_use = (int)std::min<size_t>((size_t)n_thr, std::max<size_t>(1, bytes >> 20));  // >= 1 MB per thread
-            if (t_use <= 1) {
-                memcpy(dst, src, bytes);
-            } else {
-                std::vector<std::thread> pool;
-                const size_t per = ((bytes + t_use - 1) / t_use + 4095) & ~(size_t)4095;
-                for (int t = 0; t < t_use; ++t) {
-                    const size_t lo = std::min(bytes, (size_t)t * per), hi = std::min(bytes, lo + per);
-                    if (hi > lo) pool.emplace_back([=] { memcpy(dst + lo, src + lo, hi - lo); });
-                }
-                for (auto& th : pool) th.join();
-            }
-            dma_src = dst;
-        }
-        HIP_OK(hipMemcpyAsync(ix->stage_dev[slot], dma_src, bytes, hipMemcpyHostToDevice, stream));
-        HIP_OK(ingest(ix->stage_dev[slot], n, ix->ntotal + r));
-        HIP_OK(hipEventRecord(ix->stage_done[slot], stream));
-        used[slot] = true;
-    }
+    if (rc) return -1;
     HIP_OK(hipStreamSynchronize(stream));  // synchronous for host sources: the caller may free `rows` on return
     ix->ntotal += n_rows;
+    return 0;
+}
+
+// H2u: listed or contiguous stored rows changed in place (kernels_update.hip); ntotal, the labels and the value table stay
+int vodhip_index_update_rows(vodhip_index_t* ix, const int64_t* ids, int64_t row_begin, const void* rows, int64_t n, int src_dtype, int location,
+                             int mode, float alpha, int64_t id_base, void* stream_) {
+    if (!ix) return fail("index is NULL");
+    std::lock_guard<std::mutex> guard(ix->mu);
+    if (const char* msg = update_rows_args_error(ids != nullptr, row_begin, rows, n, src_dtype, location, mode, alpha, ix->ntotal)) {
+        if (!strcmp(msg, "invalid src_dtype")) return fail("invalid src_dtype %d", src_dtype);
+        if (!strcmp(msg, "invalid location")) return fail("invalid location %d", location);
+        if (!strcmp(msg, "invalid mode")) return fail("invalid mode %d", mode);
+        if (!strncmp(msg, "alpha", 5)) return fail("alpha=%g: %s", (double)alpha, msg);
+        if (!strncmp(msg, "row range", 9)) return fail("rows [%lld, %lld + %lld), ntotal=%lld: %s", (long long)row_begin, (long long)row_begin, (long long)n, (long long)ix->ntotal, msg);
+        return fail("n=%lld: %s", (long long)n, msg);
+    }
+    if (!ix->inflight.empty() || ix->unfinished)
+        return fail("%d searches are in flight: finish them before updating rows", (int)ix->inflight.size() + ix->unfinished);
+    const bool listed = ids != nullptr;
+    ix->last_update_n = n;
+    ix->last_update_listed = listed && n > 0;
+    if (n == 0) return 0;
+    hipStream_t stream = (hipStream_t)stream_;
+    HIP_OK(hipSetDevice(ix->device));
+    if (listed && !ix->upd_owner) {
+        int* owner = nullptr;
+        HIP_OK(hipMalloc((void**)&owner, (size_t)std::max<int64_t>(1, ix->capacity) * sizeof(int)));
+        if (hipError_t e = hipMalloc((void**)&ix->upd_counts, 2 * sizeof(unsigned int)); e != hipSuccess) {
+            (void)hipFree(owner);
+            return fail("hipMalloc failed: %s", hipGetErrorString(e));
+        }
+        ix->upd_owner = owner;
+        // on the call's own stream, and over before anything else uses the table (the rule of the label fill in set_row_labels)
+        HIP_OK(hipMemsetAsync(ix->upd_owner, 0, (size_t)std::max<int64_t>(1, ix->capacity) * sizeof(int), stream));
+        HIP_OK(hipStreamSynchronize(stream));
+    }
+    if (ix->exact) {  // the outliers and - since rows LEFT - the two maxima are re-derived before the next search (refresh_exact_stats)
+        ix->stats_dirty = true;
+        ix->maxima_stale = true;
+    }
+    UpdateArgs a;
+    a.src_dtype = src_dtype;
+    a.row_begin = row_begin;
+    a.id_base = id_base;
+    a.ntotal = ix->ntotal;
+    a.dim = ix->dim;
+    a.stride = ix->dim_pad;
+    a.store_dtype = ix->dtype;
+    a.kind = ix->exact ? UPDATE_EXACT : ix->l2 ? UPDATE_L2 : UPDATE_PLAIN;
+    a.mode = mode;
+    a.alpha = alpha;
+    a.data = ix->data;
+    a.data32 = ix->data32;
+    a.row_n2 = ix->row_n2;
+    a.row_d2 = ix->row_d2;
+    a.norm_stats = ix->norm_stats;
+    a.l2_sat = ix->l2_sat;
+    a.owner = ix->upd_owner;
+    a.counts = ix->upd_counts;
+    if (listed) HIP_OK(hipMemsetAsync(ix->upd_counts, 0, 2 * sizeof(unsigned int), stream));
+    if (location == VODHIP_DEVICE) {
+        a.ids = ids;
+        a.src = rows;
+        a.n_slots = n;
+        if (listed) HIP_OK(launch_update_claim(ids, n, id_base, ix->ntotal, ix->upd_owner, stream));
+        HIP_OK(launch_update_rows(a, stream));
+        return 0;
+    }
+    // host source: the ids go up once and are claimed once - duplicates are resolved over the whole call, not per slice - then the rows
+    // go through the ingest pipeline's staging slots, one write launch per slice
+    if (listed) {
+        if (ix->upd_ids_cap < n) {
+            HIP_OK(hipStreamSynchronize(stream));
+            (void)hipFree(ix->upd_ids);
+            ix->upd_ids = nullptr;
+            ix->upd_ids_cap = 0;
+            HIP_OK(hipMalloc((void**)&ix->upd_ids, (size_t)n * sizeof(int64_t)));
+            ix->upd_ids_cap = n;
+        }
+        HIP_OK(hipMemcpyAsync(ix->upd_ids, ids, (size_t)n * sizeof(int64_t), hipMemcpyHostToDevice, stream));
+        HIP_OK(launch_update_claim(ix->upd_ids, n, id_base, ix->ntotal, ix->upd_owner, stream));
+        a.ids = ix->upd_ids;
+    }
+    int64_t src_pinned = 0;
+    const int rc = pipeline_host_rows(ix, rows, n, ix->dim * elem_size(src_dtype), stream, &src_pinned, [&](const void* dev_src, int64_t cnt, int64_t r) {
+        a.src = dev_src;
+        a.slot_begin = r;
+        a.n_slots = cnt;
+        return launch_update_rows(a, stream);
+    });
+    // (also after a failure: launches of this call may still read the staging slots, and the owner table must be back to zero before
+    // the next call - a slice that never ran leaves its claims behind)
+    hipError_t e = hipStreamSynchronize(stream);
+    if (rc != 0 && listed) {
+        if (e == hipSuccess) e = hipMemsetAsync(ix->upd_owner, 0, (size_t)std::max<int64_t>(1, ix->capacity) * sizeof(int), stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(stream);
+    }
+    if (rc) return -1;
+    HIP_OK(e);
     return 0;
 }
 
@@ -743,6 +872,7 @@ int vodhip_index_reset(vodhip_index_t* ix) {
         HIP_OK(hipMemset(ix->norm_stats, 0, EXS_WORDS * sizeof(unsigned int)));
         HIP_OK(hipStreamSynchronize(nullptr));
         ix->stats_dirty = true;
+        ix->maxima_stale = false;  // (the words were just cleared)
         ix->adapt_k = ix->adapt_kx = 0;
     }
     if (ix->l2) {  // the saturation count starts over with the store
@@ -2149,6 +2279,15 @@ int vodhip_index_get_stat(const vodhip_index_t* ix, const char* key, int64_t* ou
             HIP_OK(hipMemcpy(&w, ix->l2_sat, sizeof(w), hipMemcpyDeviceToHost));
         }
         *out = (int64_t)w;
+    } else if (!strcmp(key, "last_update_written") || !strcmp(key, "last_update_skipped") || !strcmp(key, "last_update_duplicates")) {
+        // (the last vodhip_index_update_rows; a listed call's two words are read from the device: waits for it, like the count above)
+        unsigned int w[2] = {0u, 0u};
+        if (ix->last_update_listed) {
+            HIP_OK(hipSetDevice(ix->device));
+            HIP_OK(hipDeviceSynchronize());
+            HIP_OK(hipMemcpy(w, ix->upd_counts, sizeof(w), hipMemcpyDeviceToHost));
+        }
+        *out = key[12] == 'w' ? ix->last_update_n - (int64_t)w[0] - (int64_t)w[1] : key[12] == 's' ? (int64_t)w[0] : (int64_t)w[1];
     } else if (!strcmp(key, "last_exact_kx"))
         *out = ix->last_exact_kx;
     else if (!strcmp(key, "last_exact_need"))

@@ -238,6 +238,36 @@ hipError_t launch_l2_stage_queries(const void* q_src, int q_dtype, int64_t nq, i
 // sim [nq, k] similarity-form scores (pads -inf) -> dist [nq, k] = max(0, qn - 2 sim), pads +inf
 hipError_t launch_l2_finish(const float* sim, const float* qn, int64_t nq, int k, float* dist, hipStream_t stream);
 
+// ---- launchers (kernels_update.hip): stored rows changed in place (include/vodhip.h H2u) -----------
+enum : int { UPDATE_PLAIN = 0, UPDATE_L2 = 1, UPDATE_EXACT = 2 };  // UpdateArgs::kind
+struct UpdateArgs {
+    const void* src = nullptr;        // [n_slots, dim] of src_dtype: the source rows of THIS launch's slots
+    int src_dtype = 0;
+    const int64_t* ids = nullptr;     // device: the id of every slot of the CALL (indexed by the absolute slot), or NULL = the dense form
+    int64_t slot_begin = 0;           // this launch's first slot: source row i is slot slot_begin + i
+    int64_t n_slots = 0;
+    int64_t row_begin = 0;            // dense form: slot j writes row row_begin + j
+    int64_t id_base = 0, ntotal = 0;
+    int64_t dim = 0, stride = 0;      // stride = the store's dim_pad, of both planes
+    int store_dtype = 0;              // 0 = f16, 1 = bf16
+    int kind = UPDATE_PLAIN;
+    int mode = 0;                     // VODHIP_UPDATE_SET | VODHIP_UPDATE_ADD
+    float alpha = 1.f;
+    uint16_t* data = nullptr;         // the 16-bit plane
+    float* data32 = nullptr;          // UPDATE_EXACT: the float32 plane, the per-row statistics and the two maxima words
+    float* row_n2 = nullptr;
+    float* row_d2 = nullptr;
+    unsigned int* norm_stats = nullptr;
+    unsigned int* l2_sat = nullptr;   // UPDATE_L2: the saturation count
+    int* owner = nullptr;             // listed form: one word per capacity row, zero between calls
+    unsigned int* counts = nullptr;   // listed form: [0] skipped slots, [1] duplicate slots (added to)
+};
+// listed form, once per call and before its first write launch: owner[row] = 1 + the last slot that lists the row
+hipError_t launch_update_claim(const int64_t* ids, int64_t n, int64_t id_base, int64_t ntotal, int* owner, hipStream_t stream);
+hipError_t launch_update_rows(const UpdateArgs& a, hipStream_t stream);
+// words [EXS_MAX_N2], [EXS_MAX_D2] of an exact store's statistics = the maxima of the finite row_n2 / row_d2 of rows [0, n_rows)
+hipError_t launch_update_maxima(const float* row_n2, const float* row_d2, int64_t n_rows, unsigned int* stats, hipStream_t stream);
+
 // ---- the whole-store scans (store_scan.h): what log_partition, posterior_mean, sample_posterior and the rank calls share ----------
 struct ScanInputs {
     const void* store = nullptr;      // [>= round_up(ntotal, 256) rows][dim_pad] fp16 / bf16 rows

@@ -28,6 +28,7 @@
 #include "readout_adjoint_fold.h"
 #include "readout_grad_fold.h"
 #include "key_grad_fold.h"
+#include "update_fold.h"
 #include "vodhip_internal.h"
 
 namespace {
@@ -111,6 +112,7 @@ struct vodhip_node_index {
     const int32_t* q_labels = nullptr;  // the caller's per-query labels for the next searches (host, or devices[0])
     int q_labels_per_query = 0, q_labels_location = VODHIP_HOST;
     bool has_row_labels = false;
+    int64_t update_unrouted = 0;             // slots of the last update_rows that no shard owns (id < 0 or >= ntotal): skipped here
     int64_t value_rows = 0, value_cols = 0;  // the value table of the posterior read-out as it was set (0, 0: none); the shards hold its rows
     // topology (read once at create): can devices[0] and shard g's device copy into each other's memory directly?  A shard without
     // peer access - or every shard but the first with `host_staging` set (bring-up, tests on a 1-GPU box) - exchanges its queries and
@@ -413,6 +415,51 @@ int vodhip_node_index_add(vodhip_node_index_t* nx, const void* rows, int64_t n_r
     for (size_t i = 0; i < parts.size(); ++i)
         if (rcs[i]) return nfail("shard %d: %s", parts[i].g, errors[i].c_str());
     nx->ntotal += n_rows;
+    return 0;
+}
+
+// H2u behind the one handle: routed on the host (update_fold.h) - shard g gets its own slots and rows, nothing is replicated
+int vodhip_node_index_update_rows(vodhip_node_index_t* nx, const int64_t* ids, int64_t row_begin, const void* rows, int64_t n, int src_dtype, int mode,
+                                  float alpha) {
+    if (!nx) return nfail("index is NULL");
+    std::lock_guard<std::mutex> guard(nx->mu);
+    if (const char* msg = vodhip::update_rows_args_error(ids != nullptr, row_begin, rows, n, src_dtype, VODHIP_HOST, mode, alpha, nx->ntotal)) {
+        if (!strcmp(msg, "invalid src_dtype")) return nfail("invalid src_dtype %d", src_dtype);
+        if (!strcmp(msg, "invalid mode")) return nfail("invalid mode %d", mode);
+        if (!strncmp(msg, "alpha", 5)) return nfail("alpha=%g: %s", (double)alpha, msg);
+        if (!strncmp(msg, "row range", 9)) return nfail("rows [%lld, %lld + %lld), ntotal=%lld: %s", (long long)row_begin, (long long)row_begin, (long long)n, (long long)nx->ntotal, msg);
+        return nfail("n=%lld: %s", (long long)n, msg);
+    }
+    if (nx->n_pending) return nfail("%d searches are in flight: finish them before updating rows", nx->n_pending);
+    const size_t row_bytes = (size_t)nx->dim * elem_bytes(src_dtype);
+    vodhip::UpdateRoute route;
+    if (ids) route = vodhip::route_update_slots(ids, n, nx->rows_per_shard, nx->n, nx->ntotal);
+    nx->update_unrouted = route.skipped;
+    std::vector<int64_t> shard_ids;
+    std::vector<char> shard_rows;
+    // (a shard without a slot still takes the call, with n = 0: its stats of an earlier call must not enter this call's sums)
+    for (int g = 0; g < nx->n; ++g) {
+        const int64_t base = g * nx->rows_per_shard;
+        int rc;
+        if (!ids) {
+            int64_t lo, hi;
+            vodhip::split_update_range(row_begin, n, nx->rows_per_shard, g, &lo, &hi);
+            rc = vodhip_index_update_rows(nx->shard[g], nullptr, hi > lo ? row_begin + lo - base : 0, (const char*)rows + (size_t)lo * row_bytes, hi - lo, src_dtype,
+                                          VODHIP_HOST, mode, alpha, 0, nx->stream[g]);
+        } else {
+            const int64_t first = route.first[(size_t)g], cnt = route.first[(size_t)g + 1] - first;
+            shard_ids.resize((size_t)cnt);
+            shard_rows.resize((size_t)cnt * row_bytes);
+            for (int64_t i = 0; i < cnt; ++i) {
+                const int64_t j = route.slot[(size_t)(first + i)];
+                shard_ids[(size_t)i] = ids[j];
+                memcpy(shard_rows.data() + (size_t)i * row_bytes, (const char*)rows + (size_t)j * row_bytes, row_bytes);
+            }
+            rc = vodhip_index_update_rows(nx->shard[g], cnt ? shard_ids.data() : nullptr, 0, cnt ? shard_rows.data() : nullptr, cnt, src_dtype, VODHIP_HOST, mode,
+                                          alpha, base, nx->stream[g]);
+        }
+        if (rc) return nfail("shard %d: %s", g, std::string(vodhip_last_error()).c_str());
+    }
     return 0;
 }
 
@@ -1438,6 +1485,16 @@ int vodhip_node_index_get_stat(vodhip_node_index_t* nx, const char* key, int64_t
             NODE_HIP_OK(hipEventElapsedTime(&ms, S.copy_ev[2 * g], S.copy_ev[2 * g + 1]));
             *out = std::max<int64_t>(*out, (int64_t)((double)ms * 1e6));
         }
+        NODE_HIP_OK(hipSetDevice(nx->device[0]));
+        return 0;
+    }
+    if (!strcmp(key, "last_update_written") || !strcmp(key, "last_update_skipped") || !strcmp(key, "last_update_duplicates")) {
+        for (int g = 0; g < nx->n; ++g) {  // (every shard took the last update_rows, with no slot if it owns none)
+            int64_t v = 0;
+            if (vodhip_index_get_stat(nx->shard[g], key, &v)) return -1;
+            *out += v;
+        }
+        if (!strcmp(key, "last_update_skipped")) *out += nx->update_unrouted;
         NODE_HIP_OK(hipSetDevice(nx->device[0]));
         return 0;
     }

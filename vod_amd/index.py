@@ -53,6 +53,26 @@ def pad_listed_weights(weights, shape: tuple[int, int]) -> np.ndarray:
     return arr
 
 
+def _host_update_args(vectors, ids, dim: int):
+    """Host `vectors` / `ids` of `update_rows` / `add_to_rows` as C-contiguous NumPy: float16 / float32 `[n, dim]` and int64 `[n]` (or None)."""
+    if isinstance(vectors, torch.Tensor):
+        vectors = vectors.detach()
+        vectors = vectors.numpy() if vectors.dtype != torch.bfloat16 else vectors.float().numpy()
+    v = np.ascontiguousarray(vectors)
+    if v.dtype not in (np.float16, np.float32):
+        v = v.astype(np.float32)
+    if v.ndim != 2 or v.shape[1] != dim:
+        raise ValueError(f"expected [n, {dim}] vectors, got {v.shape}")
+    ida = None
+    if ids is not None:
+        if isinstance(ids, torch.Tensor):
+            ids = ids.detach().cpu().numpy()
+        ida = np.ascontiguousarray(np.asarray(ids).reshape(-1), dtype=np.int64)
+        if ida.size != v.shape[0]:
+            raise ValueError(f"expected {v.shape[0]} ids, got {ida.size}")
+    return v, ida
+
+
 class HipFlatIndex:
     """Exact MIPS index: row-major fp16/bf16 rows in HBM, searched by the fused MFMA + top-k kernels.
 
@@ -171,6 +191,59 @@ class HipFlatIndex:
                                                     _native.current_stream_ptr(self.device))
             )
         return out
+
+    # -- rows changed in place (H2u) ------------------------------------------------------------------
+    def _update(self, mode: int, vectors, alpha: float, ids, begin: int) -> None:
+        with torch.cuda.device(self.device):
+            stream = _native.current_stream_ptr(self.device)
+            if isinstance(vectors, torch.Tensor) and vectors.is_cuda:
+                if vectors.device != self.device:
+                    raise ValueError(f"vectors live on {vectors.device}, the index on {self.device}")
+                v = vectors.detach()
+                if v.dtype not in (torch.float16, torch.bfloat16, torch.float32):
+                    v = v.float()
+                if not v.is_contiguous():  # (a contiguous view keeps its own - possibly misaligned - address: the kernel handles it)
+                    v = v.contiguous()
+                if v.ndim != 2 or v.shape[1] != self.dim:
+                    raise ValueError(f"expected [n, {self.dim}] vectors, got {tuple(v.shape)}")
+                idt = None
+                if ids is not None:
+                    idt = torch.as_tensor(ids, dtype=torch.int64).to(self.device).contiguous().reshape(-1)
+                    if idt.numel() != v.shape[0]:
+                        raise ValueError(f"expected {v.shape[0]} ids, got {idt.numel()}")
+                _native.check(self._lib.vodhip_index_update_rows(
+                    self._h, idt.data_ptr() if idt is not None and idt.numel() else None, int(begin), v.data_ptr() if v.numel() else None, v.shape[0],
+                    _native.torch_dtype_code(v.dtype), _native.DEVICE, mode, float(alpha), 0, stream))
+                torch.cuda.current_stream(self.device).synchronize()  # `v` and the ids may be freed by the caller right after
+                return
+            v, ida = _host_update_args(vectors, ids, self.dim)
+            _native.check(self._lib.vodhip_index_update_rows(
+                self._h, ida.ctypes.data if ida is not None and ida.size else None, int(begin), v.ctypes.data if v.size else None, v.shape[0],
+                _native.numpy_dtype_code(v.dtype), _native.HOST, mode, float(alpha), 0, stream))
+
+    def update_rows(self, vectors: np.ndarray | torch.Tensor, ids=None, begin: int = 0) -> None:
+        """Overwrite stored rows in place: `x[ids] = vectors`, or with `ids=None` the rows `begin .. begin + n`.  `vectors` is `[n, dim]`,
+        a device tensor (f16 / bf16 / f32) or host NumPy / CPU tensor, as for `add`; `ids` is `[n]` int64 (global row ids of THIS
+        index).  Every plane of the store is rewritten as `add` would have written it: afterwards the index equals, byte for byte, one
+        built by `add` from the final rows.  `ntotal`, the row labels and the value table stay (`set_row_values` survives, unlike
+        `reset(); add(...)`).  An id that is negative or not below `ntotal` is skipped; when an id repeats the LAST slot wins, as
+        NumPy's `x[ids] = rows`.  `get_stat("last_update_written" | "last_update_skipped" | "last_update_duplicates")` tells.
+        Refused while searches are in flight, like `add`."""
+        self._update(_native.UPDATE_SET, vectors, 1.0, ids, begin)
+
+    def add_to_rows(self, delta: np.ndarray | torch.Tensor, alpha: float = 1.0, ids=None, begin: int = 0, check: bool = True) -> None:
+        """`x[ids] += alpha * delta` in place (`ids=None`: the rows `begin .. begin + n`), in float32 with two roundings
+        (`alpha * delta`, then the sum), then stored as `add` stores the result - the SGD step `add_to_rows(keys.grad, alpha=-lr)`.
+
+        On a plain 16-bit store the master copy IS the 16-bit row: a step below half an ulp of the row is lost, every time.  An
+        `exact_f32` store keeps the float32 master and adds to that.  For optimisers with state (momentum, Adam) or steps that small
+        keep the float32 `keys` parameter yourself, step it with the optimiser, and write it back with `update_rows(keys)`.
+
+        Ids must be unique: with a repeated id only its last slot is applied.  `check=True` reads `last_update_duplicates` after a
+        listed call (one synchronisation) and raises ValueError when it is not zero - the rows are already written then."""
+        self._update(_native.UPDATE_ADD, delta, alpha, ids, begin)
+        if check and ids is not None and (dup := self.get_stat("last_update_duplicates")):
+            raise ValueError(f"add_to_rows: {dup} slots repeat an id that a later slot lists too; only the last slot of an id was applied")
 
     # -- subset filter (SURVEY 8f-3) ---------------------------------------------------------------
     def set_row_labels(self, labels: np.ndarray | torch.Tensor | None) -> None:
@@ -1630,7 +1703,8 @@ class HipNodeIndex:
         _native.check(self._lib.vodhip_node_index_set_param(self._h, key.encode(), int(value)))
 
     def get_stat(self, key: str) -> int:
-        """Node-level stats of the last search with `set_param("profile", 1)`: "last_merge_ns", "last_copy_ns_max" (HIP events)."""
+        """Node-level stats: of the last search with `set_param("profile", 1)`, "last_merge_ns" and "last_copy_ns_max" (HIP events); of
+        the last `update_rows` / `add_to_rows`, "last_update_written", "last_update_skipped", "last_update_duplicates" (sums over the shards)."""
         out = ctypes.c_int64()
         _native.check(self._lib.vodhip_node_index_get_stat(self._h, key.encode(), ctypes.byref(out)))
         return out.value
@@ -1663,6 +1737,25 @@ class HipNodeIndex:
             v = v.astype(np.float32)
         code = 2 if v.dtype == np.float32 else 0
         _native.check(self._lib.vodhip_node_index_add(self._h, v.ctypes.data, v.shape[0], code))
+
+    def _update(self, mode: int, vectors, alpha: float, ids, begin: int) -> None:
+        v, ida = _host_update_args(vectors, ids, self.dim)
+        with torch.cuda.device(self.device):
+            _native.check(self._lib.vodhip_node_index_update_rows(
+                self._h, ida.ctypes.data if ida is not None and ida.size else None, int(begin), v.ctypes.data if v.size else None, v.shape[0],
+                _native.numpy_dtype_code(v.dtype), mode, float(alpha)))
+
+    def update_rows(self, vectors: np.ndarray, ids=None, begin: int = 0) -> None:
+        """Overwrite stored rows in place from host arrays (global row ids, or the global rows `begin .. begin + n`): see
+        `HipFlatIndex.update_rows`.  The call is routed on the host: every shard receives its own slots and rows only."""
+        self._update(_native.UPDATE_SET, vectors, 1.0, ids, begin)
+
+    def add_to_rows(self, delta: np.ndarray, alpha: float = 1.0, ids=None, begin: int = 0, check: bool = True) -> None:
+        """`x[ids] += alpha * delta` in place from host arrays: see `HipFlatIndex.add_to_rows` (the 16-bit master copy of a plain
+        store, unique ids, `check`)."""
+        self._update(_native.UPDATE_ADD, delta, alpha, ids, begin)
+        if check and ids is not None and (dup := self.get_stat("last_update_duplicates")):
+            raise ValueError(f"add_to_rows: {dup} slots repeat an id that a later slot lists too; only the last slot of an id was applied")
 
     def set_row_labels(self, labels: np.ndarray | None) -> None:
         """One int32 subset label per stored row (global row order; None clears): see `HipFlatIndex.set_row_labels`."""
