@@ -479,12 +479,63 @@ int vodhip_index_posterior_key_gradient(vodhip_index_t* index, const void* queri
  * written, as vodhip_index_add.  n == 0 is a no-op that succeeds; SET ignores alpha.  REFUSED (-1, nothing written): searches in
  * flight (the rule of vodhip_index_add), a dense range outside [0, ntotal), n < 0 or n >= 2^31 - 1, NULL rows with n > 0, a bad
  * src_dtype, location or mode, a non-finite alpha with ADD.
- * NOT BUILT: removing rows, an HTTP route, the value table or the labels by id, stochastic rounding. */
+ * NOT BUILT: an HTTP route, the value table or the labels by id, stochastic rounding.  (Removing rows: H2r.) */
 #define VODHIP_UPDATE_SET 0
 #define VODHIP_UPDATE_ADD 1
 int vodhip_index_update_rows(vodhip_index_t* index, const int64_t* ids /* [n], or NULL: rows row_begin .. row_begin + n */, int64_t row_begin,
                              const void* rows /* [n, dim] */, int64_t n, int src_dtype, int location /* of ids AND rows */,
                              int mode, float alpha, int64_t id_base, void* stream);
+
+/* H2r. Stored rows REMOVED, the gaps closed in place (kernels_remove.hip, remove_fold.h): faiss IndexFlat::remove_ids.
+ * LISTED form (ids != NULL): slot j removes row ids[j] - id_base.  RANGE form (ids == NULL): rows [row_begin, row_begin + n); id_base
+ * is not read.  `ids` is at `location`.  The compaction is STABLE: survivors keep their order and move down, a survivor's new id is
+ * its old id minus the number of removed rows below it; ntotal shrinks, the capacity stays.
+ * THE CONTRACT IS THE BYTES OF vodhip_index_add: afterwards every plane the store keeps - the padded 16-bit plane with an L2 store's
+ * bias columns, a VODHIP_EXACT_F32 store's float32 plane and its two per-row statistics, the row labels if set, the value table (H2e)
+ * if attached - equals over rows [0, ntotal), byte for byte, an index freshly built by vodhip_index_add from the surviving rows in
+ * order.  Nothing is recomputed: rows are moved whole.  The labels and the value table STAY ATTACHED, compacted the same way; the
+ * table keeps value_rows == ntotal and its zero pad rows up to round_up(ntotal, 256).  Behind the last row the 16-bit plane is zero
+ * and the labels are -1 for round_up(ntotal, 256) + 512 rows (what a scan's last tile can read); further stale rows up to the old
+ * ntotal stay as they were, as after vodhip_index_reset + add of fewer rows: no result depends on them.
+ * VODHIP_EXACT_F32: the two maxima of the error bound and the outliers are re-derived from the rows NOW stored before the next search
+ * (as after H2u).  "l2_saturated_rows" counts events and is not touched.
+ * SLOTS as H2u: a slot whose id is negative, below id_base or not below id_base + ntotal is SKIPPED and counted; a repeated id removes
+ * its row once, the extra slots are counted as duplicates.  STATS: "last_remove_removed", "last_remove_skipped",
+ * "last_remove_duplicates" (host values of the last call; no wait).
+ * new_ids, when not NULL: DEVICE int64 [ntotal before the call], the new id of every old row (0-based rows of this index, as the rows
+ * of the range form), -1 for a removed one; written on `stream` unless n == 0 (then nothing at all is written: the map is the identity).
+ * *n_removed (may be NULL) receives the number of rows removed.  The call must learn the new ntotal: it WAITS FOR THE DEVICE ONCE
+ * (`stream`), between counting and moving; the moves themselves are only enqueued.  A HOST id list is copied before that wait.
+ * n == 0, or a list of which every slot is skipped, is a successful no-op that writes nothing.  Removing every row leaves ntotal == 0
+ * with the table and the labels attached and empty.
+ * HOW (DESIGN.md 4 "Row removal"): every survivor moves DOWN, so one launch over the store would overwrite rows another workgroup has
+ * not read yet.  The rows from the first removed one are cut into slabs of "remove_slab_rows" source rows (vodhip_index_set_param:
+ * a power of two in [4, 2^30], 0 = the default 65536), run in ascending order; a slab whose destination ends at or below its first
+ * source row is moved by one launch, any other is packed into the BOUNCE buffer and copied from there.  The bounce buffer holds
+ * min(remove_slab_rows, capacity) rows of every plane the store has (2 * dim_pad bytes a row; + 4 * dim_pad + 8 of an exact store,
+ * + 4 with labels, + 2 * round_up(n_cols, 64) with a table): 100 MB at the default for 768 fp16 columns, 300 MB for an exact store;
+ * allocated by the first call that needs it, freed by vodhip_index_destroy.  The result does not depend on the slab size.
+ * REFUSED (-1, nothing written): searches in flight (the rule of vodhip_index_add), a range outside [0, ntotal), n < 0 or
+ * n >= 2^31 - 1, a bad location, and a STALE VALUE TABLE - one that rows were added behind, so that it holds fewer rows than the index
+ * (the state every read-out refuses): it is neither moved nor passed off as valid; set it again or clear it first.  After any call,
+ * failed ones included, the owner table of H2u is all zero.
+ * A DEVICE ERROR during the call (a failed launch, copy or allocation: -1 with the HIP error's text) is no refusal: some slabs may have
+ * moved while ntotal is unchanged, so the store's contents are UNDEFINED and the caller must vodhip_index_reset (the node form:
+ * vodhip_node_index_reset - earlier shards may already be compacted) and add the rows again.
+ * NOT BUILT: an HTTP route, removal while a batcher serves, an unstable swap-with-tail mode, shrinking the capacity. */
+int vodhip_index_remove_rows(vodhip_index_t* index, const int64_t* ids /* [n], or NULL: rows row_begin .. row_begin + n */, int64_t row_begin,
+                             int64_t n, int location /* of ids */, int64_t id_base, int64_t* new_ids /* DEVICE [ntotal], or NULL */,
+                             int64_t* n_removed /* HOST, or NULL */, void* stream);
+/* TEST-ONLY: not part of the drop-in interface, no stability promise; the pointers are the store's own - read them, never write them.
+ * Raw views of the planes beside the rows, for the byte-for-byte tests of H2u / H2r: the device pointer (NULL when the store keeps no such plane), the rows
+ * that hold data and the row stride in elements.  LABELS int32 [ntotal]; VALUES the table, 16-bit [round_up(value_rows, 256)][c_pad];
+ * ROW_N2 / ROW_D2 float32 [ntotal] (VODHIP_EXACT_F32); OWNER the int32 word per capacity row of H2u / H2r (zero between calls). */
+#define VODHIP_PLANE_LABELS 0
+#define VODHIP_PLANE_VALUES 1
+#define VODHIP_PLANE_ROW_N2 2
+#define VODHIP_PLANE_ROW_D2 3
+#define VODHIP_PLANE_OWNER 4
+int vodhip_index_plane(const vodhip_index_t* index, int which, void** dev_ptr, int64_t* n_rows, int64_t* row_stride_elems);
 
 /* H2s. k rows drawn WITHOUT replacement from that softmax over the whole store, with priority-sampling weights
  * (kernels_sample_posterior.hip).  Gumbel-top-k: the k eligible rows with the largest keys
@@ -625,7 +676,9 @@ int vodhip_index_set_query_labels(vodhip_index_t* index, const int32_t* q_labels
  *   "survivor_ring" (records per wave of the 8-phase filter kernel's survivor rings, in [0, 8192]; 0 = auto, sized by the planner for
  *   the search's largest stage, at most 1024 (8 x CUs x 1024 x 132 B = 277 MB of workspace per lane on 256 CUs); the rings are skipped
  *   when the device cannot hold them; a query block that does not fit takes the in-loop path; speed and workspace only - results are the same),
- *   "scan_temp_bytes" (the temporary budget of the sliced whole-store scans; 0 = VODHIP_POSTERIOR_TEMP_BYTES, the default: see there).
+ *   "scan_temp_bytes" (the temporary budget of the sliced whole-store scans; 0 = VODHIP_POSTERIOR_TEMP_BYTES, the default: see there),
+ *   "remove_slab_rows" (source rows per launch of vodhip_index_remove_rows and the rows of its bounce buffer: a power of two in
+ *   [4, 2^30], 0 = the default 65536; speed and memory only - the result is the same bytes).
  * VODHIP_EXACT_F32 input range: finite float32 rows and queries of ANY magnitude whose squared norm is finite in float32 (|x| < 1.8e19)
  *   give the float32 brute-force result; values beyond the scan dtype's range (fp16: |v| > 65504) saturate in the scan copy only, and
  *   the up to 64 rows whose norm / rounding error exceeds the rest of the store's by 2x or more ("outliers") are scored exactly by
@@ -850,6 +903,16 @@ int vodhip_node_index_posterior_key_gradient(vodhip_node_index_t* index, const v
  * slots) on vodhip_node_index_get_stat.  Refusals as for the flat call. */
 int vodhip_node_index_update_rows(vodhip_node_index_t* index, const int64_t* ids /* HOST or NULL */, int64_t row_begin,
                                   const void* rows /* HOST */, int64_t n, int src_dtype, int mode, float alpha);
+/* H2r behind the one handle: HOST ids (GLOBAL row ids, or NULL with the global row_begin).  Shard g owns the global ids
+ * [g * rows_per_shard, (g + 1) * rows_per_shard) and vodhip_node_index_add fills the shards in order; removal restores that layout:
+ * the slots are routed to their shards (update_fold.h; the range is split), every shard compacts locally with the flat call, then the
+ * survivors are moved between the shards by an ordered list of segment copies, device to device, of every plane (remove_fold.h:
+ * split at destination-shard boundaries, safe one after the other, an overlapping move inside one shard through its bounce buffer).
+ * Afterwards the node index equals, byte for byte per shard, one freshly built from the survivors.  new_ids: HOST int64 [ntotal before
+ * the call] of GLOBAL new ids, or NULL.  The three stats of H2r are sums over the shards on vodhip_node_index_get_stat (+ the slots
+ * that no shard owns, skipped).  Host-synchronous.  Refusals as for the flat call. */
+int vodhip_node_index_remove_rows(vodhip_node_index_t* index, const int64_t* ids /* HOST or NULL */, int64_t row_begin, int64_t n,
+                                  int64_t* new_ids /* HOST [ntotal], or NULL */, int64_t* n_removed /* or NULL */);
 /* H2s behind the one handle: HOST buffers, host-synchronous.  Every shard runs vodhip_index_sample_posterior with id_base = its first
  * global row; keys are unnormalised and the noise is a function of the global row, so the k + 1 best of the union of the shards'
  * lists ARE the k + 1 best of the whole store: ids, scores and keys equal one index holding all the rows bit for bit.  The pairs are

@@ -78,6 +78,8 @@ SIGNATURES: dict[str, tuple] = {
     "vodhip_index_posterior_adjoint": (_i32, [_vp, _vp, _i32, _i64, _c.c_float, _vp, _i32, _vp, _vp, _vp, _i64, _i32, _vp, _vp]),
     "vodhip_index_posterior_key_gradient": (_i32, [_vp, _vp, _i32, _i64, _c.c_float, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _vp]),
     "vodhip_index_update_rows": (_i32, [_vp, _vp, _i64, _vp, _i64, _i32, _i32, _i32, _c.c_float, _i64, _vp]),
+    "vodhip_index_remove_rows": (_i32, [_vp, _vp, _i64, _i64, _i32, _i64, _vp, _vp, _vp]),
+    "vodhip_index_plane": (_i32, [_vp, _i32, _vp, _vp, _vp]),
     "vodhip_index_count_above": (_i32, [_vp, _vp, _i32, _i64, _vp, _vp, _i64, _i64, _vp, _i32, _vp, _vp]),
     "vodhip_index_rank_ids": (_i32, [_vp, _vp, _i32, _i64, _vp, _i64, _i64, _vp, _i32, _vp, _vp, _vp]),
     "vodhip_index_scan_score_ids": (_i32, [_vp, _vp, _i32, _i64, _vp, _i64, _i64, _vp, _i32, _vp, _vp, _vp]),
@@ -121,6 +123,7 @@ SIGNATURES: dict[str, tuple] = {
     "vodhip_node_index_posterior_adjoint": (_i32, [_vp, _vp, _i32, _i64, _c.c_float, _vp, _i32, _vp, _vp, _vp, _i64, _vp]),
     "vodhip_node_index_posterior_key_gradient": (_i32, [_vp, _vp, _i32, _i64, _c.c_float, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
     "vodhip_node_index_update_rows": (_i32, [_vp, _vp, _i64, _vp, _i64, _i32, _i32, _c.c_float]),
+    "vodhip_node_index_remove_rows": (_i32, [_vp, _vp, _i64, _i64, _vp, _vp]),
     "vodhip_node_index_rank_ids": (_i32, [_vp, _vp, _i32, _i64, _vp, _i64, _vp, _i32, _vp, _vp]),
     "vodhip_node_index_count_above": (_i32, [_vp, _vp, _i32, _i64, _vp, _vp, _i64, _vp, _i32, _vp]),
     "vodhip_node_index_range_search": (_i32, [_vp, _vp, _i32, _i64, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _i64]),

@@ -29,6 +29,7 @@
 #include "readout_grad_fold.h"
 #include "key_grad_fold.h"
 #include "update_fold.h"
+#include "remove_fold.h"
 #include "scan_slices.h"
 #include "search_plan.h"
 #include "collate_plan.h"
@@ -108,6 +109,7 @@ struct vodhip_index {
     // the value table of the posterior read-out (kernels_readout.hip): [round_up(value_rows, 256)][value_c_pad] of the store dtype, zero padded
     uint16_t* row_value = nullptr;
     int64_t value_rows = 0, value_cols = 0, value_c_pad = 0;
+    int64_t value_alloc_rows = 0;    // rows the table was allocated for (>= round_up(value_rows, 256): vodhip_index_remove_rows shrinks value_rows)
     // beside it: the per-column maxima of the finite |v~| (kernels_readout_grad.hip), computed by the first backward call after the
     // table was set (under `mu`) and dropped with the table
     float* value_vmax = nullptr;     // [value_c_pad]
@@ -129,6 +131,17 @@ struct vodhip_index {
     int64_t upd_ids_cap = 0;
     int64_t last_update_n = 0;
     bool last_update_listed = false;
+    // vodhip_index_remove_rows (kernels_remove.hip; it shares upd_owner / upd_ids): the call's device words, the survivor counts per
+    // count tile and their scan, and the BOUNCE buffer - one slab of every plane the store keeps, min(remove_slab_rows, capacity) rows
+    // of 2 * dim_pad bytes (+ 4 * dim_pad + 8 of an exact store, + 4 with labels, + 2 * value_c_pad with a table): 100 MB for 65536
+    // fp16 rows of 768 columns, 300 MB for an exact store.  Allocated by the first call that needs them, grown when a plane was added
+    unsigned int* rm_words = nullptr;
+    int* rm_tiles = nullptr;          // [2 * rm_tiles_cap + 1]: counts, then offsets
+    int64_t rm_tiles_cap = 0;
+    char* rm_bounce = nullptr;
+    size_t rm_bounce_bytes = 0;
+    int64_t remove_slab_rows = REMOVE_SLAB_ROWS;
+    int64_t last_remove[3] = {0, 0, 0};  // removed, skipped, duplicates of the last call
     // VODHIP_EXACT_F32 (kernels_exact.hip): the float32 rows, the statistics of the error bound, per-slot lists of the scan
     bool exact = false;
     float* data32 = nullptr;                 // [capacity + 1][dim_pad]
@@ -591,7 +604,224 @@ int pipeline_host_rows(vodhip_index* ix, const void* rows, int64_t n_rows, int64
     return 0;
 }
 
+// ---- row removal (H2r) -------------------------------------------------------------------------------------------------------------
+RemovePlanes store_planes(const vodhip_index* ix) {
+    RemovePlanes p;
+    p.data = ix->data;
+    if (ix->exact) p.data32 = ix->data32, p.row_n2 = ix->row_n2, p.row_d2 = ix->row_d2;
+    p.label = ix->row_label;
+    p.value = ix->row_value;
+    return p;
+}
+
+// the bounce buffer carved into the planes the store has now, `*rows` rows each (sections 256-byte aligned)
+int ensure_remove_bounce(vodhip_index* ix, hipStream_t stream, RemovePlanes* out, int64_t* rows) {
+    const int64_t r = std::min<int64_t>(ix->remove_slab_rows, std::max<int64_t>(1, ix->capacity));
+    size_t at = 0;
+    auto section = [&](size_t bytes) {
+        const size_t here = at;
+        at += (bytes + 255) & ~(size_t)255;
+        return here;
+    };
+    const size_t o_data = section((size_t)r * ix->dim_pad * 2);
+    const size_t o_32 = ix->exact ? section((size_t)r * ix->dim_pad * 4) : 0, o_n2 = ix->exact ? section((size_t)r * 4) : 0, o_d2 = ix->exact ? section((size_t)r * 4) : 0;
+    const size_t o_lab = ix->row_label ? section((size_t)r * 4) : 0;
+    const size_t o_val = ix->row_value ? section((size_t)r * ix->value_c_pad * 2) : 0;
+    if (at > ix->rm_bounce_bytes) {
+        HIP_OK(hipStreamSynchronize(stream));  // (launches of an earlier call may still use the old block)
+        (void)hipFree(ix->rm_bounce);
+        ix->rm_bounce = nullptr;
+        ix->rm_bounce_bytes = 0;
+        HIP_OK(hipMalloc((void**)&ix->rm_bounce, at));
+        ix->rm_bounce_bytes = at;
+    }
+    char* b = ix->rm_bounce;
+    RemovePlanes p;
+    p.data = (uint16_t*)(b + o_data);
+    if (ix->exact) p.data32 = (float*)(b + o_32), p.row_n2 = (float*)(b + o_n2), p.row_d2 = (float*)(b + o_d2);
+    if (ix->row_label) p.label = (int*)(b + o_lab);
+    if (ix->row_value) p.value = (uint16_t*)(b + o_val);
+    *out = p;
+    *rows = r;
+    return 0;
+}
+
+// rows [src_row, src_row + n) of every plane of `s` -> rows [dst_row, ..) of `d`: contiguous runs, one copy per plane
+int copy_plane_rows(const vodhip_index* ix, const RemovePlanes& s, int64_t src_row, const RemovePlanes& d, int64_t dst_row, int64_t n, hipStream_t stream) {
+    if (n <= 0) return 0;
+    const size_t st = (size_t)ix->dim_pad, cp = (size_t)ix->value_c_pad;
+    HIP_OK(hipMemcpyAsync(d.data + (size_t)dst_row * st, s.data + (size_t)src_row * st, (size_t)n * st * 2, hipMemcpyDefault, stream));
+    if (s.data32) {
+        HIP_OK(hipMemcpyAsync(d.data32 + (size_t)dst_row * st, s.data32 + (size_t)src_row * st, (size_t)n * st * 4, hipMemcpyDefault, stream));
+        HIP_OK(hipMemcpyAsync(d.row_n2 + dst_row, s.row_n2 + src_row, (size_t)n * 4, hipMemcpyDefault, stream));
+        HIP_OK(hipMemcpyAsync(d.row_d2 + dst_row, s.row_d2 + src_row, (size_t)n * 4, hipMemcpyDefault, stream));
+    }
+    if (s.label) HIP_OK(hipMemcpyAsync(d.label + dst_row, s.label + src_row, (size_t)n * 4, hipMemcpyDefault, stream));
+    if (s.value) HIP_OK(hipMemcpyAsync(d.value + (size_t)dst_row * cp, s.value + (size_t)src_row * cp, (size_t)n * cp * 2, hipMemcpyDefault, stream));
+    return 0;
+}
+
+// the store now holds `ntotal` rows, fewer than it did: the words that summarise rows, and what lies behind the last row.  The value
+// table's pad rows up to round_up(ntotal, 256) are zero again (its documented invariant); the 16-bit rows a scan's last tile may read
+// (up to round_up(ntotal, 256) + 512 - the pad of the allocation) are zero as create left them, the labels there match no query.
+int remove_set_ntotal(vodhip_index* ix, int64_t ntotal, hipStream_t stream) {
+    const int64_t pad_end = std::min<int64_t>(ix->capacity_pad, round_up(ntotal, ROW_ALIGN) + 2 * ROW_ALIGN);
+    if (pad_end > ntotal) {
+        HIP_OK(hipMemsetAsync(ix->data + (size_t)ntotal * ix->dim_pad, 0, (size_t)(pad_end - ntotal) * ix->dim_pad * 2, stream));
+        if (ix->row_label) HIP_OK(hipMemsetAsync(ix->row_label + ntotal, 0xFF, (size_t)(pad_end - ntotal) * sizeof(int), stream));
+    }
+    if (ix->row_value) {
+        const int64_t rows_pad = std::max<int64_t>(1, scan_tiles(ntotal)) * 256;
+        if (rows_pad > ntotal) HIP_OK(hipMemsetAsync(ix->row_value + (size_t)ntotal * ix->value_c_pad, 0, (size_t)(rows_pad - ntotal) * ix->value_c_pad * 2, stream));
+        ix->value_rows = ntotal;
+        ix->value_vmax_ready = false;  // (the column maxima may belong to rows that left)
+    }
+    if (ix->exact) {  // rows left: the outliers and the two maxima are re-derived before the next search (refresh_exact_stats)
+        ix->stats_dirty = true;
+        ix->maxima_stale = true;
+    }
+    ix->ntotal = ntotal;
+    return 0;
+}
+
+// the caller holds ix->mu, checked the arguments and found no search in flight
+int remove_rows_locked(vodhip_index* ix, const int64_t* ids, int64_t row_begin, int64_t n, int location, int64_t id_base, int64_t* new_ids, hipStream_t stream) {
+    const bool listed = ids != nullptr;
+    const int64_t ntotal = ix->ntotal;
+    ix->last_remove[0] = ix->last_remove[1] = ix->last_remove[2] = 0;
+    HIP_OK(hipSetDevice(ix->device));
+    const int64_t T = remove_tile_rows(ix->remove_slab_rows);
+    // listed: any row may leave, the tiles cover the store; a range: they start at the tile of its first row
+    const int64_t tile_base = listed ? 0 : row_begin / T * T;
+    const int64_t n_tiles = n == 0 ? 0 : (ntotal - tile_base + T - 1) / T;
+    if (n == 0 || n_tiles == 0) {  // nothing can leave (an empty call, or a list against an empty store: every slot is skipped)
+        ix->last_remove[1] = n;
+        return 0;  // (nothing is written, new_ids included: with n == 0 the map is the identity, with no row stored it is empty)
+    }
+    if (!ix->upd_owner) {
+        // (with the two count words of vodhip_index_update_rows, which allocates them together with the table)
+        if (!ix->upd_counts) HIP_OK(hipMalloc((void**)&ix->upd_counts, 2 * sizeof(unsigned int)));
+        HIP_OK(hipMalloc((void**)&ix->upd_owner, (size_t)std::max<int64_t>(1, ix->capacity) * sizeof(int)));
+        // on the call's own stream, and over before anything else uses the table (as in vodhip_index_update_rows)
+        HIP_OK(hipMemsetAsync(ix->upd_owner, 0, (size_t)std::max<int64_t>(1, ix->capacity) * sizeof(int), stream));
+        HIP_OK(hipStreamSynchronize(stream));
+    }
+    if (!ix->rm_words) HIP_OK(hipMalloc((void**)&ix->rm_words, RMW_WORDS * sizeof(unsigned int)));
+    if (ix->rm_tiles_cap < n_tiles) {
+        HIP_OK(hipStreamSynchronize(stream));
+        (void)hipFree(ix->rm_tiles);
+        ix->rm_tiles = nullptr;
+        ix->rm_tiles_cap = 0;
+        HIP_OK(hipMalloc((void**)&ix->rm_tiles, (2 * (size_t)n_tiles + 1) * sizeof(int)));
+        ix->rm_tiles_cap = n_tiles;
+    }
+    int* tile_cnt = ix->rm_tiles;
+    int* tile_off = ix->rm_tiles + ix->rm_tiles_cap;
+    if (listed && location == VODHIP_HOST) {
+        if (ix->upd_ids_cap < n) {
+            HIP_OK(hipStreamSynchronize(stream));
+            (void)hipFree(ix->upd_ids);
+            ix->upd_ids = nullptr;
+            ix->upd_ids_cap = 0;
+            HIP_OK(hipMalloc((void**)&ix->upd_ids, (size_t)n * sizeof(int64_t)));
+            ix->upd_ids_cap = n;
+        }
+        HIP_OK(hipMemcpyAsync(ix->upd_ids, ids, (size_t)n * sizeof(int64_t), hipMemcpyHostToDevice, stream));
+        ids = ix->upd_ids;
+    }
+    // MARK, COUNT and SCAN, then the one wait of the call: the host plans the slabs from the tile offsets and learns the new ntotal
+    static const unsigned int words0[RMW_WORDS] = {0u, 0u, ~0u, 0u};  // (static: an asynchronous copy may read it after the call returned)
+    HIP_OK(hipMemcpyAsync(ix->rm_words, words0, sizeof(words0), hipMemcpyHostToDevice, stream));
+    HIP_OK(launch_remove_mark(ids, row_begin, n, id_base, ntotal, ix->upd_owner, ix->rm_words, stream));
+    HIP_OK(launch_remove_count_scan(ix->upd_owner, tile_base, T, ntotal, n_tiles, tile_cnt, tile_off, ix->rm_words, stream));
+    std::vector<int32_t> off((size_t)n_tiles + 1);
+    unsigned int words[RMW_WORDS];
+    HIP_OK(hipMemcpyAsync(off.data(), tile_off, off.size() * sizeof(int32_t), hipMemcpyDeviceToHost, stream));
+    HIP_OK(hipMemcpyAsync(words, ix->rm_words, sizeof(words), hipMemcpyDeviceToHost, stream));
+    HIP_OK(hipStreamSynchronize(stream));
+    const int64_t first_removed = words[RMW_FIRST] == ~0u ? ntotal : (int64_t)words[RMW_FIRST];
+    const RemovePlan plan = plan_remove_slabs(off.data(), n_tiles, tile_base, T, ntotal, first_removed, ix->remove_slab_rows);
+    ix->last_remove[0] = ntotal - plan.survivors;
+    ix->last_remove[1] = words[RMW_SKIPPED];
+    ix->last_remove[2] = words[RMW_DUPLICATES];
+    if (new_ids) HIP_OK(launch_remove_map(ix->upd_owner, tile_off, tile_base, T, ntotal, new_ids, stream));
+    if (plan.survivors == ntotal) return 0;  // every slot was skipped: nothing was marked, nothing is written
+    RemoveGatherArgs a;
+    a.src = store_planes(ix);
+    a.owner = ix->upd_owner;
+    a.tile_off = tile_off;
+    a.tile_base = tile_base;
+    a.tile_rows = (int)T;
+    a.stride = ix->dim_pad;
+    a.c_pad = ix->value_c_pad;
+    a.ntotal = ntotal;
+    RemovePlanes bounce;
+    int64_t bounce_rows = 0;
+    for (const RemoveSlab& s : plan.slabs) {  // in ascending order on the one stream: a slab writes only rows that it or earlier slabs consumed
+        a.src_begin = s.src_begin;
+        a.src_rows = s.src_rows;
+        if (!s.bounced) {
+            a.dst = a.src;
+            a.dst_sub = 0;
+            HIP_OK(launch_remove_gather(a, stream));
+            continue;
+        }
+        if (!bounce_rows && ensure_remove_bounce(ix, stream, &bounce, &bounce_rows)) return -1;
+        if (s.n_keep > bounce_rows) return fail("internal: a slab keeps %lld rows, the bounce buffer holds %lld", (long long)s.n_keep, (long long)bounce_rows);
+        a.dst = bounce;
+        a.dst_sub = s.dst_begin;
+        HIP_OK(launch_remove_gather(a, stream));
+        if (copy_plane_rows(ix, bounce, 0, a.src, s.dst_begin, s.n_keep, stream)) return -1;
+    }
+    // FINISH: the owner words of this call back to zero, the pads, the new ntotal
+    HIP_OK(hipMemsetAsync(ix->upd_owner + first_removed, 0, (size_t)(ntotal - first_removed) * sizeof(int), stream));
+    return remove_set_ntotal(ix, plan.survivors, stream);
+}
+
 }  // namespace
+
+namespace vodhip {
+
+int index_remove_move_rows(vodhip_index* src, int64_t src_row, vodhip_index* dst, int64_t dst_row, int64_t n, hipStream_t stream) {
+    if (!src || !dst || n < 0 || src_row < 0 || dst_row < 0 || src_row + n > src->capacity || dst_row + n > dst->capacity) return fail("internal: invalid row move");
+    if (n == 0) return 0;
+    // both shards' planes and the source's bounce buffer are touched: a flat call on a shard's own handle (vodhip_node_index_shard)
+    // must not run beside this.  (Address order: two moves in opposite directions cannot lock each other out.)
+    std::unique_lock<std::mutex> lock_a(src < dst ? src->mu : dst->mu), lock_b;
+    if (src != dst) lock_b = std::unique_lock<std::mutex>(src < dst ? dst->mu : src->mu);
+    const RemovePlanes s = store_planes(src), d = store_planes(dst);
+    if (src->dim_pad != dst->dim_pad || (s.data32 != nullptr) != (d.data32 != nullptr) || (s.label != nullptr) != (d.label != nullptr) ||
+        (s.value != nullptr) != (d.value != nullptr) || src->value_c_pad != dst->value_c_pad)
+        return fail("internal: the shards of a row move do not keep the same planes");
+    if (s.value && (dst_row + n > dst->value_alloc_rows || src_row + n > src->value_alloc_rows)) return fail("internal: a value table is too short for the row move");
+    HIP_OK(hipSetDevice(dst->device));
+    if (src != dst || dst_row + n <= src_row || src_row + n <= dst_row) {
+        if (copy_plane_rows(src, s, src_row, d, dst_row, n, stream)) return -1;
+    } else {  // one shard, the destination covers part of the source: in ascending pieces through the bounce buffer
+        if (dst_row > src_row) return fail("internal: a row move upwards");
+        RemovePlanes bounce;
+        int64_t bounce_rows = 0;
+        if (ensure_remove_bounce(src, stream, &bounce, &bounce_rows)) return -1;
+        for (int64_t r = 0; r < n; r += bounce_rows) {
+            const int64_t m = std::min(bounce_rows, n - r);
+            if (copy_plane_rows(src, s, src_row + r, bounce, 0, m, stream)) return -1;
+            if (copy_plane_rows(src, bounce, 0, d, dst_row + r, m, stream)) return -1;
+        }
+    }
+    HIP_OK(hipStreamSynchronize(stream));
+    return 0;
+}
+
+int index_remove_set_ntotal(vodhip_index* ix, int64_t ntotal, hipStream_t stream) {
+    if (!ix || ntotal < 0 || ntotal > ix->capacity) return fail("internal: invalid ntotal");
+    std::lock_guard<std::mutex> guard(ix->mu);
+    HIP_OK(hipSetDevice(ix->device));
+    if (remove_set_ntotal(ix, ntotal, stream)) return -1;
+    HIP_OK(hipStreamSynchronize(stream));
+    return 0;
+}
+
+}  // namespace vodhip
 
 extern "C" {
 
@@ -706,6 +936,9 @@ int vodhip_index_destroy(vodhip_index_t* ix) {
     (void)hipFree(ix->upd_owner);
     (void)hipFree(ix->upd_counts);
     (void)hipFree(ix->upd_ids);
+    (void)hipFree(ix->rm_words);
+    (void)hipFree(ix->rm_tiles);
+    (void)hipFree(ix->rm_bounce);
     for (int i = 0; i < MAX_IN_FLIGHT; ++i)
         for (hipEvent_t e : ix->l2_ev[i])
             if (e) (void)hipEventDestroy(e);
@@ -863,6 +1096,37 @@ int vodhip_index_update_rows(vodhip_index_t* ix, const int64_t* ids, int64_t row
     return 0;
 }
 
+// H2r: listed or contiguous stored rows removed, the survivors moved down in order (kernels_remove.hip, remove_fold.h)
+int vodhip_index_remove_rows(vodhip_index_t* ix, const int64_t* ids, int64_t row_begin, int64_t n, int location, int64_t id_base, int64_t* new_ids,
+                             int64_t* n_removed, void* stream_) {
+    if (!ix) return fail("index is NULL");
+    std::lock_guard<std::mutex> guard(ix->mu);
+    if (const char* msg = remove_rows_args_error(ids != nullptr, row_begin, n, location, ix->ntotal)) {
+        if (!strcmp(msg, "invalid location")) return fail("invalid location %d", location);
+        if (!strncmp(msg, "row range", 9)) return fail("rows [%lld, %lld + %lld), ntotal=%lld: %s", (long long)row_begin, (long long)row_begin, (long long)n, (long long)ix->ntotal, msg);
+        return fail("n=%lld: %s", (long long)n, msg);
+    }
+    if (!ix->inflight.empty() || ix->unfinished)
+        return fail("%d searches are in flight: finish them before removing rows", (int)ix->inflight.size() + ix->unfinished);
+    // a table left short by rows added after it was set describes other rows than the store holds (every read-out refuses it): moving
+    // it with the rows would read past its allocation and then pass it off as valid
+    if (ix->row_value && ix->value_rows != ix->ntotal)
+        return fail("remove_rows: the value table holds %lld rows, the index %lld: set the table again (or clear it) after adding rows, then remove",
+                    (long long)ix->value_rows, (long long)ix->ntotal);
+    hipStream_t stream = (hipStream_t)stream_;
+    const int rc = remove_rows_locked(ix, ids, row_begin, n, location, id_base, new_ids, stream);
+    if (rc != 0 && ix->upd_owner) {
+        // whatever the call marked must not outlive it: update_rows and the next removal read the table as all zero.  (Best effort,
+        // the error text of the failure is kept.)
+        (void)hipStreamSynchronize(stream);
+        (void)hipMemsetAsync(ix->upd_owner, 0, (size_t)std::max<int64_t>(1, ix->capacity) * sizeof(int), stream);
+        (void)hipStreamSynchronize(stream);
+        (void)hipGetLastError();
+    }
+    if (rc == 0 && n_removed) *n_removed = ix->last_remove[0];
+    return rc;
+}
+
 int vodhip_index_reset(vodhip_index_t* ix) {
     if (!ix) return fail("index is NULL");
     if (!ix->inflight.empty()) return fail("%d searches are in flight: finish them before resetting the index", (int)ix->inflight.size());
@@ -938,6 +1202,32 @@ int vodhip_index_data_f32(const vodhip_index_t* ix, void** dev_ptr, int64_t* row
     if (!ix->exact) return fail("the index was not created with VODHIP_EXACT_F32: it keeps no float32 rows");
     if (dev_ptr) *dev_ptr = ix->data32;
     if (row_stride_elems) *row_stride_elems = ix->dim_pad;
+    return 0;
+}
+
+int vodhip_index_plane(const vodhip_index_t* ix, int which, void** dev_ptr, int64_t* n_rows, int64_t* row_stride_elems) {
+    if (!ix) return fail("index is NULL");
+    void* p = nullptr;
+    int64_t rows = ix->ntotal, stride = 1;
+    switch (which) {
+        case VODHIP_PLANE_LABELS: p = ix->row_label; break;
+        case VODHIP_PLANE_VALUES:
+            p = ix->row_value;
+            rows = ix->row_value ? std::max<int64_t>(1, scan_tiles(ix->value_rows)) * 256 : 0;
+            stride = ix->value_c_pad;
+            break;
+        case VODHIP_PLANE_ROW_N2: p = ix->row_n2; break;
+        case VODHIP_PLANE_ROW_D2: p = ix->row_d2; break;
+        case VODHIP_PLANE_OWNER:
+            p = ix->upd_owner;
+            rows = ix->upd_owner ? std::max<int64_t>(1, ix->capacity) : 0;
+            break;
+        default: return fail("invalid plane %d", which);
+    }
+    if (!p) rows = 0;
+    if (dev_ptr) *dev_ptr = p;
+    if (n_rows) *n_rows = rows;
+    if (row_stride_elems) *row_stride_elems = stride;
     return 0;
 }
 
@@ -1037,6 +1327,7 @@ int vodhip_index_set_row_values(vodhip_index_t* ix, const void* values, int64_t 
         return fail("building the row-value table failed: %s", hipGetErrorString(e));
     }
     ix->row_value = table;
+    ix->value_alloc_rows = rows_pad;
     ix->value_rows = n_rows;
     ix->value_cols = n_cols;
     ix->value_c_pad = c_pad;
@@ -2193,6 +2484,9 @@ int vodhip_index_set_param(vodhip_index_t* ix, const char* key, int64_t value) {
     } else if (!strcmp(key, "scan_temp_bytes")) {
         if (value < 0) return fail("scan_temp_bytes must be 0 (the default, VODHIP_POSTERIOR_TEMP_BYTES) or >= 1");
         ix->scan_temp_bytes = value == 0 ? VODHIP_POSTERIOR_TEMP_BYTES : value;
+    } else if (!strcmp(key, "remove_slab_rows")) {
+        if (value != 0 && !remove_slab_rows_ok(value)) return fail("remove_slab_rows must be 0 (the default, 65536) or a power of two in [4, 2^30]");
+        ix->remove_slab_rows = value == 0 ? REMOVE_SLAB_ROWS : value;
     } else if (!strcmp(key, "tile")) {
         PlanTunables t;
         t.tile = value;
@@ -2288,7 +2582,15 @@ int vodhip_index_get_stat(const vodhip_index_t* ix, const char* key, int64_t* ou
             HIP_OK(hipMemcpy(w, ix->upd_counts, sizeof(w), hipMemcpyDeviceToHost));
         }
         *out = key[12] == 'w' ? ix->last_update_n - (int64_t)w[0] - (int64_t)w[1] : key[12] == 's' ? (int64_t)w[0] : (int64_t)w[1];
-    } else if (!strcmp(key, "last_exact_kx"))
+    } else if (!strcmp(key, "last_remove_removed"))
+        *out = ix->last_remove[0];
+    else if (!strcmp(key, "last_remove_skipped"))
+        *out = ix->last_remove[1];
+    else if (!strcmp(key, "last_remove_duplicates"))
+        *out = ix->last_remove[2];
+    else if (!strcmp(key, "remove_slab_rows"))
+        *out = ix->remove_slab_rows;
+    else if (!strcmp(key, "last_exact_kx"))
         *out = ix->last_exact_kx;
     else if (!strcmp(key, "last_exact_need"))
         *out = ix->last_exact_need;

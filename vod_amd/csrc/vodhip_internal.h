@@ -268,6 +268,44 @@ hipError_t launch_update_rows(const UpdateArgs& a, hipStream_t stream);
 // words [EXS_MAX_N2], [EXS_MAX_D2] of an exact store's statistics = the maxima of the finite row_n2 / row_d2 of rows [0, n_rows)
 hipError_t launch_update_maxima(const float* row_n2, const float* row_d2, int64_t n_rows, unsigned int* stats, hipStream_t stream);
 
+// ---- launchers (kernels_remove.hip): stored rows removed, the gaps closed in place (include/vodhip.h H2r) -----------
+enum : int { RMW_SKIPPED = 0, RMW_DUPLICATES = 1, RMW_FIRST = 2, RMW_WORDS = 4 };  // the call's device words; [RMW_FIRST]: the lowest removed row (starts at ~0u)
+struct RemovePlanes {  // one row-indexed set of planes: the store's own, or the bounce buffer's
+    uint16_t* data = nullptr;   // [rows][stride]
+    float* data32 = nullptr;    // exact store: [rows][stride], and the two statistics per row
+    float* row_n2 = nullptr;
+    float* row_d2 = nullptr;
+    int* label = nullptr;       // row labels, when set
+    uint16_t* value = nullptr;  // value table, when attached: [rows][c_pad]
+};
+struct RemoveGatherArgs {
+    RemovePlanes src, dst;            // which planes exist is read from `src`
+    const int* owner = nullptr;       // != 0: the row leaves
+    const int* tile_off = nullptr;    // exclusive scan of the survivors per count tile
+    int64_t tile_base = 0;            // first row of count tile 0 (every row below survives)
+    int tile_rows = 256;
+    int64_t src_begin = 0, src_rows = 0;  // this launch's source rows
+    int64_t dst_sub = 0;              // a survivor with the new id r is written to row r - dst_sub of `dst` (0, or the slab's first new id)
+    int64_t stride = 0, c_pad = 0;
+    int64_t ntotal = 0;
+};
+// ids == NULL: the range [row_begin, row_begin + n)
+hipError_t launch_remove_mark(const int64_t* ids, int64_t row_begin, int64_t n, int64_t id_base, int64_t ntotal, int* owner, unsigned int* words,
+                              hipStream_t stream);
+// tile_cnt [n_tiles], tile_off [n_tiles + 1], n_tiles = ceil((ntotal - tile_base) / tile_rows); words[RMW_FIRST] receives the lowest removed row
+hipError_t launch_remove_count_scan(const int* owner, int64_t tile_base, int64_t tile_rows, int64_t ntotal, int64_t n_tiles, int* tile_cnt, int* tile_off,
+                                    unsigned int* words, hipStream_t stream);
+hipError_t launch_remove_gather(const RemoveGatherArgs& a, hipStream_t stream);
+hipError_t launch_remove_map(const int* owner, const int* tile_off, int64_t tile_base, int64_t tile_rows, int64_t ntotal, int64_t* new_ids, hipStream_t stream);
+}  // namespace vodhip
+// what a node index needs of its shards to put them back into the layout `add` fills (vodhip_api.hip; the shards compacted already):
+// rows [src_row, src_row + n) of every plane of `src` copied to rows [dst_row, ..) of `dst` on `stream` (an overlapping move inside one
+// shard goes through its bounce buffer), and a shard told how many rows it now holds.  Both wait for `stream`.
+struct vodhip_index;
+namespace vodhip {
+int index_remove_move_rows(vodhip_index* src, int64_t src_row, vodhip_index* dst, int64_t dst_row, int64_t n, hipStream_t stream);
+int index_remove_set_ntotal(vodhip_index* ix, int64_t ntotal, hipStream_t stream);
+
 // ---- the whole-store scans (store_scan.h): what log_partition, posterior_mean, sample_posterior and the rank calls share ----------
 struct ScanInputs {
     const void* store = nullptr;      // [>= round_up(ntotal, 256) rows][dim_pad] fp16 / bf16 rows

@@ -29,6 +29,7 @@
 #include "readout_grad_fold.h"
 #include "key_grad_fold.h"
 #include "update_fold.h"
+#include "remove_fold.h"
 #include "vodhip_internal.h"
 
 namespace {
@@ -113,6 +114,7 @@ struct vodhip_node_index {
     int q_labels_per_query = 0, q_labels_location = VODHIP_HOST;
     bool has_row_labels = false;
     int64_t update_unrouted = 0;             // slots of the last update_rows that no shard owns (id < 0 or >= ntotal): skipped here
+    int64_t remove_unrouted = 0;             // the same of the last remove_rows
     int64_t value_rows = 0, value_cols = 0;  // the value table of the posterior read-out as it was set (0, 0: none); the shards hold its rows
     // topology (read once at create): can devices[0] and shard g's device copy into each other's memory directly?  A shard without
     // peer access - or every shard but the first with `host_staging` set (bring-up, tests on a 1-GPU box) - exchanges its queries and
@@ -461,6 +463,106 @@ int vodhip_node_index_update_rows(vodhip_node_index_t* nx, const int64_t* ids, i
         if (rc) return nfail("shard %d: %s", g, std::string(vodhip_last_error()).c_str());
     }
     return 0;
+}
+
+// H2r behind the one handle: the slots routed as for H2u, every shard compacted by the flat call, then the survivors moved between the
+// shards until the layout is the one `add` fills (remove_fold.h: plan_remove_segments)
+int vodhip_node_index_remove_rows(vodhip_node_index_t* nx, const int64_t* ids, int64_t row_begin, int64_t n, int64_t* new_ids, int64_t* n_removed) {
+    if (!nx) return nfail("index is NULL");
+    std::lock_guard<std::mutex> guard(nx->mu);
+    if (const char* msg = vodhip::remove_rows_args_error(ids != nullptr, row_begin, n, VODHIP_HOST, nx->ntotal)) {
+        if (!strncmp(msg, "row range", 9)) return nfail("rows [%lld, %lld + %lld), ntotal=%lld: %s", (long long)row_begin, (long long)row_begin, (long long)n, (long long)nx->ntotal, msg);
+        return nfail("n=%lld: %s", (long long)n, msg);
+    }
+    if (nx->n_pending) return nfail("%d searches are in flight: finish them before removing rows", nx->n_pending);
+    if (nx->value_cols && nx->value_rows != nx->ntotal)  // (before any shard compacts: the flat call would refuse on the short shard only)
+        return nfail("remove_rows: the value table holds %lld rows, the index %lld: set the table again (or clear it) after adding rows, then remove",
+                     (long long)nx->value_rows, (long long)nx->ntotal);
+    const int G = nx->n;
+    vodhip::UpdateRoute route;
+    if (ids) route = vodhip::route_update_slots(ids, n, nx->rows_per_shard, G, nx->ntotal);
+    nx->remove_unrouted = route.skipped;
+    std::vector<int64_t> old_rows((size_t)G), keep((size_t)G), shard_ids;
+    std::vector<std::vector<int64_t>> local_map((size_t)(new_ids ? G : 0));
+    auto restore = [&](int rc) {
+        (void)hipSetDevice(nx->device[0]);
+        return rc;
+    };
+    // (a shard without a slot still takes the call, with n = 0: its stats of an earlier call must not enter this call's sums)
+    for (int g = 0; g < G; ++g) {
+        const int64_t base = g * nx->rows_per_shard;
+        if (vodhip_index_ntotal(nx->shard[g], &old_rows[(size_t)g])) return restore(-1);
+        int64_t* map_dev = nullptr;
+        int64_t cnt = 0;
+        if (new_ids && old_rows[(size_t)g] > 0) {
+            NODE_HIP_OK(hipSetDevice(nx->device[g]));
+            NODE_HIP_OK(hipMalloc((void**)&map_dev, (size_t)old_rows[(size_t)g] * sizeof(int64_t)));
+        }
+        int rc;
+        if (!ids) {
+            int64_t lo, hi;
+            vodhip::split_remove_range(row_begin, n, nx->rows_per_shard, g, &lo, &hi);
+            cnt = hi - lo;
+            rc = vodhip_index_remove_rows(nx->shard[g], nullptr, lo, cnt, VODHIP_HOST, 0, map_dev, nullptr, nx->stream[g]);
+        } else {
+            const int64_t first = route.first[(size_t)g];
+            cnt = route.first[(size_t)g + 1] - first;
+            shard_ids.resize((size_t)cnt);
+            for (int64_t i = 0; i < cnt; ++i) shard_ids[(size_t)i] = ids[route.slot[(size_t)(first + i)]];
+            rc = vodhip_index_remove_rows(nx->shard[g], cnt ? shard_ids.data() : nullptr, 0, cnt, VODHIP_HOST, base, map_dev, nullptr, nx->stream[g]);
+        }
+        std::string err = rc ? std::string(vodhip_last_error()) : std::string();
+        if (map_dev) {
+            local_map[(size_t)g].resize((size_t)old_rows[(size_t)g]);
+            hipError_t e = hipSetDevice(nx->device[g]);
+            if (rc == 0 && cnt == 0) {  // (the flat call writes no map for an empty call: the identity)
+                for (int64_t r = 0; r < old_rows[(size_t)g]; ++r) local_map[(size_t)g][(size_t)r] = r;
+            } else if (rc == 0) {
+                if (e == hipSuccess) e = hipMemcpyAsync(local_map[(size_t)g].data(), map_dev, (size_t)old_rows[(size_t)g] * sizeof(int64_t), hipMemcpyDeviceToHost, nx->stream[g]);
+            }
+            if (e == hipSuccess) e = hipStreamSynchronize(nx->stream[g]);
+            (void)hipFree(map_dev);
+            if (rc == 0 && e != hipSuccess) {
+                (void)hipGetLastError();
+                return restore(nfail("shard %d: reading the id map failed: %s", g, hipGetErrorString(e)));
+            }
+        }
+        if (rc) return restore(nfail("shard %d: %s", g, err.c_str()));
+        if (vodhip_index_ntotal(nx->shard[g], &keep[(size_t)g])) return restore(-1);
+    }
+    // every shard holds its survivors in rows [0, keep[g]): move them to where `add` would have put them, one segment after the other
+    const vodhip::RemoveSegmentPlan plan = vodhip::plan_remove_segments(keep.data(), G, nx->rows_per_shard);
+    for (int g = 0; g < G; ++g) {  // (a shard's own compaction is only enqueued, and a segment reads another shard's rows)
+        NODE_HIP_OK(hipSetDevice(nx->device[g]));
+        NODE_HIP_OK(hipStreamSynchronize(nx->stream[g]));
+    }
+    for (const vodhip::RemoveSegment& s : plan.segments) {
+        if (vodhip::index_remove_move_rows(nx->shard[(size_t)s.src_shard], s.src_row, nx->shard[(size_t)s.dst_shard], s.dst_row, s.n, nx->stream[(size_t)s.dst_shard]))
+            return restore(nfail("moving rows from shard %d to shard %d: %s", s.src_shard, s.dst_shard, std::string(vodhip_last_error()).c_str()));
+    }
+    int64_t total = 0;
+    for (int g = 0; g < G; ++g) {
+        if (plan.ntotal[(size_t)g] != keep[(size_t)g] || !plan.segments.empty()) {
+            if (vodhip::index_remove_set_ntotal(nx->shard[g], plan.ntotal[(size_t)g], nx->stream[g]))
+                return restore(nfail("shard %d: %s", g, std::string(vodhip_last_error()).c_str()));
+        }
+        total += plan.ntotal[(size_t)g];
+    }
+    if (new_ids) {
+        int64_t before = 0;  // survivors of the shards below
+        for (int g = 0; g < G; ++g) {
+            int64_t* out = new_ids + g * nx->rows_per_shard;
+            for (int64_t r = 0; r < old_rows[(size_t)g]; ++r) {
+                const int64_t v = local_map[(size_t)g].empty() ? -1 : local_map[(size_t)g][(size_t)r];
+                out[r] = v < 0 ? -1 : before + v;
+            }
+            before += keep[(size_t)g];
+        }
+    }
+    if (n_removed) *n_removed = nx->ntotal - total;
+    if (nx->value_cols) nx->value_rows = total;
+    nx->ntotal = total;
+    return restore(0);
 }
 
 int vodhip_node_index_reset(vodhip_node_index_t* nx) {
@@ -1496,6 +1598,15 @@ int vodhip_node_index_get_stat(vodhip_node_index_t* nx, const char* key, int64_t
         }
         if (!strcmp(key, "last_update_skipped")) *out += nx->update_unrouted;
         NODE_HIP_OK(hipSetDevice(nx->device[0]));
+        return 0;
+    }
+    if (!strcmp(key, "last_remove_removed") || !strcmp(key, "last_remove_skipped") || !strcmp(key, "last_remove_duplicates")) {
+        for (int g = 0; g < nx->n; ++g) {  // (every shard took the last remove_rows, with no slot if it owns none)
+            int64_t v = 0;
+            if (vodhip_index_get_stat(nx->shard[g], key, &v)) return -1;
+            *out += v;
+        }
+        if (!strcmp(key, "last_remove_skipped")) *out += nx->remove_unrouted;
         return 0;
     }
     return nfail("unknown stat '%s'", key);

@@ -73,6 +73,37 @@ def _host_update_args(vectors, ids, dim: int):
     return v, ida
 
 
+def remove_rows_args(ids, begin: int, n, mask, ntotal: int):
+    """The three spellings of `remove_rows` as the native call takes them: `(ids, begin, n)` with `ids` None (the range
+    `begin .. begin + n`) or an int64 id list (`begin` is 0 and `n` its length then).  A list stays what it was - a device tensor is
+    not copied to the host; a boolean `mask` of length `ntotal` becomes the ids of its True entries.  Exactly one spelling per call."""
+    given = [ids is not None, mask is not None, n is not None]
+    if sum(given) != 1 or (begin != 0 and n is None):
+        raise ValueError("remove_rows takes exactly one of: ids=, mask=, or the range begin= / n=")
+    if n is not None:
+        begin, n = int(begin), int(n)
+        if n < 0 or begin < 0 or begin + n > ntotal:
+            raise ValueError(f"rows [{begin}, {begin} + {n}) are outside the {ntotal} stored rows")
+        return None, begin, n
+    if mask is not None:
+        if isinstance(mask, torch.Tensor):
+            if mask.dtype != torch.bool or mask.ndim != 1 or mask.numel() != ntotal:
+                raise ValueError(f"expected a boolean mask of length {ntotal}, got {mask.dtype} {tuple(mask.shape)}")
+            ids = torch.nonzero(mask.detach()).reshape(-1)
+        else:
+            m = np.asarray(mask)
+            if m.dtype != np.bool_ or m.ndim != 1 or m.size != ntotal:
+                raise ValueError(f"expected a boolean mask of length {ntotal}, got {m.dtype} {m.shape}")
+            ids = np.flatnonzero(m).astype(np.int64)
+    if isinstance(ids, torch.Tensor):
+        ids = ids.detach().to(torch.int64).contiguous().reshape(-1)
+        if not ids.is_cuda:
+            ids = ids.numpy()
+    if not isinstance(ids, torch.Tensor):
+        ids = np.ascontiguousarray(np.asarray(ids).reshape(-1), dtype=np.int64)
+    return ids, 0, int(ids.numel() if isinstance(ids, torch.Tensor) else ids.size)
+
+
 class HipFlatIndex:
     """Exact MIPS index: row-major fp16/bf16 rows in HBM, searched by the fused MFMA + top-k kernels.
 
@@ -244,6 +275,38 @@ class HipFlatIndex:
         self._update(_native.UPDATE_ADD, delta, alpha, ids, begin)
         if check and ids is not None and (dup := self.get_stat("last_update_duplicates")):
             raise ValueError(f"add_to_rows: {dup} slots repeat an id that a later slot lists too; only the last slot of an id was applied")
+
+    # -- rows removed, the gaps closed in place (H2r) ------------------------------------------------------
+    def remove_rows(self, ids=None, begin: int = 0, n: int | None = None, mask=None, return_map: bool = False):
+        """Remove stored rows and close the gaps in place, as faiss `IndexFlat.remove_ids`: `ids` (int64 row ids, host or device),
+        or the range `begin .. begin + n`, or a boolean `mask` of length `ntotal` (True = remove).  The compaction is stable: a
+        survivor's new id is its old id minus the number of removed rows below it.  Every plane of the store - the rows, an
+        `exact_f32` store's float32 rows and statistics, the row labels, the value table - is compacted the same way and equals,
+        byte for byte, an index freshly built by `add` from the survivors; labels and table stay attached (unlike `reset(); add(...)`).
+        An id that is negative or not below `ntotal` is skipped, a repeated id removes its row once:
+        `get_stat("last_remove_removed" | "last_remove_skipped" | "last_remove_duplicates")` tells.  Returns the number of rows
+        removed; with `return_map=True` the pair `(removed, new_ids)`, `new_ids` a device int64 tensor `[old ntotal]` with the new id
+        of every old row and -1 for a removed one - what remaps gold ids and side tables.  Waits for the device once.  Refused while
+        searches are in flight, like `add`, and when rows were added after `set_row_values` (the table is short then and describes
+        other rows: set it again or clear it first).  A device error during the call leaves the store undefined: `reset()` it."""
+        old = self.ntotal
+        ida, begin, n = remove_rows_args(ids, begin, n, mask, old)
+        with torch.cuda.device(self.device):
+            stream = _native.current_stream_ptr(self.device)
+            on_device = isinstance(ida, torch.Tensor)
+            if on_device and ida.device != self.device:
+                raise ValueError(f"ids live on {ida.device}, the index on {self.device}")
+            new_ids = torch.arange(old, dtype=torch.int64, device=self.device) if return_map else None  # (an empty call writes no map: the identity)
+            ptr = None
+            if ida is not None and n:
+                ptr = ida.data_ptr() if on_device else ida.ctypes.data
+            removed = ctypes.c_int64()
+            _native.check(self._lib.vodhip_index_remove_rows(
+                self._h, ptr, begin, n, _native.DEVICE if on_device else _native.HOST, 0, new_ids.data_ptr() if return_map and old else None,
+                ctypes.byref(removed), stream))
+            if on_device:
+                torch.cuda.current_stream(self.device).synchronize()  # the ids may be freed by the caller right after
+        return (removed.value, new_ids) if return_map else removed.value
 
     # -- subset filter (SURVEY 8f-3) ---------------------------------------------------------------
     def set_row_labels(self, labels: np.ndarray | torch.Tensor | None) -> None:
@@ -1704,7 +1767,8 @@ class HipNodeIndex:
 
     def get_stat(self, key: str) -> int:
         """Node-level stats: of the last search with `set_param("profile", 1)`, "last_merge_ns" and "last_copy_ns_max" (HIP events); of
-        the last `update_rows` / `add_to_rows`, "last_update_written", "last_update_skipped", "last_update_duplicates" (sums over the shards)."""
+        the last `update_rows` / `add_to_rows`, "last_update_written", "last_update_skipped", "last_update_duplicates", of the last `remove_rows`
+        "last_remove_removed", "last_remove_skipped", "last_remove_duplicates" (sums over the shards)."""
         out = ctypes.c_int64()
         _native.check(self._lib.vodhip_node_index_get_stat(self._h, key.encode(), ctypes.byref(out)))
         return out.value
@@ -1756,6 +1820,23 @@ class HipNodeIndex:
         self._update(_native.UPDATE_ADD, delta, alpha, ids, begin)
         if check and ids is not None and (dup := self.get_stat("last_update_duplicates")):
             raise ValueError(f"add_to_rows: {dup} slots repeat an id that a later slot lists too; only the last slot of an id was applied")
+
+    def remove_rows(self, ids=None, begin: int = 0, n: int | None = None, mask=None, return_map: bool = False):
+        """Remove stored rows (global row ids, the global range `begin .. begin + n`, or a boolean mask) and restore the layout `add`
+        fills - every shard full before the next one starts: see `HipFlatIndex.remove_rows`.  Each shard compacts on its device, the
+        survivors then move between the shards device to device.  `return_map=True` adds the host int64 array `[old ntotal]` of new
+        global ids (-1: removed)."""
+        old = self.ntotal
+        ida, begin, n = remove_rows_args(ids, begin, n, mask, old)
+        if isinstance(ida, torch.Tensor):
+            ida = ida.cpu().numpy()
+        new_ids = np.arange(old, dtype=np.int64) if return_map else None
+        removed = ctypes.c_int64()
+        with torch.cuda.device(self.device):
+            _native.check(self._lib.vodhip_node_index_remove_rows(
+                self._h, ida.ctypes.data if ida is not None and n else None, begin, n, new_ids.ctypes.data if return_map and old else None,
+                ctypes.byref(removed)))
+        return (removed.value, new_ids) if return_map else removed.value
 
     def set_row_labels(self, labels: np.ndarray | None) -> None:
         """One int32 subset label per stored row (global row order; None clears): see `HipFlatIndex.set_row_labels`."""
