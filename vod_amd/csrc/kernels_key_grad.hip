@@ -40,7 +40,9 @@
 // NOT BUILT: the form in which each wave owns a column range and the scores are computed once per tile - K-loop steps (K + K) per
 // tile against this design's chunks * (K + slices) (K = dim_pad / 64 steps; chunks = ceil(K / slices)); it needs the weights exchanged
 // through the LDS between the waves and half-tiles of queries to fit 160 KB.
-#include "store_scan.h"
+// The slice-image geometry, the fp16 weight scale, acc_scale and the host dispatch are scan_contract.h's, which also records why the
+// second product itself stays spelled out in this file.
+#include "scan_contract.h"
 
 #include "../../include/vodhip.h"
 
@@ -60,15 +62,13 @@ constexpr int KG_BZ = 64;                       // stored rows of a workgroup: t
 #endif
 constexpr int KG_NSL_LOGZ = VODHIP_KEY_GRAD_SLICES_LOGZ;    // 64-column slices of a full chunk, a only
 constexpr int KG_NSL_TABLE = VODHIP_KEY_GRAD_SLICES_TABLE;  // with a table term
-constexpr int KG_A_BYTES = KG_BQ * 128;         // one slice image
-constexpr int KG_IMG = 4 * KG_A_BYTES;          // the slices of the second product; >= the K loop's ring
+constexpr int KG_A_BYTES = CT_SLICE_BYTES;      // one slice image
+constexpr int KG_IMG = CT_IMG;                  // the slices of the second product; >= the K loop's ring
 constexpr int KG_LDS = KG_IMG + KG_BQ * (int)sizeof(float4);  // + the tile's (max_score, log_rel, a', ubar) words
 static_assert(KG_NSL_LOGZ == 3 || KG_NSL_LOGZ == 4, "3 or 4 slices");
 static_assert(KG_NSL_TABLE == 3 || KG_NSL_TABLE == 4, "3 or 4 slices");
-static_assert(KG_IMG >= scan_ring_bytes(KG_BZ), "the ring fits under the slices");
+static_assert(KG_BZ == CT_BN, "the geometry of scan_contract.h");
 
-typedef short s16x4 __attribute__((ext_vector_type(4)));
-typedef short s16x8 __attribute__((ext_vector_type(8)));
 
 // what the staging leaves per query of the batch
 struct KgQuery {
@@ -431,7 +431,7 @@ void key_grad_kernel(const uint16_t* __restrict__ Qs, const uint16_t* __restrict
                     if constexpr (DT == 0) {
                         f16x8 v;
 #pragma unroll
-                        for (int e = 0; e < 8; ++e) v[e] = (_Float16)(w8[j][e] * 32768.f);
+                        for (int e = 0; e < 8; ++e) v[e] = (_Float16)(w8[j][e] * CT_FP16_SCALE);
                         wf[i][s][j] = __builtin_bit_cast(u32x4, v);
                     } else {
                         bf16x8 v;
@@ -508,7 +508,7 @@ void key_grad_kernel(const uint16_t* __restrict__ Qs, const uint16_t* __restrict
     }
     // column c of the chunk, row column `col`: block b = c / 32, lane half (c >> 2) & 1, register (c & 3) + 4 ((c & 31) >> 3) - the C
     // layout of the second product (its rows are the store columns).  The batch's power of two (and the 2^-15 of the fp16 weights) is exact
-    const int shift = sc->shift - (DT == 0 ? 15 : 0);
+    const int shift = sc->shift - (DT == 0 ? CT_FP16_SHIFT : 0);
     const bool nan = sc->nan != 0;
     for (int idx = wave * 64 + lane_e; idx < BN * C_W; idx += scan_threads(1)) {  // (wave * 64 + lane_e = tid)
         const int col = idx / C_W, c = idx % C_W;
@@ -524,47 +524,25 @@ void key_grad_kernel(const uint16_t* __restrict__ Qs, const uint16_t* __restrict
     }
 }
 
-template <int DT, bool SUBSET, bool TABLE, int NSL>
-hipError_t launch_kg_scan_n(const KeyGradArgs& a, int64_t q_first, int64_t nq, int add, int col_first, int n_dchunks, const FilterExtra& ex, hipStream_t stream) {
-    const int n_rtiles = (int)((a.p.ntotal + KG_BZ - 1) / KG_BZ);
-    const int n_qtiles = (int)((nq + KG_BQ - 1) / KG_BQ);
-    const int64_t grid = (int64_t)((n_rtiles + 7) / 8) * 8 * n_dchunks;
-    if (grid > 0x7fffffffll) return hipErrorInvalidValue;
-    auto kern = key_grad_kernel<DT, SUBSET, TABLE, NSL>;
-    if (hipError_t e = allow_dynamic_lds((const void*)kern, KG_LDS); e != hipSuccess) return e;
-    hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(scan_threads(1)), KG_LDS, stream, (const uint16_t*)a.p.q_stage, (const uint16_t*)a.p.store,
-                       (const uint16_t*)a.values, (const uint16_t*)a.g_stage, (const KgQuery*)a.aux + q_first, (const KgScales*)a.scales, a.p.out_max + q_first,
-                       a.p.out_log_rel + q_first, (int)a.p.dim_pad, a.c_pad, (int)a.p.dim, (int)a.p.ntotal, n_rtiles, n_qtiles, n_dchunks, col_first, (int)nq, a.p.beta,
-                       add, a.out, ex);
-    return hipGetLastError();
-}
-
 // the full chunks in one launch, the last narrower chunk (if any) in a second one
 template <int DT, bool SUBSET, bool TABLE>
 hipError_t launch_kg_scan(const KeyGradArgs& a, int64_t q_first, int64_t nq, int add, const FilterExtra& ex, hipStream_t stream) {
-    constexpr int NSL = TABLE ? KG_NSL_TABLE : KG_NSL_LOGZ;
-    const int n_slices = (int)(a.p.dim_pad / 64);
-    const int n_full = n_slices / NSL, rem = n_slices % NSL;
-    if (n_full > 0)
-        if (hipError_t e = launch_kg_scan_n<DT, SUBSET, TABLE, NSL>(a, q_first, nq, add, 0, n_full, ex, stream); e != hipSuccess) return e;
-    const int col = n_full * NSL * 64;
-    if (rem == 1) return launch_kg_scan_n<DT, SUBSET, TABLE, 1>(a, q_first, nq, add, col, 1, ex, stream);
-    if (rem == 2) return launch_kg_scan_n<DT, SUBSET, TABLE, 2>(a, q_first, nq, add, col, 1, ex, stream);
-    if constexpr (NSL == 4)
-        if (rem == 3) return launch_kg_scan_n<DT, SUBSET, TABLE, 3>(a, q_first, nq, add, col, 1, ex, stream);
-    return hipSuccess;
-}
-
-template <int DT, bool SUBSET>
-hipError_t launch_kg_table(const KeyGradArgs& a, int64_t q_first, int64_t nq, int add, const FilterExtra& ex, hipStream_t stream) {
-    return a.g ? launch_kg_scan<DT, SUBSET, true>(a, q_first, nq, add, ex, stream) : launch_kg_scan<DT, SUBSET, false>(a, q_first, nq, add, ex, stream);
+    constexpr int NFULL = TABLE ? KG_NSL_TABLE : KG_NSL_LOGZ;
+    const int n_rtiles = (int)((a.p.ntotal + KG_BZ - 1) / KG_BZ);
+    const int n_qtiles = (int)((nq + KG_BQ - 1) / KG_BQ);
+    return chunks_dispatch<NFULL>((int)(a.p.dim_pad / 64), [&](auto nsl, int first_chunk, int n_dchunks) {
+        return scan_launch_lds<1>(key_grad_kernel<DT, SUBSET, TABLE, nsl.value>, scan_grid(n_rtiles, n_dchunks), KG_LDS, stream, (const uint16_t*)a.p.q_stage,
+                                  (const uint16_t*)a.p.store, (const uint16_t*)a.values, (const uint16_t*)a.g_stage, (const KgQuery*)a.aux + q_first,
+                                  (const KgScales*)a.scales, a.p.out_max + q_first, a.p.out_log_rel + q_first, (int)a.p.dim_pad, a.c_pad, (int)a.p.dim, (int)a.p.ntotal,
+                                  n_rtiles, n_qtiles, n_dchunks, first_chunk * NFULL * 64, (int)nq, a.p.beta, add, a.out, ex);
+    });
 }
 
 bool key_grad_args_ok(const KeyGradArgs& a) {
-    if (a.p.dim_pad % 64 != 0 || a.p.dim_pad <= 0 || a.p.dim < 1 || a.p.dim > a.p.dim_pad || a.p.ntotal < 0 || a.p.ntotal >= (1ll << 31) - 512) return false;
+    if (!scan_store_ok(a.p) || a.p.dim < 1 || a.p.dim > a.p.dim_pad) return false;
     if (!a.a && !a.g) return false;
     if (a.g) {
-        if (a.c_pad % 64 != 0 || a.c_pad < 64 || a.c_pad > 256 || a.n_cols < 1 || a.n_cols > a.c_pad) return false;
+        if (!readout_cols_ok(a.c_pad, a.n_cols)) return false;
         if (!a.y || !a.vmax || !a.values || !a.g_stage) return false;
     }
     return a.aux && a.scales && a.out;
@@ -602,9 +580,9 @@ hipError_t launch_posterior_key_gradient(const KeyGradArgs& a, int64_t q_first, 
         if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
     }
     const FilterExtra ex = scan_filter_extra(a.p, q_first);
-    const bool subset = ex.row_label != nullptr;
-    if (a.p.store_dtype == 0) return subset ? launch_kg_table<0, true>(a, q_first, nq, add, ex, stream) : launch_kg_table<0, false>(a, q_first, nq, add, ex, stream);
-    return subset ? launch_kg_table<1, true>(a, q_first, nq, add, ex, stream) : launch_kg_table<1, false>(a, q_first, nq, add, ex, stream);
+    return contract_dispatch(a.p.store_dtype, ex.row_label != nullptr, [&](auto dt, auto subset) {
+        return a.g ? launch_kg_scan<dt.value, subset.value, true>(a, q_first, nq, add, ex, stream) : launch_kg_scan<dt.value, subset.value, false>(a, q_first, nq, add, ex, stream);
+    });
 }
 
 }  // namespace vodhip

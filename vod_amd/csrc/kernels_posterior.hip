@@ -14,7 +14,7 @@
 //            uses and read column-wise with ds_read_b64_tr_b16, in the permuted k order of the packed accumulator: element j of lane
 //            half h is row 16 s + 8 (j >> 2) + 4 h + (j & 3) of the block.  Every lane is active at those reads (no divergence above
 //            them; the tile is padded, not masked).
-//            fp16: a weight is multiplied by 2^15 before it is rounded (the largest becomes 32768 < 65504), so it is a NORMAL fp16
+//            fp16: a weight is multiplied by 2^15 before it is rounded (the largest stays below 65504), so it is a NORMAL fp16
 //            number down to 2^-29 of the group's largest; the group's sum is multiplied by 2^-15 in float32 (both exact).  bf16 has
 //            float32's exponent range and needs no scale.
 //            The workgroup keeps its [256 columns x 64 queries] float32 accumulator in registers across the tiles of its group and
@@ -32,7 +32,9 @@
 // There are no atomics.  A row is eligible by the rule of the scan core (store_scan.h: row < ntotal, score not NaN, subset_allows); an
 // ineligible row has weight +0 - and 0 * NaN is NaN on the MFMA: a stored NaN / infinity in column d of any scanned tile (rows past
 // ntotal up to the tile's end included) makes column d of every query's mean NaN.  No eligible row or a +inf score: the mean row is 0.
-#include "store_scan.h"
+// The slice-image geometry, the fp16 weight scale, acc_scale and the host dispatch are scan_contract.h's, which also records why the
+// second product itself stays spelled out in this file.
+#include "scan_contract.h"
 
 #include "../../include/vodhip.h"
 
@@ -45,12 +47,11 @@ namespace {
 constexpr int PM_BN = 64;      // queries of a workgroup
 constexpr int PM_DC = 256;     // columns of a workgroup's accumulator
 constexpr int PM_GT = 64;      // tiles of a group: VODHIP_POSTERIOR_GROUP_ROWS / 256
-constexpr int PM_A_BYTES = SCAN_BM * 128;
-constexpr int PM_LDS = (PM_DC / 64) * PM_A_BYTES;  // the 4 slices of the second product; >= the K loop's ring
-static_assert(PM_LDS >= scan_ring_bytes(PM_BN), "the ring fits under the slices");
+constexpr int PM_A_BYTES = CT_SLICE_BYTES;
+constexpr int PM_LDS = CT_IMG;  // the 4 slices of the second product; >= the K loop's ring
+static_assert(PM_BN == CT_BN && PM_DC == 64 * CT_MAX_SLICES, "the geometry of scan_contract.h");
 static_assert(PM_GT * SCAN_BM == VODHIP_POSTERIOR_GROUP_ROWS, "the header states the group size");
 
-typedef short s16x4 __attribute__((ext_vector_type(4)));
 
 // X, Q, part: as partition_scan_kernel (part [n_qtiles * 64][n_xtiles], already written); acc_out [n_groups][n_qtiles * 64][dim_pad]
 template <int DT, bool SUBSET, int NSL>
@@ -165,7 +166,7 @@ void posterior_scan_kernel(const uint16_t* __restrict__ X, const uint16_t* __res
 #pragma unroll
                         for (int e = 0; e < 8; ++e) {
                             const int r = 8 * s + e;
-                            const float w = expf(beta * (acc[i][j][r] - m)) * 32768.f;
+                            const float w = expf(beta * (acc[i][j][r] - m)) * CT_FP16_SCALE;
                             v[e] = (_Float16)((mask & (1u << (i * 16 + r))) ? w : 0.f);
                         }
                         wf[i][s][j] = __builtin_bit_cast(u32x4, v);
@@ -202,8 +203,7 @@ void posterior_scan_kernel(const uint16_t* __restrict__ X, const uint16_t* __res
                                 const char* at = smem + sl * A_BYTES + row * ROW_BYTES + (phys << 4) + t_sub;
                                 half[e] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((VOD_AS3 s16x4*)at);
                             }
-                            typedef short s16x8 __attribute__((ext_vector_type(8)));
-                            const s16x8 both = __builtin_shufflevector(half[0], half[1], 0, 1, 2, 3, 4, 5, 6, 7);
+                                                        const s16x8 both = __builtin_shufflevector(half[0], half[1], 0, 1, 2, 3, 4, 5, 6, 7);
                             const u32x4 af = __builtin_bit_cast(u32x4, both);
 #pragma unroll
                             for (int j = 0; j < NJ; ++j) yacc[sl * 2 + mb][j] = mfma32<DT>(af, wf[i][s][j], yacc[sl * 2 + mb][j]);
@@ -233,7 +233,7 @@ void posterior_scan_kernel(const uint16_t* __restrict__ X, const uint16_t* __res
         __syncthreads();
     }
     if (wave == WM - 1) {
-        const float unscale = DT == 0 ? 1.f / 32768.f : 1.f;
+        const float unscale = DT == 0 ? 1.f / CT_FP16_SCALE : 1.f;
 #pragma unroll
         for (int b = 0; b < NYB; ++b) {
             {
@@ -299,31 +299,6 @@ __global__ void __launch_bounds__(PF_T) posterior_finish_kernel(const float2* __
     }
 }
 
-template <int DT, bool SUBSET, int NSL>
-hipError_t launch_pm_scan_n(const PosteriorArgs& a, int64_t nq, int n_qtiles, int n_tiles, int n_groups, int dc_first, int n_dchunks, const FilterExtra& ex,
-                            hipStream_t stream) {
-    const int64_t grid = (int64_t)((n_groups + 7) / 8) * 8 * n_qtiles * n_dchunks;
-    if (grid > 0x7fffffffll) return hipErrorInvalidValue;
-    auto kern = posterior_scan_kernel<DT, SUBSET, NSL>;
-    if (hipError_t e = allow_dynamic_lds((const void*)kern, PM_LDS); e != hipSuccess) return e;
-    hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(scan_threads(1)), PM_LDS, stream, (const uint16_t*)a.p.store, (const uint16_t*)a.p.q_stage, (int)a.p.dim_pad,
-                       (int)a.p.ntotal, n_tiles, n_qtiles, n_dchunks, dc_first, (int)nq, a.p.beta, (const float2*)a.p.part, a.acc, ex);
-    return hipGetLastError();
-}
-
-// the full 256-column chunks in one launch, the last chunk of 64 | 128 | 192 columns (if any) in a second one
-template <int DT, bool SUBSET>
-hipError_t launch_pm_scan(const PosteriorArgs& a, int64_t nq, int n_qtiles, int n_tiles, int n_groups, const FilterExtra& ex, hipStream_t stream) {
-    const int n_slices = (int)(a.p.dim_pad / 64);
-    const int n_full = n_slices / (PM_DC / 64), rem = n_slices % (PM_DC / 64);
-    if (n_full > 0)
-        if (hipError_t e = launch_pm_scan_n<DT, SUBSET, PM_DC / 64>(a, nq, n_qtiles, n_tiles, n_groups, 0, n_full, ex, stream); e != hipSuccess) return e;
-    if (rem == 1) return launch_pm_scan_n<DT, SUBSET, 1>(a, nq, n_qtiles, n_tiles, n_groups, n_full, 1, ex, stream);
-    if (rem == 2) return launch_pm_scan_n<DT, SUBSET, 2>(a, nq, n_qtiles, n_tiles, n_groups, n_full, 1, ex, stream);
-    if (rem == 3) return launch_pm_scan_n<DT, SUBSET, 3>(a, nq, n_qtiles, n_tiles, n_groups, n_full, 1, ex, stream);
-    return hipSuccess;
-}
-
 }  // namespace
 
 int64_t posterior_mean_groups(int64_t ntotal) { return (scan_tiles(ntotal) + PM_GT - 1) / PM_GT; }
@@ -337,12 +312,14 @@ hipError_t launch_posterior_mean(const PosteriorArgs& a, int64_t q_first, int64_
     if (n_tiles > 0) {
         const FilterExtra ex = scan_filter_extra(a.p, q_first);
         const int n_qtiles = (int)(nq_pad / PM_BN);
-        const bool subset = ex.row_label != nullptr;
-        hipError_t e;
-        if (a.p.store_dtype == 0)
-            e = subset ? launch_pm_scan<0, true>(a, nq, n_qtiles, n_tiles, n_groups, ex, stream) : launch_pm_scan<0, false>(a, nq, n_qtiles, n_tiles, n_groups, ex, stream);
-        else
-            e = subset ? launch_pm_scan<1, true>(a, nq, n_qtiles, n_tiles, n_groups, ex, stream) : launch_pm_scan<1, false>(a, nq, n_qtiles, n_tiles, n_groups, ex, stream);
+        // the full 256-column chunks in one launch, the last chunk of 64 | 128 | 192 columns (if any) in a second one
+        const hipError_t e = contract_dispatch(a.p.store_dtype, ex.row_label != nullptr, [&](auto dt, auto subset) {
+            return chunks_dispatch<PM_DC / 64>((int)(a.p.dim_pad / 64), [&](auto nsl, int dc_first, int n_dchunks) {
+                return scan_launch_lds<1>(posterior_scan_kernel<dt.value, subset.value, nsl.value>, scan_grid(n_groups, n_qtiles * n_dchunks), PM_LDS, stream,
+                                          (const uint16_t*)a.p.store, (const uint16_t*)a.p.q_stage, (int)a.p.dim_pad, (int)a.p.ntotal, n_tiles, n_qtiles, n_dchunks, dc_first,
+                                          (int)nq, a.p.beta, (const float2*)a.p.part, a.acc, ex);
+            });
+        });
         if (e != hipSuccess) return e;
     }
     const unsigned dblocks = (unsigned)((a.p.dim + PF_T * PF_PER - 1) / (PF_T * PF_PER));

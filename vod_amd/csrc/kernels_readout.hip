@@ -30,7 +30,9 @@
 // MFMA's own order), tile after tile in increasing t with the rescales between them (a rescale by exactly 1 is skipped or done: the same
 // bits); then the waves, then the groups.  There are no atomics.  An ineligible row has weight +0 - and 0 * NaN is NaN on the MFMA: a
 // NaN / infinity in column c of the table makes column c of every query NaN; the other columns and the two scalar words are unaffected.
-#include "store_scan.h"
+// The slice-image geometry, the fp16 weight scale, acc_scale and the host dispatch are scan_contract.h's, which also records why the
+// second product itself stays spelled out in this file.
+#include "scan_contract.h"
 
 #include "../../include/vodhip.h"
 
@@ -42,30 +44,12 @@ namespace {
 
 constexpr int RO_BN = 64;                                   // queries of a workgroup
 constexpr int RO_GT = VODHIP_READOUT_GROUP_ROWS / SCAN_BM;  // tiles of a group
-constexpr int RO_A_BYTES = SCAN_BM * 128;                   // one slice image
-constexpr int RO_IMG = 4 * RO_A_BYTES;                      // the slices of the second product; >= the K loop's ring
+constexpr int RO_A_BYTES = CT_SLICE_BYTES;                  // one slice image
+constexpr int RO_IMG = CT_IMG;                              // the slices of the second product; >= the K loop's ring
 constexpr int RO_LDS = RO_IMG + 2 * SCAN_WM * RO_BN * (int)sizeof(float);  // + the two reduction arrays of the epilogue
-static_assert(RO_IMG >= scan_ring_bytes(RO_BN), "the ring fits under the slices");
+static_assert(RO_BN == CT_BN, "the geometry of scan_contract.h");
 static_assert(RO_GT * SCAN_BM == VODHIP_READOUT_GROUP_ROWS && RO_GT >= 1, "the header states the group size");
 
-typedef short s16x4 __attribute__((ext_vector_type(4)));
-typedef short s16x8 __attribute__((ext_vector_type(8)));
-
-// acc * f for an MFMA accumulator block that stays in the accumulation registers (AGPRs): the block is copied into 16 vector registers,
-// multiplied there and copied back, one block at a time.  Written as a plain product the compiler keeps every block in the vector
-// registers the K loop needs (measured: 1.1 KB of scratch per lane at NSL = 4); the empty asm statements pin the register class.
-__device__ __forceinline__ void acc_scale(f32x16& acc, float f) {
-    f32x16 a = acc;
-    asm volatile("" : "+a"(a));
-    f32x16 v = a;
-    asm volatile("" : "+v"(v));
-#pragma unroll
-    for (int r = 0; r < 16; ++r) v[r] *= f;
-    asm volatile("" : "+v"(v));
-    a = v;
-    asm volatile("" : "+a"(a));
-    acc = a;
-}
 
 // X, Q: as partition_scan_kernel; V: the value table [>= n_xtiles * 256][c_pad]; part [nq_pad][n_xtiles] (rows below n_qtiles * 64 are
 // written here); acc_out [n_groups][nq_pad][c_pad], c_pad = 64 NSL.  n_qtiles = ceil(nq / 64) <= nq_pad / 64: the staging pads a batch
@@ -251,7 +235,7 @@ void readout_scan_kernel(const uint16_t* __restrict__ X, const uint16_t* __restr
                     if constexpr (DT == 0) {
                         f16x8 v;
 #pragma unroll
-                        for (int e = 0; e < 8; ++e) v[e] = (_Float16)((acc[i][j][8 * s + e] * gamma[j]) * 32768.f);
+                        for (int e = 0; e < 8; ++e) v[e] = (_Float16)((acc[i][j][8 * s + e] * gamma[j]) * CT_FP16_SCALE);
                         wf[i][s][j] = __builtin_bit_cast(u32x4, v);
                     } else {
                         bf16x8 v;
@@ -328,7 +312,7 @@ void readout_scan_kernel(const uint16_t* __restrict__ X, const uint16_t* __restr
     }
     // column c of query column `col`: block b = c / 32, lane half (c >> 2) & 1, register (c & 3) + 4 ((c & 31) >> 3) - the C layout of
     // the second product (its rows are the value columns)
-    const float unscale = DT == 0 ? 1.f / 32768.f : 1.f;
+    const float unscale = DT == 0 ? 1.f / CT_FP16_SCALE : 1.f;
     float* dst = acc_out + ((size_t)grp * (size_t)nq_pad + (size_t)q0) * C_PAD;
     for (int idx = wave * 64 + lane_e; idx < BN * C_PAD; idx += scan_threads(1)) {  // (wave * 64 + lane_e = tid)
         const int col = idx / C_PAD, c = idx % C_PAD;
@@ -371,28 +355,6 @@ __global__ void __launch_bounds__(RF_T) readout_finish_kernel(const float2* __re
     if (tid < n_cols) out_values[q * n_cols + tid] = sum;
 }
 
-template <int DT, bool SUBSET, int NSL>
-hipError_t launch_ro_scan_n(const ReadoutArgs& a, int64_t nq, int64_t nq_pad, int n_qtiles, int n_tiles, int n_groups, const FilterExtra& ex, hipStream_t stream) {
-    const int64_t grid = (int64_t)((n_groups + 7) / 8) * 8 * n_qtiles;
-    if (grid > 0x7fffffffll) return hipErrorInvalidValue;
-    auto kern = readout_scan_kernel<DT, SUBSET, NSL>;
-    if (hipError_t e = allow_dynamic_lds((const void*)kern, RO_LDS); e != hipSuccess) return e;
-    hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(scan_threads(1)), RO_LDS, stream, (const uint16_t*)a.p.store, (const uint16_t*)a.p.q_stage,
-                       (const uint16_t*)a.values, (int)a.p.dim_pad, (int)a.p.ntotal, n_tiles, n_qtiles, (int)nq_pad, (int)nq, a.p.beta, (float2*)a.p.part, a.acc, ex);
-    return hipGetLastError();
-}
-
-template <int DT, bool SUBSET>
-hipError_t launch_ro_scan(const ReadoutArgs& a, int64_t nq, int64_t nq_pad, int n_qtiles, int n_tiles, int n_groups, const FilterExtra& ex, hipStream_t stream) {
-    switch (a.c_pad / 64) {
-        case 1: return launch_ro_scan_n<DT, SUBSET, 1>(a, nq, nq_pad, n_qtiles, n_tiles, n_groups, ex, stream);
-        case 2: return launch_ro_scan_n<DT, SUBSET, 2>(a, nq, nq_pad, n_qtiles, n_tiles, n_groups, ex, stream);
-        case 3: return launch_ro_scan_n<DT, SUBSET, 3>(a, nq, nq_pad, n_qtiles, n_tiles, n_groups, ex, stream);
-        case 4: return launch_ro_scan_n<DT, SUBSET, 4>(a, nq, nq_pad, n_qtiles, n_tiles, n_groups, ex, stream);
-    }
-    return hipErrorInvalidValue;
-}
-
 }  // namespace
 
 int64_t readout_groups(int64_t ntotal) { return (scan_tiles(ntotal) + RO_GT - 1) / RO_GT; }
@@ -402,19 +364,19 @@ hipError_t launch_posterior_expectation(const ReadoutArgs& a, int64_t q_first, i
     const int64_t nq_pad = scan_nq_pad(nq);
     const int64_t n_tiles = scan_tiles(a.p.ntotal);
     const int n_groups = (int)readout_groups(a.p.ntotal);
-    if (a.p.dim_pad % 64 != 0 || a.p.dim_pad <= 0 || a.p.ntotal < 0 || a.p.ntotal >= (1ll << 31) - 512 || nq > (1 << 20)) return hipErrorInvalidValue;
-    if (a.c_pad % 64 != 0 || a.c_pad < 64 || a.c_pad > 256 || a.n_cols < 1 || a.n_cols > a.c_pad) return hipErrorInvalidValue;
+    if (!scan_store_ok(a.p) || nq > (1 << 20) || !readout_cols_ok(a.c_pad, a.n_cols)) return hipErrorInvalidValue;
     if (n_tiles > 0) {
         if (!a.values) return hipErrorInvalidValue;
         if (hipError_t e = launch_scan_stage(a.p, q_first, nq, nq_pad, stream); e != hipSuccess) return e;
         const FilterExtra ex = scan_filter_extra(a.p, q_first);
         const int n_qtiles = (int)((nq + RO_BN - 1) / RO_BN);  // (<= nq_pad / 64: only the tiles that hold a query)
-        const bool subset = ex.row_label != nullptr;
-        hipError_t e;
-        if (a.p.store_dtype == 0)
-            e = subset ? launch_ro_scan<0, true>(a, nq, nq_pad, n_qtiles, (int)n_tiles, n_groups, ex, stream) : launch_ro_scan<0, false>(a, nq, nq_pad, n_qtiles, (int)n_tiles, n_groups, ex, stream);
-        else
-            e = subset ? launch_ro_scan<1, true>(a, nq, nq_pad, n_qtiles, (int)n_tiles, n_groups, ex, stream) : launch_ro_scan<1, false>(a, nq, nq_pad, n_qtiles, (int)n_tiles, n_groups, ex, stream);
+        const hipError_t e = contract_dispatch(a.p.store_dtype, ex.row_label != nullptr, [&](auto dt, auto subset) {
+            return slices_dispatch<CT_MAX_SLICES>(a.c_pad / 64, [&](auto nsl) {
+                return scan_launch_lds<1>(readout_scan_kernel<dt.value, subset.value, nsl.value>, scan_grid(n_groups, n_qtiles), RO_LDS, stream, (const uint16_t*)a.p.store,
+                                          (const uint16_t*)a.p.q_stage, (const uint16_t*)a.values, (int)a.p.dim_pad, (int)a.p.ntotal, (int)n_tiles, n_qtiles, (int)nq_pad,
+                                          (int)nq, a.p.beta, (float2*)a.p.part, a.acc, ex);
+            });
+        });
         if (e != hipSuccess) return e;
     }
     if (hipError_t e = launch_partition_finish(a.p, q_first, nq, stream); e != hipSuccess) return e;

@@ -27,7 +27,9 @@
 // ONE order per (row, column), fixed by the query's position in the batch alone - not by ntotal, the row's neighbours or the grid: wave w
 // adds queries 256 t + 64 w .. + 63 in k-step order, tile after tile, then the waves, then the slices of 1024 queries in slice order.  A
 // row has ONE owning workgroup: no atomics, no partials, no fold.  An element depends on its row, the queries and their words alone.
-#include "store_scan.h"
+// The slice-image geometry, the fp16 weight scale, acc_scale and the host dispatch are scan_contract.h's, which also records why the
+// second product itself stays spelled out in this file.
+#include "scan_contract.h"
 
 #include "../../include/vodhip.h"
 
@@ -40,14 +42,12 @@ namespace {
 
 constexpr int ADJ_BQ = SCAN_BM;                  // queries of a tile: the streamed operand of the K loop
 constexpr int ADJ_BZ = 64;                       // stored rows of a workgroup: the resident operand
-constexpr int ADJ_A_BYTES = ADJ_BQ * 128;        // one slice image
-constexpr int ADJ_IMG = 4 * ADJ_A_BYTES;         // the slices of the second product; >= the K loop's ring
+constexpr int ADJ_A_BYTES = CT_SLICE_BYTES;      // one slice image
+constexpr int ADJ_IMG = CT_IMG;                  // the slices of the second product; >= the K loop's ring
 constexpr int ADJ_LDS = ADJ_IMG + ADJ_BQ * (int)sizeof(float2);  // + the tile's (max_score, log_rel) words
 constexpr int ADJ_K_NAN = INT_MIN;               // col_k of a column that holds a NaN or an infinity
-static_assert(ADJ_IMG >= scan_ring_bytes(ADJ_BZ), "the ring fits under the slices");
+static_assert(ADJ_BZ == CT_BN, "the geometry of scan_contract.h");
 
-typedef short s16x4 __attribute__((ext_vector_type(4)));
-typedef short s16x8 __attribute__((ext_vector_type(8)));
 
 // ---- k_c per weight column over the whole batch: one workgroup per column, the queries strided over its threads (a maximum is the same
 // in every order)
@@ -237,7 +237,7 @@ void readout_adjoint_kernel(const uint16_t* __restrict__ Qs, const uint16_t* __r
                     if constexpr (DT == 0) {
                         f16x8 v;
 #pragma unroll
-                        for (int e = 0; e < 8; ++e) v[e] = (_Float16)(w8[e] * 32768.f);
+                        for (int e = 0; e < 8; ++e) v[e] = (_Float16)(w8[e] * CT_FP16_SCALE);
                         wf[i][s][j] = __builtin_bit_cast(u32x4, v);
                     } else {
                         bf16x8 v;
@@ -314,7 +314,7 @@ void readout_adjoint_kernel(const uint16_t* __restrict__ Qs, const uint16_t* __r
     }
     // column c of row column `col`: block b = c / 32, lane half (c >> 2) & 1, register (c & 3) + 4 ((c & 31) >> 3) - the C layout of the
     // second product (its rows are the weight columns).  The column's power of two (and the 2^-15 of the fp16 weights) is exact
-    constexpr int unscale = DT == 0 ? 15 : 0;
+    constexpr int unscale = DT == 0 ? CT_FP16_SHIFT : 0;
     for (int idx = wave * 64 + lane_e; idx < BN * C_PAD; idx += scan_threads(1)) {  // (wave * 64 + lane_e = tid)
         const int col = idx / C_PAD, c = idx % C_PAD;
         const int z = z0 + col;
@@ -330,35 +330,7 @@ void readout_adjoint_kernel(const uint16_t* __restrict__ Qs, const uint16_t* __r
     }
 }
 
-template <int DT, bool SUBSET, int NSL>
-hipError_t launch_adj_scan_n(const ReadoutAdjointArgs& a, int64_t q_first, int64_t nq, int add, const FilterExtra& ex, hipStream_t stream) {
-    const int n_rtiles = (int)((a.p.ntotal + ADJ_BZ - 1) / ADJ_BZ);
-    const int n_qtiles = (int)((nq + ADJ_BQ - 1) / ADJ_BQ);
-    const int64_t grid = (int64_t)((n_rtiles + 7) / 8) * 8;
-    auto kern = readout_adjoint_kernel<DT, SUBSET, NSL>;
-    if (hipError_t e = allow_dynamic_lds((const void*)kern, ADJ_LDS); e != hipSuccess) return e;
-    hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(scan_threads(1)), ADJ_LDS, stream, (const uint16_t*)a.p.q_stage, (const uint16_t*)a.p.store,
-                       (const uint16_t*)a.w_stage, (const int*)a.col_k, a.p.out_max + q_first, a.p.out_log_rel + q_first, (int)a.p.dim_pad, (int)a.p.ntotal, n_rtiles,
-                       n_qtiles, (int)nq, a.n_cols, a.p.beta, add, a.out, ex);
-    return hipGetLastError();
-}
-
-template <int DT, bool SUBSET>
-hipError_t launch_adj_scan(const ReadoutAdjointArgs& a, int64_t q_first, int64_t nq, int add, const FilterExtra& ex, hipStream_t stream) {
-    switch (a.c_pad / 64) {
-        case 1: return launch_adj_scan_n<DT, SUBSET, 1>(a, q_first, nq, add, ex, stream);
-        case 2: return launch_adj_scan_n<DT, SUBSET, 2>(a, q_first, nq, add, ex, stream);
-        case 3: return launch_adj_scan_n<DT, SUBSET, 3>(a, q_first, nq, add, ex, stream);
-        case 4: return launch_adj_scan_n<DT, SUBSET, 4>(a, q_first, nq, add, ex, stream);
-    }
-    return hipErrorInvalidValue;
-}
-
-bool adjoint_args_ok(const ReadoutAdjointArgs& a) {
-    if (a.p.dim_pad % 64 != 0 || a.p.dim_pad <= 0 || a.p.ntotal < 0 || a.p.ntotal >= (1ll << 31) - 512) return false;
-    if (a.c_pad % 64 != 0 || a.c_pad < 64 || a.c_pad > 256 || a.n_cols < 1 || a.n_cols > a.c_pad) return false;
-    return a.w && a.col_k && a.w_stage && a.out;
-}
+bool adjoint_args_ok(const ReadoutAdjointArgs& a) { return scan_store_ok(a.p) && readout_cols_ok(a.c_pad, a.n_cols) && a.w && a.col_k && a.w_stage && a.out; }
 
 }  // namespace
 
@@ -380,9 +352,15 @@ hipError_t launch_posterior_adjoint(const ReadoutAdjointArgs& a, int64_t q_first
                        a.n_cols, a.c_pad, (const int*)a.col_k, a.p.store_dtype, (uint16_t*)a.w_stage);
     if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
     const FilterExtra ex = scan_filter_extra(a.p, q_first);
-    const bool subset = ex.row_label != nullptr;
-    if (a.p.store_dtype == 0) return subset ? launch_adj_scan<0, true>(a, q_first, nq, add, ex, stream) : launch_adj_scan<0, false>(a, q_first, nq, add, ex, stream);
-    return subset ? launch_adj_scan<1, true>(a, q_first, nq, add, ex, stream) : launch_adj_scan<1, false>(a, q_first, nq, add, ex, stream);
+    const int n_rtiles = (int)((a.p.ntotal + ADJ_BZ - 1) / ADJ_BZ);
+    const int n_qtiles = (int)(nq_pad / ADJ_BQ);
+    return contract_dispatch(a.p.store_dtype, ex.row_label != nullptr, [&](auto dt, auto subset) {
+        return slices_dispatch<CT_MAX_SLICES>(a.c_pad / 64, [&](auto nsl) {
+            return scan_launch_lds<1>(readout_adjoint_kernel<dt.value, subset.value, nsl.value>, scan_grid(n_rtiles, 1), ADJ_LDS, stream, (const uint16_t*)a.p.q_stage,
+                                      (const uint16_t*)a.p.store, (const uint16_t*)a.w_stage, (const int*)a.col_k, a.p.out_max + q_first, a.p.out_log_rel + q_first,
+                                      (int)a.p.dim_pad, (int)a.p.ntotal, n_rtiles, n_qtiles, (int)nq, a.n_cols, a.p.beta, add, a.out, ex);
+        });
+    });
 }
 
 }  // namespace vodhip

@@ -26,7 +26,9 @@
 //   finish   grad[q, d] = ldexp(beta * sum_g expf(beta (M_g - max_score) - log_rel) acc_g[q, d], k_q + e_q) in increasing g; a query
 //            without a finite max_score or with flag 1 gets +0, one with flag 2 NaN.
 // ONE order per (query, column), fixed by ntotal, dim_pad and c_pad alone (kernels_readout.hip: the same argument); no atomics.
-#include "store_scan.h"
+// The slice-image geometry, the fp16 weight scale, acc_scale and the host dispatch are scan_contract.h's, which also records why the
+// second product itself stays spelled out in this file.
+#include "scan_contract.h"
 
 #include "../../include/vodhip.h"
 
@@ -46,15 +48,13 @@ constexpr int RG_GT = VODHIP_READOUT_GROUP_ROWS / SCAN_BM;  // tiles of a group
 #endif
 constexpr int RG_NSL = VODHIP_READOUT_GRAD_SLICES;
 constexpr int RG_DC = 64 * RG_NSL;                          // columns of a full chunk
-constexpr int RG_A_BYTES = SCAN_BM * 128;                   // one slice image
-constexpr int RG_IMG = 4 * RG_A_BYTES;                      // the slices of the second product; >= the K loop's ring
+constexpr int RG_A_BYTES = CT_SLICE_BYTES;                  // one slice image
+constexpr int RG_IMG = CT_IMG;                              // the slices of the second product; >= the K loop's ring
 constexpr int RG_LDS = RG_IMG + SCAN_WM * RG_BN * (int)sizeof(float);  // + the reduction array of the tile maximum
 static_assert(RG_NSL == 3 || RG_NSL == 4, "3 or 4 slices");
-static_assert(RG_IMG >= scan_ring_bytes(RG_BN), "the ring fits under the slices");
+static_assert(RG_BN == CT_BN, "the geometry of scan_contract.h");
 static_assert(RG_GT * SCAN_BM == VODHIP_READOUT_GROUP_ROWS && RG_GT >= 1, "the header states the group size");
 
-typedef short s16x4 __attribute__((ext_vector_type(4)));
-typedef short s16x8 __attribute__((ext_vector_type(8)));
 
 // what the stage kernel leaves per staged query
 struct RgQuery {
@@ -143,20 +143,6 @@ void readout_grad_stage_kernel(const float* __restrict__ g, const float* __restr
     __syncthreads();
     // a row that is not scanned stages zeros (decided by thread 0 after the bits were written)
     if (flag != 0 && tid < c_pad) g_stage[(size_t)q * c_pad + tid] = 0;
-}
-
-// acc * f for an accumulator block that stays in AGPRs: kernels_readout.hip's acc_scale
-__device__ __forceinline__ void rg_acc_scale(f32x16& acc, float f) {
-    f32x16 a = acc;
-    asm volatile("" : "+a"(a));
-    f32x16 v = a;
-    asm volatile("" : "+v"(v));
-#pragma unroll
-    for (int r = 0; r < 16; ++r) v[r] *= f;
-    asm volatile("" : "+v"(v));
-    a = v;
-    asm volatile("" : "+a"(a));
-    acc = a;
 }
 
 // X, Q: as partition_scan_kernel; V: the value table [>= n_xtiles * 256][c_pad]; G: g_stage [nq_pad][c_pad]; aux [nq_pad];
@@ -320,7 +306,7 @@ void readout_grad_scan_kernel(const uint16_t* __restrict__ X, const uint16_t* __
         for (int j = 0; j < NJ; ++j) {
             if (__any(scale[j] != 1.f)) {  // (uniform over the wave; a lane whose scale is 1 multiplies by exactly 1)
 #pragma unroll
-                for (int b = 0; b < NYB; ++b) rg_acc_scale(yacc[b][j], scale[j]);
+                for (int b = 0; b < NYB; ++b) acc_scale(yacc[b][j], scale[j]);
             }
         }
 
@@ -344,7 +330,7 @@ void readout_grad_scan_kernel(const uint16_t* __restrict__ X, const uint16_t* __
                     if constexpr (DT == 0) {
                         f16x8 v;
 #pragma unroll
-                        for (int e = 0; e < 8; ++e) v[e] = (_Float16)(w8[e] * 32768.f);
+                        for (int e = 0; e < 8; ++e) v[e] = (_Float16)(w8[e] * CT_FP16_SCALE);
                         wf[i][s][j] = __builtin_bit_cast(u32x4, v);
                     } else {
                         bf16x8 v;
@@ -425,7 +411,7 @@ void readout_grad_scan_kernel(const uint16_t* __restrict__ X, const uint16_t* __
         __syncthreads();
     }
     // column c of the chunk, query column `col`: block b = c / 32, lane half (c >> 2) & 1, register (c & 3) + 4 ((c & 31) >> 3)
-    const float unscale = DT == 0 ? 1.f / 32768.f : 1.f;
+    const float unscale = DT == 0 ? 1.f / CT_FP16_SCALE : 1.f;
     float* dst = acc_out + ((size_t)grp * (size_t)nq_pad + (size_t)q0) * dim_pad + (size_t)dc * RG_DC;
     for (int idx = wave * 64 + lane_e; idx < BN * C_W; idx += scan_threads(1)) {
         const int col = idx / C_W, c = idx % C_W;
@@ -476,39 +462,12 @@ __global__ void __launch_bounds__(GF_T) readout_grad_finish_kernel(const float* 
     }
 }
 
-template <int DT, bool SUBSET, int NSL>
-hipError_t launch_rg_scan_n(const ReadoutGradArgs& a, int64_t nq, int64_t nq_pad, int n_qtiles, int n_tiles, int n_groups, int dc_first, int n_dchunks,
-                            const FilterExtra& ex, hipStream_t stream) {
-    const int64_t grid = (int64_t)((n_groups + 7) / 8) * 8 * n_qtiles * n_dchunks;
-    if (grid > 0x7fffffffll) return hipErrorInvalidValue;
-    auto kern = readout_grad_scan_kernel<DT, SUBSET, NSL>;
-    if (hipError_t e = allow_dynamic_lds((const void*)kern, RG_LDS); e != hipSuccess) return e;
-    hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(scan_threads(1)), RG_LDS, stream, (const uint16_t*)a.p.store, (const uint16_t*)a.p.q_stage,
-                       (const uint16_t*)a.values, (const uint16_t*)a.g_stage, (const RgQuery*)a.aux, (int)a.p.dim_pad, a.c_pad, (int)a.p.ntotal, n_tiles, n_qtiles,
-                       n_dchunks, dc_first, (int)nq_pad, (int)nq, a.p.beta, a.acc, a.mg, ex);
-    return hipGetLastError();
-}
-
-// the full chunks in one launch, the last narrower chunk (if any) in a second one
-template <int DT, bool SUBSET>
-hipError_t launch_rg_scan(const ReadoutGradArgs& a, int64_t nq, int64_t nq_pad, int n_qtiles, int n_tiles, int n_groups, const FilterExtra& ex, hipStream_t stream) {
-    const int n_slices = (int)(a.p.dim_pad / 64);
-    const int n_full = n_slices / RG_NSL, rem = n_slices % RG_NSL;
-    if (n_full > 0)
-        if (hipError_t e = launch_rg_scan_n<DT, SUBSET, RG_NSL>(a, nq, nq_pad, n_qtiles, n_tiles, n_groups, 0, n_full, ex, stream); e != hipSuccess) return e;
-    if (rem == 1) return launch_rg_scan_n<DT, SUBSET, 1>(a, nq, nq_pad, n_qtiles, n_tiles, n_groups, n_full, 1, ex, stream);
-    if (rem == 2) return launch_rg_scan_n<DT, SUBSET, 2>(a, nq, nq_pad, n_qtiles, n_tiles, n_groups, n_full, 1, ex, stream);
-    if constexpr (RG_NSL == 4)
-        if (rem == 3) return launch_rg_scan_n<DT, SUBSET, 3>(a, nq, nq_pad, n_qtiles, n_tiles, n_groups, n_full, 1, ex, stream);
-    return hipSuccess;
-}
-
 }  // namespace
 
 size_t readout_grad_aux_bytes() { return sizeof(RgQuery); }
 
 hipError_t launch_readout_grad_vmax(const void* values, int64_t n_rows, int c_pad, int store_dtype, float* vmax, hipStream_t stream) {
-    if (c_pad % 64 != 0 || c_pad < 64 || c_pad > 256) return hipErrorInvalidValue;
+    if (!readout_cols_ok(c_pad, 1)) return hipErrorInvalidValue;
     if (hipError_t e = hipMemsetAsync(vmax, 0, (size_t)c_pad * sizeof(float), stream); e != hipSuccess) return e;
     if (n_rows <= 0) return hipSuccess;
     const unsigned grid = (unsigned)std::min<int64_t>(n_rows, 2048);
@@ -521,8 +480,7 @@ hipError_t launch_posterior_expectation_backward(const ReadoutGradArgs& a, int64
     const int64_t nq_pad = scan_nq_pad(nq);
     const int64_t n_tiles = scan_tiles(a.p.ntotal);
     const int n_groups = (int)readout_groups(a.p.ntotal);
-    if (a.p.dim_pad % 64 != 0 || a.p.dim_pad <= 0 || a.p.ntotal < 0 || a.p.ntotal >= (1ll << 31) - 512 || nq > (1 << 20)) return hipErrorInvalidValue;
-    if (a.c_pad % 64 != 0 || a.c_pad < 64 || a.c_pad > 256 || a.n_cols < 1 || a.n_cols > a.c_pad) return hipErrorInvalidValue;
+    if (!scan_store_ok(a.p) || nq > (1 << 20) || !readout_cols_ok(a.c_pad, a.n_cols)) return hipErrorInvalidValue;
     if (!a.vmax || !a.g || !a.y || !a.g_stage || !a.aux) return hipErrorInvalidValue;
     hipLaunchKernelGGL(readout_grad_stage_kernel, dim3((unsigned)nq_pad), dim3(RGS_T), 0, stream, a.g + (size_t)q_first * a.n_cols, a.y + (size_t)q_first * a.n_cols,
                        a.vmax, a.n_cols, a.c_pad, (int)nq, a.p.store_dtype, (uint16_t*)a.g_stage, (RgQuery*)a.aux);
@@ -532,12 +490,14 @@ hipError_t launch_posterior_expectation_backward(const ReadoutGradArgs& a, int64
         if (hipError_t e = launch_scan_stage(a.p, q_first, nq, nq_pad, stream); e != hipSuccess) return e;
         const FilterExtra ex = scan_filter_extra(a.p, q_first);
         const int n_qtiles = (int)((nq + RG_BN - 1) / RG_BN);  // (<= nq_pad / 64: only the tiles that hold a query)
-        const bool subset = ex.row_label != nullptr;
-        hipError_t e;
-        if (a.p.store_dtype == 0)
-            e = subset ? launch_rg_scan<0, true>(a, nq, nq_pad, n_qtiles, (int)n_tiles, n_groups, ex, stream) : launch_rg_scan<0, false>(a, nq, nq_pad, n_qtiles, (int)n_tiles, n_groups, ex, stream);
-        else
-            e = subset ? launch_rg_scan<1, true>(a, nq, nq_pad, n_qtiles, (int)n_tiles, n_groups, ex, stream) : launch_rg_scan<1, false>(a, nq, nq_pad, n_qtiles, (int)n_tiles, n_groups, ex, stream);
+        const hipError_t e = contract_dispatch(a.p.store_dtype, ex.row_label != nullptr, [&](auto dt, auto subset) {
+            return chunks_dispatch<RG_NSL>((int)(a.p.dim_pad / 64), [&](auto nsl, int dc_first, int n_dchunks) {
+                return scan_launch_lds<1>(readout_grad_scan_kernel<dt.value, subset.value, nsl.value>, scan_grid(n_groups, n_qtiles * n_dchunks), RG_LDS, stream,
+                                          (const uint16_t*)a.p.store, (const uint16_t*)a.p.q_stage, (const uint16_t*)a.values, (const uint16_t*)a.g_stage,
+                                          (const RgQuery*)a.aux, (int)a.p.dim_pad, a.c_pad, (int)a.p.ntotal, (int)n_tiles, n_qtiles, n_dchunks, dc_first, (int)nq_pad,
+                                          (int)nq, a.p.beta, a.acc, a.mg, ex);
+            });
+        });
         if (e != hipSuccess) return e;
     }
     const unsigned dblocks = (unsigned)((a.p.dim + GF_T * GF_PER - 1) / (GF_T * GF_PER));

@@ -1,8 +1,12 @@
 // The core of the whole-store scans: log_partition (kernels_partition.hip), posterior_stats (kernels_stats.hip), posterior_divergence
-// (kernels_divergence.hip), posterior_mean (kernels_posterior.hip), sample_posterior (kernels_sample_posterior.hip) and rank_ids /
-// count_above (kernels_rank.hip).  Each of them scores a tile of 256 stored rows against 64 | 128 staged queries with the ONE K loop
-// below and differs from the others in its epilogue alone (posterior_divergence also in the row map of its staging: the two queries of
-// a pair sit 32 columns apart, in the two accumulator columns of one lane).
+// (kernels_divergence.hip), range_search (kernels_range.hip), sample_posterior (kernels_sample_posterior.hip), rank_ids / count_above
+// (kernels_rank.hip), and the five that contract their weights with a second operand (scan_contract.h: their geometry and host side):
+// posterior_mean (kernels_posterior.hip), posterior_expectation (kernels_readout.hip), its gradient in the query
+// (kernels_readout_grad.hip), its adjoint in the value table (kernels_readout_adjoint.hip) and key_gradient (kernels_key_grad.hip).  Each
+// of them scores a tile of 256 streamed rows against 64 | 128 resident ones with the ONE K loop below and differs from the others in its
+// epilogue alone (posterior_divergence also in the row map of its staging: the two queries of a pair sit 32 columns apart, in the two
+// accumulator columns of one lane).  The streamed rows are stored rows and the resident ones staged queries, except in the adjoint and
+// the key gradient, which exchange the operands: the loop is symmetric in the two.
 //
 // THE CONTRACT.  A (query, row) pair has one score, the same bits in every scan and the bits a search returns:
 //   score     scan_k_loop is the K loop of mips_filter_kernel (kernels_mips.hip): LDS-DMA with the source-side XOR swizzle, a 3-slot
@@ -195,14 +199,18 @@ hipError_t scan_dispatch(int store_dtype, int64_t nq_pad, bool subset, F&& f) {
 // one workgroup per (row tile, query tile) in the order scan_block_tile decodes: the row tiles padded to the 8 XCDs
 inline int64_t scan_grid(int n_tiles, int n_qtiles) { return (int64_t)((n_tiles + 7) / 8) * 8 * n_qtiles; }
 
-// a kernel of the (BN, WN) geometry on `grid` workgroups with the ring as its dynamic LDS
-template <int BN, int WN, class K, class... A>
-hipError_t scan_launch(K kern, int64_t grid, hipStream_t stream, A... args) {
+// a kernel of WN column waves on `grid` workgroups with `lds` bytes of dynamic LDS
+template <int WN, class K, class... A>
+hipError_t scan_launch_lds(K kern, int64_t grid, int lds, hipStream_t stream, A... args) {
     if (grid > 0x7fffffffll) return hipErrorInvalidValue;
-    constexpr int lds = scan_ring_bytes(BN);
     if (hipError_t e = allow_dynamic_lds((const void*)kern, lds); e != hipSuccess) return e;
     hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(scan_threads(WN)), lds, stream, args...);
     return hipGetLastError();
+}
+// a kernel of the (BN, WN) geometry with the ring as its dynamic LDS
+template <int BN, int WN, class K, class... A>
+hipError_t scan_launch(K kern, int64_t grid, hipStream_t stream, A... args) {
+    return scan_launch_lds<WN>(kern, grid, scan_ring_bytes(BN), stream, args...);
 }
 
 }  // namespace vodhip
